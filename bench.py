@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X co-attention path: QA-pairs/sec of the `--model attention` train step.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (N > 1: either under torch.distributed.run, one rank per GPU, or from a plain shell -- bench.py then
 starts the N ranks itself)
 
 Workload (BASELINE.json configs[1], per GPU): HierarchicalCoAttentionNet, K=1000 answers (1001
 logits), batch 160, synthetic 224x224 images (-> 7x7x512 grid, N=49), 26-token questions, fp32;
 one step = forward + CrossEntropy + backward + Adam (+ RCCL gradient all-reduce when N > 1), all
-inputs resident in HBM before the timed region.  Rank 0 prints ONE JSON line; besides the
-contract fields it carries
+inputs resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times
+exactly K steps and prints the headline: `value` (QA-pairs/s), `ms_per_step` (one timed step), the run's configuration
+and, for N > 1, the ranks and the GPU each ran on.  --dump-outputs DIR then writes what the last timed step computed
+(loss, gradients, updated parameters; dump_outputs).  Everything below is measured with --full only; with it the line
+also carries
+  value_fast16 / exchange  the same step in the tolerance mode (N = 1) / under the other gradient exchanges (N > 1)
 ARITHMETIC: everything on the line -- `value`, `roofline`, every per-kernel leg, `hot_path` -- runs the reference's arithmetic:
 fp32 storage and accumulation, fp32-ACCURATE products (C-ABI flags = 0, train.Trainer's default: three bf16 pieces per operand, six
 partial products per fp32 product).  The opt-in tolerance mode (22-bit forward / 16-bit backward products) appears only under
@@ -59,6 +63,49 @@ sys.path.insert(0, ROOT)
 ALG_BYTES_PER_PAIR_LEVEL = lambda N, T, d: 4 * (T * d + d * N + N * d + T * d + 2 * d)   # Q + V + P_v + P_q + v,q
 HBM_PEAK_GBS = 8000.0
 
+MIOPEN_DB_SEED = os.path.join(ROOT, "miopen_db")     # committed: MIOpen find records of the default workload on an MI355X
+
+
+def seed_miopen_db():
+    """The first forward of every convolution shape runs MIOpen's find step, which times each applicable solver: about 40 s
+    for the eight VGG layers of the default workload, before the first step, wherever MIOpen has no records yet.  MIOpen
+    keeps those records in its user database (MIOPEN_USER_DB_PATH, by default ~/.config/miopen); every committed record file
+    of MIOPEN_DB_SEED that the database lacks is copied into it here, so that MIOpen runs the solvers those records rank
+    first, without timing runs.  A file already there is left alone (shapes it does not hold are found and added as usual).
+    Where that directory cannot be written, a temporary one, removed at exit, is seeded and used instead (for MIOpen's kernel
+    cache as well, unless MIOPEN_CUSTOM_CACHE_DIR is set); if that fails too, the run goes on without the seed.  Nothing is written into the repository.  Called before anything calls MIOpen;
+    ranks started by self_launch inherit the environment."""
+    import atexit
+    import shutil
+    import tempfile
+    if not os.path.isdir(MIOPEN_DB_SEED):
+        return
+    seed = [f for f in os.listdir(MIOPEN_DB_SEED) if f.endswith(".txt")]
+
+    def fill(d):
+        os.makedirs(d, exist_ok=True)
+        for f in seed:
+            dst = os.path.join(d, f)
+            if not os.path.exists(dst):
+                tmp = "%s.%d.tmp" % (dst, os.getpid())          # (renamed into place: a concurrent run never reads half a file)
+                shutil.copyfile(os.path.join(MIOPEN_DB_SEED, f), tmp)
+                os.replace(tmp, dst)
+
+    try:
+        fill(os.environ.get("MIOPEN_USER_DB_PATH") or os.path.join(os.path.expanduser("~"), ".config", "miopen"))
+        return
+    except OSError:
+        pass
+    try:
+        d = tempfile.mkdtemp(prefix="miopen_db_")
+        atexit.register(shutil.rmtree, d, True)
+        fill(d)
+    except OSError:
+        return
+    os.environ["MIOPEN_USER_DB_PATH"] = d
+    # (an unwritable home also denies MIOpen its kernel cache, ~/.cache/miopen, and MIOpen then fails the first convolution)
+    os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", os.path.join(d, "cache"))
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -70,9 +117,10 @@ def parse():
     ap.add_argument("--num-cls", type=int, default=1000)
     ap.add_argument("--vocab", type=int, default=10000)
     ap.add_argument("--seq-len", type=int, default=26)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the roofline / hot_path legs")
-    ap.add_argument("--no-configs", action="store_true", help="skip the compact config4 / config5 objects (BASELINE configs[3], [4])")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline legs")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the tolerance-mode step and the roofline / hot_path legs")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="--full: skip the compact config4 / config5 objects (BASELINE configs[3], [4])")
     ap.add_argument("--only", type=str, default="", help="developer switch: run only 'roofline' or 'hot' legs")
     ap.add_argument("--cpu-batch", type=int, default=0, help="batch of the CPU baseline leg (0: the GPU step's own batch)")
     ap.add_argument("--exchange-p2p", action="store_true",
@@ -94,6 +142,12 @@ def parse():
     ap.add_argument("--nchw", dest="channels_last", action="store_false",
                     help="keep the stock VGG encoder in NCHW (default: channels_last, MIOpen NHWC kernels, ~25 %% "
                          "faster forward; its first call tunes for up to a minute)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the tolerance-mode step, the exchange legs (N > 1), the roofline / per-kernel / "
+                         "hot_path legs, configs 4 and 5 and the CPU baselines (default: the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (loss, gradients, updated parameters) "
+                         "as float32 DIR/<name>.npy, a fixed sample of each large tensor where the whole exceeds 60 MiB")
     return ap.parse_args()
 
 
@@ -130,7 +184,8 @@ PRIME_STEPS = 2      # untimed, before the W warm-up steps: MIOpen kernel select
 
 
 def timed_steps(trainer, batch, steps, warmup, sync):
-    """W untimed warm-up steps, then exactly K timed steps between two device+rank synchronisations.
+    """W untimed warm-up steps, then exactly K timed steps between two device+rank synchronisations; returns the
+    seconds between them and the last step's loss.
     Every step is handed the next step's image batch (here: the same resident synthetic batch), so the
     frozen image encoder of step i+1 is queued on its own stream while step i's remaining work runs;
     each timed step still launches exactly one encoder forward, and the closing synchronisation waits
@@ -140,10 +195,48 @@ def timed_steps(trainer, batch, steps, warmup, sync):
         trainer.step(*batch, next_image=nxt)
     sync()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(steps):
-        trainer.step(*batch, next_image=nxt)
+        loss = trainer.step(*batch, next_image=nxt)
     sync()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, loss
+
+
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs writes at most this much (one step of the default model holds ~100 MB)
+DUMP_WHOLE = 1 << 16           # tensors of at most this many elements are always written whole
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what the timed step hands its caller, from its last step -- the loss, the gradient of every trainable
+    parameter and the parameter after the optimiser update -- as float32 <path>/<name>.npy (loss, grad.<param>,
+    param.<param>).  When the whole set exceeds DUMP_BYTES, every tensor above DUMP_WHOLE elements is written as a fixed
+    sample of its flattened entries (the same fraction for all of them): sorted positions drawn from a generator seeded by
+    the file name, so runs with the same arguments write the same positions."""
+    import zlib
+
+    import numpy as np
+    arrays = [("loss", loss.detach().reshape(1))]
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        if p.grad is not None:
+            arrays.append(("grad." + name, p.grad))
+        arrays.append(("param." + name, p))
+    n_whole = sum(t.numel() for _, t in arrays if t.numel() <= DUMP_WHOLE)
+    n_big = sum(t.numel() for _, t in arrays if t.numel() > DUMP_WHOLE)
+    frac = min(1.0, max(0, DUMP_BYTES // 4 - n_whole) / max(n_big, 1))
+    os.makedirs(path, exist_ok=True)
+    n_bytes = 0
+    for name, t in arrays:
+        x = t.detach().float().cpu()
+        if x.numel() > DUMP_WHOLE and frac < 1.0:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            x = x.reshape(-1)[torch.randperm(x.numel(), generator=g)[:int(x.numel() * frac)].sort().values]
+        np.save(os.path.join(path, name + ".npy"), x.numpy())
+        n_bytes += x.numel() * 4
+    print("bench.py: wrote %d arrays (%.1f MB%s) to %s" % (len(arrays), n_bytes / 1e6,
+                                                          ", sampled %.3f of each large tensor" % frac if frac < 1.0 else "",
+                                                          path), file=sys.stderr)
 
 
 def _lib_flag(bf16, fast=False):
@@ -868,7 +961,7 @@ def config_leg(T, args, device, model_name, opt_lvl, num_cls, steps=10, warmup=3
     batch = device_batch(T, a, 0, device)
     if args.channels_last:
         batch = (batch[0].contiguous(memory_format=torch.channels_last),) + batch[1:]
-    dt = timed_steps(trainer, batch, steps, warmup, torch.cuda.synchronize)
+    dt, _ = timed_steps(trainer, batch, steps, warmup, torch.cuda.synchronize)
     d = model.co_attention.hidden_dim
     n_grid = (args.image_size // 32) ** 2
     out = {"model": model_name, "value": round(args.batch * steps / dt, 2), "unit": "QA-pairs/s", "ms_per_step": round(dt / steps * 1e3, 3),
@@ -1001,6 +1094,7 @@ def self_launch(args) -> int:
 
 def main():
     args = parse()
+    seed_miopen_db()
     if args.gpus > 1 and "RANK" not in os.environ:       # not under torch.distributed.run: launch the ranks ourselves
         sys.exit(self_launch(args))
     if args.stock_graph:
@@ -1054,11 +1148,13 @@ def main():
             torch.distributed.barrier()
             torch.cuda.synchronize()
 
-    dt = timed_steps(trainer, batch, args.steps, args.warmup, sync)
+    dt, loss = timed_steps(trainer, batch, args.steps, args.warmup, sync)
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
     out = None
     if rank == 0:
         value = world * args.batch * args.steps / dt
@@ -1102,17 +1198,17 @@ def main():
                        "coattn_impl": "fused" if vqa_amd._lib.load().coattn_fused_supported(
                            args.batch, n_grid, args.seq_len, model.co_attention.hidden_dim, 3, 0) else "general"},
         }
-    if world == 1 and args.opt_lvl == 0 and args.precision == "exact" and not args.no_extras:
+    if args.full and world == 1 and args.opt_lvl == 0 and args.precision == "exact" and not args.no_extras:
         # side key: the same step in the opt-in tolerance mode (a shorter window; the headline above is the exact mode)
         trainer.set_precision("fast")
         f_steps = max(5, args.steps // 2)
-        dt_f = timed_steps(trainer, batch, f_steps, 2, sync)
+        dt_f, _ = timed_steps(trainer, batch, f_steps, 2, sync)
         ok = trainer.check_range()                           # (sticky range report over every one of those steps)
         trainer.set_precision("exact")
         out["value_fast16"] = {"value": round(args.batch * f_steps / dt_f, 2), "ms_per_step": round(dt_f / f_steps * 1e3, 3),
                                "steps": f_steps, "precision": "fast", "range_ok": bool(ok),
                                "note": "opt-in tolerance mode (22-bit forward / 16-bit backward products); NOT the headline"}
-    if world > 1 and trainer.reducer is not None:
+    if args.full and world > 1 and trainer.reducer is not None:
         # the exchange step, measurable: the same step under RCCL's all-reduce (the timed run above), under the
         # one-shot all-to-all / sum / all-gather pattern, and with no collective at all (compute-only: local
         # gradients, timing only) -- fewer steps each; exposed time = step time minus the compute-only step time
@@ -1125,7 +1221,7 @@ def main():
         for mode in ("direct",) + (("p2p",) if p2p else ()) + ("none",):
             try:
                 trainer.reducer.reset(mode)
-                t_m = timed_steps(trainer, batch, ex_steps, 2, sync)
+                t_m, _ = timed_steps(trainer, batch, ex_steps, 2, sync)
                 tt = torch.tensor([t_m], device=device, dtype=torch.float64)
                 torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
                 ex[mode] = float(tt) / ex_steps * 1e3
@@ -1164,7 +1260,7 @@ def main():
                 out["allreduce_buckets"] = len(trainer.reducer.buckets or [])
                 out["grad_exchange_fallback"] = trainer.reducer.fallback_reason
         vdist.shutdown()
-    if rank == 0 and not args.no_extras:
+    if args.full and rank == 0 and not args.no_extras:
         del trainer, model, batch
         torch.cuda.empty_cache()
         n_step = (args.image_size // 32) ** 2
@@ -1202,9 +1298,10 @@ def main():
                                                    backward_legs(device, fast=True)]
             if world == 1:
                 out["hot_path"] = [hot_path_leg(device, n, lay) for n in (196, 49) for lay in ("lm", "cm")]
-    if rank == 0 and world == 1 and not args.no_extras and args.model == "attention" and args.opt_lvl == 0 and not args.no_configs:
+    if (args.full and rank == 0 and world == 1 and not args.no_extras and args.model == "attention" and args.opt_lvl == 0
+            and not args.no_configs):
         # BASELINE configs 4 and 5 as compact objects on the same line (each ~10 timed steps of its own model; their full
-        # lines: `bench.py --model attention_resnet --opt-lvl 1 --num-cls 3000`, `bench.py --model attention_bert`)
+        # lines: `bench.py --full --model attention_resnet --opt-lvl 1 --num-cls 3000`, `bench.py --full --model attention_bert`)
         t_cfg = time.time()
         try:
             c4 = config_leg(T, args, device, "attention_resnet", 1, 3000)
@@ -1231,7 +1328,7 @@ def main():
             out["config5"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
         out["configs_4_5_seconds"] = round(time.time() - t_cfg, 1)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.model == "attention":   # (the oracle port has no ResNet encoder)
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == "attention":   # (the oracle port has no ResNet encoder)
             out["cpu_baseline"] = cpu_baseline_leg(args)
             out["cpu_baseline_hot_path"] = [cpu_hot_path_leg(196), cpu_hot_path_leg(49)]
         print(json.dumps(out))

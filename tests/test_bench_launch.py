@@ -27,7 +27,7 @@ def _run(args, env=None, timeout=600):
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_on_one_gpu_prints_the_scale_line():
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--no-extras", "--no-cpu-baseline"],
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--full", "--no-extras", "--no-cpu-baseline"],
              env={"VQA_BENCH_OVERSUBSCRIBE": "1", "VQA_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -16,8 +16,8 @@ R="timeout 400 rocprofv3"
 drop_traces() { find gpurun_out/refresh -name '*_trace.csv' -delete; }
 want() { { [ "$PART" = all ] && [ "$1" != 3b ]; } || [ "$PART" = "$1" ]; }
 if want 1; then
-timeout 500 python3 bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-$R --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 bench.py --no-cpu-baseline > $O/bench_stats.log 2>&1
+timeout 500 python3 bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+$R --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 bench.py --full --no-cpu-baseline > $O/bench_stats.log 2>&1
 $R --kernel-trace --stats --output-format csv -d $O/roofline -- python3 bench.py --only roofline > $O/roofline.log 2>&1
 $R --kernel-trace --stats --output-format csv -d $O/hot -- python3 bench.py --only hot > $O/hot.log 2>&1
 $R --kernel-trace --stats --output-format csv -d $O/step -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/step.log 2>&1
@@ -29,7 +29,7 @@ tail -c 300 $O/bench.json
 fi
 if want 2; then
 # config 4 (ResNet 7x7x2048 grid, reduced precision): its own bench line, and the kernels of its hot path
-timeout 400 python3 bench.py --model attention_resnet --opt-lvl 1 --num-cls 3000 --no-cpu-baseline > $O/cfg4_bench.json 2> $O/cfg4_bench.err
+timeout 400 python3 bench.py --full --model attention_resnet --opt-lvl 1 --num-cls 3000 --no-cpu-baseline > $O/cfg4_bench.json 2> $O/cfg4_bench.err
 $R --kernel-trace --stats --output-format csv -d $O/cfg4_hot -- python3 bench.py --model attention_resnet --opt-lvl 1 --num-cls 3000 --only hot > $O/cfg4_hot.log 2>&1
 # config 5 (frozen BERT-base token embeddings as the word level): its bench line on ONE GPU (the driver runs it at --gpus 4)
 timeout 300 python3 bench.py --model attention_bert --no-cpu-baseline --no-extras > $O/cfg5_bench.json 2> $O/cfg5_bench.err
