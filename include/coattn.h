@@ -142,7 +142,7 @@ int coattn_workspace_bytes(int B, int N, int T, int d, int L, int dtype, int fla
 
 /* Forward of model.py:372-395 for all L levels.
  *   Q      : host array of L device pointers.
- *   saved  : NULL for inference (nothing kept), else a buffer of `saved` bytes.
+ *   saved  : NULL for inference (nothing kept: the call is coattn_infer with no map buffers), else a buffer of `saved` bytes.
  *   v_out,q_out : [L,B,d].
  * Rows of Q_l that are all zeros -- the pad tokens of the reference's question hierarchy (model.py:263 padding_idx,
  * :292-296 pad_packed_sequence) -- project to the bias alone, and the exact mode (flags = 0) uses that: the launch that
@@ -159,6 +159,22 @@ int coattn_workspace_bytes(int B, int N, int T, int d, int L, int dtype, int fla
 int coattn_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
                    const coattn_params* p, void* v_out, void* q_out, void* saved, void* ws,
                    int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+
+/* Inference (v0.7.0): the forward of coattn_forward with no `saved`, and the attention maps handed to the caller.
+ *   av_out : [L,B,N] or NULL -- a_v, the softmax over the N image locations (model.py:387), per level;
+ *   aq_out : [L,B,T] or NULL -- a_q, the softmax over the T question tokens (model.py:388).  UNMASKED, as the reference's:
+ *            pad tokens hold weight too (their rows of Q are zeros, so they add nothing to q_out);
+ *   ws     : ws_fwd bytes of coattn_workspace_bytes (the state of the call lives there).
+ * v_out / q_out are bit-identical to those of coattn_forward with a `saved` buffer, in every mode (flags 0, COATTN_FLAG_FAST16,
+ * COATTN_FLAG_BF16_PROJ) and on both paths.  Forward only: the fused kernel forms C = tanh(Q V^T) for its own use but
+ * stores neither C nor H_q (the backward's state; zero-byte buffer resources, the stores are dropped), and the projection
+ * launch writes no image of W_q^T.  The maps are written where the kernels would write them into `saved` (the fused
+ * kernel's softmax, or the general path's score kernels), with no extra pass; with NULL maps they go to `ws`.  P_v / P_q,
+ * the row bitmap and the status words of the tolerance mode stay in `ws`: coattn_status / coattn_status_accumulate take
+ * `ws` in place of `saved` after this call.  Nothing of it can feed coattn_backward. */
+int coattn_infer(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const coattn_params* p,
+                 void* v_out, void* q_out, void* av_out, void* aq_out, void* ws, int B, int N, int T, int d, int L,
+                 int dtype, int flags, void* stream);
 
 /* Second half of coattn_forward only: everything after the projections P_v, P_q (affinity +
  * tanh model.py:377, H_v/H_q :380-384, scores + row softmax :387-388, attended reductions

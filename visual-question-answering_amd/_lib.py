@@ -19,7 +19,7 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_head_workspace_bytes", "coattn_head_forward", "coattn_head_backward", "coattn_head_status",
            "coattn_ce_status", "coattn_p2p_enable_peer", "coattn_p2p_reduce_scatter", "coattn_p2p_all_gather",
            "coattn_profile_begin", "coattn_profile_end", "coattn_features_native", "coattn_status",
-           "coattn_phrase_status", "coattn_status_accumulate", "coattn_phrase_status_accumulate")
+           "coattn_phrase_status", "coattn_status_accumulate", "coattn_phrase_status_accumulate", "coattn_infer")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -115,6 +115,8 @@ def load() -> C.CDLL:
     lib.coattn_forward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(Params),
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
     lib.coattn_attention_forward.argtypes = lib.coattn_forward.argtypes
+    lib.coattn_infer.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(Params),
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
     lib.coattn_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(Params),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                     C.POINTER(C.c_void_p), C.POINTER(ParamGrads), C.c_int,

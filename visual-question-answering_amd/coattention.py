@@ -225,3 +225,47 @@ class ParallelCoAttention(nn.Module):
                            self.W_q.bias, self.w_v.weight, self.w_v.bias, self.w_q.weight, self.w_q.bias, impl=impl)
         n = v.shape[0]
         return [v[l] for l in range(n)], [q[l] for l in range(n)]
+
+    def forward_with_attention(self, x_img: torch.Tensor, x_ques_hierarchy: Sequence[torch.Tensor]):
+        """Inference with the attention maps: (list of v_l [B,d], list of q_l [B,d], a_v [L,B,N], a_q [L,B,T]) through
+        coattn_infer -- the forward that keeps no backward state (include/coattn.h).  v / q equal `forward`'s bit for bit.
+        a_v[l, b] is the softmax over the N image locations (model.py:387), a_q[l, b] the one over the T tokens
+        (model.py:388), unmasked as the reference's: pad tokens carry weight.  Raises if a gradient would be needed."""
+        ques = list(x_ques_hierarchy)
+        params = (self.W_v.weight, self.W_v.bias, self.W_q.weight, self.W_q.bias, self.w_v.weight, self.w_v.bias,
+                  self.w_q.weight, self.w_q.bias)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (x_img, *ques, *params)):
+            raise RuntimeError("forward_with_attention is forward only: run it under torch.no_grad() (the maps come from "
+                               "the inference path, which keeps no state for a backward)")
+        if not x_img.is_cuda:
+            raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
+        impl = _impl_flag() | (_lib.FLAG_BF16_PROJ if self.bf16_projections else 0) | _lib.precision_flag(self.fast_products)
+        V = native_features(x_img)
+        if V.dtype != torch.float32 or any(q.dtype != torch.float32 for q in ques):
+            raise RuntimeError("ParallelCoAttention (HIP) computes in fp32; got %s" % V.dtype)
+        lib = _lib.load()
+        L = len(ques)
+        B, N, d = V.shape
+        T = ques[0].shape[1]
+        for q in ques:
+            if tuple(q.shape) != (B, T, d):
+                raise RuntimeError("question features must all be [B,T,d] = %s, got %s" % ((B, T, d), tuple(q.shape)))
+        Qs = [q.contiguous() for q in ques]
+        ps = [t.detach().contiguous() for t in params]
+        _, fb, _ = _lib.workspace_bytes(B, N, T, d, L, impl)
+        dev = V.device
+        out_v = torch.empty((L, B, d), device=dev, dtype=torch.float32)
+        out_q = torch.empty((L, B, d), device=dev, dtype=torch.float32)
+        a_v = torch.empty((L, B, N), device=dev, dtype=torch.float32)
+        a_q = torch.empty((L, B, T), device=dev, dtype=torch.float32)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws = _lib.scratch(fb, dev, stream)
+        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
+        p = _lib.Params(*[t.data_ptr() for t in ps])
+        with _lib.on_device(dev):
+            _lib.check(lib.coattn_infer(_ptr(V), *_strides(V), qptr, C.byref(p), _ptr(out_v), _ptr(out_q), _ptr(a_v),
+                                        _ptr(a_q), _ptr(ws), B, N, T, d, L, _lib.F32, impl, C.c_void_p(stream)),
+                       "coattn_infer")
+        if impl & _lib.FLAG_FAST16:                   # tolerance mode: the status words are in the workspace
+            _lib.note_status("coattn", ws, (B, N, T, d, L), dev)
+        return [out_v[l] for l in range(L)], [out_q[l] for l in range(L)], a_v, a_q

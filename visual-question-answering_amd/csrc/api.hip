@@ -16,7 +16,7 @@ void coattn_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int coattn_version(void) { return 601; }   // 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
+extern "C" int coattn_version(void) { return 700; }   // 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
 
 // ---------------------------------------------------------------------------------------
 // per-kernel timing (bench.py's backward roofline legs): HIP events recorded between the launches of the calls made
@@ -509,8 +509,9 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
 }
 
 // everything after the projections: affinity, H_v / H_q, scores, softmax, attended reductions
+// av_out / aq_out: the caller's map buffers [L][B][N] / [L][B][T] (coattn_infer), else NULL: the maps go to `sv`
 int general_attention(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, float* v_out,
-                      float* q_out, float* sv, float* Hv) {
+                      float* q_out, float* sv, float* Hv, float* av_out = nullptr, float* aq_out = nullptr) {
   const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
   float* Pv = sv + sp.Pv;
   const size_t BTd = (size_t)c.B * c.T * c.d, BTN = (size_t)c.B * c.T * c.N;
@@ -518,8 +519,8 @@ int general_attention(const Ctx& c, const float* V, const float* const* Q, const
     float* Pq = sv + sp.Pq + l * BTd;
     float* C = sv + sp.C + l * BTN;
     float* Hq = sv + sp.Hq + l * BTd;
-    float* av = sv + sp.av + (size_t)l * c.B * c.N;
-    float* aq = sv + sp.aq + (size_t)l * c.B * c.T;
+    float* av = (av_out ? av_out : sv + sp.av) + (size_t)l * c.B * c.N;
+    float* aq = (aq_out ? aq_out : sv + sp.aq) + (size_t)l * c.B * c.T;
     CA_TRY(affinity(c, Q[l], V, C));
     CA_TRY(ct_times(c, C, Pq, Pv, Hv, 1));
     CA_TRY(c_times(c, C, Pv, Pq, Hq, 1));
@@ -704,9 +705,11 @@ static int check_vlayout(const VLayout& v, int B, int N, int d, const char* what
   return 0;
 }
 
+// saved == NULL: forward only -- the state lives in the workspace, and the fused kernel stores no C / H_q (nothing reads
+// them); av_out / aq_out (may be NULL): the attention maps go straight to the caller's buffers
 static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, const coattn_params* p, void* v_out,
                         void* q_out, void* saved, void* ws, int B, int N, int T, int d, int L, int dtype, int flags,
-                        void* stream, bool do_proj, bool do_attn) {
+                        void* stream, bool do_proj, bool do_attn, void* av_out = nullptr, void* aq_out = nullptr) {
   CA_TRY(check_shape(B, N, T, d, L, dtype));
   CA_CHECK_ARG(V && Q && p && v_out && q_out && ws, "forward: null argument");
   CA_TRY(check_vlayout(vl, B, N, d, "forward: V"));
@@ -731,8 +734,10 @@ static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, 
   if (!do_attn) return 0;
   if (fused)
     return fused_attention_forward(B, N, T, d, L, (const float*)V, vl, (const float* const*)Q, p, (float*)v_out,
-                                   (float*)q_out, sv, tail, c.s, c.bf16_proj ? 1 : 0, np_fwd(flags, c.f16_proj));
-  return general_attention(c, (const float*)V, (const float* const*)Q, p, (float*)v_out, (float*)q_out, sv, tail);
+                                   (float*)q_out, sv, tail, c.s, c.bf16_proj ? 1 : 0, np_fwd(flags, c.f16_proj),
+                                   (float*)av_out, (float*)aq_out, saved != nullptr ? 1 : 0);
+  return general_attention(c, (const float*)V, (const float* const*)Q, p, (float*)v_out, (float*)q_out, sv, tail,
+                           (float*)av_out, (float*)aq_out);
 }
 
 extern "C" int coattn_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -740,6 +745,13 @@ extern "C" int coattn_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t
                               int T, int d, int L, int dtype, int flags, void* stream) {
   return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
                       dtype, flags, stream, true, true);
+}
+
+extern "C" int coattn_infer(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                            const coattn_params* p, void* v_out, void* q_out, void* av_out, void* aq_out, void* ws, int B,
+                            int N, int T, int d, int L, int dtype, int flags, void* stream) {
+  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, nullptr, ws, B, N, T, d, L,
+                      dtype, flags, stream, true, true, av_out, aq_out);
 }
 
 extern "C" int coattn_attention_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,

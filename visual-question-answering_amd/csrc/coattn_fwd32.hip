@@ -431,8 +431,9 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
   // image [piece][n][t] (8-byte writes).  All the slot reads come first: slot 1 lies inside the image region.
   {
     // C of this (sample, level) as a buffer: rows t >= T fall outside it (stores dropped), and a lane of a padded
-    // column n >= N is sent outside it through its offset -- no branches around the stores
-    const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(a.C + pair * (size_t)T * N, (unsigned)T * N * 4u);
+    // column n >= N is sent outside it through its offset -- no branches around the stores.  Forward only (a.keep = 0):
+    // a zero-byte buffer, every store dropped; the LDS image below is formed all the same (phase 2 reads it)
+    const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(a.C + pair * (size_t)T * N, a.keep ? (unsigned)T * N * 4u : 0u);
     constexpr int PER = 8 * NPAD / (NW * 64);        // (location, token quad) items per thread (exact: NPAD = 32 NT)
     static_assert(8 * NPAD % (NW * 64) == 0, "the image pass covers the slot in whole sweeps");
     f32x4 sum[PER];
@@ -458,7 +459,7 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
       for (int i = 0; i < 4; ++i) {
         const float th = tanh_fast(sum[k][i]);
         c[i] = in ? th : 0.f;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, th), rs_c, cvoff, i * N * 4, 0);
+        if constexpr (!COATTN_KO_BWD_STORES) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, th), rs_c, cvoff, i * N * 4, 0);
       }
       unsigned hh[2] = {0, 0}, mm[2] = {0, 0}, ll[2] = {0, 0};
       split_pair_x<NP, HF>(c[0], c[1], hh[0], mm[0], ll[0]);
@@ -661,9 +662,9 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
       store_scores(U - 1, (U & 2) ? finish_last(ring[1]) : finish_last(ring[3]));
       CA_STAMP(9 + 3 * pi);
       // H_q epilogue: hq = tanh(acc) (the accumulators started from P_q); saved for backward; s_q partials.  Branch-free: rows t >= T fall
-      // outside the per-sample buffers (loads give 0, stores are dropped)
+      // outside the per-sample buffers (loads give 0, stores are dropped); forward only (a.keep = 0): a zero-byte buffer
       {
-        const __amdgpu_buffer_rsrc_t rs_hq = make_rsrc(a.Hq + pair * (size_t)T * d, (unsigned)T * d * 4u);
+        const __amdgpu_buffer_rsrc_t rs_hq = make_rsrc(a.Hq + pair * (size_t)T * d, a.keep ? (unsigned)T * d * 4u : 0u);
         // the row offsets are recomputed here in every pass: hoisted out of the pass loop they would be 16 registers
         // that live (spilled) across the unit pipeline
         int hrow = (4 * h * d + r) * 4;
@@ -676,7 +677,8 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
             const float hq = tanh_scaled(accq[ct][g]);          // P_q, P_v carry the factor 2 log2(e) (fused.h: kPScale)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hq), rs_hq, eoff(g, ct), c0 * 4, 0);
+            if constexpr (!COATTN_KO_BWD_STORES)
+              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hq), rs_hq, eoff(g, ct), c0 * 4, 0);
             part[g] = ct ? fmaf(hq, wq, part[g]) : hq * wq;
           }
         }

@@ -15,9 +15,11 @@ inline bool v_is_cm(const VLayout& v, int N, int d) { (void)d; return v.sN == 1 
 int fused_supported(int B, int N, int T, int d, int L);
 inline bool fused_layout_ok(const VLayout& v, int N, int d) { return v_is_lm(v, N, d) || v_is_cm(v, N, d); }
 // everything after the projections (P_v, P_q already in `saved`)
+// av / aq: where a_v [L][B][N] / a_q [L][B][T] go (NULL: into `saved`); keep = 0: forward only, no C / H_q stored
 int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl,
                             const float* const* Q, const coattn_params* p, float* v_out, float* q_out, float* saved,
-                            float* ws, hipStream_t s, int bf16 = 0, int np = 3);   // bf16: reduced precision, one MFMA per product; np: width of phase 2
+                            float* ws, hipStream_t s, int bf16 = 0, int np = 3,   // bf16: reduced precision, one MFMA per product; np: width of phase 2
+                            float* av = nullptr, float* aq = nullptr, int keep = 1);
 int fused_backward_supported(int B, int N, int T, int d, int L);
 int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl, const float* const* Q,
                    const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
@@ -26,6 +28,12 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
 
 // Diagnostic build only (tools/probe_stamps.py, -DCOATTN_STAMPS=1): wave 0 of every workgroup writes the
 // 100 MHz constant clock at its phase boundaries into the (otherwise unused) forward workspace tail.
+// Knock-out build only (tools/build_variant.sh ko coattn_fwd32 -DCOATTN_KO_BWD_STORES=1): the forward kernel's C and H_q
+// store instructions compiled out -- the bound on what a template flag could save over coattn_infer's zero-byte buffers.
+// Its C / H_q are garbage: not a library to train with.
+#ifndef COATTN_KO_BWD_STORES
+#define COATTN_KO_BWD_STORES 0
+#endif
 #ifndef COATTN_STAMPS
 #define COATTN_STAMPS 0
 #endif
@@ -430,6 +438,8 @@ struct FwdArgs {
   int B, N, T, d, L;
   int bf16;              // reduced-precision mode: operands rounded to bf16, one MFMA per product (d % 512 == 0)
   int np;                // (bf16 = 0) width of the phase-2 contractions C^T P_q, C P_v: 3 or 2 pieces (the affinity: always 3)
+  int keep;              // 1: C and H_q are stored for the backward; 0 (forward only, coattn_infer): their buffer resources are
+                         // zero bytes long, so every store to them is dropped in hardware (same code, no new instantiation)
 };
 
 // arguments of the two big fused backward kernels (coattn_fused_bwd.hip, coattn_bwd32.hip)

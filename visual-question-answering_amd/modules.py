@@ -346,6 +346,19 @@ class HierarchicalCoAttentionNet(nn.Module):
             return self.mlp_classify.forward_loss(x_img_attn, x_ques_attn, labels)
         return self.mlp_classify(x_img_attn, x_ques_attn)
 
+    def forward_with_attention(self, x_img, x_ques, x_ques_lens):
+        """Inference with the co-attention maps: (logits [B,K], a_v [3,B,N], a_q [3,B,T]) for the word, phrase and sentence
+        levels.  Index n of a_v is location n of the encoder's flattened grid (model.py:215-217: row-major over 7 x 7 at
+        224 px, 14 x 14 at 448 px); a_q is unmasked over the T token positions (model.py:388).  The logits equal
+        `forward`'s under no_grad bit for bit.  Forward only: raises where a gradient would be needed."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("forward_with_attention is forward only: run it under torch.no_grad()")
+        x_img_features = self.image_encoder(x_img)
+        x_ques_features = [q if q.dtype == torch.float32 else q.float()       # (the fp32 island, as _CoAttentionFn's cast)
+                           for q in self.question_encoder(x_ques, x_ques_lens)]
+        v, q, a_v, a_q = self.co_attention.forward_with_attention(x_img_features, x_ques_features)
+        return self.mlp_classify(v, q), a_v, a_q
+
     def _graphed(self, x_img_features, x_ques_features, labels):
         """co-attention + answer head + loss, forward AND backward, as one autograd node over static buffers (graph.py),
         built per (B, N, T) on first use: replayed from captured HIP graphs (``net.hot_path_graph = True``,

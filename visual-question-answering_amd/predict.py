@@ -1,0 +1,152 @@
+"""Inference of a trained checkpoint over a question set, with the co-attention maps: what the reference leaves as
+``--mode test`` (main.py:285-287, ``raise NotImplementedError``) and the "Inference & Attention Visualization" line of its
+README roadmap.  Same command line as ``train.py`` (the reference's flags) plus the outputs:
+
+    python -m vqa_amd.predict --model attention --model_ckpt model.pth --test_size 1000 \\
+        --predictions preds.jsonl --attention_maps maps.npz
+
+* ``--predictions`` (JSONL): one record per sample in dataset order, ``{index, label, top, prob}`` -- the ``--topk``
+  answer indices and their softmax probabilities, best first (index 0 is UNKNOWN, main.py:155).
+* ``--attention_maps`` (``.npz``, ``attention*`` models only): ``a_v [S,3,H,W]`` -- the image attention of the word,
+  phrase and sentence levels over the encoder's H x W grid (7 x 7 at 224 px, 14 x 14 at 448 px; model.py:215-217
+  flattens it row-major) --, ``a_q [S,3,T]`` -- the question attention over the T token positions, UNMASKED as the
+  reference's softmax (model.py:388): positions past ``ques_len`` carry weight too --, ``ques_len [S]`` and ``index [S]``.
+* stdout: one JSON line ``{samples, accuracy, top{K}_accuracy, loss, pairs_per_s}`` (accuracies in percent, as
+  ``Trainer.validate``; loss = mean cross entropy per sample).
+
+The maps come from the forward-only co-attention (``coattn_infer``): no state for a backward is written.  One process:
+multi-GPU prediction is not offered.  Data: the synthetic test split (its own seed), every sample (no drop_last).
+"""
+from __future__ import annotations
+
+import json
+import math
+import os
+import time
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+import torch.utils.data
+
+from . import train as T
+
+TEST_SEED = 555555
+
+
+def build_parser():
+    ap = T.build_parser()
+    ap.description = "Visual Question Answering: predictions and attention maps of a trained checkpoint"
+    ap.add_argument("--predictions", type=str, default=None, help="write one JSON record per sample here (JSONL)")
+    ap.add_argument("--topk", type=int, default=5, help="answers per record, best first")
+    ap.add_argument("--attention_maps", type=str, default=None,
+                    help="write the co-attention maps here (.npz; attention* models only)")
+    ap.add_argument("--test_size", type=int, default=1000, help="test samples (synthetic)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if not args.model_ckpt:
+        ap.error("--model_ckpt is required: prediction runs a trained checkpoint (train.py --save_path / model_{step}.pth)")
+    if args.attention_maps and not args.model.startswith("attention"):
+        ap.error("--attention_maps needs a co-attention model (--model attention*); %r has no attention maps" % args.model)
+    if args.topk < 1 or args.test_size < 1:
+        ap.error("--topk and --test_size must be >= 1")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("prediction runs in one process (WORLD_SIZE=%s): multi-GPU prediction is not offered"
+                 % os.environ["WORLD_SIZE"])
+    if not args.synthetic:
+        raise SystemExit("only --synthetic true is available: the VQA dataset is not present in this environment")
+
+    if torch.cuda.is_available():
+        device = torch.device("cuda", args.gpu_id)
+        torch.cuda.set_device(device)
+        torch.set_num_threads(max(1, min(4, T.usable_cpus())))
+    else:
+        device = torch.device("cpu")
+    torch.manual_seed(0)
+    model, cfg = T.model_from_args(args)
+    model.load_state_dict(torch.load(T.checkpoint_path(args), map_location="cpu"))
+    model.to(device)
+    cl = args.channels_last and device.type == "cuda" and args.model.startswith("attention")
+    if cl:
+        model.image_encoder.to(memory_format=torch.channels_last)
+    T.set_products(model, args.precision)                       # the settings Trainer applies for --precision / --opt_lvl
+    T.set_reduced_precision(model, args.opt_lvl)
+    criterion = T.CrossEntropyLoss()
+    size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
+    n_cls = args.num_cls + 1
+    k = min(args.topk, n_cls)
+    ds = T.SyntheticVQADataset(args.test_size, size, args.max_seq_length, args.vocab_size, n_cls, TEST_SEED)
+    loader = torch.utils.data.DataLoader(ds, args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
+    maps = bool(args.attention_maps)
+
+    S = len(ds)
+    top = torch.zeros((S, k), dtype=torch.int64)
+    prob = torch.zeros((S, k), dtype=torch.float32)
+    labels = torch.zeros(S, dtype=torch.int64)
+    lens = torch.zeros(S, dtype=torch.int64)
+    a_v = a_q = None
+    loss_sum = 0.0
+    model.eval()
+    t0 = time.time()
+    start = 0
+    with torch.no_grad():
+        for b in loader:
+            n = b["label"].numel()
+            index = torch.arange(start, start + n)
+            start += n
+            # sorted by question length for packing (main.py:196-202); the index rides along as a second label column
+            image, question, il, ques_len = T.sort_batch(b["image"], b["question"], torch.stack([index, b["label"]], 1),
+                                                         b["ques_len"])
+            idx, label = il[:, 0], il[:, 1]
+            image = image.to(device)
+            if cl:
+                image = image.contiguous(memory_format=torch.channels_last)
+            question, label_d = question.to(device), label.to(device)
+            with T.autocast_for(args.opt_lvl, device):
+                if maps:
+                    logits, av, aq = model.forward_with_attention(image, question, ques_len)
+                else:
+                    logits = model(image, question, ques_len)
+            loss_sum += float(criterion(logits.float(), label_d)) * n
+            pv, pi = F.softmax(logits.float(), dim=1).topk(k, dim=1)
+            top[idx], prob[idx], labels[idx], lens[idx] = pi.cpu(), pv.cpu(), label, ques_len
+            if maps:
+                if a_v is None:
+                    a_v = torch.zeros((S,) + tuple(av.shape[:1]) + tuple(av.shape[2:]), dtype=torch.float32)
+                    a_q = torch.zeros((S,) + tuple(aq.shape[:1]) + tuple(aq.shape[2:]), dtype=torch.float32)
+                a_v[idx] = av.permute(1, 0, 2).float().cpu()
+                a_q[idx] = aq.permute(1, 0, 2).float().cpu()
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+        if args.precision == "fast" and args.opt_lvl == 0:
+            from . import _lib
+            _lib.check_range()                   # raises if an operand of the tolerance mode left the FP16-piece range
+    elapsed = time.time() - t0
+
+    hit1 = top[:, 0] == labels
+    hitk = (top == labels[:, None]).any(dim=1)
+    if args.predictions:
+        with open(args.predictions, "w") as fh:
+            for i in range(S):
+                fh.write(json.dumps({"index": i, "label": int(labels[i]), "top": top[i].tolist(),
+                                     "prob": [float(x) for x in prob[i]]}) + "\n")
+    if maps:
+        N = a_v.shape[-1]
+        H = int(round(math.sqrt(N)))
+        if H * H != N:
+            raise RuntimeError("the image grid of %d locations is not square" % N)
+        np.savez(args.attention_maps, a_v=a_v.view(S, a_v.shape[1], H, H).numpy(), a_q=a_q.numpy(),
+                 ques_len=lens.numpy(), index=np.arange(S))
+    summary = {"samples": S, "accuracy": round(100.0 * float(hit1.float().mean()), 4),
+               "top%d_accuracy" % k: round(100.0 * float(hitk.float().mean()), 4),
+               "loss": round(loss_sum / S, 6), "pairs_per_s": round(S / max(elapsed, 1e-9), 2)}
+    print(json.dumps(summary))
+    return summary
+
+
+if __name__ == "__main__":
+    main()

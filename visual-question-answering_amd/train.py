@@ -104,6 +104,55 @@ def build_model(model_name: str, vocab_size: int, num_cls: int, **kw) -> nn.Modu
     return cfg["model"](cfg["question_params"], cfg["image_params"], K=num_cls + 1)
 
 
+def model_from_args(args):
+    """The model of a parsed command line, as main.py:388 builds it: (model, registry entry).  attention_bert: the token ids
+    are BERT's, so args.vocab_size becomes BERT's vocabulary.  (train.main, predict.main)"""
+    cfg = setup_model_configs(args, args.vocab_size)             # (as main.py:388)
+    args.vocab_size = cfg.get("vocab_size", args.vocab_size)
+    model = cfg["model"](cfg["question_params"], cfg["image_params"], K=args.num_cls + 1)
+    return model, cfg
+
+
+def log_dir_of(args):
+    """expt_dir/expt_name/run_name (main.py:110-114), or None without --expt_dir."""
+    return os.path.join(args.expt_dir, args.expt_name, args.run_name) if args.expt_dir else None
+
+
+def checkpoint_path(args):
+    """--model_ckpt as a path: a relative name that exists inside the log directory is taken from there (main.py:169)."""
+    ckpt = args.model_ckpt
+    log_dir = log_dir_of(args)
+    if ckpt and log_dir and not os.path.isabs(ckpt) and os.path.exists(os.path.join(log_dir, ckpt)):
+        ckpt = os.path.join(log_dir, ckpt)
+    return ckpt
+
+
+def set_products(model: nn.Module, precision: str) -> None:
+    """Width of the HIP path's fp32 products on every module that has the switch: "fast" = the tolerance mode."""
+    fast = precision == "fast"
+    co = getattr(model, "co_attention", None)
+    if co is not None and hasattr(co, "fast_products"):
+        co.fast_products = fast
+    for m in model.modules():
+        if m is not co and hasattr(m, "fast_products"):
+            m.fast_products = fast
+
+
+def set_reduced_precision(model: nn.Module, opt_lvl: int) -> None:
+    """--opt_lvl >= 1 (AMP): the co-attention projections and the answer head on the bf16 MFMA as well."""
+    if opt_lvl > 0 and hasattr(model, "co_attention"):
+        model.co_attention.bf16_projections = True
+        if hasattr(getattr(model, "mlp_classify", None), "bf16_products"):
+            model.mlp_classify.bf16_products = True
+
+
+def autocast_for(opt_lvl: int, device):
+    """bf16 autocast around the stock encoders for --opt_lvl >= 1 on the GPU, else nothing."""
+    if opt_lvl > 0 and device.type == "cuda":
+        return torch.autocast("cuda", dtype=torch.bfloat16)
+    return contextlib.nullcontext()
+
+
 def sort_batch(images, questions, answers, ques_seq_lens):
     """Descending by question length, as packing requires (utils.py:33-45)."""
     ques_seq_lens, order = ques_seq_lens.sort(dim=0, descending=True)
@@ -253,10 +302,7 @@ class Trainer:
         self.criterion = CrossEntropyLoss()      # nn.CrossEntropyLoss() semantics (main.py:94); fused HIP kernel on CUDA
         self.optimizer = torch.optim.Adam(model.parameters(), lr)
         self.opt_lvl = opt_lvl
-        if opt_lvl > 0 and hasattr(model, "co_attention"):      # AMP: projections on the bf16 MFMA as well
-            model.co_attention.bf16_projections = True
-            if hasattr(getattr(model, "mlp_classify", None), "bf16_products"):
-                model.mlp_classify.bf16_products = True
+        set_reduced_precision(model, opt_lvl)                    # AMP: projections on the bf16 MFMA as well
         # graph=True: co-attention + answer head + loss, forward and backward, replayed from one captured HIP graph
         # (graph.py): one host call instead of ~25 launches; same values bit for bit
         if graph and hasattr(model, "hot_path_graph") and self.device.type == "cuda":
@@ -281,9 +327,7 @@ class Trainer:
         self._resident = None                                    # last image batch consumed on the device
 
     def _autocast(self):
-        if self.opt_lvl > 0 and self.device.type == "cuda":
-            return torch.autocast("cuda", dtype=torch.bfloat16)
-        return contextlib.nullcontext()
+        return autocast_for(self.opt_lvl, self.device)
 
     def _queue_encoder(self, image, ready=None):
         """Queue the frozen image encoder for `image` on the encoder stream; returns (image, features,
@@ -349,13 +393,7 @@ class Trainer:
 
     def set_precision(self, precision: str) -> None:
         self.precision = precision
-        fast = precision == "fast"
-        co = getattr(self.model, "co_attention", None)
-        if co is not None and hasattr(co, "fast_products"):
-            co.fast_products = fast
-        for m in self.model.modules():
-            if m is not co and hasattr(m, "fast_products"):
-                m.fast_products = fast
+        set_products(self.model, precision)
 
     def check_range(self) -> bool:
         """Tolerance mode only: True if every operand of EVERY forward since the last check lay inside the FP16-piece range
@@ -509,18 +547,13 @@ def main(argv=None):
         # one thread per logical CPU oversubscribes a containerised rank (measured: 39.7 vs 26.3 ms/step)
         torch.set_num_threads(max(1, min(4, usable_cpus())))
     torch.manual_seed(0)                                        # identical weights on every rank
-    cfg = setup_model_configs(args, args.vocab_size)             # (as main.py:388)
-    args.vocab_size = cfg.get("vocab_size", args.vocab_size)     # attention_bert: token ids are BERT's
-    model = cfg["model"](cfg["question_params"], cfg["image_params"], K=args.num_cls + 1)
+    model, cfg = model_from_args(args)
     # log directory expt_dir/expt_name/run_name (main.py:110-114): checkpoints model_{step}.pth live there (main.py:260-263)
-    log_dir = os.path.join(args.expt_dir, args.expt_name, args.run_name) if args.expt_dir else None
+    log_dir = log_dir_of(args)
     if log_dir and rank == 0:
         os.makedirs(log_dir, exist_ok=True)
     if args.model_ckpt:
-        ckpt = args.model_ckpt
-        if log_dir and not os.path.isabs(ckpt) and os.path.exists(os.path.join(log_dir, ckpt)):
-            ckpt = os.path.join(log_dir, ckpt)                   # (main.py:169)
-        model.load_state_dict(torch.load(ckpt, map_location="cpu"))
+        model.load_state_dict(torch.load(checkpoint_path(args), map_location="cpu"))
     model.to(device)
     cl = args.channels_last and device.type == "cuda" and args.model.startswith("attention")
     if cl:
