@@ -163,7 +163,8 @@ int coattn_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, cons
 /* Inference (v0.7.0): the forward of coattn_forward with no `saved`, and the attention maps handed to the caller.
  *   av_out : [L,B,N] or NULL -- a_v, the softmax over the N image locations (model.py:387), per level;
  *   aq_out : [L,B,T] or NULL -- a_q, the softmax over the T question tokens (model.py:388).  UNMASKED, as the reference's:
- *            pad tokens hold weight too (their rows of Q are zeros, so they add nothing to q_out);
+ *            pad tokens hold weight too (their rows of Q are zeros, so they add nothing to q_out); coattn_infer_len (below)
+ *            restricts it to the first len_b tokens;
  *   ws     : ws_fwd bytes of coattn_workspace_bytes (the state of the call lives there).
  * v_out / q_out are bit-identical to those of coattn_forward with a `saved` buffer, in every mode (flags 0, COATTN_FLAG_FAST16,
  * COATTN_FLAG_BF16_PROJ) and on both paths.  Forward only: the fused kernel forms C = tanh(Q V^T) for its own use but
@@ -184,6 +185,37 @@ int coattn_infer(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const 
 int coattn_attention_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
                              const coattn_params* p, void* v_out, void* q_out, void* saved, void* ws,
                              int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+
+/* ---- length-masked question attention (v0.8.0) ----------------------------------------------------------------
+ * The forms above keep the reference's UNMASKED softmax over the T question positions (model.py:388): pad tokens take weight
+ * in a_q.  The *_len forms take one more argument,
+ *   q_len : DEVICE int32 [B], the length len_b of question b, shared by all L levels; NULL = unmasked (the call is then the
+ *           one above, bit for bit).  Values outside [1, T] are CLAMPED into it on the device (0 acts as 1, T + 5 as T): the
+ *           host cannot check device values without a synchronisation.
+ * and compute, for every sample b, the reference's unmasked computation on Q_l[b, :len_b] alone (T = len_b):
+ *   - a_q[l,b,t] = 0 exactly for t >= len_b, the softmax runs over t < len_b (q_out = sum_{t < len_b} a_q Q);
+ *   - rows t >= len_b of C = tanh(Q V^T) are taken as ZERO (selected, not multiplied) in H_v = tanh(P_v + C^T P_q) and
+ *     H_q = tanh(P_q + C P_v);
+ *   - backward: dQ[l,b,t,:] = 0 for t >= len_b, and those rows contribute nothing to dV or to any parameter gradient.
+ * The rows past len_b are not read for their values: outputs and gradients are the same whether they hold zeros or other
+ * finite values (in the tolerance mode, values inside its operand range -- the projection launch still converts them).  In the
+ * exact mode the bitmap of live question rows counts a row only if it is non-zero AND t < len_b.
+ * coattn_backward_len MUST receive the same q_len (same values) as the coattn_forward_len that filled `saved`: nothing in
+ * `saved` records it.  Same buffers, sizes (coattn_workspace_bytes), paths and modes as the unmasked forms. */
+int coattn_forward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const int32_t* q_len,
+                       const coattn_params* p, void* v_out, void* q_out, void* saved, void* ws,
+                       int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+int coattn_infer_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const int32_t* q_len,
+                     const coattn_params* p, void* v_out, void* q_out, void* av_out, void* aq_out, void* ws, int B, int N,
+                     int T, int d, int L, int dtype, int flags, void* stream);
+int coattn_attention_forward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                 const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* saved,
+                                 void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+int coattn_backward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const int32_t* q_len,
+                        const coattn_params* p, const void* saved, const void* gv, const void* gq,
+                        void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                        const coattn_param_grads* pg, int accumulate,
+                        void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
 
 /* Backward (autograd of model.py:372-392).
  *   gv,gq : [L,B,d] upstream gradients of v_out,q_out.

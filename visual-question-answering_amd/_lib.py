@@ -19,7 +19,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_head_workspace_bytes", "coattn_head_forward", "coattn_head_backward", "coattn_head_status",
            "coattn_ce_status", "coattn_p2p_enable_peer", "coattn_p2p_reduce_scatter", "coattn_p2p_all_gather",
            "coattn_profile_begin", "coattn_profile_end", "coattn_features_native", "coattn_status",
-           "coattn_phrase_status", "coattn_status_accumulate", "coattn_phrase_status_accumulate", "coattn_infer")
+           "coattn_phrase_status", "coattn_status_accumulate", "coattn_phrase_status_accumulate", "coattn_infer",
+           "coattn_forward_len", "coattn_infer_len", "coattn_attention_forward_len", "coattn_backward_len")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -121,6 +122,13 @@ def load() -> C.CDLL:
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                     C.POINTER(C.c_void_p), C.POINTER(ParamGrads), C.c_int,
                                     C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
+    # the length-masked forms: one more argument after Q, the device int32 [B] lengths (NULL = unmasked)
+    def _with_len(argtypes):
+        return argtypes[:5] + [C.c_void_p] + argtypes[5:]
+    lib.coattn_forward_len.argtypes = _with_len(lib.coattn_forward.argtypes)
+    lib.coattn_attention_forward_len.argtypes = _with_len(lib.coattn_attention_forward.argtypes)
+    lib.coattn_infer_len.argtypes = _with_len(lib.coattn_infer.argtypes)
+    lib.coattn_backward_len.argtypes = _with_len(lib.coattn_backward.argtypes)
     lib.coattn_gemm_f32.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
     lib.coattn_gemm_bf16.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
     lib.coattn_phrase_workspace_bytes.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_size_t)] * 3

@@ -3,6 +3,8 @@
 Same constructor, attribute names (=> identical ``state_dict`` keys ``W_b, W_v, W_q, w_v, w_q``)
 and ``forward(x_img, x_ques_hierarchy)`` signature as the reference class; the computation runs
 in the HIP library through the C-ABI of ``include/coattn.h`` on the caller's current stream.
+Opt-in beyond the reference: ``question_mask=True`` restricts the question-side attention to the
+first ``x_ques_lens[b]`` tokens of every question (the C-ABI's ``*_len`` entry points).
 """
 from __future__ import annotations
 
@@ -96,6 +98,21 @@ def native_features(x_img: torch.Tensor, out: torch.Tensor = None) -> torch.Tens
     return out
 
 
+def question_lengths(x_ques_lens, B: int, device) -> torch.Tensor:
+    """The question lengths as the *_len entry points read them: a contiguous int32 [B] tensor on `device`.  A device
+    tensor is converted there (no host synchronisation); host lengths (a list, a CPU tensor -- what the question encoder's
+    pack_padded_sequence takes) are copied up asynchronously.  Values are not checked here (that would synchronise): the
+    kernels clamp them into [1, T]."""
+    if x_ques_lens is None:
+        raise ValueError("question_mask=True needs the question lengths (x_ques_lens)")
+    t = x_ques_lens if torch.is_tensor(x_ques_lens) else torch.as_tensor(x_ques_lens)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError("question lengths must be integers, got %s" % t.dtype)
+    if tuple(t.shape) != (B,):
+        raise ValueError("question lengths must have shape [B] = [%d], got %s" % (B, tuple(t.shape)))
+    return t.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
+
+
 def _strides(x: torch.Tensor):
     """Element strides of x[B,N,d] for the C-ABI.  The stride torch reports for a size-1 dimension is arbitrary (and
     ``.contiguous()`` keeps it): such dimensions get the stride a contiguous [B,N,d] tensor would have."""
@@ -111,11 +128,12 @@ def _strides(x: torch.Tensor):
 
 
 class _CoAttentionFn(torch.autograd.Function):
-    """forward -> coattn_forward, backward -> coattn_backward (autograd of model.py:372-392)."""
+    """forward -> coattn_forward, backward -> coattn_backward (autograd of model.py:372-392); with question lengths
+    (int32 [B] on the device) coattn_forward_len / coattn_backward_len, both given the same lengths."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
-    def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, *x_ques):
+    def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques):
         if not x_img.is_cuda:
             raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
         if x_img.dtype != torch.float32 or any(q.dtype != torch.float32 for q in x_ques):
@@ -141,14 +159,21 @@ class _CoAttentionFn(torch.autograd.Function):
         qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
         p = _lib.Params(*[t.data_ptr() for t in params])
         with _lib.on_device(dev):
-            _lib.check(lib.coattn_forward(_ptr(V), *_strides(V), qptr, C.byref(p), _ptr(out_v), _ptr(out_q), _ptr(saved),
-                                          _ptr(ws), B, N, T, d, L, _lib.F32, impl, C.c_void_p(stream)),
-                       "coattn_forward")
+            if q_len is None:
+                _lib.check(lib.coattn_forward(_ptr(V), *_strides(V), qptr, C.byref(p), _ptr(out_v), _ptr(out_q), _ptr(saved),
+                                              _ptr(ws), B, N, T, d, L, _lib.F32, impl, C.c_void_p(stream)),
+                           "coattn_forward")
+            else:
+                _lib.check(lib.coattn_forward_len(_ptr(V), *_strides(V), qptr, _ptr(q_len), C.byref(p), _ptr(out_v),
+                                                  _ptr(out_q), _ptr(saved), _ptr(ws), B, N, T, d, L, _lib.F32, impl,
+                                                  C.c_void_p(stream)),
+                           "coattn_forward_len")
         if impl & _lib.FLAG_FAST16:                   # tolerance mode: where _lib.check_range() finds this call's status words
             _lib.note_status("coattn", saved if saved is not None else ws, (B, N, T, d, L), dev)
         if need_grad:
             ctx.save_for_backward(V, saved, *params, *Qs)
             ctx.dims = (B, N, T, d, L, impl)
+            ctx.q_len = q_len                         # (the backward must see the forward's lengths)
         return out_v, out_q
 
     @staticmethod
@@ -175,20 +200,25 @@ class _CoAttentionFn(torch.autograd.Function):
         p = _lib.Params(*[t.data_ptr() for t in params])
         qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
         dqptr = (C.c_void_p * L)(*[q.data_ptr() for q in dQs])
+        args = (C.byref(p), _ptr(saved), _ptr(g_v), _ptr(g_q), _ptr(dV), *(_strides(dV) if need_dv else (0, 0, 0)), dqptr,
+                C.byref(pg), 0, _ptr(ws), B, N, T, d, L, _lib.F32, impl, C.c_void_p(stream))
         with _lib.on_device(dev):
-            _lib.check(lib.coattn_backward(_ptr(V), *_strides(V), qptr, C.byref(p), _ptr(saved), _ptr(g_v), _ptr(g_q),
-                                           _ptr(dV), *(_strides(dV) if need_dv else (0, 0, 0)), dqptr, C.byref(pg), 0,
-                                           _ptr(ws), B, N, T, d, L, _lib.F32, impl, C.c_void_p(stream)),
-                       "coattn_backward")
-        return (dV, *grads, None, *dQs)
+            if ctx.q_len is None:
+                _lib.check(lib.coattn_backward(_ptr(V), *_strides(V), qptr, *args), "coattn_backward")
+            else:
+                _lib.check(lib.coattn_backward_len(_ptr(V), *_strides(V), qptr, _ptr(ctx.q_len), *args), "coattn_backward_len")
+        return (dV, *grads, None, None, *dQs)
 
 
 def coattention(x_img: torch.Tensor, x_ques: Sequence[torch.Tensor], W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q,
-                impl: int | None = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Functional form: returns (v, q), each [L,B,d]."""
+                impl: int | None = None, q_len: torch.Tensor | None = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Functional form: returns (v, q), each [L,B,d].  q_len: None (the reference's unmasked softmax over the T tokens), or
+    the question lengths (see `question_lengths`): attention over the first q_len[b] tokens of question b."""
     if impl is None:
         impl = _impl_flag()
-    return _CoAttentionFn.apply(x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, *x_ques)
+    if q_len is not None:
+        q_len = question_lengths(q_len, x_img.shape[0], x_img.device)
+    return _CoAttentionFn.apply(x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques)
 
 
 class ParallelCoAttention(nn.Module):
@@ -198,11 +228,18 @@ class ParallelCoAttention(nn.Module):
     (model.py:347 vs :377) so it stays in the state_dict and never receives a gradient;
     W_v/W_q/w_v/w_q are ``nn.Linear`` with biases; one weight set serves all levels; the
     softmax over question positions is unmasked (model.py:388).
+
+    ``question_mask=True`` (opt-in; not in the reference): ``forward`` / ``forward_with_attention`` then REQUIRE
+    ``x_ques_lens`` and compute, per sample b, the reference's co-attention on the first ``x_ques_lens[b]`` question tokens
+    alone: a_q is 0 past the length and sums to 1 before it, the affinity rows there count as zero, their gradients are zero
+    (include/coattn.h, "length-masked question attention").  With the default (False) the lengths are ignored, as the
+    reference ignores them.  The flag is not part of the ``state_dict``: a checkpoint does not say which form trained it.
     """
 
-    def __init__(self, hidden_dim: int):
+    def __init__(self, hidden_dim: int, question_mask: bool = False):
         super().__init__()
         self.hidden_dim = hidden_dim
+        self.question_mask = bool(question_mask)
         self.W_b = nn.Linear(hidden_dim, hidden_dim)     # dead in the reference's forward
         self.W_v = nn.Linear(hidden_dim, hidden_dim)
         self.W_q = nn.Linear(hidden_dim, hidden_dim)
@@ -216,21 +253,33 @@ class ParallelCoAttention(nn.Module):
         # magnitude; `vqa_amd.check_range()` reports an operand that was not): what train.Trainer(precision="fast") sets.
         self.fast_products = _lib.default_fast()
 
-    def forward(self, x_img: torch.Tensor, x_ques_hierarchy: Sequence[torch.Tensor]) -> Tuple[List, List]:
-        """x_img [B,N,d]; x_ques_hierarchy: list of [B,T,d] -> (list of v_l [B,d], list of q_l [B,d])."""
+    def _lengths(self, x_img: torch.Tensor, x_ques_lens):
+        """int32 [B] lengths on the features' device when the mask is on (required then), else None (ignored)."""
+        if not self.question_mask:
+            return None
+        if x_ques_lens is None:
+            raise ValueError("ParallelCoAttention(question_mask=True) needs x_ques_lens, the length of every question")
+        return question_lengths(x_ques_lens, x_img.shape[0], x_img.device)
+
+    def forward(self, x_img: torch.Tensor, x_ques_hierarchy: Sequence[torch.Tensor], x_ques_lens=None) -> Tuple[List, List]:
+        """x_img [B,N,d]; x_ques_hierarchy: list of [B,T,d] -> (list of v_l [B,d], list of q_l [B,d]).
+        x_ques_lens ([B] integers, host or device): read only under ``question_mask``."""
         impl = _impl_flag() | (_lib.FLAG_BF16_PROJ if self.bf16_projections else 0) | _lib.precision_flag(self.fast_products)
+        q_len = self._lengths(x_img, x_ques_lens)
         if x_img.is_cuda and not (x_img.requires_grad and torch.is_grad_enabled()):
             x_img = native_features(x_img)           # frozen encoder: bf16 / non-native strides in one library pass
         v, q = coattention(x_img, list(x_ques_hierarchy), self.W_v.weight, self.W_v.bias, self.W_q.weight,
-                           self.W_q.bias, self.w_v.weight, self.w_v.bias, self.w_q.weight, self.w_q.bias, impl=impl)
+                           self.W_q.bias, self.w_v.weight, self.w_v.bias, self.w_q.weight, self.w_q.bias, impl=impl,
+                           q_len=q_len)
         n = v.shape[0]
         return [v[l] for l in range(n)], [q[l] for l in range(n)]
 
-    def forward_with_attention(self, x_img: torch.Tensor, x_ques_hierarchy: Sequence[torch.Tensor]):
+    def forward_with_attention(self, x_img: torch.Tensor, x_ques_hierarchy: Sequence[torch.Tensor], x_ques_lens=None):
         """Inference with the attention maps: (list of v_l [B,d], list of q_l [B,d], a_v [L,B,N], a_q [L,B,T]) through
         coattn_infer -- the forward that keeps no backward state (include/coattn.h).  v / q equal `forward`'s bit for bit.
         a_v[l, b] is the softmax over the N image locations (model.py:387), a_q[l, b] the one over the T tokens
-        (model.py:388), unmasked as the reference's: pad tokens carry weight.  Raises if a gradient would be needed."""
+        (model.py:388), unmasked as the reference's: pad tokens carry weight -- under ``question_mask`` (coattn_infer_len)
+        a_q[l, b, t] is 0 for t >= x_ques_lens[b].  Raises if a gradient would be needed."""
         ques = list(x_ques_hierarchy)
         params = (self.W_v.weight, self.W_v.bias, self.W_q.weight, self.W_q.bias, self.w_v.weight, self.w_v.bias,
                   self.w_q.weight, self.w_q.bias)
@@ -240,6 +289,7 @@ class ParallelCoAttention(nn.Module):
         if not x_img.is_cuda:
             raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
         impl = _impl_flag() | (_lib.FLAG_BF16_PROJ if self.bf16_projections else 0) | _lib.precision_flag(self.fast_products)
+        q_len = self._lengths(x_img, x_ques_lens)
         V = native_features(x_img)
         if V.dtype != torch.float32 or any(q.dtype != torch.float32 for q in ques):
             raise RuntimeError("ParallelCoAttention (HIP) computes in fp32; got %s" % V.dtype)
@@ -262,10 +312,13 @@ class ParallelCoAttention(nn.Module):
         ws = _lib.scratch(fb, dev, stream)
         qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
         p = _lib.Params(*[t.data_ptr() for t in ps])
+        args = (C.byref(p), _ptr(out_v), _ptr(out_q), _ptr(a_v), _ptr(a_q), _ptr(ws), B, N, T, d, L, _lib.F32, impl,
+                C.c_void_p(stream))
         with _lib.on_device(dev):
-            _lib.check(lib.coattn_infer(_ptr(V), *_strides(V), qptr, C.byref(p), _ptr(out_v), _ptr(out_q), _ptr(a_v),
-                                        _ptr(a_q), _ptr(ws), B, N, T, d, L, _lib.F32, impl, C.c_void_p(stream)),
-                       "coattn_infer")
+            if q_len is None:
+                _lib.check(lib.coattn_infer(_ptr(V), *_strides(V), qptr, *args), "coattn_infer")
+            else:
+                _lib.check(lib.coattn_infer_len(_ptr(V), *_strides(V), qptr, _ptr(q_len), *args), "coattn_infer_len")
         if impl & _lib.FLAG_FAST16:                   # tolerance mode: the status words are in the workspace
             _lib.note_status("coattn", ws, (B, N, T, d, L), dev)
         return [out_v[l] for l in range(L)], [out_q[l] for l in range(L)], a_v, a_q

@@ -16,7 +16,7 @@ void coattn_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int coattn_version(void) { return 700; }   // 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
+extern "C" int coattn_version(void) { return 800; }   // 0.8.0: the length-masked forms coattn_forward_len / _infer_len / _attention_forward_len / _backward_len; 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
 
 // ---------------------------------------------------------------------------------------
 // per-kernel timing (bench.py's backward roofline legs): HIP events recorded between the launches of the calls made
@@ -291,6 +291,7 @@ struct Ctx {
   int np_pq = 3;              // width of the P_q projection in the fp32 mode (3 | 2)
   bool f16_proj = false;      // fp32 mode: both projections on two FP16 pieces (fused.h kF16WScale)
   float pscale = 1.f;         // factor on P_v, P_q as stored (fused path: kPScale, fused.h)
+  const int* qlen = nullptr;  // [B] question lengths (the *_len entry points), NULL: unmasked
 };
 
 int launch_proj(const Ctx& c, const coattn_gemm_desc& g) {
@@ -473,6 +474,7 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
       rj.a_sm = c.d; rj.C = sv + sp.Pq; rj.c_sz = (long)BTd; rj.c_sm = c.d;
       rj.bias_n = (const float*)p->b_q; rj.out_scale = c.pscale; rj.M = c.B * c.T; rj.N = c.d; rj.K = c.d; rj.batch = c.L;
       rj.rowbits = bits;
+      rj.qlen = c.qlen; rj.T = c.T;                 // (length mask: rows past a question's length are not live)
       wq.rowbits = bits;
       // COATTN_FLAGS_IN_GEMM=1 (developer switch, DEV builds): the flag workgroups at the head of the PROJECTION launch instead,
       // its P_q tiles waiting on a counter the weight-split launch zeroes.  Measured and not adopted: the weight-split launch
@@ -522,10 +524,11 @@ int general_attention(const Ctx& c, const float* V, const float* const* Q, const
     float* av = (av_out ? av_out : sv + sp.av) + (size_t)l * c.B * c.N;
     float* aq = (aq_out ? aq_out : sv + sp.aq) + (size_t)l * c.B * c.T;
     CA_TRY(affinity(c, Q[l], V, C));
+    if (c.qlen) CA_TRY(launch_mask_rows(C, c.qlen, c.B, c.T, c.N, c.s));   // length mask: C rows t >= len_b are zero
     CA_TRY(ct_times(c, C, Pq, Pv, Hv, 1));
     CA_TRY(c_times(c, C, Pv, Pq, Hq, 1));
     CA_TRY(launch_score_softmax(Hv, (const float*)p->w_v, (const float*)p->c_v, av, c.B, c.N, c.d, c.s));
-    CA_TRY(launch_score_softmax(Hq, (const float*)p->w_q, (const float*)p->c_q, aq, c.B, c.T, c.d, c.s));
+    CA_TRY(launch_score_softmax(Hq, (const float*)p->w_q, (const float*)p->c_q, aq, c.B, c.T, c.d, c.s, c.qlen));
     // v = sum_n a_v[n] V[:,n]   (model.py:391);  q = sum_t a_q[t] Q[t,:]   (model.py:392)
     CA_TRY(launch_gemv(V, av, v_out + (size_t)l * c.B * c.d, c.B, c.d, c.N, c.vl.sB, c.vl.sD, c.vl.sN, c.N, c.d, c.s));
     CA_TRY(launch_gemv(Q[l], aq, q_out + (size_t)l * c.B * c.d, c.B, c.d, c.T, (int64_t)c.T * c.d, 1, c.d, c.T, c.d, c.s));
@@ -567,6 +570,7 @@ int backward_general(const Ctx& c, const float* V, const float* const* Q, const 
     CA_TRY(launch_gemv(V, gv + l * Bd, dav, B, N, d, c.vl.sB, c.vl.sN, c.vl.sD, d, N, c.s));
     CA_TRY(launch_softmax_bwd(av, dav, dsv, B, N, c.s));
     CA_TRY(launch_gemv(Q[l], gq + l * Bd, daq, B, T, d, (int64_t)T * d, d, 1, d, T, c.s));
+    if (c.qlen) CA_TRY(launch_mask_rows(daq, c.qlen, B, T, 1, c.s));   // (a_q = 0 there: ds_q = 0 whatever the pad rows hold)
     CA_TRY(launch_softmax_bwd(aq, daq, dsq, B, T, c.s));
     // dw_v += ds_v^T H_v ; dc_v += sum ds_v ; same for q
     const int rpc_v = (B * N + 255) / 256 > 32 ? (B * N + 255) / 256 : 32;
@@ -594,6 +598,7 @@ int backward_general(const Ctx& c, const float* V, const float* const* Q, const 
       CA_TRY(launch_gemm_f32(g, c.s));
     }
     CA_TRY(launch_dtanh(dC, C, dC, (int64_t)BTN, c.s));
+    if (c.qlen) CA_TRY(launch_mask_rows(dC, c.qlen, B, T, N, c.s));     // length mask: dA rows t >= len_b are zero
     // dP_v(level) = dZ_v + C^T dZ_q   (in place), accumulate over levels
     CA_TRY(ct_times(c, C, dZq, Hv, Hv, 0));
     CA_TRY(launch_add_inplace(dPv, Hv, (int64_t)BNd, l > 0 ? 1 : 0, c.s));
@@ -709,7 +714,8 @@ static int check_vlayout(const VLayout& v, int B, int N, int d, const char* what
 // them); av_out / aq_out (may be NULL): the attention maps go straight to the caller's buffers
 static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, const coattn_params* p, void* v_out,
                         void* q_out, void* saved, void* ws, int B, int N, int T, int d, int L, int dtype, int flags,
-                        void* stream, bool do_proj, bool do_attn, void* av_out = nullptr, void* aq_out = nullptr) {
+                        void* stream, bool do_proj, bool do_attn, void* av_out = nullptr, void* aq_out = nullptr,
+                        const int32_t* q_len = nullptr) {
   CA_TRY(check_shape(B, N, T, d, L, dtype));
   CA_CHECK_ARG(V && Q && p && v_out && q_out && ws, "forward: null argument");
   CA_TRY(check_vlayout(vl, B, N, d, "forward: V"));
@@ -722,6 +728,7 @@ static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, 
   float* sv = saved ? (float*)saved : (float*)ws;      // inference: state lives in the workspace
   float* tail = (float*)ws + sp.total;
   Ctx c{B, N, T, d, L, (hipStream_t)stream, vl};
+  c.qlen = q_len;
   c.bf16_proj = (flags & COATTN_FLAG_BF16_PROJ) != 0;
   c.f16_proj = f16_path(c, (const float*)V, (const float* const*)Q, flags, fused);
   // (the general-shape path stays exact throughout; a fused shape without the FP16 path too -- unless the developer switch
@@ -735,38 +742,58 @@ static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, 
   if (fused)
     return fused_attention_forward(B, N, T, d, L, (const float*)V, vl, (const float* const*)Q, p, (float*)v_out,
                                    (float*)q_out, sv, tail, c.s, c.bf16_proj ? 1 : 0, np_fwd(flags, c.f16_proj),
-                                   (float*)av_out, (float*)aq_out, saved != nullptr ? 1 : 0);
+                                   (float*)av_out, (float*)aq_out, saved != nullptr ? 1 : 0, q_len);
   return general_attention(c, (const float*)V, (const float* const*)Q, p, (float*)v_out, (float*)q_out, sv, tail,
                            (float*)av_out, (float*)aq_out);
+}
+
+extern "C" int coattn_forward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                  const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* saved, void* ws,
+                                  int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
+  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
+                      dtype, flags, stream, true, true, nullptr, nullptr, q_len);
 }
 
 extern "C" int coattn_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
                               const coattn_params* p, void* v_out, void* q_out, void* saved, void* ws, int B, int N,
                               int T, int d, int L, int dtype, int flags, void* stream) {
-  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
-                      dtype, flags, stream, true, true);
+  return coattn_forward_len(V, v_sB, v_sN, v_sD, Q, nullptr, p, v_out, q_out, saved, ws, B, N, T, d, L, dtype, flags, stream);
+}
+
+extern "C" int coattn_infer_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* av_out,
+                                void* aq_out, void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
+  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, nullptr, ws, B, N, T, d, L,
+                      dtype, flags, stream, true, true, av_out, aq_out, q_len);
 }
 
 extern "C" int coattn_infer(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
                             const coattn_params* p, void* v_out, void* q_out, void* av_out, void* aq_out, void* ws, int B,
                             int N, int T, int d, int L, int dtype, int flags, void* stream) {
-  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, nullptr, ws, B, N, T, d, L,
-                      dtype, flags, stream, true, true, av_out, aq_out);
+  return coattn_infer_len(V, v_sB, v_sN, v_sD, Q, nullptr, p, v_out, q_out, av_out, aq_out, ws, B, N, T, d, L, dtype, flags,
+                          stream);
+}
+
+extern "C" int coattn_attention_forward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                            const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* saved,
+                                            void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
+  CA_CHECK_ARG(saved != nullptr, "attention_forward: needs the saved buffer of a previous coattn_forward");
+  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
+                      dtype, flags, stream, false, true, nullptr, nullptr, q_len);
 }
 
 extern "C" int coattn_attention_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
                                         const coattn_params* p, void* v_out, void* q_out, void* saved, void* ws,
                                         int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
-  CA_CHECK_ARG(saved != nullptr, "attention_forward: needs the saved buffer of a previous coattn_forward");
-  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
-                      dtype, flags, stream, false, true);
+  return coattn_attention_forward_len(V, v_sB, v_sN, v_sD, Q, nullptr, p, v_out, q_out, saved, ws, B, N, T, d, L, dtype,
+                                      flags, stream);
 }
 
-extern "C" int coattn_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
-                               const coattn_params* p, const void* saved, const void* gv, const void* gq, void* dV,
-                               int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
-                               const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d,
-                               int L, int dtype, int flags, void* stream) {
+extern "C" int coattn_backward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                   const int32_t* q_len, const coattn_params* p, const void* saved, const void* gv,
+                                   const void* gq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                                   const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d,
+                                   int L, int dtype, int flags, void* stream) {
   CA_TRY(check_shape(B, N, T, d, L, dtype));
   CA_CHECK_ARG(V && Q && p && saved && gv && gq && dQ && pg && ws, "backward: null argument");  // dV may be NULL
   const VLayout vl{(long)v_sB, (long)v_sN, (long)v_sD};
@@ -780,6 +807,7 @@ extern "C" int coattn_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_
   int fused = 0;
   CA_TRY(pick_impl(flags, B, N, T, d, L, vl, &fused));
   Ctx c{B, N, T, d, L, (hipStream_t)stream, vl};
+  c.qlen = q_len;
   c.bf16_proj = (flags & COATTN_FLAG_BF16_PROJ) != 0;
   // (`saved` of the fused forward holds P_v, P_q scaled by kPScale: only the fused backward may read it)
   CA_CHECK_ARG(!fused || fused_backward_supported(B, N, T, d, L), "backward: the fused forward's saved state has no fused backward for this shape");
@@ -788,7 +816,17 @@ extern "C" int coattn_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_
                           (const float*)gv, (const float*)gq, (float*)dV, dvl, (float* const*)dQ, pg, accumulate,
                           (float*)ws, c.s, c.bf16_proj ? 1 : 0,
                           gemm_w_enabled() ? 1 : 0, np_bwd(flags),
-                          rowbits_in_saved(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, flags, fused) ? 1 : 0);
+                          rowbits_in_saved(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, flags, fused) ? 1 : 0,
+                          q_len);
   return backward_general(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, (const float*)gv,
                           (const float*)gq, (float*)dV, dvl, (float* const*)dQ, pg, accumulate, (float*)ws);
+}
+
+extern "C" int coattn_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                               const coattn_params* p, const void* saved, const void* gv, const void* gq, void* dV,
+                               int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                               const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d,
+                               int L, int dtype, int flags, void* stream) {
+  return coattn_backward_len(V, v_sB, v_sN, v_sD, Q, nullptr, p, saved, gv, gq, dV, dv_sB, dv_sN, dv_sD, dQ, pg, accumulate,
+                             ws, B, N, T, d, L, dtype, flags, stream);
 }

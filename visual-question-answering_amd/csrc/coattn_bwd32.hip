@@ -1,7 +1,8 @@
 // The three big kernels of the fused backward (autograd of model.py:377-392; SURVEY.md section 8 "Backward"), all on
 // the bf16 MFMA 32x32x16 with the exact 3-way split (fused.h):
 //   bwd_nat32_kernel  orientation [locations][channels]: dP_q = dZ_q + C dZ_v, dP_v = dZ_v + C^T dZ_q, dw_v, db_v, db_q
-//   bwd_dc32_kernel   orientation [channels][locations]: dC = P_q dZ_v^T + dZ_q P_v^T, dA = dC (.) (1 - C^2)
+//   bwd_dc32_kernel   orientation [channels][locations]: dC = P_q dZ_v^T + dZ_q P_v^T, dA = dC (.) (1 - C^2) (rows t >= len_b
+//                     zero under the length mask)
 //   bwd_dq32_kernel   dQ_l (+)= a_q (x) gq + dA_l V (location-major image features; channel-major when N % 4 == 0)
 // (an accumulator tile feeds the next MFMA only along its row index, hence the two orientations: each recomputes H_v).
 //
@@ -358,7 +359,8 @@ __global__ __launch_bounds__(NW * 64, 2) void bwd_nat32_kernel(const BwdArgs a) 
 #ifndef DC32_KO
 #define DC32_KO 0   // developer knock-outs of bwd_dc32_kernel (wrong results; tools/ab_dc32.sh): 1 the tanh' arithmetic (one VALU
 #endif              // operation per element instead of five), 2 the operand splits (one conversion per pair), 4 the MFMAs, 8 the P_v fragment loads
-template <int NT, int NW, int NP>
+// MASK: the length-masked form (coattn_backward_len, BwdArgs::qlen) -- a template flag: the unmasked code objects unchanged
+template <int NT, int NW, int NP, bool MASK = false>
 __global__ __launch_bounds__(NW * 64, 2) void bwd_dc32_kernel(const BwdArgs a) {
   constexpr int NPAD = 32 * NT, PIECE = NPAD * 32, NTHR = NW * 64, SLD = 36;
   constexpr int GT = NT > COATTN_DC_GT ? COATTN_DC_GT : NT;   // location tiles per group
@@ -378,7 +380,11 @@ __global__ __launch_bounds__(NW * 64, 2) void bwd_dc32_kernel(const BwdArgs a) {
   const __amdgpu_buffer_rsrc_t rs_hq = make_rsrc(a.Hq + pair * (size_t)T * d, (unsigned)T * d * 4u);
   const __amdgpu_buffer_rsrc_t rs_c = make_rsrc(a.C + pair * (size_t)T * N, (unsigned)T * N * 4u);
   const float dsq_r = a.dsq[pair * 32 + r];          // ds_q of this lane's token (0 for t >= T)
-  const __amdgpu_buffer_rsrc_t rs_da = make_rsrc(a.dA + pair * (size_t)T * N, (unsigned)T * N * 4u);
+  // MASK: the question length of the forward.  dA rows t >= tl must be zero (dC there is P_q[t] dZ_v^T + ..., not zero):
+  // bwd_pre_kernel has zeroed them, and the buffer below ends at row tl, so the epilogue's stores to them are dropped.
+  // (A select in the epilogue instead costs the exact N > 64 instantiation spilled dwords.)
+  const int tl = MASK ? min(max(a.qlen[b], 1), T) : T;
+  const __amdgpu_buffer_rsrc_t rs_da = make_rsrc(a.dA + pair * (size_t)T * N, (unsigned)tl * N * 4u);
   const int nsl = d / (128 * NW);
   // ---- the image of C (as in bwd_nat32_kernel) and ds_v
   {
@@ -566,12 +572,12 @@ __global__ __launch_bounds__(NW * 64, 2) void bwd_dc32_kernel(const BwdArgs a) {
   if (GT > 3 && rest == 3) group(t0, std::integral_constant<int, 3>());
 }
 
-template <int NT, int NW, int NP>
+template <int NT, int NW, int NP, bool MASK = false>
 int launch_dc32(const BwdArgs& a, hipStream_t s) {
   constexpr int NPAD = 32 * NT;
   const size_t lds = (size_t)3 * NPAD * 32 * 2 + (size_t)NPAD * 4 + (size_t)NW * 32 * 36 * 4;
   const int groups = (a.B + 7) / 8;
-  hipLaunchKernelGGL((bwd_dc32_kernel<NT, NW, NP>), dim3(groups * a.L * 8), dim3(NW * 64), lds, s, a);
+  hipLaunchKernelGGL((bwd_dc32_kernel<NT, NW, NP, MASK>), dim3(groups * a.L * 8), dim3(NW * 64), lds, s, a);
   CA_CHECK_LAUNCH("bwd_dc32");
   return 0;
 }
@@ -858,13 +864,17 @@ int launch_bwd_dq32(const DqArgs& a, int lm, hipStream_t s) {
   return go(std::integral_constant<int, 3>());
 }
 
-int launch_bwd_dc32(const BwdArgs& a, hipStream_t s) {
+template <bool M>
+int dispatch_dc32(const BwdArgs& a, hipStream_t s) {
   const bool small_n = a.N <= 64, w2 = a.np == 2;
   if (a.d % 512 == 0) {
-    if (a.bf16) return small_n ? launch_dc32<2, 4, 1>(a, s) : launch_dc32<7, 4, 1>(a, s);
-    if (w2) return small_n ? launch_dc32<2, 4, 2>(a, s) : launch_dc32<7, 4, 2>(a, s);
-    return small_n ? launch_dc32<2, 4, 3>(a, s) : launch_dc32<7, 4, 3>(a, s);
+    if (a.bf16) return small_n ? launch_dc32<2, 4, 1, M>(a, s) : launch_dc32<7, 4, 1, M>(a, s);
+    if (w2) return small_n ? launch_dc32<2, 4, 2, M>(a, s) : launch_dc32<7, 4, 2, M>(a, s);
+    return small_n ? launch_dc32<2, 4, 3, M>(a, s) : launch_dc32<7, 4, 3, M>(a, s);
   }
-  if (w2) return small_n ? launch_dc32<2, 2, 2>(a, s) : launch_dc32<7, 2, 2>(a, s);
-  return small_n ? launch_dc32<2, 2, 3>(a, s) : launch_dc32<7, 2, 3>(a, s);
+  if (w2) return small_n ? launch_dc32<2, 2, 2, M>(a, s) : launch_dc32<7, 2, 2, M>(a, s);
+  return small_n ? launch_dc32<2, 2, 3, M>(a, s) : launch_dc32<7, 2, 3, M>(a, s);
+}
+int launch_bwd_dc32(const BwdArgs& a, hipStream_t s) {
+  return a.qlen ? dispatch_dc32<true>(a, s) : dispatch_dc32<false>(a, s);   // (length-masked: dA rows past len_b zero)
 }

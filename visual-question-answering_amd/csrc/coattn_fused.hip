@@ -58,7 +58,7 @@ int fused_supported(int B, int N, int T, int d, int L) {
 
 int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl,
                             const float* const* Q, const coattn_params* p, float* v_out, float* q_out, float* saved,
-                            float* ws, hipStream_t s, int bf16, int np, float* av, float* aq, int keep) {
+                            float* ws, hipStream_t s, int bf16, int np, float* av, float* aq, int keep, const int* qlen) {
   CA_CHECK_ARG(fused_supported(B, N, T, d, L), "fused forward: unsupported shape");
   const bool lm = v_is_lm(vl, N, d);
   CA_CHECK_ARG(lm || v_is_cm(vl, N, d), "fused forward: image features must be channel-major [B,d,N] or location-major [B,N,d]");
@@ -71,6 +71,7 @@ int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, c
   a.C = saved + so.C; a.Hq = saved + so.Hq;
   a.av = av ? av : saved + so.av; a.aq = aq ? aq : saved + so.aq;   // the caller's map buffers (coattn_infer), else `saved`
   a.keep = keep ? 1 : 0;
+  a.qlen = qlen;
   a.q_out = q_out;
   // Small grids (the 7 x 7 grid of 224 x 224 images: N = 49) on location-major features: the attended image feature
   // v_l = a_v^T V is computed by the affinity kernel's own workgroup -- its 100 KB of V come from L2, where phase 1 left

@@ -104,6 +104,8 @@ struct PreArgs {
   const float* V; long v_sB; const float* gv; float* dav_out; int dav_lm, dav_gx;
   float* dsq;                            // [L*B][32] ds_q, zeros for t >= T
   float* dcs_part;                       // [2][L*B]
+  const int* qlen;                       // [B] question lengths of the forward, or NULL: da_q rows t >= len_b count as 0, and
+  float* dA;                             //   the rows t >= len_b of dA [L][B][T][N] are zeroed here (bwd_dc32_kernel skips them)
   int B, N, T, d, L;
   TnDyn dyn; TnDynPlan* plan_out;        // plan_out != NULL: ONE more workgroup (the launch's last) evaluates the split-K plan of the
                                          // weight gradients over the live question rows (fused.h tn_dyn_plan) and leaves it there
@@ -160,8 +162,15 @@ __global__ __launch_bounds__(256) void bwd_pre_kernel(const PreArgs a) {
   }
   __syncthreads();
   if (w == 0) {
+    // (a masked token has a_q = 0, so ds_q = 0 there; its da_q -- of whatever the pad row holds -- is read as 0 as well, so
+    //  that not even the sign of that zero depends on the padding)
+    const int tl = a.qlen ? min(max(a.qlen[b], 1), T) : T;
     const float aqv = (lane < T) ? a.aq[pair * T + lane] : 0.f;
-    const float x = (lane < T) ? daq[lane] : 0.f;
+    const float x = (lane < tl) ? daq[lane] : 0.f;
+    if (tl < T) {                                    // (length mask only) dA rows past the question
+      float* da = a.dA + pair * (size_t)T * a.N;
+      for (int i = tl * a.N + lane; i < T * a.N; i += 64) da[i] = 0.f;
+    }
     const float dq = wave_sum(aqv * x);
     const float sq = aqv * (x - dq);
     if (lane < 32) a.dsq[pair * 32 + lane] = sq;                     // (lanes >= T: zeros)
@@ -299,7 +308,7 @@ int fused_backward_supported(int B, int N, int T, int d, int L) { return fused_s
 int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl, const float* const* Q,
                    const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
                    const VLayout& dvl, float* const* dQ, const coattn_param_grads* pg, int accumulate, float* ws,
-                   hipStream_t s, int bf16_proj, int wgemm, int np, int live_rows) {
+                   hipStream_t s, int bf16_proj, int wgemm, int np, int live_rows, const int* qlen) {
   // np: width of the fp32 mode's contractions (fused.h): 2 = hi + mid in the three fused kernels and in the GEMM launch
   // (dW_v, dW_q, dQ = dP_q W_q), 3 = the exact split everywhere; dV (general GEMM) is always exact
   np = (np == 2 && !bf16_proj) ? 2 : 3;
@@ -321,7 +330,7 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
   pa.nkc = lm ? 1 : d / 64;
   for (int l = 0; l < 8; ++l) pa.Q[l] = l < L ? Q[l] : nullptr;
   pa.gq = gq; pa.av = saved + so.av; pa.aq = saved + so.aq;
-  pa.dsq = ws + wo.dsq; pa.dcs_part = ws + wo.dcs_part;
+  pa.dsq = ws + wo.dsq; pa.dcs_part = ws + wo.dcs_part; pa.qlen = qlen; pa.dA = ws + wo.dA;
   pa.B = B; pa.N = N; pa.T = T; pa.d = d; pa.L = L;
   // (exact mode: the forward's bitmap of the live question rows is in `saved`; the plan of the weight gradients over those rows
   //  is a function of it and of shapes known here -- evaluated once, by an extra workgroup of this launch)
@@ -352,6 +361,7 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
   static const int ko_sum3 = dev_env_int("COATTN_KO_SUM3", 0);    // ONE sum_l dP_v array save in bwd_nat32's stores / the GEMM's reads
   ba.ko_dpv = ko_dpv;
   ba.dp_bf16 = 0;
+  ba.qlen = qlen;
   CA_TRY(launch_bwd_dc32(ba, s));                    // dC, dA                       (coattn_bwd32.hip)
   prof_mark(s, "bwd_dc32");
   // which of the backward's GEMMs take the hand-scheduled kernels (decided here: when all three do, they share ONE

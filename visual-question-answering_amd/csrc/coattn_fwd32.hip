@@ -20,7 +20,8 @@
 //            s_v[n] += H_v[n][:] . w_v is taken from 1 / (1 + e^{2 H}) without ever writing H_v (or the tanh), the
 //            16 score registers of a tile are summed over their channel lanes by a transposing butterfly;
 //            the H_q accumulators start from P_q.
-//   phase 3  score reduction over waves / passes in a fixed order, un-masked row softmax over N and over T
+//   phase 3  score reduction over waves / passes in a fixed order, row softmax over N and over T (un-masked, or over the
+//            first len_b tokens under coattn_forward_len's length mask)
 //            (model.py:387-388) by wave shuffles, H_q saved, q = a_q^T Q.
 //   attend_v_lm_kernel : v_l = a_{v,l}^T V for all levels with one more pass over a location-major V.
 #include "fused.h"
@@ -75,7 +76,9 @@ __device__ __forceinline__ void vmcnt_wait(int n) {
 // projections, tanh values); less error than the exact bf16 split of phase 1 next to two bf16 pieces in phase 2
 // (tests/test_split_emulation.py), at half the MFMAs and 6 instead of 11 split instructions per pair in phase 1.
 // FV: the kernel also attends the image features, v_l = a_v^T V (model.py:391) -- location-major V, NT = 2, four waves.
-template <int NT, int NW, bool LM, int NP_, bool FV = false>
+// MASK: the length-masked form (coattn_forward_len, FwdArgs::qlen); a template flag so that the unmasked code objects stay
+// what they were (the runtime test alone moved the tolerance instantiations by 2 - 4 VGPRs).
+template <int NT, int NW, bool LM, int NP_, bool FV = false, bool MASK = false>
 __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs a) {
   static_assert(!FV || (LM && NT == 2 && NW == 4), "the fused v pass: location-major features, N <= 64, 256 threads");
   constexpr bool HF = NP_ == 4;
@@ -104,6 +107,10 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
   if (HF) f16_saturating_conversions();
   CA_STAMP(0);
   const int N = a.N, T = a.T, d = a.d;
+  // MASK: the question length of this sample (uniform over the workgroup: one scalar load), clamped into [1, T].  Rows
+  // t >= tl are masked: the Q buffer below ends at row tl (they read 0 in phases 1 and 3), the C epilogue selects 0 for them
+  // and the a_q softmax runs over t < tl.  Unmasked: tl = T.
+  const int tl = MASK ? min(max(a.qlen[b], 1), T) : T;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // The lane id is re-derived (v_mbcnt) at every phase: kept from kernel entry, the values computed from it would
   // live across the fully unrolled phase 1 and be spilled (a kernel with scratch pays for it at every launch).
@@ -116,8 +123,8 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
   const float* Pvp = a.Pv + (size_t)b * N * d;
   const size_t pair = (size_t)l * a.B + b;
   const float* Pqp = a.Pq + pair * (size_t)T * d;
-  // buffer resources over exactly this sample's tensors: rows beyond T / N read as 0, stores there are dropped
-  const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(Qp, (unsigned)T * d * 4u);
+  // buffer resources over exactly this sample's tensors: rows beyond T / N (Q: beyond tl) read as 0, stores there are dropped
+  const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(Qp, (unsigned)tl * d * 4u);
   const __amdgpu_buffer_rsrc_t rs_v = make_rsrc(Vp, (unsigned)d * N * 4u);
   const __amdgpu_buffer_rsrc_t rs_pq = make_rsrc(Pqp, (unsigned)T * d * 4u);
   const int nsl = d / (128 * NW);                    // 128-channel slices per wave (1 at d = 512)
@@ -457,7 +464,7 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
       float c[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float th = tanh_fast(sum[k][i]);
+        const float th = (!MASK || 4 * tq + i < tl) ? tanh_fast(sum[k][i]) : 0.f;   // masked rows: C = 0 (select, whatever V holds)
         c[i] = in ? th : 0.f;
         if constexpr (!COATTN_KO_BWD_STORES) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, th), rs_c, cvoff, i * N * 4, 0);
       }
@@ -755,15 +762,16 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
     }
   }
   if (w == 1) {
-    // a_q = softmax_t(s_q + c_q), un-masked over all T positions (model.py:388), by the second wave
+    // a_q = softmax_t(s_q + c_q) by the second wave: over all T positions, un-masked as the reference's (model.py:388), or
+    // over t < tl under a length mask (a_q = 0 exactly beyond it)
     float s = -INFINITY;
-    if (lane < T) {
+    if (lane < tl) {
       s = a.cq[0];
 #pragma unroll
       for (int p = 0; p < NW * 2; ++p) s += sqpart[p * 32 + lane];
     }
     const float mq = wave_max(s);
-    const float e = (lane < T) ? expf(s - mq) : 0.f;
+    const float e = (lane < tl) ? expf(s - mq) : 0.f;
     const float se = wave_sum(e);
     const float aqv = e / se;
     if (lane < 32) aqs[lane] = aqv;                  // zeros beyond T
@@ -875,7 +883,7 @@ __global__ __launch_bounds__(256) void attend_v_lm_kernel(const float* V, long v
   }
 }
 
-template <int NT, int NW, bool LM, int NP, bool FV = false>
+template <int NT, int NW, bool LM, int NP, bool FV = false, bool MASK = false>
 int launch_fwd32(const FwdArgs& a, hipStream_t s) {
   constexpr int NPAD = 32 * NT;
   constexpr int RING_SLOTS = (NT + 1) * ((NT + 1 >= 6) ? 1 : 2);
@@ -884,17 +892,17 @@ int launch_fwd32(const FwdArgs& a, hipStream_t s) {
   const size_t lds = lds_p2 > lds_p1 ? lds_p2 : lds_p1;
   static DeviceOnce once;                            // the attribute is per device
   CA_TRY(once.run([&] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(coattn_fwd32_kernel<NT, NW, LM, NP, FV>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }, "coattn_fwd32"));
   const int groups = (a.B + 7) / 8;
   dim3 grid(groups * a.L * 8), block(NW * 64);
-  hipLaunchKernelGGL((coattn_fwd32_kernel<NT, NW, LM, NP, FV>), grid, block, lds, s, a);
+  hipLaunchKernelGGL((coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK>), grid, block, lds, s, a);
   CA_CHECK_LAUNCH("coattn_fwd32");
   return 0;
 }
 
-template <bool LM>
+template <bool LM, bool M>
 int dispatch_fwd32(const FwdArgs& a, hipStream_t s) {
   const bool small_n = a.N <= 64;
   const bool w2 = a.np == 2;                         // phase 2 on two bf16 pieces
@@ -902,26 +910,27 @@ int dispatch_fwd32(const FwdArgs& a, hipStream_t s) {
   if (a.d % 512 == 0) {
     if constexpr (LM) {
       if (small_n && a.v_out) {                      // the kernel attends the image features too (FwdArgs::v_out)
-        if (a.bf16) return launch_fwd32<2, 4, true, 1, true>(a, s);
-        if (hf) return launch_fwd32<2, 4, true, 4, true>(a, s);
-        return w2 ? launch_fwd32<2, 4, true, 2, true>(a, s) : launch_fwd32<2, 4, true, 3, true>(a, s);
+        if (a.bf16) return launch_fwd32<2, 4, true, 1, true, M>(a, s);
+        if (hf) return launch_fwd32<2, 4, true, 4, true, M>(a, s);
+        return w2 ? launch_fwd32<2, 4, true, 2, true, M>(a, s) : launch_fwd32<2, 4, true, 3, true, M>(a, s);
       }
     }
-    if (a.bf16) return small_n ? launch_fwd32<2, 4, LM, 1>(a, s) : launch_fwd32<7, 4, LM, 1>(a, s);
-    if (hf) return small_n ? launch_fwd32<2, 4, LM, 4>(a, s) : launch_fwd32<7, 4, LM, 4>(a, s);
-    if (w2) return small_n ? launch_fwd32<2, 4, LM, 2>(a, s) : launch_fwd32<7, 4, LM, 2>(a, s);
-    return small_n ? launch_fwd32<2, 4, LM, 3>(a, s) : launch_fwd32<7, 4, LM, 3>(a, s);
+    if (a.bf16) return small_n ? launch_fwd32<2, 4, LM, 1, false, M>(a, s) : launch_fwd32<7, 4, LM, 1, false, M>(a, s);
+    if (hf) return small_n ? launch_fwd32<2, 4, LM, 4, false, M>(a, s) : launch_fwd32<7, 4, LM, 4, false, M>(a, s);
+    if (w2) return small_n ? launch_fwd32<2, 4, LM, 2, false, M>(a, s) : launch_fwd32<7, 4, LM, 2, false, M>(a, s);
+    return small_n ? launch_fwd32<2, 4, LM, 3, false, M>(a, s) : launch_fwd32<7, 4, LM, 3, false, M>(a, s);
   }
-  if (hf) return small_n ? launch_fwd32<2, 2, LM, 4>(a, s) : launch_fwd32<7, 2, LM, 4>(a, s);
-  if (w2) return small_n ? launch_fwd32<2, 2, LM, 2>(a, s) : launch_fwd32<7, 2, LM, 2>(a, s);
-  return small_n ? launch_fwd32<2, 2, LM, 3>(a, s) : launch_fwd32<7, 2, LM, 3>(a, s);   // (the fp32 mode at these widths)
+  if (hf) return small_n ? launch_fwd32<2, 2, LM, 4, false, M>(a, s) : launch_fwd32<7, 2, LM, 4, false, M>(a, s);
+  if (w2) return small_n ? launch_fwd32<2, 2, LM, 2, false, M>(a, s) : launch_fwd32<7, 2, LM, 2, false, M>(a, s);
+  return small_n ? launch_fwd32<2, 2, LM, 3, false, M>(a, s) : launch_fwd32<7, 2, LM, 3, false, M>(a, s);   // (the fp32 mode at these widths)
 }
 
 }  // namespace
 
 int fused32_forward(const FwdArgs& a, hipStream_t s) {
   CA_CHECK_ARG(!a.v_out || (a.lm && a.N <= 64 && a.d % 512 == 0), "fused forward: the in-kernel v pass needs location-major features, N <= 64, d %% 512 == 0");
-  return a.lm ? dispatch_fwd32<true>(a, s) : dispatch_fwd32<false>(a, s);
+  if (a.qlen) return a.lm ? dispatch_fwd32<true, true>(a, s) : dispatch_fwd32<false, true>(a, s);   // length-masked
+  return a.lm ? dispatch_fwd32<true, false>(a, s) : dispatch_fwd32<false, false>(a, s);
 }
 
 int launch_attend_v_lm(const float* V, long v_sB, const float* av, float* v_out, int B, int N, int d, int L, hipStream_t s) {

@@ -242,9 +242,12 @@ int launch_gemm_bf16in(const coattn_gemm_desc& g, hipStream_t s);
 // y[z][i] = sum_k X[z*x_sz + i*x_si + k*x_sk] * u[z*u_sz + k]      (i < I, k < K)
 int launch_gemv(const float* X, const float* u, float* y, int Z, int I, int K,
                 int64_t x_sz, int64_t x_si, int64_t x_sk, int64_t u_sz, int64_t y_sz, hipStream_t s);
-// a[z][r] = softmax_r( H[z][r][:] . w + c[0] ),  H rows contiguous (length d)
+// a[z][r] = softmax_r( H[z][r][:] . w + c[0] ),  H rows contiguous (length d); len (may be NULL): [Z] lengths, the softmax
+// over r < clamp(len[z], 1, R) and a = 0 beyond
 int launch_score_softmax(const float* H, const float* w, const float* c, float* a,
-                         int Z, int R, int d, hipStream_t s);
+                         int Z, int R, int d, hipStream_t s, const int* len = nullptr);
+// X[z][r][0 .. W) = 0 for r >= clamp(len[z], 1, R)   (X: [Z][R][W] contiguous)
+int launch_mask_rows(float* X, const int* len, int Z, int R, int W, hipStream_t s);
 // ds[z][r] = a[z][r] * (da[z][r] - sum_r a*da)
 int launch_softmax_bwd(const float* a, const float* da, float* ds, int Z, int R, hipStream_t s);
 // part[chunk][j] = sum_{r in chunk} s[r] * X[r][j]   (s may be NULL -> 1); X: [R][d] contiguous

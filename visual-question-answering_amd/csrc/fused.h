@@ -19,12 +19,14 @@ inline bool fused_layout_ok(const VLayout& v, int N, int d) { return v_is_lm(v, 
 int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl,
                             const float* const* Q, const coattn_params* p, float* v_out, float* q_out, float* saved,
                             float* ws, hipStream_t s, int bf16 = 0, int np = 3,   // bf16: reduced precision, one MFMA per product; np: width of phase 2
-                            float* av = nullptr, float* aq = nullptr, int keep = 1);
+                            float* av = nullptr, float* aq = nullptr, int keep = 1,
+                            const int* qlen = nullptr);   // qlen: [B] question lengths (coattn_forward_len), NULL = unmasked
 int fused_backward_supported(int B, int N, int T, int d, int L);
 int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl, const float* const* Q,
                    const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
                    const VLayout& dvl, float* const* dQ, const coattn_param_grads* pg, int accumulate, float* ws,
-                   hipStream_t s, int bf16_proj, int wgemm, int np = 3, int live_rows = 0);   // wgemm: gemm_w / gemm_tn enabled; np: width of the contractions (3 | 2); live_rows: `saved` holds the forward's bitmap of the non-zero question rows
+                   hipStream_t s, int bf16_proj, int wgemm, int np = 3, int live_rows = 0,   // wgemm: gemm_w / gemm_tn enabled; np: width of the contractions (3 | 2); live_rows: `saved` holds the forward's bitmap of the non-zero question rows
+                   const int* qlen = nullptr);   // qlen: the forward's question lengths (NULL = unmasked)
 
 // Diagnostic build only (tools/probe_stamps.py, -DCOATTN_STAMPS=1): wave 0 of every workgroup writes the
 // 100 MHz constant clock at its phase boundaries into the (otherwise unused) forward workspace tail.
@@ -282,6 +284,7 @@ struct RowFlagJob {
   unsigned* rowbits;                             // [batch][(M + 31) / 32]
   unsigned* rowcnt;                              // (job inside a GEMM launch) [8] words finished per batch entry: zeroed by the launch
                                                  // before, raised by every workgroup of the job behind its word; NULL otherwise
+  const int* qlen; int T;                        // qlen != NULL: row m = (b, t = m % T) is live only if t < clamp(qlen[b], 1, T) too
 };
 constexpr int kRowBitsMaxWords = 512;            // per batch entry (M <= 16,384 rows): the GEMM tiles scan the words serially
 inline size_t rowbits_words(int M, int batch) { return (size_t)batch * ((M + 31) / 32); }
@@ -440,6 +443,7 @@ struct FwdArgs {
   int np;                // (bf16 = 0) width of the phase-2 contractions C^T P_q, C P_v: 3 or 2 pieces (the affinity: always 3)
   int keep;              // 1: C and H_q are stored for the backward; 0 (forward only, coattn_infer): their buffer resources are
                          // zero bytes long, so every store to them is dropped in hardware (same code, no new instantiation)
+  const int* qlen;       // [B] question lengths (coattn_forward_len), clamped into [1, T]; NULL: every row counts (the reference)
 };
 
 // arguments of the two big fused backward kernels (coattn_fused_bwd.hip, coattn_bwd32.hip)
@@ -467,6 +471,7 @@ struct BwdArgs {
   int np;                 // (bf16 = 0) width of the contractions: 3 or 2 pieces
   int dp_bf16;            // (with bf16, bwd_nat32_kernel) dPv / dPq are bf16 arrays of the same index order
   int ko_dpv;             // developer knock-out (DEV builds only, wrong results): bwd_nat32 stores dP_v of level 0 alone
+  const int* qlen;        // [B] question lengths of the forward (clamped into [1, T]): dA rows t >= len are zero; NULL: unmasked
 };
 
 // Image-side softmax backward of one (sample, level) by ONE wave: da_v = the sum of the channel-chunk partials,

@@ -36,7 +36,9 @@ struct SplitArgs { SplitJob job[3]; int njobs; float* status_hdr; float f16; Row
 // The RowFlagJob's workgroups (the FIRST row_blocks of the launch: they have the most to wait for): workgroup x takes 32 rows of one batch entry, a wave 8 of them, all
 // requested before the first test (one memory latency per wave, not per row); a row is read in whole 1 KB segments (a lane
 // per 16 bytes, KC = K / 256 of them), any non-zero (or NaN) element sets its bit; an all-zero row gets its output written
-// here (16-byte stores; a live row's store is sent outside the buffer instead of branched around).
+// here (16-byte stores; a live row's store is sent outside the buffer instead of branched around).  Under a length mask a
+// row t >= len_b is treated as all-zero whatever it holds, so the bitmap -- and the weight gradients' split-K plan read from
+// it -- does not depend on the padding.
 template <int KC>
 __device__ __forceinline__ void rowflag_block(const RowFlagJob& j, const int bx) {
   __shared__ unsigned wbits[4];
@@ -66,7 +68,11 @@ __device__ __forceinline__ void rowflag_block(const RowFlagJob& j, const int bx)
     bool nz = false;
 #pragma unroll
     for (int k = 0; k < KC; ++k) nz = nz || !(x[i][k][0] == 0.f && x[i][k][1] == 0.f && x[i][k][2] == 0.f && x[i][k][3] == 0.f);
-    const bool live = __builtin_amdgcn_ballot_w64(nz) != 0;
+    bool live = __builtin_amdgcn_ballot_w64(nz) != 0;
+    if (j.qlen) {                                    // length mask (coattn_forward_len): a row past its question's length is not
+      const int m = r0 + i, bq = m / j.T;            // live whatever it holds (wave-uniform: one scalar load per row)
+      live = live && m < j.M && m - bq * j.T < min(max(j.qlen[bq], 1), j.T);
+    }
     if (live) bits |= 1u << (8 * wave + i);
     // (branch-free: a live row's store goes to an offset outside the buffer)
 #pragma unroll
@@ -184,6 +190,7 @@ size_t wsplit_bytes(int N, int K) { return (size_t)((N + 31) / 32) * ((K + 15) /
 
 static int check_rowflag_job(const RowFlagJob* rows) {
   CA_CHECK_ARG(rows->rowbits && rows->C && rows->bias_n && rows->M > 0 && rows->batch >= 1 && rows->batch <= 8 && rows->K % 256 == 0 &&
+               (!rows->qlen || (rows->T > 0 && rows->M % rows->T == 0)) &&
                rows->K <= 1024 && rows->N == rows->K && (rows->c_sm & 3) == 0 && ((long)(rows->M - 1) * rows->c_sm + rows->N) * 4 < 0x40000000L &&
                ((((uintptr_t)rows->C) | ((uintptr_t)rows->bias_n)) & 15) == 0 && ((rows->c_sz & 3) == 0) &&
                (rows->a_sm & 3) == 0 && ((long)(rows->M - 1) * rows->a_sm + rows->K) * 4 < 0x40000000L,

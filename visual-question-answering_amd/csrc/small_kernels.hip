@@ -45,13 +45,19 @@ __global__ __launch_bounds__(256) void gemv_generic(const float* X, const float*
 
 // ---- scores + softmax over the R rows of one batch item -----------------------------------
 // one workgroup per z; wave w handles rows w, w+4, ...; scores kept in LDS (R <= 4096).
+// len (may be NULL): the softmax runs over rows r < clamp(len[z], 1, R) only, the other rows get a = 0 exactly (the
+// question-length mask of coattn_forward_len); NULL: all R rows.
 __global__ __launch_bounds__(256) void score_softmax_kernel(const float* H, const float* w, const float* c,
-                                                            float* a, int R, int d) {
+                                                            float* a, int R, int d, const int* len) {
   extern __shared__ __attribute__((aligned(16))) float sc[];
   __shared__ float red[8];
   const int z = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* Hz = H + (long)z * R * d;
   const float c0 = c[0];
+  float* az = a + (long)z * R;
+  const int Rz = len ? min(max(len[z], 1), R) : R;
+  for (int r = Rz + (int)threadIdx.x; r < R; r += 256) az[r] = 0.f;   // rows past the length (only under a mask)
+  R = Rz;                                            // from here on: the rows the softmax runs over
   for (int r = wave; r < R; r += 4) {
     const float* hr = Hz + (long)r * d;
     float acc = 0.f;
@@ -77,7 +83,7 @@ __global__ __launch_bounds__(256) void score_softmax_kernel(const float* H, cons
   __syncthreads();
   s = (red[4] + red[5]) + (red[6] + red[7]);
   const float inv = 1.0f / s;
-  for (int r = threadIdx.x; r < R; r += 256) a[(long)z * R + r] = sc[r] * inv;
+  for (int r = threadIdx.x; r < R; r += 256) az[r] = sc[r] * inv;
 }
 
 // ds = a * (da - <a,da>), one wave per z
@@ -200,6 +206,15 @@ __global__ __launch_bounds__(256) void dtanh_kernel(const float* dC, const float
   out[idx] = dC[idx] * (1.0f - c * c);
 }
 
+// X[z][r][:W] = 0 for rows r >= clamp(len[z], 1, R): the rows past a question's length (C and dA of the general-shape path,
+// da_q before the softmax backward) under the length mask
+__global__ __launch_bounds__(256) void mask_rows_kernel(float* X, const int* len, int R, int W) {
+  const int z = blockIdx.y;
+  const int lz = min(max(len[z], 1), R);
+  for (long idx = (long)lz * W + (long)blockIdx.x * 256 + threadIdx.x; idx < (long)R * W; idx += (long)gridDim.x * 256)
+    X[(long)z * R * W + idx] = 0.f;
+}
+
 __global__ __launch_bounds__(256) void add_inplace_kernel(float* y, const float* x, long n, int accumulate) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= n) return;
@@ -239,10 +254,19 @@ int launch_gemv(const float* X, const float* u, float* y, int Z, int I, int K, i
 }
 
 int launch_score_softmax(const float* H, const float* w, const float* c, float* a, int Z, int R, int d,
-                         hipStream_t s) {
+                         hipStream_t s, const int* len) {
   CA_CHECK_ARG(Z > 0 && R > 0 && R <= 4096 && d > 0, "score_softmax: bad shape Z=%d R=%d d=%d", Z, R, d);
-  hipLaunchKernelGGL(score_softmax_kernel, dim3(Z), dim3(256), (size_t)R * sizeof(float), s, H, w, c, a, R, d);
+  hipLaunchKernelGGL(score_softmax_kernel, dim3(Z), dim3(256), (size_t)R * sizeof(float), s, H, w, c, a, R, d, len);
   CA_CHECK_LAUNCH("score_softmax");
+  return 0;
+}
+
+int launch_mask_rows(float* X, const int* len, int Z, int R, int W, hipStream_t s) {
+  CA_CHECK_ARG(X && len && Z > 0 && Z <= 65535 && R > 0 && W > 0, "mask_rows: bad argument");
+  const long n = (long)R * W;
+  const int gx = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+  hipLaunchKernelGGL(mask_rows_kernel, dim3(gx, Z), dim3(256), 0, s, X, len, R, W);
+  CA_CHECK_LAUNCH("mask_rows");
   return 0;
 }
 

@@ -28,6 +28,10 @@ reference to it across steps (a gradient logger, an EMA of gradients) must clone
 the buffers (C-ABI ``accumulate = 1``); with captured graphs, or when only some of the 16 parameters still hold the static
 buffer, it raises instead of dropping the earlier gradient.
 
+``question_mask=True``: the co-attention calls are the length-masked ones (``coattn_forward_len`` / ``coattn_backward_len``)
+reading a static int32 [B] length buffer, which every call of the node refills from its ``q_len`` argument before the
+forward is issued or replayed -- captured graphs read the lengths of the step they run.
+
 ``logits`` is returned as a fresh tensor (``alias_outputs=True``: the static buffer itself, overwritten by the next
 step).  A gradient arriving for ``logits`` is added by the head's backward in eager mode; under graph capture it raises.
 """
@@ -55,7 +59,8 @@ class HotPathGraph:
     MAX_KEYS = 8
 
     def __init__(self, co_attention, mlp_classify, B: int, N: int, T: int, need_dv: bool = False, flags: int = 0,
-                 capture: bool = True, direct_grads: bool = False, alias_outputs: bool = False):
+                 capture: bool = True, direct_grads: bool = False, alias_outputs: bool = False,
+                 question_mask: bool = False):
         self.co, self.mlp = co_attention, mlp_classify
         self.capture, self.direct_grads, self.alias_outputs = capture, direct_grads, alias_outputs
         self._warned_accumulate = False                          # (one warning when a backward adds into held gradients)
@@ -71,6 +76,8 @@ class HotPathGraph:
         self.V = torch.zeros((B, N, d), **f32)
         self.Q = [torch.zeros((B, T, d), **f32) for _ in range(3)]
         self.labels = torch.zeros((B,), device=dev, dtype=torch.int64)
+        # question lengths of the masked form (static: the plans / graphs hold its address), None when unmasked
+        self.q_len = torch.full((B,), T, device=dev, dtype=torch.int32) if question_mask else None
         # static outputs
         self.v = torch.empty((3, B, d), **f32); self.q = torch.empty((3, B, d), **f32)
         # logits and loss share one buffer: a step hands out ONE copy of it (two views), not two
@@ -99,6 +106,8 @@ class HotPathGraph:
         self._warm = False
         self._static = (self.V, self.Q[0], self.Q[1], self.Q[2], self.labels)
         self._lib = _lib.load()
+        self._co_fwd = self._lib.coattn_forward_len if question_mask else self._lib.coattn_forward
+        self._co_bwd = self._lib.coattn_backward_len if question_mask else self._lib.coattn_backward
         self.pair(self._static)
 
     @staticmethod
@@ -140,23 +149,25 @@ class HotPathGraph:
         rv, rq, rdx = rows(self.v), rows(self.q), rows(self.dx)
         vs = _strides(V)
         dvs = (N * d, d, 1) if self.dV is not None else (0, 0, 0)   # the static dV buffer is location-major
+        ql = (_ptr(self.q_len),) if self.q_len is not None else ()  # (the *_len calls: the lengths follow Q)
         plan = {
             "keep": (qptr, dqptr, p, pg, hp, hg, rv, rq, rdx),
-            "co_fwd": (_ptr(V), *vs, qptr, C.byref(p), _ptr(self.v), _ptr(self.q), _ptr(self.saved), _ptr(self.ws),
+            "co_fwd": (_ptr(V), *vs, qptr, *ql, C.byref(p), _ptr(self.v), _ptr(self.q), _ptr(self.saved), _ptr(self.ws),
                        B, N, T, d, 3, _lib.F32, self.flags),
             "head_fwd": (rv, rq, C.byref(hp), _ptr(labels), _ptr(self.logits), _ptr(self.loss), _ptr(self.hsaved),
                          B, d, mlp, K, _lib.F32, self.head_flags),
             "head_bwd": (rv, rq, C.byref(hp), _ptr(self.hsaved), _ptr(self.g_loss), None, rdx, None, C.byref(hg), 0,
                          _ptr(self.hws), B, d, mlp, K, _lib.F32, self.head_flags),
-            "co_bwd": (_ptr(V), *vs, qptr, C.byref(p), _ptr(self.saved), _ptr(self.dx), _ptr(self.dx), _ptr(self.dV), *dvs,
-                       dqptr, C.byref(pg), 0, _ptr(self.ws), B, N, T, d, 3, _lib.F32, self.flags),
+            "co_bwd": (_ptr(V), *vs, qptr, *ql, C.byref(p), _ptr(self.saved), _ptr(self.dx), _ptr(self.dx), _ptr(self.dV),
+                       *dvs, dqptr, C.byref(pg), 0, _ptr(self.ws), B, N, T, d, 3, _lib.F32, self.flags),
         }
+        ai = 15 + len(ql)                                        # index of co_bwd's `accumulate`
         # (variants of the two backward calls: a gradient arriving for the logits; accumulate = 1 for a second backward
         #  onto the same static gradient buffers; the loss's upstream gradient read where autograd left it)
         plan["head_bwd_args"] = lambda g_logits, acc, g_loss=None: (plan["head_bwd"][:4] + (_ptr(self.g_loss if g_loss is None else g_loss), _ptr(g_logits))   # noqa: E731
                                                                     + plan["head_bwd"][6:9] + (acc,) + plan["head_bwd"][10:])
-        plan["co_bwd_args"] = lambda acc: plan["co_bwd"][:15] + (acc,) + plan["co_bwd"][16:]   # noqa: E731
-        assert plan["head_bwd"][9] == 0 and plan["head_bwd"][5] is None and plan["co_bwd"][15] == 0
+        plan["co_bwd_args"] = lambda acc: plan["co_bwd"][:ai] + (acc,) + plan["co_bwd"][ai + 1:]   # noqa: E731
+        assert plan["head_bwd"][9] == 0 and plan["head_bwd"][5] is None and plan["co_bwd"][ai] == 0
         self._plans[key] = plan
         return plan
 
@@ -166,11 +177,11 @@ class HotPathGraph:
         plan = self._plan(ins)
         st = C.c_void_p(stream)
         if fwd:
-            _lib.check(lib.coattn_forward(*plan["co_fwd"], st), "coattn_forward")
+            _lib.check(self._co_fwd(*plan["co_fwd"], st), "coattn_forward")
             _lib.check(lib.coattn_head_forward(*plan["head_fwd"], st), "coattn_head_forward")
         if bwd:
             _lib.check(lib.coattn_head_backward(*plan["head_bwd"], st), "coattn_head_backward")
-            _lib.check(lib.coattn_backward(*plan["co_bwd"], st), "coattn_backward")
+            _lib.check(self._co_bwd(*plan["co_bwd"], st), "coattn_backward")
 
     def usable_in_place(self, ins) -> bool:
         B, N, T, d, _, _ = self.dims
@@ -229,7 +240,7 @@ class HotPathGraph:
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             with _lib.on_device(self.device):
                 _lib.check(self._lib.coattn_head_backward(*plan["head_bwd_args"](g_logits, accumulate, g_loss), st), "coattn_head_backward")
-                _lib.check(self._lib.coattn_backward(*plan["co_bwd_args"](accumulate), st), "coattn_backward")
+                _lib.check(self._co_bwd(*plan["co_bwd_args"](accumulate), st), "coattn_backward")
             return
         if pair is _EAGER:
             plan = plan or self._plan(ins)
@@ -237,11 +248,11 @@ class HotPathGraph:
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             with _lib.on_device(self.device):
                 if fwd:
-                    _lib.check(lib.coattn_forward(*plan["co_fwd"], st), "coattn_forward")
+                    _lib.check(self._co_fwd(*plan["co_fwd"], st), "coattn_forward")
                     _lib.check(lib.coattn_head_forward(*plan["head_fwd"], st), "coattn_head_forward")
                 else:
                     _lib.check(lib.coattn_head_backward(*plan["head_bwd"], st), "coattn_head_backward")
-                    _lib.check(lib.coattn_backward(*plan["co_bwd"], st), "coattn_backward")
+                    _lib.check(self._co_bwd(*plan["co_bwd"], st), "coattn_backward")
         else:
             pair[0 if fwd else 1].replay()
 
@@ -251,7 +262,7 @@ class HotPathGraph:
         self.run(pair, ins, True)
         self.run(pair, ins, False)
 
-    def __call__(self, x_img: torch.Tensor, x_ques: Sequence[torch.Tensor], labels: torch.Tensor):
+    def __call__(self, x_img: torch.Tensor, x_ques: Sequence[torch.Tensor], labels: torch.Tensor, q_len=None):
         # With direct gradients the parameters need not be inputs of the autograd node (their gradients do not travel through
         # autograd) as long as some input keeps the node alive -- the question levels of a trainable question encoder do;
         # 6 arguments instead of 22 through the Function machinery on every step.
@@ -263,6 +274,8 @@ class HotPathGraph:
                 and x_img.device == self.device
                 and (x_img.dtype != torch.float32 or not _is_native(x_img, lm_only=_coattention.CM_FEATURES != "inplace"))):
             x_img = native_features(x_img, out=self.V)
+        if self.q_len is not None:                               # (asynchronous: the calls below read the buffer in stream order)
+            self.q_len.copy_(_coattention.question_lengths(q_len, self.dims[0], self.device))
         if self.direct_grads and (x_ques[0].requires_grad or x_ques[1].requires_grad or x_ques[2].requires_grad or x_img.requires_grad):
             return _HotPathFn.apply(self, x_img, labels, *x_ques)
         return _HotPathFn.apply(self, x_img, labels, *x_ques, *self.co_params, *self.head_params)

@@ -334,14 +334,19 @@ class HierarchicalCoAttentionNet(nn.Module):
         """The forward pass from already-encoded image features [B,N,d] (model.py:171-187 minus the
         image encoder call): lets a frozen encoder run ahead on its own stream (train.Trainer).
         `x_img_features` may be a zero-argument callable returning the features.  With `labels` (int64 [B]) the
-        mean cross entropy of main.py:214 comes out of the answer head's own call: returns (logits, loss)."""
+        mean cross entropy of main.py:214 comes out of the answer head's own call: returns (logits, loss).
+        `x_ques_lens` reaches the co-attention too when its ``question_mask`` is on (ParallelCoAttention)."""
         x_ques_features = list(self.question_encoder(x_ques, x_ques_lens))
         if callable(x_img_features):            # resolved only now: the question side is queued first
             x_img_features = x_img_features()
+        masked = self._question_mask()
         if (labels is not None and (self.hot_path_graph or self.hot_path_static) and x_img_features.is_cuda
                 and torch.is_grad_enabled()):
-            return self._graphed(x_img_features, x_ques_features, labels)
-        x_img_attn, x_ques_attn = self.co_attention(x_img_features, x_ques_features)
+            return self._graphed(x_img_features, x_ques_features, labels, x_ques_lens if masked else None)
+        if masked:
+            x_img_attn, x_ques_attn = self.co_attention(x_img_features, x_ques_features, x_ques_lens)
+        else:
+            x_img_attn, x_ques_attn = self.co_attention(x_img_features, x_ques_features)
         if labels is not None:
             return self.mlp_classify.forward_loss(x_img_attn, x_ques_attn, labels)
         return self.mlp_classify(x_img_attn, x_ques_attn)
@@ -349,17 +354,24 @@ class HierarchicalCoAttentionNet(nn.Module):
     def forward_with_attention(self, x_img, x_ques, x_ques_lens):
         """Inference with the co-attention maps: (logits [B,K], a_v [3,B,N], a_q [3,B,T]) for the word, phrase and sentence
         levels.  Index n of a_v is location n of the encoder's flattened grid (model.py:215-217: row-major over 7 x 7 at
-        224 px, 14 x 14 at 448 px); a_q is unmasked over the T token positions (model.py:388).  The logits equal
-        `forward`'s under no_grad bit for bit.  Forward only: raises where a gradient would be needed."""
+        224 px, 14 x 14 at 448 px); a_q is unmasked over the T token positions (model.py:388) -- or, with the co-attention's
+        ``question_mask`` on, 0 past each question's length.  The logits equal `forward`'s under no_grad bit for bit.
+        Forward only: raises where a gradient would be needed."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("forward_with_attention is forward only: run it under torch.no_grad()")
         x_img_features = self.image_encoder(x_img)
         x_ques_features = [q if q.dtype == torch.float32 else q.float()       # (the fp32 island, as _CoAttentionFn's cast)
                            for q in self.question_encoder(x_ques, x_ques_lens)]
-        v, q, a_v, a_q = self.co_attention.forward_with_attention(x_img_features, x_ques_features)
+        if self._question_mask():
+            v, q, a_v, a_q = self.co_attention.forward_with_attention(x_img_features, x_ques_features, x_ques_lens)
+        else:
+            v, q, a_v, a_q = self.co_attention.forward_with_attention(x_img_features, x_ques_features)
         return self.mlp_classify(v, q), a_v, a_q
 
-    def _graphed(self, x_img_features, x_ques_features, labels):
+    def _question_mask(self) -> bool:
+        return bool(getattr(self.co_attention, "question_mask", False))
+
+    def _graphed(self, x_img_features, x_ques_features, labels, x_ques_lens=None):
         """co-attention + answer head + loss, forward AND backward, as one autograd node over static buffers (graph.py),
         built per (B, N, T) on first use: replayed from captured HIP graphs (``net.hot_path_graph = True``,
         ``Trainer(graph=True)``) or with its four C-ABI calls issued eagerly (``net.hot_path_static``, the Trainer's
@@ -370,7 +382,7 @@ class HierarchicalCoAttentionNet(nn.Module):
         T = x_ques_features[0].shape[1]
         key = (B, N, T, bool(x_img_features.requires_grad), bool(self.co_attention.bf16_projections),
                bool(self.mlp_classify.bf16_products), bool(self.hot_path_graph), bool(self.hot_path_direct_grads),
-               bool(self.co_attention.fast_products))
+               bool(self.co_attention.fast_products), self._question_mask())
         hp = self._graphs.get(key)
         # (the node reads the parameters where they lie: one built before the module was moved -- .to(), .cuda(), new
         #  Parameter objects -- would read the old storage)
@@ -379,8 +391,8 @@ class HierarchicalCoAttentionNet(nn.Module):
         if hp is None:
             hp = self._graphs[key] = HotPathGraph(self.co_attention, self.mlp_classify, B, N, T, need_dv=key[3],
                                                   flags=(_lib.FLAG_BF16_PROJ if key[4] else 0) | _lib.precision_flag(key[8] and not key[4]),
-                                                  capture=key[6], direct_grads=key[7])
-        return hp(x_img_features, x_ques_features, labels)
+                                                  capture=key[6], direct_grads=key[7], question_mask=key[9])
+        return hp(x_img_features, x_ques_features, labels, q_len=x_ques_lens)
 
 
 # ---- baseline model (BASELINE config 1: CPU plumbing, no custom kernels) ------------------

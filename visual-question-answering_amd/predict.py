@@ -9,8 +9,10 @@ README roadmap.  Same command line as ``train.py`` (the reference's flags) plus 
   answer indices and their softmax probabilities, best first (index 0 is UNKNOWN, main.py:155).
 * ``--attention_maps`` (``.npz``, ``attention*`` models only): ``a_v [S,3,H,W]`` -- the image attention of the word,
   phrase and sentence levels over the encoder's H x W grid (7 x 7 at 224 px, 14 x 14 at 448 px; model.py:215-217
-  flattens it row-major) --, ``a_q [S,3,T]`` -- the question attention over the T token positions, UNMASKED as the
-  reference's softmax (model.py:388): positions past ``ques_len`` carry weight too --, ``ques_len [S]`` and ``index [S]``.
+  flattens it row-major) --, ``a_q [S,3,T]`` -- the question attention over the T token positions: by default UNMASKED as
+  the reference's softmax (model.py:388), so positions past ``ques_len`` carry weight too; with ``--question_mask true``
+  (the flag the checkpoint was trained with: it is not stored in the checkpoint) it is 0 past ``ques_len`` and sums to 1
+  over the question's words --, ``ques_len [S]`` and ``index [S]``.
 * stdout: one JSON line ``{samples, accuracy, top{K}_accuracy, loss, pairs_per_s}`` (accuracies in percent, as
   ``Trainer.validate``; loss = mean cross entropy per sample).
 

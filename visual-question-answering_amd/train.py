@@ -98,18 +98,35 @@ def bert_question_params(hidden_dim: int = 512, vocab_size: int = BERT_VOCAB, be
     return dict(bert=BertEmbeddings(cfg), bert_dim=bert_dim, hidden_dim=hidden_dim)
 
 
-def build_model(model_name: str, vocab_size: int, num_cls: int, **kw) -> nn.Module:
-    """K + 1 output classes: index 0 is UNKNOWN (main.py:155)."""
+def set_question_mask(model: nn.Module, question_mask: bool) -> None:
+    """--question_mask: the co-attention's softmax over question tokens restricted to each question's length
+    (ParallelCoAttention.question_mask; off = the reference's unmasked softmax, model.py:388).  The models without a
+    co-attention have nothing to mask: asking for it there is an error."""
+    co = getattr(model, "co_attention", None)
+    if co is None or not hasattr(co, "question_mask"):
+        if question_mask:
+            raise ValueError("--question_mask applies to the co-attention models (--model attention*), not to %s"
+                             % type(model).__name__)
+        return
+    co.question_mask = bool(question_mask)
+
+
+def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, **kw) -> nn.Module:
+    """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`."""
     cfg = setup_model_configs(model_name, vocab_size, **kw)
-    return cfg["model"](cfg["question_params"], cfg["image_params"], K=num_cls + 1)
+    model = cfg["model"](cfg["question_params"], cfg["image_params"], K=num_cls + 1)
+    set_question_mask(model, question_mask)
+    return model
 
 
 def model_from_args(args):
     """The model of a parsed command line, as main.py:388 builds it: (model, registry entry).  attention_bert: the token ids
-    are BERT's, so args.vocab_size becomes BERT's vocabulary.  (train.main, predict.main)"""
+    are BERT's, so args.vocab_size becomes BERT's vocabulary.  --question_mask is applied to the co-attention (the Trainer's
+    steps and `validate` then pass the lengths through).  (train.main, predict.main)"""
     cfg = setup_model_configs(args, args.vocab_size)             # (as main.py:388)
     args.vocab_size = cfg.get("vocab_size", args.vocab_size)
     model = cfg["model"](cfg["question_params"], cfg["image_params"], K=args.num_cls + 1)
+    set_question_mask(model, getattr(args, "question_mask", False))
     return model, cfg
 
 
@@ -526,6 +543,10 @@ def build_parser():
                     help="validate every this many steps (0: at --log_interval, as main.py:225-246, when --val_size > 0)")
     ap.add_argument("--val_batches", type=int, default=0, help="validation batches (overrides --val_size // --batch_size)")
     ap.add_argument("--save_path", type=str, default=None, help="also save the final state_dict here")
+    ap.add_argument("--question_mask", type=str2bool, default="false",
+                    help="co-attention over each question's first ques_len tokens only (a_q = 0 on pad tokens); default: "
+                         "unmasked, as the reference (model.py:388).  Checkpoints hold only the state_dict, so the flag is not "
+                         "recorded: give prediction the value the checkpoint was trained with (a mismatch goes undetected)")
     return ap
 
 
