@@ -232,6 +232,44 @@ int coattn_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, con
                     const coattn_param_grads* pg, int accumulate,
                     void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
 
+/* ---- differentiable attention maps (v0.9.0) ----------------------------------------------------------------------
+ * For a training loss ON the maps (attention supervision such as a KL term against human attention maps, an entropy penalty,
+ * logging the maps of the batch being trained on).
+ *   coattn_forward_maps(_len) : coattn_forward(_len) that also hands a_v [L,B,N] / a_q [L,B,T] to the caller.  `saved`, av_out
+ *       and aq_out are REQUIRED (NULL: a negative code and coattn_last_error()).  v_out, q_out and `saved` are bit-identical to
+ *       coattn_forward(_len)'s, the maps to coattn_infer(_len)'s: the kernels store each map twice from the same epilogue --
+ *       into `saved`, where the backward reads it, and into the caller's buffer -- with no extra launch.
+ *   coattn_backward_maps(_len) : coattn_backward(_len) with two more arguments right after gq,
+ *       g_av : [L,B,N] upstream gradient of a_v, or NULL (= 0);
+ *       g_aq : [L,B,T] upstream gradient of a_q, or NULL (= 0).
+ *     Per sample b and level l only the two softmax backward steps change:
+ *       da_v = V g_v + G_av,  ds_v = a_v (.) (da_v - sum_n a_v da_v)
+ *       da_q = Q g_q + G_aq,  ds_q = a_q (.) (da_q - sum_t a_q da_q)
+ *     and everything downstream of ds_v / ds_q (dZ, dP_v, dP_q, dC, dA, dV, dQ, every parameter gradient) is the backward of
+ *     coattn_backward(_len).  With both NULL every output is bit-identical to coattn_backward(_len)'s, accumulate included.
+ *     Under the length mask G_aq[l,b,t] for t >= len_b is READ AS 0: a NaN or inf a caller leaves in a pad slot changes no
+ *     output bit.
+ *   `saved` must come from a coattn_forward_maps(_len) or a coattn_forward(_len) with the same inputs, parameter values, flags
+ *   (and q_len) -- both leave the same bits in it.  Same buffer sizes (coattn_workspace_bytes), paths and modes as the forms
+ *   above. */
+int coattn_forward_maps(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                        const coattn_params* p, void* v_out, void* q_out, void* av_out, void* aq_out, void* saved, void* ws,
+                        int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+int coattn_forward_maps_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                            const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* av_out,
+                            void* aq_out, void* saved, void* ws, int B, int N, int T, int d, int L, int dtype, int flags,
+                            void* stream);
+int coattn_backward_maps(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                         const coattn_params* p, const void* saved, const void* gv, const void* gq, const void* g_av,
+                         const void* g_aq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                         const coattn_param_grads* pg, int accumulate,
+                         void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+int coattn_backward_maps_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                             const int32_t* q_len, const coattn_params* p, const void* saved, const void* gv, const void* gq,
+                             const void* g_av, const void* g_aq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD,
+                             void* const* dQ, const coattn_param_grads* pg, int accumulate,
+                             void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+
 /* Range report of the tolerance mode (COATTN_FLAG_FAST16).  SYNCHRONISES `stream`, reads the status words the last
  * coattn_forward left in `saved` (or in `ws`, when that call was given saved = NULL) and returns
  *    0  every operand converted to FP16 pieces lay inside the exact-piece range (or the call did not use FP16 pieces:

@@ -20,7 +20,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_ce_status", "coattn_p2p_enable_peer", "coattn_p2p_reduce_scatter", "coattn_p2p_all_gather",
            "coattn_profile_begin", "coattn_profile_end", "coattn_features_native", "coattn_status",
            "coattn_phrase_status", "coattn_status_accumulate", "coattn_phrase_status_accumulate", "coattn_infer",
-           "coattn_forward_len", "coattn_infer_len", "coattn_attention_forward_len", "coattn_backward_len")
+           "coattn_forward_len", "coattn_infer_len", "coattn_attention_forward_len", "coattn_backward_len",
+           "coattn_forward_maps", "coattn_forward_maps_len", "coattn_backward_maps", "coattn_backward_maps_len")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -129,6 +130,11 @@ def load() -> C.CDLL:
     lib.coattn_attention_forward_len.argtypes = _with_len(lib.coattn_attention_forward.argtypes)
     lib.coattn_infer_len.argtypes = _with_len(lib.coattn_infer.argtypes)
     lib.coattn_backward_len.argtypes = _with_len(lib.coattn_backward.argtypes)
+    # differentiable maps: the forward takes av_out, aq_out before `saved`; the backward g_av, g_aq right after gq
+    lib.coattn_forward_maps.argtypes = lib.coattn_forward.argtypes[:8] + [C.c_void_p, C.c_void_p] + lib.coattn_forward.argtypes[8:]
+    lib.coattn_backward_maps.argtypes = lib.coattn_backward.argtypes[:9] + [C.c_void_p, C.c_void_p] + lib.coattn_backward.argtypes[9:]
+    lib.coattn_forward_maps_len.argtypes = _with_len(lib.coattn_forward_maps.argtypes)
+    lib.coattn_backward_maps_len.argtypes = _with_len(lib.coattn_backward_maps.argtypes)
     lib.coattn_gemm_f32.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
     lib.coattn_gemm_bf16.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
     lib.coattn_phrase_workspace_bytes.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_size_t)] * 3

@@ -4,7 +4,9 @@ Same constructor, attribute names (=> identical ``state_dict`` keys ``W_b, W_v, 
 and ``forward(x_img, x_ques_hierarchy)`` signature as the reference class; the computation runs
 in the HIP library through the C-ABI of ``include/coattn.h`` on the caller's current stream.
 Opt-in beyond the reference: ``question_mask=True`` restricts the question-side attention to the
-first ``x_ques_lens[b]`` tokens of every question (the C-ABI's ``*_len`` entry points).
+first ``x_ques_lens[b]`` tokens of every question (the C-ABI's ``*_len`` entry points), and
+``forward(..., return_attention=True)`` also returns the attention maps a_v, a_q as differentiable
+tensors (the C-ABI's ``coattn_forward_maps`` / ``coattn_backward_maps``), for losses on the maps.
 """
 from __future__ import annotations
 
@@ -210,14 +212,113 @@ class _CoAttentionFn(torch.autograd.Function):
         return (dV, *grads, None, None, *dQs)
 
 
+class _CoAttentionMapsFn(torch.autograd.Function):
+    """The co-attention with differentiable attention maps: forward -> coattn_forward_maps(_len), returning (v, q, a_v, a_q)
+    with v, q [L,B,d], a_v [L,B,N], a_q [L,B,T]; backward -> coattn_backward_maps(_len), which adds the maps' own upstream
+    gradients in the two softmax backward steps (include/coattn.h).  A map whose gradient autograd gives as None goes in as
+    NULL (the backward is then coattn_backward's bit for bit), a missing g_v / g_q as zeros.  With no input that needs a
+    gradient the forward is coattn_infer(_len): the same maps, no backward state."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
+    def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques):
+        if not x_img.is_cuda:
+            raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
+        if x_img.dtype != torch.float32 or any(q.dtype != torch.float32 for q in x_ques):
+            raise RuntimeError("ParallelCoAttention (HIP) computes in fp32; got %s" % x_img.dtype)
+        lib = _lib.load()
+        L = len(x_ques)
+        B, N, d = x_img.shape
+        T = x_ques[0].shape[1]
+        for q in x_ques:
+            if tuple(q.shape) != (B, T, d):
+                raise RuntimeError("question features must all be [B,T,d] = %s, got %s" % ((B, T, d), tuple(q.shape)))
+        V = _native_layout(x_img)
+        Qs = [q.contiguous() for q in x_ques]
+        params = [t.contiguous() for t in (W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q)]
+        need_grad = any(ctx.needs_input_grad)
+        sb, fb, _ = _lib.workspace_bytes(B, N, T, d, L, impl)
+        dev = x_img.device
+        out_v = torch.empty((L, B, d), device=dev, dtype=torch.float32)
+        out_q = torch.empty((L, B, d), device=dev, dtype=torch.float32)
+        a_v = torch.empty((L, B, N), device=dev, dtype=torch.float32)
+        a_q = torch.empty((L, B, T), device=dev, dtype=torch.float32)
+        saved = torch.empty(sb // 4, device=dev, dtype=torch.float32) if need_grad else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws = _lib.scratch(fb, dev, stream)
+        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
+        p = _lib.Params(*[t.data_ptr() for t in params])
+        lens = () if q_len is None else (_ptr(q_len),)
+        with _lib.on_device(dev):
+            if need_grad:
+                fn = "coattn_forward_maps" if q_len is None else "coattn_forward_maps_len"
+                _lib.check(getattr(lib, fn)(_ptr(V), *_strides(V), qptr, *lens, C.byref(p), _ptr(out_v), _ptr(out_q),
+                                            _ptr(a_v), _ptr(a_q), _ptr(saved), _ptr(ws), B, N, T, d, L, _lib.F32, impl,
+                                            C.c_void_p(stream)), fn)
+            else:
+                fn = "coattn_infer" if q_len is None else "coattn_infer_len"
+                _lib.check(getattr(lib, fn)(_ptr(V), *_strides(V), qptr, *lens, C.byref(p), _ptr(out_v), _ptr(out_q),
+                                            _ptr(a_v), _ptr(a_q), _ptr(ws), B, N, T, d, L, _lib.F32, impl,
+                                            C.c_void_p(stream)), fn)
+        if impl & _lib.FLAG_FAST16:                   # tolerance mode: where _lib.check_range() finds this call's status words
+            _lib.note_status("coattn", saved if saved is not None else ws, (B, N, T, d, L), dev)
+        ctx.set_materialize_grads(False)              # (an unused map's gradient stays None: NULL for the C-ABI)
+        if need_grad:
+            ctx.save_for_backward(V, saved, *params, *Qs)
+            ctx.dims = (B, N, T, d, L, impl)
+            ctx.q_len = q_len                         # (the backward must see the forward's lengths)
+        return out_v, out_q, a_v, a_q
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g_v, g_q, g_av, g_aq):
+        lib = _lib.load()
+        B, N, T, d, L, impl = ctx.dims
+        sv = ctx.saved_tensors
+        V, saved, params, Qs = sv[0], sv[1], sv[2:10], sv[10:]
+        dev = V.device
+        g_v = g_v.contiguous() if g_v is not None else torch.zeros((L, B, d), device=dev)
+        g_q = g_q.contiguous() if g_q is not None else torch.zeros((L, B, d), device=dev)
+        g_av = g_av.contiguous() if g_av is not None else None
+        g_aq = g_aq.contiguous() if g_aq is not None else None
+        _, _, bb = _lib.workspace_bytes(B, N, T, d, L, impl)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ws = _lib.scratch(bb, dev, stream)
+        need_dv = ctx.needs_input_grad[0]
+        dV = None
+        if need_dv:                         # gradient of x_img[B,N,d] in the layout of x_img itself
+            dV = (torch.empty((B, N, d), device=dev) if V.stride(2) == 1
+                  else torch.empty((B, d, N), device=dev).permute(0, 2, 1))
+        dQs = [torch.empty_like(q) for q in Qs]
+        grads = [torch.empty_like(t) for t in params]
+        pg = _lib.ParamGrads(*[t.data_ptr() for t in grads])
+        p = _lib.Params(*[t.data_ptr() for t in params])
+        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
+        dqptr = (C.c_void_p * L)(*[q.data_ptr() for q in dQs])
+        args = (C.byref(p), _ptr(saved), _ptr(g_v), _ptr(g_q), _ptr(g_av), _ptr(g_aq), _ptr(dV),
+                *(_strides(dV) if need_dv else (0, 0, 0)), dqptr, C.byref(pg), 0, _ptr(ws), B, N, T, d, L, _lib.F32, impl,
+                C.c_void_p(stream))
+        with _lib.on_device(dev):
+            if ctx.q_len is None:
+                _lib.check(lib.coattn_backward_maps(_ptr(V), *_strides(V), qptr, *args), "coattn_backward_maps")
+            else:
+                _lib.check(lib.coattn_backward_maps_len(_ptr(V), *_strides(V), qptr, _ptr(ctx.q_len), *args),
+                           "coattn_backward_maps_len")
+        return (dV, *grads, None, None, *dQs)
+
+
 def coattention(x_img: torch.Tensor, x_ques: Sequence[torch.Tensor], W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q,
-                impl: int | None = None, q_len: torch.Tensor | None = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                impl: int | None = None, q_len: torch.Tensor | None = None, return_attention: bool = False):
     """Functional form: returns (v, q), each [L,B,d].  q_len: None (the reference's unmasked softmax over the T tokens), or
-    the question lengths (see `question_lengths`): attention over the first q_len[b] tokens of question b."""
+    the question lengths (see `question_lengths`): attention over the first q_len[b] tokens of question b.
+    return_attention=True: returns (v, q, a_v [L,B,N], a_q [L,B,T]), the maps differentiable (a loss on them reaches every
+    input through coattn_backward_maps)."""
     if impl is None:
         impl = _impl_flag()
     if q_len is not None:
         q_len = question_lengths(q_len, x_img.shape[0], x_img.device)
+    if return_attention:
+        return _CoAttentionMapsFn.apply(x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques)
     return _CoAttentionFn.apply(x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques)
 
 
@@ -261,17 +362,32 @@ class ParallelCoAttention(nn.Module):
             raise ValueError("ParallelCoAttention(question_mask=True) needs x_ques_lens, the length of every question")
         return question_lengths(x_ques_lens, x_img.shape[0], x_img.device)
 
-    def forward(self, x_img: torch.Tensor, x_ques_hierarchy: Sequence[torch.Tensor], x_ques_lens=None) -> Tuple[List, List]:
+    def forward(self, x_img: torch.Tensor, x_ques_hierarchy: Sequence[torch.Tensor], x_ques_lens=None,
+                return_attention: bool = False):
         """x_img [B,N,d]; x_ques_hierarchy: list of [B,T,d] -> (list of v_l [B,d], list of q_l [B,d]).
-        x_ques_lens ([B] integers, host or device): read only under ``question_mask``."""
+        x_ques_lens ([B] integers, host or device): read only under ``question_mask``.
+        return_attention=True -> (list of v_l, list of q_l, a_v [L,B,N], a_q [L,B,T]) with the maps DIFFERENTIABLE: a loss on
+        them (attention supervision, an entropy penalty) reaches the parameters, the question features and x_img
+        (coattn_forward_maps / coattn_backward_maps).  v / q and every gradient through them are those of the plain call.
+        Where no gradient can be needed (no_grad, or no input that requires one) this is `forward_with_attention`, bit for
+        bit."""
+        if return_attention:
+            ques = list(x_ques_hierarchy)
+            params = (self.W_v.weight, self.W_v.bias, self.W_q.weight, self.W_q.bias, self.w_v.weight, self.w_v.bias,
+                      self.w_q.weight, self.w_q.bias)
+            if not (torch.is_grad_enabled() and any(t.requires_grad for t in (x_img, *ques, *params))):
+                return self.forward_with_attention(x_img, ques, x_ques_lens)
         impl = _impl_flag() | (_lib.FLAG_BF16_PROJ if self.bf16_projections else 0) | _lib.precision_flag(self.fast_products)
         q_len = self._lengths(x_img, x_ques_lens)
         if x_img.is_cuda and not (x_img.requires_grad and torch.is_grad_enabled()):
             x_img = native_features(x_img)           # frozen encoder: bf16 / non-native strides in one library pass
-        v, q = coattention(x_img, list(x_ques_hierarchy), self.W_v.weight, self.W_v.bias, self.W_q.weight,
-                           self.W_q.bias, self.w_v.weight, self.w_v.bias, self.w_q.weight, self.w_q.bias, impl=impl,
-                           q_len=q_len)
+        out = coattention(x_img, list(x_ques_hierarchy), self.W_v.weight, self.W_v.bias, self.W_q.weight,
+                          self.W_q.bias, self.w_v.weight, self.w_v.bias, self.w_q.weight, self.w_q.bias, impl=impl,
+                          q_len=q_len, return_attention=return_attention)
+        v, q = out[0], out[1]
         n = v.shape[0]
+        if return_attention:
+            return [v[l] for l in range(n)], [q[l] for l in range(n)], out[2], out[3]
         return [v[l] for l in range(n)], [q[l] for l in range(n)]
 
     def forward_with_attention(self, x_img: torch.Tensor, x_ques_hierarchy: Sequence[torch.Tensor], x_ques_lens=None):

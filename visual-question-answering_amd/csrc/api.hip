@@ -16,7 +16,7 @@ void coattn_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int coattn_version(void) { return 800; }   // 0.8.0: the length-masked forms coattn_forward_len / _infer_len / _attention_forward_len / _backward_len; 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
+extern "C" int coattn_version(void) { return 900; }   // 0.9.0: coattn_forward_maps(_len) / coattn_backward_maps(_len) (differentiable attention maps); 0.8.0: the length-masked forms coattn_forward_len / _infer_len / _attention_forward_len / _backward_len; 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
 
 // ---------------------------------------------------------------------------------------
 // per-kernel timing (bench.py's backward roofline legs): HIP events recorded between the launches of the calls made
@@ -511,9 +511,10 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
 }
 
 // everything after the projections: affinity, H_v / H_q, scores, softmax, attended reductions
-// av_out / aq_out: the caller's map buffers [L][B][N] / [L][B][T] (coattn_infer), else NULL: the maps go to `sv`
+// av_out / aq_out: the caller's map buffers [L][B][N] / [L][B][T] (coattn_infer), else NULL: the maps go to `sv`;
+// dual (coattn_forward_maps): the maps go to `sv` AND to av_out / aq_out, from the same softmax launches
 int general_attention(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, float* v_out,
-                      float* q_out, float* sv, float* Hv, float* av_out = nullptr, float* aq_out = nullptr) {
+                      float* q_out, float* sv, float* Hv, float* av_out = nullptr, float* aq_out = nullptr, bool dual = false) {
   const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
   float* Pv = sv + sp.Pv;
   const size_t BTd = (size_t)c.B * c.T * c.d, BTN = (size_t)c.B * c.T * c.N;
@@ -521,14 +522,16 @@ int general_attention(const Ctx& c, const float* V, const float* const* Q, const
     float* Pq = sv + sp.Pq + l * BTd;
     float* C = sv + sp.C + l * BTN;
     float* Hq = sv + sp.Hq + l * BTd;
-    float* av = (av_out ? av_out : sv + sp.av) + (size_t)l * c.B * c.N;
-    float* aq = (aq_out ? aq_out : sv + sp.aq) + (size_t)l * c.B * c.T;
+    float* av = (av_out && !dual ? av_out : sv + sp.av) + (size_t)l * c.B * c.N;
+    float* aq = (aq_out && !dual ? aq_out : sv + sp.aq) + (size_t)l * c.B * c.T;
+    float* av2 = dual ? av_out + (size_t)l * c.B * c.N : nullptr;
+    float* aq2 = dual ? aq_out + (size_t)l * c.B * c.T : nullptr;
     CA_TRY(affinity(c, Q[l], V, C));
     if (c.qlen) CA_TRY(launch_mask_rows(C, c.qlen, c.B, c.T, c.N, c.s));   // length mask: C rows t >= len_b are zero
     CA_TRY(ct_times(c, C, Pq, Pv, Hv, 1));
     CA_TRY(c_times(c, C, Pv, Pq, Hq, 1));
-    CA_TRY(launch_score_softmax(Hv, (const float*)p->w_v, (const float*)p->c_v, av, c.B, c.N, c.d, c.s));
-    CA_TRY(launch_score_softmax(Hq, (const float*)p->w_q, (const float*)p->c_q, aq, c.B, c.T, c.d, c.s, c.qlen));
+    CA_TRY(launch_score_softmax(Hv, (const float*)p->w_v, (const float*)p->c_v, av, c.B, c.N, c.d, c.s, nullptr, av2));
+    CA_TRY(launch_score_softmax(Hq, (const float*)p->w_q, (const float*)p->c_q, aq, c.B, c.T, c.d, c.s, c.qlen, aq2));
     // v = sum_n a_v[n] V[:,n]   (model.py:391);  q = sum_t a_q[t] Q[t,:]   (model.py:392)
     CA_TRY(launch_gemv(V, av, v_out + (size_t)l * c.B * c.d, c.B, c.d, c.N, c.vl.sB, c.vl.sD, c.vl.sN, c.N, c.d, c.s));
     CA_TRY(launch_gemv(Q[l], aq, q_out + (size_t)l * c.B * c.d, c.B, c.d, c.T, (int64_t)c.T * c.d, 1, c.d, c.T, c.d, c.s));
@@ -538,7 +541,8 @@ int general_attention(const Ctx& c, const float* V, const float* const* Q, const
 
 int backward_general(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, const float* sv,
                      const float* gv, const float* gq, float* dV, const VLayout& dvl, float* const* dQ,
-                     const coattn_param_grads* pg, int accumulate, float* ws) {
+                     const coattn_param_grads* pg, int accumulate, float* ws, const float* g_av = nullptr,
+                     const float* g_aq = nullptr) {
   const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
   const BwdPlan bp = plan_bwd(c.B, c.N, c.T, c.d, c.L);
   const int B = c.B, N = c.N, T = c.T, d = c.d, L = c.L;
@@ -568,10 +572,11 @@ int backward_general(const Ctx& c, const float* V, const float* const* Q, const 
     CA_TRY(ct_times(c, C, Pq, Pv, Hv, 1));
     // softmax backward of a_v, a_q
     CA_TRY(launch_gemv(V, gv + l * Bd, dav, B, N, d, c.vl.sB, c.vl.sN, c.vl.sD, d, N, c.s));
-    CA_TRY(launch_softmax_bwd(av, dav, dsv, B, N, c.s));
+    // (coattn_backward_maps: da + G, the map's own upstream gradient -- G_aq read as 0 past a question's length)
+    CA_TRY(launch_softmax_bwd(av, dav, dsv, B, N, c.s, g_av ? g_av + (size_t)l * B * N : nullptr));
     CA_TRY(launch_gemv(Q[l], gq + l * Bd, daq, B, T, d, (int64_t)T * d, d, 1, d, T, c.s));
     if (c.qlen) CA_TRY(launch_mask_rows(daq, c.qlen, B, T, 1, c.s));   // (a_q = 0 there: ds_q = 0 whatever the pad rows hold)
-    CA_TRY(launch_softmax_bwd(aq, daq, dsq, B, T, c.s));
+    CA_TRY(launch_softmax_bwd(aq, daq, dsq, B, T, c.s, g_aq ? g_aq + (size_t)l * B * T : nullptr, c.qlen));
     // dw_v += ds_v^T H_v ; dc_v += sum ds_v ; same for q
     const int rpc_v = (B * N + 255) / 256 > 32 ? (B * N + 255) / 256 : 32;
     CA_TRY(launch_colsum_partial(dsv, Hv, part, B * N, d, rpc_v, &nch, c.s));
@@ -711,7 +716,8 @@ static int check_vlayout(const VLayout& v, int B, int N, int d, const char* what
 }
 
 // saved == NULL: forward only -- the state lives in the workspace, and the fused kernel stores no C / H_q (nothing reads
-// them); av_out / aq_out (may be NULL): the attention maps go straight to the caller's buffers
+// them); av_out / aq_out (may be NULL): the attention maps go straight to the caller's buffers -- with `saved` as well
+// (coattn_forward_maps) the maps go to both, from the same epilogue
 static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, const coattn_params* p, void* v_out,
                         void* q_out, void* saved, void* ws, int B, int N, int T, int d, int L, int dtype, int flags,
                         void* stream, bool do_proj, bool do_attn, void* av_out = nullptr, void* aq_out = nullptr,
@@ -739,12 +745,14 @@ static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, 
     CA_TRY(general_projections(c, (const float*)V, (const float* const*)Q, p, sv,
                                (char*)ws + fwd_ws_floats(B, N, T, d, L) * sizeof(float), saved != nullptr));
   if (!do_attn) return 0;
+  const bool dual = saved && av_out;                  // coattn_forward_maps
   if (fused)
     return fused_attention_forward(B, N, T, d, L, (const float*)V, vl, (const float* const*)Q, p, (float*)v_out,
                                    (float*)q_out, sv, tail, c.s, c.bf16_proj ? 1 : 0, np_fwd(flags, c.f16_proj),
-                                   (float*)av_out, (float*)aq_out, saved != nullptr ? 1 : 0, q_len);
+                                   dual ? nullptr : (float*)av_out, dual ? nullptr : (float*)aq_out, saved != nullptr ? 1 : 0,
+                                   q_len, dual ? (float*)av_out : nullptr, dual ? (float*)aq_out : nullptr);
   return general_attention(c, (const float*)V, (const float* const*)Q, p, (float*)v_out, (float*)q_out, sv, tail,
-                           (float*)av_out, (float*)aq_out);
+                           (float*)av_out, (float*)aq_out, dual);
 }
 
 extern "C" int coattn_forward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -758,6 +766,23 @@ extern "C" int coattn_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t
                               const coattn_params* p, void* v_out, void* q_out, void* saved, void* ws, int B, int N,
                               int T, int d, int L, int dtype, int flags, void* stream) {
   return coattn_forward_len(V, v_sB, v_sN, v_sD, Q, nullptr, p, v_out, q_out, saved, ws, B, N, T, d, L, dtype, flags, stream);
+}
+
+extern "C" int coattn_forward_maps_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                       const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* av_out,
+                                       void* aq_out, void* saved, void* ws, int B, int N, int T, int d, int L, int dtype, int flags,
+                                       void* stream) {
+  CA_CHECK_ARG(saved != nullptr, "forward_maps: null `saved` (the backward state is required; coattn_infer keeps none)");
+  CA_CHECK_ARG(av_out && aq_out, "forward_maps: null map buffer (av_out [L,B,N] and aq_out [L,B,T] are required)");
+  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
+                      dtype, flags, stream, true, true, av_out, aq_out, q_len);
+}
+
+extern "C" int coattn_forward_maps(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                   const coattn_params* p, void* v_out, void* q_out, void* av_out, void* aq_out, void* saved,
+                                   void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
+  return coattn_forward_maps_len(V, v_sB, v_sN, v_sD, Q, nullptr, p, v_out, q_out, av_out, aq_out, saved, ws, B, N, T, d, L,
+                                 dtype, flags, stream);
 }
 
 extern "C" int coattn_infer_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -789,11 +814,12 @@ extern "C" int coattn_attention_forward(const void* V, int64_t v_sB, int64_t v_s
                                       flags, stream);
 }
 
-extern "C" int coattn_backward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
-                                   const int32_t* q_len, const coattn_params* p, const void* saved, const void* gv,
-                                   const void* gq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
-                                   const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d,
-                                   int L, int dtype, int flags, void* stream) {
+// g_av / g_aq (may be NULL = 0; coattn_backward_maps): the upstream gradients of the maps [L][B][N] / [L][B][T]
+static int backward_impl(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const int32_t* q_len,
+                         const coattn_params* p, const void* saved, const void* gv, const void* gq, const void* g_av,
+                         const void* g_aq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                         const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d, int L, int dtype,
+                         int flags, void* stream) {
   CA_TRY(check_shape(B, N, T, d, L, dtype));
   CA_CHECK_ARG(V && Q && p && saved && gv && gq && dQ && pg && ws, "backward: null argument");  // dV may be NULL
   const VLayout vl{(long)v_sB, (long)v_sN, (long)v_sD};
@@ -817,9 +843,38 @@ extern "C" int coattn_backward_len(const void* V, int64_t v_sB, int64_t v_sN, in
                           (float*)ws, c.s, c.bf16_proj ? 1 : 0,
                           gemm_w_enabled() ? 1 : 0, np_bwd(flags),
                           rowbits_in_saved(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, flags, fused) ? 1 : 0,
-                          q_len);
+                          q_len, (const float*)g_av, (const float*)g_aq);
   return backward_general(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, (const float*)gv,
-                          (const float*)gq, (float*)dV, dvl, (float* const*)dQ, pg, accumulate, (float*)ws);
+                          (const float*)gq, (float*)dV, dvl, (float* const*)dQ, pg, accumulate, (float*)ws, (const float*)g_av,
+                          (const float*)g_aq);
+}
+
+extern "C" int coattn_backward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                   const int32_t* q_len, const coattn_params* p, const void* saved, const void* gv,
+                                   const void* gq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                                   const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d,
+                                   int L, int dtype, int flags, void* stream) {
+  return backward_impl(V, v_sB, v_sN, v_sD, Q, q_len, p, saved, gv, gq, nullptr, nullptr, dV, dv_sB, dv_sN, dv_sD, dQ, pg,
+                       accumulate, ws, B, N, T, d, L, dtype, flags, stream);
+}
+
+extern "C" int coattn_backward_maps_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                        const int32_t* q_len, const coattn_params* p, const void* saved, const void* gv,
+                                        const void* gq, const void* g_av, const void* g_aq, void* dV, int64_t dv_sB,
+                                        int64_t dv_sN, int64_t dv_sD, void* const* dQ, const coattn_param_grads* pg,
+                                        int accumulate, void* ws, int B, int N, int T, int d, int L, int dtype, int flags,
+                                        void* stream) {
+  return backward_impl(V, v_sB, v_sN, v_sD, Q, q_len, p, saved, gv, gq, g_av, g_aq, dV, dv_sB, dv_sN, dv_sD, dQ, pg,
+                       accumulate, ws, B, N, T, d, L, dtype, flags, stream);
+}
+
+extern "C" int coattn_backward_maps(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                    const coattn_params* p, const void* saved, const void* gv, const void* gq, const void* g_av,
+                                    const void* g_aq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                                    const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d, int L,
+                                    int dtype, int flags, void* stream) {
+  return backward_impl(V, v_sB, v_sN, v_sD, Q, nullptr, p, saved, gv, gq, g_av, g_aq, dV, dv_sB, dv_sN, dv_sD, dQ, pg,
+                       accumulate, ws, B, N, T, d, L, dtype, flags, stream);
 }
 
 extern "C" int coattn_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,

@@ -35,7 +35,9 @@ namespace {
 // DPB (with SP): dP_v and dP_q are stored as bf16 (same index order, 2-byte elements) -- every consumer is a GEMM of the
 // reduced-precision mode, which would round them on its way in anyway.  Lane pairs (r, r + 1) meet through a DPP quad
 // permute, the even lane stores one dword for both channels.
-template <int NT, int NW, int NP, bool DPB>
+// GMAP: ds_v with the map's own upstream gradient (coattn_backward_maps, BwdArgs::gav; fused.h softmax_bwd_v) -- a template
+// flag, as the length mask: the code objects without it unchanged.
+template <int NT, int NW, int NP, bool DPB, bool GMAP = false>
 __global__ __launch_bounds__(NW * 64, 2) void bwd_nat32_kernel(const BwdArgs a) {
   static_assert(!DPB || NP == 1, "bf16 dP storage belongs to the reduced-precision mode");
   constexpr int NPAD = 32 * NT;
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(NW * 64, 2) void bwd_nat32_kernel(const BwdArgs a) 
       if (NP == 3) *reinterpret_cast<u32x2*>(Cimg + 2 * PIECE + off) = u32x2{ll[0], ll[1]};
     }
     if (w == NW - 1) {                               // ds_v of this (sample, level); its sum is the dc_v partial
-      const float tot = softmax_bwd_v(a, b, l, lane, dsvs, NPAD);
+      const float tot = softmax_bwd_v<GMAP>(a, b, l, lane, dsvs, NPAD);
       if (lane == 0) a.dcs_part[pair] = tot;
     }
     if (w == 0 && lane < 32) dsqs[lane] = a.dsq[pair * 32 + lane];
@@ -360,7 +362,8 @@ __global__ __launch_bounds__(NW * 64, 2) void bwd_nat32_kernel(const BwdArgs a) 
 #define DC32_KO 0   // developer knock-outs of bwd_dc32_kernel (wrong results; tools/ab_dc32.sh): 1 the tanh' arithmetic (one VALU
 #endif              // operation per element instead of five), 2 the operand splits (one conversion per pair), 4 the MFMAs, 8 the P_v fragment loads
 // MASK: the length-masked form (coattn_backward_len, BwdArgs::qlen) -- a template flag: the unmasked code objects unchanged
-template <int NT, int NW, int NP, bool MASK = false>
+// GMAP: as bwd_nat32_kernel's
+template <int NT, int NW, int NP, bool MASK = false, bool GMAP = false>
 __global__ __launch_bounds__(NW * 64, 2) void bwd_dc32_kernel(const BwdArgs a) {
   constexpr int NPAD = 32 * NT, PIECE = NPAD * 32, NTHR = NW * 64, SLD = 36;
   constexpr int GT = NT > COATTN_DC_GT ? COATTN_DC_GT : NT;   // location tiles per group
@@ -405,7 +408,7 @@ __global__ __launch_bounds__(NW * 64, 2) void bwd_dc32_kernel(const BwdArgs a) {
       if (NP >= 2) *reinterpret_cast<u32x2*>(Cimg + PIECE + off) = u32x2{mm[0], mm[1]};
       if (NP == 3) *reinterpret_cast<u32x2*>(Cimg + 2 * PIECE + off) = u32x2{ll[0], ll[1]};
     }
-    if (w == NW - 1) softmax_bwd_v(a, b, l, lane, dsvs, NPAD);   // ds_v of this (sample, level), as bwd_nat32_kernel computes it
+    if (w == NW - 1) softmax_bwd_v<GMAP>(a, b, l, lane, dsvs, NPAD);   // ds_v of this (sample, level), as bwd_nat32_kernel computes it
   }
   lds_barrier();
   const int ntiles = (N + 31) >> 5;
@@ -572,12 +575,12 @@ __global__ __launch_bounds__(NW * 64, 2) void bwd_dc32_kernel(const BwdArgs a) {
   if (GT > 3 && rest == 3) group(t0, std::integral_constant<int, 3>());
 }
 
-template <int NT, int NW, int NP, bool MASK = false>
+template <int NT, int NW, int NP, bool MASK = false, bool GMAP = false>
 int launch_dc32(const BwdArgs& a, hipStream_t s) {
   constexpr int NPAD = 32 * NT;
   const size_t lds = (size_t)3 * NPAD * 32 * 2 + (size_t)NPAD * 4 + (size_t)NW * 32 * 36 * 4;
   const int groups = (a.B + 7) / 8;
-  hipLaunchKernelGGL((bwd_dc32_kernel<NT, NW, NP, MASK>), dim3(groups * a.L * 8), dim3(NW * 64), lds, s, a);
+  hipLaunchKernelGGL((bwd_dc32_kernel<NT, NW, NP, MASK, GMAP>), dim3(groups * a.L * 8), dim3(NW * 64), lds, s, a);
   CA_CHECK_LAUNCH("bwd_dc32");
   return 0;
 }
@@ -822,12 +825,12 @@ int launch_dq32(const DqArgs& a, hipStream_t s) {
   return 0;
 }
 
-template <int NT, int NW, int NP, bool DPB>
+template <int NT, int NW, int NP, bool DPB, bool GMAP = false>
 int launch_nat32(const BwdArgs& a, hipStream_t s) {
   constexpr int NPAD = 32 * NT;
   const size_t lds = (size_t)3 * NPAD * 32 * 2 + (size_t)NPAD * 4 + 32 * 4;
   const int groups = (a.B + 7) / 8;
-  hipLaunchKernelGGL((bwd_nat32_kernel<NT, NW, NP, DPB>), dim3(groups * a.L * 8), dim3(NW * 64), lds, s, a);
+  hipLaunchKernelGGL((bwd_nat32_kernel<NT, NW, NP, DPB, GMAP>), dim3(groups * a.L * 8), dim3(NW * 64), lds, s, a);
   CA_CHECK_LAUNCH("bwd_nat32");
   return 0;
 }
@@ -836,18 +839,22 @@ int launch_nat32(const BwdArgs& a, hipStream_t s) {
 
 // The reduced-precision mode (a.bf16: one MFMA per product) exists for the four-wave kernels (d % 512 == 0); other widths
 // run the fp32 mode.  a.np = 2 selects the two-piece width of the fp32 mode (fused.h), anything else the exact split.
-int launch_bwd_nat32(const BwdArgs& a, hipStream_t s) {
+template <bool G>
+int dispatch_nat32(const BwdArgs& a, hipStream_t s) {
   const bool small_n = a.N <= 64, w2 = a.np == 2;
   if (a.d % 512 == 0) {
-    if (a.bf16 && a.dp_bf16) return small_n ? launch_nat32<2, 4, 1, true>(a, s) : launch_nat32<7, 4, 1, true>(a, s);
+    if (a.bf16 && a.dp_bf16) return small_n ? launch_nat32<2, 4, 1, true, G>(a, s) : launch_nat32<7, 4, 1, true, G>(a, s);
     CA_CHECK_ARG(!a.dp_bf16, "bwd_nat32: bf16 dP storage exists in the reduced-precision mode only");
-    if (a.bf16) return small_n ? launch_nat32<2, 4, 1, false>(a, s) : launch_nat32<7, 4, 1, false>(a, s);
-    if (w2) return small_n ? launch_nat32<2, 4, 2, false>(a, s) : launch_nat32<7, 4, 2, false>(a, s);
-    return small_n ? launch_nat32<2, 4, 3, false>(a, s) : launch_nat32<7, 4, 3, false>(a, s);
+    if (a.bf16) return small_n ? launch_nat32<2, 4, 1, false, G>(a, s) : launch_nat32<7, 4, 1, false, G>(a, s);
+    if (w2) return small_n ? launch_nat32<2, 4, 2, false, G>(a, s) : launch_nat32<7, 4, 2, false, G>(a, s);
+    return small_n ? launch_nat32<2, 4, 3, false, G>(a, s) : launch_nat32<7, 4, 3, false, G>(a, s);
   }
   CA_CHECK_ARG(!a.dp_bf16, "bwd_nat32: bf16 dP storage needs d % 512 == 0");
-  if (w2) return small_n ? launch_nat32<2, 2, 2, false>(a, s) : launch_nat32<7, 2, 2, false>(a, s);
-  return small_n ? launch_nat32<2, 2, 3, false>(a, s) : launch_nat32<7, 2, 3, false>(a, s);
+  if (w2) return small_n ? launch_nat32<2, 2, 2, false, G>(a, s) : launch_nat32<7, 2, 2, false, G>(a, s);
+  return small_n ? launch_nat32<2, 2, 3, false, G>(a, s) : launch_nat32<7, 2, 3, false, G>(a, s);
+}
+int launch_bwd_nat32(const BwdArgs& a, hipStream_t s) {
+  return a.gav ? dispatch_nat32<true>(a, s) : dispatch_nat32<false>(a, s);   // (coattn_backward_maps: da_v += G_av)
 }
 
 int launch_bwd_dq32(const DqArgs& a, int lm, hipStream_t s) {
@@ -864,17 +871,18 @@ int launch_bwd_dq32(const DqArgs& a, int lm, hipStream_t s) {
   return go(std::integral_constant<int, 3>());
 }
 
-template <bool M>
+template <bool M, bool G>
 int dispatch_dc32(const BwdArgs& a, hipStream_t s) {
   const bool small_n = a.N <= 64, w2 = a.np == 2;
   if (a.d % 512 == 0) {
-    if (a.bf16) return small_n ? launch_dc32<2, 4, 1, M>(a, s) : launch_dc32<7, 4, 1, M>(a, s);
-    if (w2) return small_n ? launch_dc32<2, 4, 2, M>(a, s) : launch_dc32<7, 4, 2, M>(a, s);
-    return small_n ? launch_dc32<2, 4, 3, M>(a, s) : launch_dc32<7, 4, 3, M>(a, s);
+    if (a.bf16) return small_n ? launch_dc32<2, 4, 1, M, G>(a, s) : launch_dc32<7, 4, 1, M, G>(a, s);
+    if (w2) return small_n ? launch_dc32<2, 4, 2, M, G>(a, s) : launch_dc32<7, 4, 2, M, G>(a, s);
+    return small_n ? launch_dc32<2, 4, 3, M, G>(a, s) : launch_dc32<7, 4, 3, M, G>(a, s);
   }
-  if (w2) return small_n ? launch_dc32<2, 2, 2, M>(a, s) : launch_dc32<7, 2, 2, M>(a, s);
-  return small_n ? launch_dc32<2, 2, 3, M>(a, s) : launch_dc32<7, 2, 3, M>(a, s);
+  if (w2) return small_n ? launch_dc32<2, 2, 2, M, G>(a, s) : launch_dc32<7, 2, 2, M, G>(a, s);
+  return small_n ? launch_dc32<2, 2, 3, M, G>(a, s) : launch_dc32<7, 2, 3, M, G>(a, s);
 }
 int launch_bwd_dc32(const BwdArgs& a, hipStream_t s) {
-  return a.qlen ? dispatch_dc32<true>(a, s) : dispatch_dc32<false>(a, s);   // (length-masked: dA rows past len_b zero)
+  if (a.gav) return a.qlen ? dispatch_dc32<true, true>(a, s) : dispatch_dc32<false, true>(a, s);   // (coattn_backward_maps)
+  return a.qlen ? dispatch_dc32<true, false>(a, s) : dispatch_dc32<false, false>(a, s);   // (length-masked: dA rows past len_b zero)
 }

@@ -109,6 +109,8 @@ struct PreArgs {
   int B, N, T, d, L;
   TnDyn dyn; TnDynPlan* plan_out;        // plan_out != NULL: ONE more workgroup (the launch's last) evaluates the split-K plan of the
                                          // weight gradients over the live question rows (fused.h tn_dyn_plan) and leaves it there
+  const float* gaq;                      // (bwd_pre_maps_kernel, coattn_backward_maps) [L][B][T] upstream gradient of a_q: da_q += G_aq
+                                         // for t < len_b, read as 0 beyond (whatever the pad slots hold)
 };
 
 // Blocks [0, L*B): one workgroup (256 threads) per (sample, level), question side -- softmax backward of a_q
@@ -118,8 +120,9 @@ struct PreArgs {
 //  rows of the da_q dot products, all 14 / 2 x 7 H_q rows of the sweep, the 4 V rows of a da_v wave -- costs registers the
 //  da_v blocks of the same launch pay for with occupancy: 60 -> 102 / 128 VGPRs, 27.7 -> 32.6 / 37.3 us at N = 196,
 //  22.7 -> 22.3 / 21.6 at N = 49.)
-__global__ __launch_bounds__(256) void bwd_pre_kernel(const PreArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
+// GMAP: the map-gradient form (bwd_pre_maps_kernel); the body is shared so that bwd_pre_kernel's code object stays as it was.
+template <bool GMAP>
+__device__ __forceinline__ void bwd_pre_body(const PreArgs& a, float* lds) {
   if (a.plan_out && (int)blockIdx.x == a.L * a.B + a.dav_gx * a.B) {
     if (threadIdx.x < 64) {                          // one full wave
       const TnDynPlan pl = tn_dyn_plan(a.dyn);
@@ -166,7 +169,11 @@ __global__ __launch_bounds__(256) void bwd_pre_kernel(const PreArgs a) {
     //  that not even the sign of that zero depends on the padding)
     const int tl = a.qlen ? min(max(a.qlen[b], 1), T) : T;
     const float aqv = (lane < T) ? a.aq[pair * T + lane] : 0.f;
-    const float x = (lane < tl) ? daq[lane] : 0.f;
+    float x = (lane < tl) ? daq[lane] : 0.f;
+    if constexpr (GMAP) {                            // da_q += G_aq on the live tokens; a pad slot's value is selected away
+      const float g = a.gaq[pair * T + min(lane, T - 1)];
+      x = (lane < tl) ? x + g : 0.f;
+    }
     if (tl < T) {                                    // (length mask only) dA rows past the question
       float* da = a.dA + pair * (size_t)T * a.N;
       for (int i = tl * a.N + lane; i < T * a.N; i += 64) da[i] = 0.f;
@@ -177,6 +184,14 @@ __global__ __launch_bounds__(256) void bwd_pre_kernel(const PreArgs a) {
     const float tot_q = wave_sum(sq);
     if (lane == 0) a.dcs_part[(size_t)a.L * B + pair] = tot_q;       // [2][L*B]
   }
+}
+__global__ __launch_bounds__(256) void bwd_pre_kernel(const PreArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  bwd_pre_body<false>(a, lds);
+}
+__global__ __launch_bounds__(256) void bwd_pre_maps_kernel(const PreArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  bwd_pre_body<true>(a, lds);
 }
 
 
@@ -292,7 +307,9 @@ hipError_t set_lds(K kern, size_t bytes) {
 
 int launch_pre(const PreArgs& a, hipStream_t s) {
   const size_t lds = 768;                                           // the 3 x 64 g values of a channel-major da_v block; 32 da_q
-  hipLaunchKernelGGL(bwd_pre_kernel, dim3(a.L * a.B + a.dav_gx * a.B + (a.plan_out ? 1 : 0)), dim3(256), lds, s, a);
+  const dim3 grid(a.L * a.B + a.dav_gx * a.B + (a.plan_out ? 1 : 0));
+  if (a.gaq) hipLaunchKernelGGL(bwd_pre_maps_kernel, grid, dim3(256), lds, s, a);
+  else hipLaunchKernelGGL(bwd_pre_kernel, grid, dim3(256), lds, s, a);
   CA_CHECK_LAUNCH("bwd_pre");
   // (the image side's softmax backward -- ds_v from these partials -- happens in the prologues of bwd_dc32_kernel and
   //  bwd_nat32_kernel: fused.h softmax_bwd_v)
@@ -308,7 +325,8 @@ int fused_backward_supported(int B, int N, int T, int d, int L) { return fused_s
 int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl, const float* const* Q,
                    const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
                    const VLayout& dvl, float* const* dQ, const coattn_param_grads* pg, int accumulate, float* ws,
-                   hipStream_t s, int bf16_proj, int wgemm, int np, int live_rows, const int* qlen) {
+                   hipStream_t s, int bf16_proj, int wgemm, int np, int live_rows, const int* qlen, const float* g_av,
+                   const float* g_aq) {
   // np: width of the fp32 mode's contractions (fused.h): 2 = hi + mid in the three fused kernels and in the GEMM launch
   // (dW_v, dW_q, dQ = dP_q W_q), 3 = the exact split everywhere; dV (general GEMM) is always exact
   np = (np == 2 && !bf16_proj) ? 2 : 3;
@@ -331,6 +349,7 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
   for (int l = 0; l < 8; ++l) pa.Q[l] = l < L ? Q[l] : nullptr;
   pa.gq = gq; pa.av = saved + so.av; pa.aq = saved + so.aq;
   pa.dsq = ws + wo.dsq; pa.dcs_part = ws + wo.dcs_part; pa.qlen = qlen; pa.dA = ws + wo.dA;
+  pa.gaq = g_aq;                                     // (coattn_backward_maps; NULL: the plain pre-pass)
   pa.B = B; pa.N = N; pa.T = T; pa.d = d; pa.L = L;
   // (exact mode: the forward's bitmap of the live question rows is in `saved`; the plan of the weight gradients over those rows
   //  is a function of it and of shapes known here -- evaluated once, by an extra workgroup of this launch)
@@ -362,6 +381,7 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
   ba.ko_dpv = ko_dpv;
   ba.dp_bf16 = 0;
   ba.qlen = qlen;
+  ba.gav = g_av;                                     // (coattn_backward_maps; NULL: the kernels without the G_av operand)
   CA_TRY(launch_bwd_dc32(ba, s));                    // dC, dA                       (coattn_bwd32.hip)
   prof_mark(s, "bwd_dc32");
   // which of the backward's GEMMs take the hand-scheduled kernels (decided here: when all three do, they share ONE

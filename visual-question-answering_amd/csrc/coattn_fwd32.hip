@@ -78,7 +78,8 @@ __device__ __forceinline__ void vmcnt_wait(int n) {
 // FV: the kernel also attends the image features, v_l = a_v^T V (model.py:391) -- location-major V, NT = 2, four waves.
 // MASK: the length-masked form (coattn_forward_len, FwdArgs::qlen); a template flag so that the unmasked code objects stay
 // what they were (the runtime test alone moved the tolerance instantiations by 2 - 4 VGPRs).
-template <int NT, int NW, bool LM, int NP_, bool FV = false, bool MASK = false>
+// MAPS: the maps are stored twice from the same epilogue (coattn_forward_maps, FwdArgs::av2 / aq2) -- a template flag too.
+template <int NT, int NW, bool LM, int NP_, bool FV = false, bool MASK = false, bool MAPS = false>
 __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs a) {
   static_assert(!FV || (LM && NT == 2 && NW == 4), "the fused v pass: location-major features, N <= 64, 256 threads");
   constexpr bool HF = NP_ == 4;
@@ -758,6 +759,7 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
     for (int k = 0; k < PER; ++k) {
       const int n = lane + 64 * k;
       if (n < N) avg[n] = sc[k] * inv;
+      if (MAPS && n < N) a.av2[pair * (size_t)N + n] = sc[k] * inv;
       if (FV) avs[n] = sc[k] * inv;                  // (zeros beyond N)
     }
   }
@@ -776,6 +778,7 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
     const float aqv = e / se;
     if (lane < 32) aqs[lane] = aqv;                  // zeros beyond T
     if (lane < T) a.aq[pair * (size_t)T + lane] = aqv;
+    if (MAPS && lane < T) a.aq2[pair * (size_t)T + lane] = aqv;
   }
   lds_barrier();
   float aqr[kTRows];
@@ -883,7 +886,7 @@ __global__ __launch_bounds__(256) void attend_v_lm_kernel(const float* V, long v
   }
 }
 
-template <int NT, int NW, bool LM, int NP, bool FV = false, bool MASK = false>
+template <int NT, int NW, bool LM, int NP, bool FV = false, bool MASK = false, bool MAPS = false>
 int launch_fwd32(const FwdArgs& a, hipStream_t s) {
   constexpr int NPAD = 32 * NT;
   constexpr int RING_SLOTS = (NT + 1) * ((NT + 1 >= 6) ? 1 : 2);
@@ -892,17 +895,17 @@ int launch_fwd32(const FwdArgs& a, hipStream_t s) {
   const size_t lds = lds_p2 > lds_p1 ? lds_p2 : lds_p1;
   static DeviceOnce once;                            // the attribute is per device
   CA_TRY(once.run([&] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK, MAPS>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }, "coattn_fwd32"));
   const int groups = (a.B + 7) / 8;
   dim3 grid(groups * a.L * 8), block(NW * 64);
-  hipLaunchKernelGGL((coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK>), grid, block, lds, s, a);
+  hipLaunchKernelGGL((coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK, MAPS>), grid, block, lds, s, a);
   CA_CHECK_LAUNCH("coattn_fwd32");
   return 0;
 }
 
-template <bool LM, bool M>
+template <bool LM, bool M, bool MP>
 int dispatch_fwd32(const FwdArgs& a, hipStream_t s) {
   const bool small_n = a.N <= 64;
   const bool w2 = a.np == 2;                         // phase 2 on two bf16 pieces
@@ -910,27 +913,32 @@ int dispatch_fwd32(const FwdArgs& a, hipStream_t s) {
   if (a.d % 512 == 0) {
     if constexpr (LM) {
       if (small_n && a.v_out) {                      // the kernel attends the image features too (FwdArgs::v_out)
-        if (a.bf16) return launch_fwd32<2, 4, true, 1, true, M>(a, s);
-        if (hf) return launch_fwd32<2, 4, true, 4, true, M>(a, s);
-        return w2 ? launch_fwd32<2, 4, true, 2, true, M>(a, s) : launch_fwd32<2, 4, true, 3, true, M>(a, s);
+        if (a.bf16) return launch_fwd32<2, 4, true, 1, true, M, MP>(a, s);
+        if (hf) return launch_fwd32<2, 4, true, 4, true, M, MP>(a, s);
+        return w2 ? launch_fwd32<2, 4, true, 2, true, M, MP>(a, s) : launch_fwd32<2, 4, true, 3, true, M, MP>(a, s);
       }
     }
-    if (a.bf16) return small_n ? launch_fwd32<2, 4, LM, 1, false, M>(a, s) : launch_fwd32<7, 4, LM, 1, false, M>(a, s);
-    if (hf) return small_n ? launch_fwd32<2, 4, LM, 4, false, M>(a, s) : launch_fwd32<7, 4, LM, 4, false, M>(a, s);
-    if (w2) return small_n ? launch_fwd32<2, 4, LM, 2, false, M>(a, s) : launch_fwd32<7, 4, LM, 2, false, M>(a, s);
-    return small_n ? launch_fwd32<2, 4, LM, 3, false, M>(a, s) : launch_fwd32<7, 4, LM, 3, false, M>(a, s);
+    if (a.bf16) return small_n ? launch_fwd32<2, 4, LM, 1, false, M, MP>(a, s) : launch_fwd32<7, 4, LM, 1, false, M, MP>(a, s);
+    if (hf) return small_n ? launch_fwd32<2, 4, LM, 4, false, M, MP>(a, s) : launch_fwd32<7, 4, LM, 4, false, M, MP>(a, s);
+    if (w2) return small_n ? launch_fwd32<2, 4, LM, 2, false, M, MP>(a, s) : launch_fwd32<7, 4, LM, 2, false, M, MP>(a, s);
+    return small_n ? launch_fwd32<2, 4, LM, 3, false, M, MP>(a, s) : launch_fwd32<7, 4, LM, 3, false, M, MP>(a, s);
   }
-  if (hf) return small_n ? launch_fwd32<2, 2, LM, 4, false, M>(a, s) : launch_fwd32<7, 2, LM, 4, false, M>(a, s);
-  if (w2) return small_n ? launch_fwd32<2, 2, LM, 2, false, M>(a, s) : launch_fwd32<7, 2, LM, 2, false, M>(a, s);
-  return small_n ? launch_fwd32<2, 2, LM, 3, false, M>(a, s) : launch_fwd32<7, 2, LM, 3, false, M>(a, s);   // (the fp32 mode at these widths)
+  if (hf) return small_n ? launch_fwd32<2, 2, LM, 4, false, M, MP>(a, s) : launch_fwd32<7, 2, LM, 4, false, M, MP>(a, s);
+  if (w2) return small_n ? launch_fwd32<2, 2, LM, 2, false, M, MP>(a, s) : launch_fwd32<7, 2, LM, 2, false, M, MP>(a, s);
+  return small_n ? launch_fwd32<2, 2, LM, 3, false, M, MP>(a, s) : launch_fwd32<7, 2, LM, 3, false, M, MP>(a, s);   // (the fp32 mode at these widths)
 }
 
 }  // namespace
 
 int fused32_forward(const FwdArgs& a, hipStream_t s) {
   CA_CHECK_ARG(!a.v_out || (a.lm && a.N <= 64 && a.d % 512 == 0), "fused forward: the in-kernel v pass needs location-major features, N <= 64, d %% 512 == 0");
-  if (a.qlen) return a.lm ? dispatch_fwd32<true, true>(a, s) : dispatch_fwd32<false, true>(a, s);   // length-masked
-  return a.lm ? dispatch_fwd32<true, false>(a, s) : dispatch_fwd32<false, false>(a, s);
+  CA_CHECK_ARG(!a.av2 == !a.aq2, "fused forward: both map copies or neither");
+  if (a.av2) {                                       // coattn_forward_maps: the maps to `saved` and to the caller's buffers
+    if (a.qlen) return a.lm ? dispatch_fwd32<true, true, true>(a, s) : dispatch_fwd32<false, true, true>(a, s);
+    return a.lm ? dispatch_fwd32<true, false, true>(a, s) : dispatch_fwd32<false, false, true>(a, s);
+  }
+  if (a.qlen) return a.lm ? dispatch_fwd32<true, true, false>(a, s) : dispatch_fwd32<false, true, false>(a, s);   // length-masked
+  return a.lm ? dispatch_fwd32<true, false, false>(a, s) : dispatch_fwd32<false, false, false>(a, s);
 }
 
 int launch_attend_v_lm(const float* V, long v_sB, const float* av, float* v_out, int B, int N, int d, int L, hipStream_t s) {

@@ -243,13 +243,15 @@ int launch_gemm_bf16in(const coattn_gemm_desc& g, hipStream_t s);
 int launch_gemv(const float* X, const float* u, float* y, int Z, int I, int K,
                 int64_t x_sz, int64_t x_si, int64_t x_sk, int64_t u_sz, int64_t y_sz, hipStream_t s);
 // a[z][r] = softmax_r( H[z][r][:] . w + c[0] ),  H rows contiguous (length d); len (may be NULL): [Z] lengths, the softmax
-// over r < clamp(len[z], 1, R) and a = 0 beyond
+// over r < clamp(len[z], 1, R) and a = 0 beyond; a2 (may be NULL): every value of a is stored there too (coattn_forward_maps)
 int launch_score_softmax(const float* H, const float* w, const float* c, float* a,
-                         int Z, int R, int d, hipStream_t s, const int* len = nullptr);
+                         int Z, int R, int d, hipStream_t s, const int* len = nullptr, float* a2 = nullptr);
 // X[z][r][0 .. W) = 0 for r >= clamp(len[z], 1, R)   (X: [Z][R][W] contiguous)
 int launch_mask_rows(float* X, const int* len, int Z, int R, int W, hipStream_t s);
-// ds[z][r] = a[z][r] * (da[z][r] - sum_r a*da)
-int launch_softmax_bwd(const float* a, const float* da, float* ds, int Z, int R, hipStream_t s);
+// ds[z][r] = a[z][r] * (da[z][r] - sum_r a*da); g (may be NULL; coattn_backward_maps): da + g in place of da on the rows
+// r < clamp(len[z], 1, R) (len NULL: all rows), 0 in place of da beyond
+int launch_softmax_bwd(const float* a, const float* da, float* ds, int Z, int R, hipStream_t s, const float* g = nullptr,
+                       const int* len = nullptr);
 // part[chunk][j] = sum_{r in chunk} s[r] * X[r][j]   (s may be NULL -> 1); X: [R][d] contiguous
 // returns number of chunks through *nchunks; part must hold nchunks*d floats
 int launch_colsum_partial(const float* s, const float* X, float* part, int R, int d, int rows_per_chunk,

@@ -20,13 +20,15 @@ int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, c
                             const float* const* Q, const coattn_params* p, float* v_out, float* q_out, float* saved,
                             float* ws, hipStream_t s, int bf16 = 0, int np = 3,   // bf16: reduced precision, one MFMA per product; np: width of phase 2
                             float* av = nullptr, float* aq = nullptr, int keep = 1,
-                            const int* qlen = nullptr);   // qlen: [B] question lengths (coattn_forward_len), NULL = unmasked
+                            const int* qlen = nullptr,    // qlen: [B] question lengths (coattn_forward_len), NULL = unmasked
+                            float* av_copy = nullptr, float* aq_copy = nullptr);   // (coattn_forward_maps) the maps ALSO go here
 int fused_backward_supported(int B, int N, int T, int d, int L);
 int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl, const float* const* Q,
                    const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
                    const VLayout& dvl, float* const* dQ, const coattn_param_grads* pg, int accumulate, float* ws,
                    hipStream_t s, int bf16_proj, int wgemm, int np = 3, int live_rows = 0,   // wgemm: gemm_w / gemm_tn enabled; np: width of the contractions (3 | 2); live_rows: `saved` holds the forward's bitmap of the non-zero question rows
-                   const int* qlen = nullptr);   // qlen: the forward's question lengths (NULL = unmasked)
+                   const int* qlen = nullptr,    // qlen: the forward's question lengths (NULL = unmasked)
+                   const float* g_av = nullptr, const float* g_aq = nullptr);   // (coattn_backward_maps) upstream gradients of the maps, NULL = 0
 
 // Diagnostic build only (tools/probe_stamps.py, -DCOATTN_STAMPS=1): wave 0 of every workgroup writes the
 // 100 MHz constant clock at its phase boundaries into the (otherwise unused) forward workspace tail.
@@ -444,6 +446,8 @@ struct FwdArgs {
   int keep;              // 1: C and H_q are stored for the backward; 0 (forward only, coattn_infer): their buffer resources are
                          // zero bytes long, so every store to them is dropped in hardware (same code, no new instantiation)
   const int* qlen;       // [B] question lengths (coattn_forward_len), clamped into [1, T]; NULL: every row counts (the reference)
+  float* av2;            // (MAPS instantiations, coattn_forward_maps) a second store of a_v [L][B][N] / a_q [L][B][T] from the same
+  float* aq2;            // epilogue: the caller's map buffers, while av / aq stay the copies in `saved` the backward reads
 };
 
 // arguments of the two big fused backward kernels (coattn_fused_bwd.hip, coattn_bwd32.hip)
@@ -472,30 +476,42 @@ struct BwdArgs {
   int dp_bf16;            // (with bf16, bwd_nat32_kernel) dPv / dPq are bf16 arrays of the same index order
   int ko_dpv;             // developer knock-out (DEV builds only, wrong results): bwd_nat32 stores dP_v of level 0 alone
   const int* qlen;        // [B] question lengths of the forward (clamped into [1, T]): dA rows t >= len are zero; NULL: unmasked
+  const float* gav;       // (GMAP instantiations, coattn_backward_maps) upstream gradient of a_v [L][B][N], added to da_v
 };
 
 // Image-side softmax backward of one (sample, level) by ONE wave: da_v = the sum of the channel-chunk partials,
 // ds_v = a_v (da_v - <a_v, da_v>) into the LDS array dsvs[0 .. npad) (zeros beyond N); returns sum_n ds_v (the dc_v partial,
 // valid in every lane).  Both big backward kernels run it in their prologue (same arithmetic, same values) -- it used to
 // be a launch of its own (one wave per pair, 5 us of launch latency).  N <= 256.
+// GMAP (coattn_backward_maps): da_v += G_av, the upstream gradient of the map itself, before the dot product.
+template <bool GMAP = false>
 __device__ __forceinline__ float softmax_bwd_v(const BwdArgs& a, int b, int l, int lane, float* dsvs, int npad) {
   const int N = a.N, nkc = a.nkc;
   const float* pp = a.dav_part + (size_t)b * nkc * 3 * N + (size_t)l * N;
   const float* avp = a.av + ((size_t)l * a.B + b) * N;
   // the lane's four locations are requested TOGETHER, from clamped addresses (a guarded load is a branch and a wait of its own:
   // four memory latencies in a row at the head of both big kernels); per location the chunks add up in the same order as before
-  float da[4] = {0.f, 0.f, 0.f, 0.f}, avv[4];
+  float da[4] = {0.f, 0.f, 0.f, 0.f}, avv[4], gav[4];
   int idx[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) idx[k] = min(lane + 64 * k, N - 1);
 #pragma unroll
   for (int k = 0; k < 4; ++k) avv[k] = avp[idx[k]];
+  if constexpr (GMAP) {                              // (with the a_v values: same clamped addresses, no wait of its own)
+    const float* gp = a.gav + ((size_t)l * a.B + b) * N;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) gav[k] = gp[idx[k]];
+  }
   for (int kc = 0; kc < nkc; ++kc) {
     float t[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) t[k] = pp[(size_t)kc * 3 * N + idx[k]];
 #pragma unroll
     for (int k = 0; k < 4; ++k) da[k] += t[k];
+  }
+  if constexpr (GMAP) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) da[k] += gav[k];
   }
   float dot = 0.f, tot = 0.f;
 #pragma unroll

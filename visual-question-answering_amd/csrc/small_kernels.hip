@@ -47,16 +47,21 @@ __global__ __launch_bounds__(256) void gemv_generic(const float* X, const float*
 // one workgroup per z; wave w handles rows w, w+4, ...; scores kept in LDS (R <= 4096).
 // len (may be NULL): the softmax runs over rows r < clamp(len[z], 1, R) only, the other rows get a = 0 exactly (the
 // question-length mask of coattn_forward_len); NULL: all R rows.
-__global__ __launch_bounds__(256) void score_softmax_kernel(const float* H, const float* w, const float* c,
-                                                            float* a, int R, int d, const int* len) {
-  extern __shared__ __attribute__((aligned(16))) float sc[];
-  __shared__ float red[8];
+// DUAL (score_softmax2_kernel, coattn_forward_maps): every value of a is also stored into a2 (the caller's map buffer).  The body
+// is shared so that score_softmax_kernel's code object stays as it was.
+template <bool DUAL>
+__device__ __forceinline__ void score_softmax_body(const float* H, const float* w, const float* c, float* a, float* a2, int R,
+                                                   int d, const int* len, float* sc, float* red) {
   const int z = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* Hz = H + (long)z * R * d;
   const float c0 = c[0];
   float* az = a + (long)z * R;
   const int Rz = len ? min(max(len[z], 1), R) : R;
-  for (int r = Rz + (int)threadIdx.x; r < R; r += 256) az[r] = 0.f;   // rows past the length (only under a mask)
+  float* az2 = DUAL ? a2 + (long)z * R : nullptr;
+  for (int r = Rz + (int)threadIdx.x; r < R; r += 256) {   // rows past the length (only under a mask)
+    az[r] = 0.f;
+    if (DUAL) az2[r] = 0.f;
+  }
   R = Rz;                                            // from here on: the rows the softmax runs over
   for (int r = wave; r < R; r += 4) {
     const float* hr = Hz + (long)r * d;
@@ -83,7 +88,22 @@ __global__ __launch_bounds__(256) void score_softmax_kernel(const float* H, cons
   __syncthreads();
   s = (red[4] + red[5]) + (red[6] + red[7]);
   const float inv = 1.0f / s;
-  for (int r = threadIdx.x; r < R; r += 256) az[r] = sc[r] * inv;
+  for (int r = threadIdx.x; r < R; r += 256) {
+    az[r] = sc[r] * inv;
+    if (DUAL) az2[r] = sc[r] * inv;
+  }
+}
+__global__ __launch_bounds__(256) void score_softmax_kernel(const float* H, const float* w, const float* c,
+                                                            float* a, int R, int d, const int* len) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];
+  __shared__ float red[8];
+  score_softmax_body<false>(H, w, c, a, nullptr, R, d, len, sc, red);
+}
+__global__ __launch_bounds__(256) void score_softmax2_kernel(const float* H, const float* w, const float* c,
+                                                             float* a, float* a2, int R, int d, const int* len) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];
+  __shared__ float red[8];
+  score_softmax_body<true>(H, w, c, a, a2, R, d, len, sc, red);
 }
 
 // ds = a * (da - <a,da>), one wave per z
@@ -95,6 +115,21 @@ __global__ __launch_bounds__(64) void softmax_bwd_kernel(const float* a, const f
   for (int r = lane; r < R; r += 64) dot = fmaf(az[r], dz[r], dot);
   dot = wave_sum(dot);
   for (int r = lane; r < R; r += 64) ds[(long)z * R + r] = az[r] * (dz[r] - dot);
+}
+
+// The same with the map's own upstream gradient (coattn_backward_maps): ds = a * (x - <a,x>), x = da + g on the rows
+// r < clamp(len[z], 1, R) and 0 beyond (len may be NULL: all rows), so that a pad slot of g changes nothing.
+__global__ __launch_bounds__(64) void softmax_bwd_g_kernel(const float* a, const float* da, const float* g, float* ds, int R,
+                                                           const int* len) {
+  const int z = blockIdx.x, lane = threadIdx.x;
+  const float* az = a + (long)z * R;
+  const float* dz = da + (long)z * R;
+  const float* gz = g + (long)z * R;
+  const int Rz = len ? min(max(len[z], 1), R) : R;
+  float dot = 0.f;
+  for (int r = lane; r < R; r += 64) dot = fmaf(az[r], r < Rz ? dz[r] + gz[r] : 0.f, dot);
+  dot = wave_sum(dot);
+  for (int r = lane; r < R; r += 64) ds[(long)z * R + r] = az[r] * ((r < Rz ? dz[r] + gz[r] : 0.f) - dot);
 }
 
 // part[chunk][j] = sum_{r in chunk} s[r] * X[r][j]
@@ -254,9 +289,10 @@ int launch_gemv(const float* X, const float* u, float* y, int Z, int I, int K, i
 }
 
 int launch_score_softmax(const float* H, const float* w, const float* c, float* a, int Z, int R, int d,
-                         hipStream_t s, const int* len) {
+                         hipStream_t s, const int* len, float* a2) {
   CA_CHECK_ARG(Z > 0 && R > 0 && R <= 4096 && d > 0, "score_softmax: bad shape Z=%d R=%d d=%d", Z, R, d);
-  hipLaunchKernelGGL(score_softmax_kernel, dim3(Z), dim3(256), (size_t)R * sizeof(float), s, H, w, c, a, R, d, len);
+  if (a2) hipLaunchKernelGGL(score_softmax2_kernel, dim3(Z), dim3(256), (size_t)R * sizeof(float), s, H, w, c, a, a2, R, d, len);
+  else hipLaunchKernelGGL(score_softmax_kernel, dim3(Z), dim3(256), (size_t)R * sizeof(float), s, H, w, c, a, R, d, len);
   CA_CHECK_LAUNCH("score_softmax");
   return 0;
 }
@@ -270,8 +306,9 @@ int launch_mask_rows(float* X, const int* len, int Z, int R, int W, hipStream_t 
   return 0;
 }
 
-int launch_softmax_bwd(const float* a, const float* da, float* ds, int Z, int R, hipStream_t s) {
-  hipLaunchKernelGGL(softmax_bwd_kernel, dim3(Z), dim3(64), 0, s, a, da, ds, R);
+int launch_softmax_bwd(const float* a, const float* da, float* ds, int Z, int R, hipStream_t s, const float* g, const int* len) {
+  if (g) hipLaunchKernelGGL(softmax_bwd_g_kernel, dim3(Z), dim3(64), 0, s, a, da, g, ds, R, len);
+  else hipLaunchKernelGGL(softmax_bwd_kernel, dim3(Z), dim3(64), 0, s, a, da, ds, R);
   CA_CHECK_LAUNCH("softmax_bwd");
   return 0;
 }

@@ -327,19 +327,28 @@ class HierarchicalCoAttentionNet(nn.Module):
         self.hot_path_direct_grads = False
         self._graphs = {}
 
-    def forward(self, x_img, x_ques, x_ques_lens):
-        return self.forward_features(self.image_encoder(x_img), x_ques, x_ques_lens)
+    def forward(self, x_img, x_ques, x_ques_lens, return_attention=False):
+        return self.forward_features(self.image_encoder(x_img), x_ques, x_ques_lens, return_attention=return_attention)
 
-    def forward_features(self, x_img_features, x_ques, x_ques_lens, labels=None):
+    def forward_features(self, x_img_features, x_ques, x_ques_lens, labels=None, return_attention=False):
         """The forward pass from already-encoded image features [B,N,d] (model.py:171-187 minus the
         image encoder call): lets a frozen encoder run ahead on its own stream (train.Trainer).
         `x_img_features` may be a zero-argument callable returning the features.  With `labels` (int64 [B]) the
         mean cross entropy of main.py:214 comes out of the answer head's own call: returns (logits, loss).
-        `x_ques_lens` reaches the co-attention too when its ``question_mask`` is on (ParallelCoAttention)."""
+        `x_ques_lens` reaches the co-attention too when its ``question_mask`` is on (ParallelCoAttention).
+        return_attention=True: the co-attention maps a_v [3,B,N], a_q [3,B,T] come out as well -- (logits, a_v, a_q), or
+        (logits, loss, a_v, a_q) with `labels` -- differentiable, for a loss on them (ParallelCoAttention.forward).  This
+        takes the per-module path, never the hot-path node (`hot_path_static` / `hot_path_graph`)."""
         x_ques_features = list(self.question_encoder(x_ques, x_ques_lens))
         if callable(x_img_features):            # resolved only now: the question side is queued first
             x_img_features = x_img_features()
         masked = self._question_mask()
+        if return_attention:
+            lens = (x_ques_lens,) if masked else ()
+            v, q, a_v, a_q = self.co_attention(x_img_features, x_ques_features, *lens, return_attention=True)
+            if labels is not None:
+                return (*self.mlp_classify.forward_loss(v, q, labels), a_v, a_q)
+            return self.mlp_classify(v, q), a_v, a_q
         if (labels is not None and (self.hot_path_graph or self.hot_path_static) and x_img_features.is_cuda
                 and torch.is_grad_enabled()):
             return self._graphed(x_img_features, x_ques_features, labels, x_ques_lens if masked else None)
