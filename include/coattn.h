@@ -225,7 +225,12 @@ int coattn_backward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD,
  *   pg    : parameter gradients; accumulate = 0 overwrites, 1 adds into them (grads of the
  *           three levels are always summed: one weight set is shared, model.py:167, :372).
  *   saved : of a coattn_forward call with the SAME inputs, parameter values and flags (it holds projections of
- *           them and an image of W_q; autograd's forward -> backward order guarantees this). */
+ *           them and an image of W_q; autograd's forward -> backward order guarantees this).  The same VALUES are enough:
+ *           V, Q, the parameters and gradients may sit at other addresses (other alignments included) than in that
+ *           forward, and `saved` may have held the state of an earlier forward.  What the forward keeps for the backward
+ *           depends on the shape and mode alone (the image of W_q^T), or is tagged in `saved` by the forward that wrote it
+ *           (the bitmap of the live question rows: without the tag the backward contracts over all rows)
+ *           (tests/test_gpu_saved_state.py). */
 int coattn_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
                     const coattn_params* p, const void* saved, const void* gv, const void* gq,
                     void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,

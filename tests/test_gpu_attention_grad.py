@@ -37,11 +37,14 @@ def same_bits(a, b):
 
 
 def call(V, Qs, P, lens=None, gv=None, gq=None, g_av=None, g_aq=None, mode="exact", impl="fused", layout="lm",
-         api="maps", accumulate=0, grads_init=None):
+         api="maps", accumulate=0, grads_init=None, api_bwd=None, Qs_bwd=None, saved=None):
     """One forward (+ backward) through the C-ABI.  api: "maps" (coattn_forward_maps / coattn_backward_maps), "maps_zero"
     (the same with g_av / g_aq given as zero tensors where they are None), "plain" (coattn_forward / coattn_backward) or
     "infer" (coattn_infer).  lens: None (the unmasked entry points) or host ints (the *_len ones).  V [B,d,N] values, handed
-    over in the physical `layout`.  Every output buffer is NaN-filled first."""
+    over in the physical `layout`.  Every output buffer is NaN-filled first.
+    api_bwd: the backward's family when it differs from the forward's ("plain" / "maps"); Qs_bwd: other device tensors (same
+    values) as the backward's Q; saved: a caller-owned state buffer, used as it is (not refilled).  Device tensors in Qs /
+    Qs_bwd that are contiguous are handed over at their own addresses (views at an offset included)."""
     lib = _lib.load()
     V = V.to(DEV).contiguous()
     B, d, N = V.shape
@@ -66,7 +69,7 @@ def call(V, Qs, P, lens=None, gv=None, gq=None, g_av=None, g_aq=None, mode="exac
                                                       d, L, _lib.F32, flag, st), "infer")
         torch.cuda.synchronize()
         return {"v": v, "q": q, "a_v": a_v, "a_q": a_q}
-    saved = nan(sb // 4)
+    saved = nan(sb // 4) if saved is None else saved
     if api == "plain":
         _lib.check(getattr(lib, "coattn_forward" + sfx)(Vbuf.data_ptr(), *vstr, qptr, *qa, C.byref(p), v.data_ptr(),
                                                         q.data_ptr(), saved.data_ptr(), ws.data_ptr(), B, N, T, d, L,
@@ -96,7 +99,9 @@ def call(V, Qs, P, lens=None, gv=None, gq=None, g_av=None, g_aq=None, mode="exac
     pg = _lib.ParamGrads(*[t.data_ptr() for t in grads])
     dqptr = (C.c_void_p * L)(*[t.data_ptr() for t in dQs])
     tail = (dV.data_ptr(), *vstr, dqptr, C.byref(pg), accumulate, ws2.data_ptr(), B, N, T, d, L, _lib.F32, flag, st)
-    if api == "plain":
+    if Qs_bwd is not None:
+        qptr = (C.c_void_p * L)(*[t.data_ptr() for t in Qs_bwd])
+    if (api_bwd or api) == "plain":
         _lib.check(getattr(lib, "coattn_backward" + sfx)(Vbuf.data_ptr(), *vstr, qptr, *qa, C.byref(p), saved.data_ptr(),
                                                          gv.data_ptr(), gq.data_ptr(), *tail), "backward")
     else:

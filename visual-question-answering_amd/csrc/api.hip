@@ -418,8 +418,9 @@ bool f16_path(const Ctx& c, const float* V, const float* const* Q, int flags, in
   return v_w && q_w;
 }
 
-// Does the forward write the bitmap of the live question rows (and run P_q over them alone)?  A pure function of the call's
-// shapes, pointers and mode: the backward asks the same question about the same call (rowbits_in_saved).
+// Does the forward write the bitmap of the live question rows (and run P_q over them alone)?  A function of the call's shapes,
+// pointers and mode.  The backward asks it of its own arguments (rowbits_in_saved) to learn whether it MAY use a bitmap; whether
+// there is one it learns from the tag the forward left beside it (fused.h kRowTag).
 static bool rowbits_predicate(const Ctx& c, const WGemm& wq, const coattn_params* p, const float* sv, bool f16) {
   static const int rows_env = dev_env_int("COATTN_SKIP_ZERO_ROWS", 1);   // developer switch
   const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
@@ -452,7 +453,12 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
   if (f16) wv.status = wq.status = status;            // both on two FP16 pieces, range-checked
   RowFlagJob rj = {};
   bool rows_in_gemm = false;
-  if (v_w || q_w) {
+  // the image of W_q^T for the backward's dQ projection: whenever that job runs on the pre-split-weight kernels -- a question of
+  // the shape and the mode alone, the backward asks the same one (fused.h dq_proj_job), whatever the alignment of Q here
+  const WGemm wdq = dq_proj_job(c.B, c.T, c.d, c.L, c.bf16_proj ? 1 : 0, 3);
+  const bool wqT = keep_wqT && gemm_w_enabled() && gemm_w_supported(wdq);
+  unsigned* row_tag = reinterpret_cast<unsigned*>(sv + sp.rowcnt) + kRowTagWord;
+  if (v_w || q_w || wqT) {
     WSplit jobs[3];
     int nj = 0;
     // (the image of W_q^T is read by the backward's dQ projection: a GEMM of P_q's shape with row-major A in the same
@@ -460,9 +466,7 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
     const int chunks = ((c.d + 31) / 32) * ((c.d + 15) / 16);
     if (v_w) jobs[nj++] = WSplit{(const float*)p->W_v, const_cast<void*>(wv.Wf), c.d, c.d, 0, c.d, wimg_pieces(wv), status + kStatusHdr};
     if (q_w) jobs[nj++] = WSplit{(const float*)p->W_q, const_cast<void*>(wq.Wf), c.d, c.d, 0, c.d, wimg_pieces(wq), status + kStatusHdr + chunks};
-    WGemm wqb = wq;                                   // (the backward's operands are gradients: bf16 pieces, fused.h)
-    wqb.f16 = 0;
-    if (q_w && keep_wqT) jobs[nj++] = WSplit{(const float*)p->W_q, sv + sp.wqT, c.d, c.d, 1, c.d, wimg_pieces(wqb), nullptr};
+    if (wqT) jobs[nj++] = WSplit{(const float*)p->W_q, sv + sp.wqT, c.d, c.d, 1, c.d, wimg_pieces(wdq), nullptr};
     // Question rows of exact zeros -- the pad tokens (model.py:263, :292-296) -- project to the bias alone: the launch's extra
     // workgroups flag the rows of Q_l that hold anything, write (0 + b_q) * scale into the others' rows of P_q, and the exact
     // four-wave GEMM runs over the flagged rows only (same values bit for bit; 44 % fewer rows on BASELINE's synthetic
@@ -485,10 +489,12 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
     }
     rows_in_gemm = skip_rows && rj.rowcnt != nullptr;
     CA_TRY(launch_wsplit(jobs, nj, c.s, status, f16 ? 1 : 0, (skip_rows && !rows_in_gemm) ? &rj : nullptr,
-                         rows_in_gemm ? rj.rowcnt : nullptr));   // (also writes the header of the call's status words)
+                         rows_in_gemm ? rj.rowcnt : nullptr, row_tag, skip_rows ? &rj : nullptr));
+    // (also writes the header of the call's status words, and sets or clears the bitmap's tag)
     prof_mark(c.s, "wsplit");
-  } else {                                            // no weight-split launch on this path: header = "no FP16 pieces"
-    if (hipMemsetAsync(status, 0, 2 * sizeof(float), c.s) != hipSuccess) { coattn_set_error("forward: hipMemsetAsync failed"); return -3; }
+  } else {                                            // no weight-split launch on this path: header = "no FP16 pieces", no bitmap
+    if (hipMemsetAsync(status, 0, 2 * sizeof(float), c.s) != hipSuccess ||
+        hipMemsetAsync(row_tag, 0, 3 * sizeof(unsigned), c.s) != hipSuccess) { coattn_set_error("forward: hipMemsetAsync failed"); return -3; }
   }
   if (v_w && q_w) {                                   // both projections in one launch
     const WGemm both[2] = {wv, wq};
@@ -707,6 +713,21 @@ int pick_impl(int flags, int B, int N, int T, int d, int L, const VLayout& vl, i
 
 }  // namespace
 
+// The context of a call, built alike by the forward and by the backward of its state: the backward re-asks the forward's
+// questions about the same call (rowbits_in_saved), on the same Ctx.
+static Ctx call_ctx(int B, int N, int T, int d, int L, void* stream, const VLayout& vl, const int32_t* q_len, const void* V,
+                    const void* const* Q, int flags, int fused) {
+  Ctx c{B, N, T, d, L, (hipStream_t)stream, vl};
+  c.qlen = q_len;
+  c.bf16_proj = (flags & COATTN_FLAG_BF16_PROJ) != 0;
+  c.f16_proj = f16_path(c, (const float*)V, (const float* const*)Q, flags, fused);
+  // (the general-shape path stays exact throughout; a fused shape without the FP16 path too -- unless the developer switch
+  //  COATTN_FWD_F16=0 asks for round 4's bf16 widths)
+  c.np_pq = (fused && fast16(flags) && !f16_fwd(flags)) ? np_projq(flags) : 3;
+  c.pscale = fused ? kPScale : 1.f;
+  return c;
+}
+
 static int check_vlayout(const VLayout& v, int B, int N, int d, const char* what) {
   (void)B;
   CA_CHECK_ARG(v.sN > 0 && v.sD > 0 && v.sB > 0, "%s: strides must be positive (sB=%ld sN=%ld sD=%ld)", what, v.sB, v.sN, v.sD);
@@ -733,14 +754,7 @@ static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, 
   const SavedPlan sp = plan_saved(B, N, T, d, L);
   float* sv = saved ? (float*)saved : (float*)ws;      // inference: state lives in the workspace
   float* tail = (float*)ws + sp.total;
-  Ctx c{B, N, T, d, L, (hipStream_t)stream, vl};
-  c.qlen = q_len;
-  c.bf16_proj = (flags & COATTN_FLAG_BF16_PROJ) != 0;
-  c.f16_proj = f16_path(c, (const float*)V, (const float* const*)Q, flags, fused);
-  // (the general-shape path stays exact throughout; a fused shape without the FP16 path too -- unless the developer switch
-  //  COATTN_FWD_F16=0 asks for round 4's bf16 widths)
-  c.np_pq = (fused && fast16(flags) && !f16_fwd(flags)) ? np_projq(flags) : 3;
-  c.pscale = fused ? kPScale : 1.f;
+  const Ctx c = call_ctx(B, N, T, d, L, stream, vl, q_len, V, Q, flags, fused);
   if (do_proj)
     CA_TRY(general_projections(c, (const float*)V, (const float* const*)Q, p, sv,
                                (char*)ws + fwd_ws_floats(B, N, T, d, L) * sizeof(float), saved != nullptr));
@@ -832,9 +846,7 @@ static int backward_impl(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD
                "backward: null parameter-gradient pointer");
   int fused = 0;
   CA_TRY(pick_impl(flags, B, N, T, d, L, vl, &fused));
-  Ctx c{B, N, T, d, L, (hipStream_t)stream, vl};
-  c.qlen = q_len;
-  c.bf16_proj = (flags & COATTN_FLAG_BF16_PROJ) != 0;
+  const Ctx c = call_ctx(B, N, T, d, L, stream, vl, q_len, V, Q, flags, fused);
   // (`saved` of the fused forward holds P_v, P_q scaled by kPScale: only the fused backward may read it)
   CA_CHECK_ARG(!fused || fused_backward_supported(B, N, T, d, L), "backward: the fused forward's saved state has no fused backward for this shape");
   if (fused)

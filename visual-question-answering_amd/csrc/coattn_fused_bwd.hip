@@ -108,7 +108,9 @@ struct PreArgs {
   float* dA;                             //   the rows t >= len_b of dA [L][B][T][N] are zeroed here (bwd_dc32_kernel skips them)
   int B, N, T, d, L;
   TnDyn dyn; TnDynPlan* plan_out;        // plan_out != NULL: ONE more workgroup (the launch's last) evaluates the split-K plan of the
-                                         // weight gradients over the live question rows (fused.h tn_dyn_plan) and leaves it there
+                                         // weight gradients over the live question rows (fused.h tn_dyn_plan) and leaves it there,
+  const unsigned* saved_bits;            //   over the forward's bitmap in `saved` when the forward's tag (row_tag, fused.h kRowTag)
+  const unsigned* row_tag;               //   says it wrote one, else over all rows; the words it counted go to dyn.bits
   const float* gaq;                      // (bwd_pre_maps_kernel, coattn_backward_maps) [L][B][T] upstream gradient of a_q: da_q += G_aq
                                          // for t < len_b, read as 0 beyond (whatever the pad slots hold)
 };
@@ -125,7 +127,8 @@ template <bool GMAP>
 __device__ __forceinline__ void bwd_pre_body(const PreArgs& a, float* lds) {
   if (a.plan_out && (int)blockIdx.x == a.L * a.B + a.dav_gx * a.B) {
     if (threadIdx.x < 64) {                          // one full wave
-      const TnDynPlan pl = tn_dyn_plan(a.dyn);
+      const bool tagged = a.row_tag[0] == kRowTag && a.row_tag[1] == (unsigned)(a.B * a.T) && a.row_tag[2] == (unsigned)a.L;
+      const TnDynPlan pl = tn_dyn_plan(a.dyn, tagged ? a.saved_bits : nullptr, a.B * a.T);
       if (threadIdx.x == 0) *a.plan_out = pl;
     }
     return;
@@ -351,14 +354,17 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
   pa.dsq = ws + wo.dsq; pa.dcs_part = ws + wo.dcs_part; pa.qlen = qlen; pa.dA = ws + wo.dA;
   pa.gaq = g_aq;                                     // (coattn_backward_maps; NULL: the plain pre-pass)
   pa.B = B; pa.N = N; pa.T = T; pa.d = d; pa.L = L;
-  // (exact mode: the forward's bitmap of the live question rows is in `saved`; the plan of the weight gradients over those rows
-  //  is a function of it and of shapes known here -- evaluated once, by an extra workgroup of this launch)
+  // (exact mode: the forward's bitmap of the live question rows may be in `saved` -- live_rows: the shape and mode allow one,
+  //  its tag says whether the forward wrote it; the plan of the weight gradients over those rows is a function of it and of
+  //  shapes known here -- evaluated once, by an extra workgroup of this launch, which copies the words it counted to `ws`)
   static const int tn_budget_env = dev_env_int("COATTN_TN_PARTS", 0);   // developer switch
   const int tn_budget = tn_budget_env > 0 ? tn_budget_env : 32;
   TnDyn dyn_all = {};
-  pa.dyn = dyn_all; pa.plan_out = nullptr;
+  pa.dyn = dyn_all; pa.plan_out = nullptr; pa.saved_bits = nullptr; pa.row_tag = nullptr;
   if (live_rows && L <= kDynLevels && (B * T + 31) / 32 <= kRowBitsMaxWords && tn_budget > L) {
-    dyn_all.bits = reinterpret_cast<const unsigned*>(saved + so.rowbits);
+    dyn_all.bits = reinterpret_cast<const unsigned*>(ws + wo.rowbits);
+    pa.saved_bits = reinterpret_cast<const unsigned*>(saved + so.rowbits);
+    pa.row_tag = reinterpret_cast<const unsigned*>(saved + so.rowcnt) + kRowTagWord;
     dyn_all.words = (B * T + 31) / 32; dyn_all.levels = L; dyn_all.P = tn_budget; dyn_all.K0 = B * N;
     dyn_all.plan = reinterpret_cast<const TnDynPlan*>(ws + wo.dynplan);
     pa.dyn = dyn_all; pa.plan_out = reinterpret_cast<TnDynPlan*>(ws + wo.dynplan);
@@ -404,15 +410,12 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
   tnq.bf16 = bf16_proj; tnq.np = np;
   const bool tn_q = wgemm && gemm_tn_supported(tnq);       // levels as extra split-K parts (gemm_tn.hip)
   const bool dq32 = lm || (N % 4) == 0;              // the bf16 dA V kernel takes both layouts (channel-major: aligned rows)
-  WGemm wdq = {};                                    // dQ_l = dP_q,l W_q against the W_q image the forward left in `saved`
-  wdq.A = ws + wo.dPq; wdq.a_sz = (long)BTd; wdq.a_sm = d; wdq.Wf = saved + so.wqT;
+  // dQ_l = dP_q,l W_q against the W_q image the forward left in `saved` -- written whenever this job is supported (the same
+  // test, api.hip general_projections: fused.h dq_proj_job)
+  WGemm wdq = dq_proj_job(B, T, d, L, bf16_proj, np);
+  const bool wdq_ok = wgemm && gemm_w_supported(wdq);
+  wdq.A = ws + wo.dPq; wdq.Wf = saved + so.wqT;
   for (int l = 0; l < L; ++l) wdq.c_ptrs[l] = dQ[l];
-  wdq.c_sm = d; wdq.M = B * T; wdq.N = d; wdq.K = d; wdq.batch = L;
-  // (exactly the forward's test for writing that image, api.hip general_projections: same shape, and its A rows were Q_l)
-  bool q_al = true;
-  for (int l = 0; l < L; ++l) q_al = q_al && (((uintptr_t)Q[l]) & 15) == 0;
-  wdq.bf16 = bf16_proj; wdq.np = np;
-  const bool wdq_ok = wgemm && q_al && gemm_w_supported(wdq);
   // (a dQ projection on gemm_bf.hip -- 512-thread workgroups -- cannot ride in the weight-gradient launch)
   static const int no_combine = dev_env_int("COATTN_NO_COMBINE", 0);   // developer switch
   // COATTN_OWN_DQ=1 (developer switch; round 5, measured and NOT kept): the dQ projection as a launch of its own on the

@@ -294,8 +294,10 @@ size_t wsplit_bytes(int N, int K);
 // status_hdr (may be NULL): the launch's first thread writes [0] = 0 and [1] = f16 ? 1 : 0 (the status words' header)
 // rows (may be NULL): a RowFlagJob done by extra workgroups of the same launch; zero8 (may be NULL): eight words the launch zeroes
 // (RowFlagJob.rowcnt of a job that rides in the NEXT launch)
+// row_tag (may be NULL): the three words of the bitmap's tag in `saved` (kRowTagWord), written by the same thread as the header:
+// {kRowTag, M, batch} of `rows` (or of the job riding in the next launch: tag_rows), zeros when the call writes no bitmap
 int launch_wsplit(const WSplit* jobs, int njobs, hipStream_t s, float* status_hdr = nullptr, int f16 = 0, const RowFlagJob* rows = nullptr,
-                  unsigned* zero8 = nullptr);
+                  unsigned* zero8 = nullptr, unsigned* row_tag = nullptr, const RowFlagJob* tag_rows = nullptr);
 int gemm_w_supported(const WGemm& d);
 // n = 1 or 2 GEMMs in one launch.  rows (may be NULL; exact four-wave launches only): a RowFlagJob whose workgroups come FIRST in
 // the launch; the tiles of a job with WGemm.rowbits then wait (per batch entry) until rows->rowcnt says its words are written --
@@ -310,6 +312,16 @@ int gemm_h2_supported(const WGemm& d);
 int launch_gemm_h2(const WGemm* d, int n, hipStream_t s);
 // the kernel a pre-split-weight GEMM runs on: gemm_bf / gemm_h2 when they take the shape and mode, else gemm_w
 inline int gemm_wx_kernel(const WGemm& d) { return gemm_bf_supported(d) ? 1 : (gemm_h2_supported(d) ? 2 : 0); }
+// The backward's dQ projection dQ_l = dP_q,l W_q (coattn_fused_bwd.hip) against the image of W_q^T that the forward's weight-split
+// launch leaves in `saved` (SavedOff::wqT).  Its operands are dP_q in the backward's workspace and that image -- never Q -- so
+// whether it runs on the pre-split-weight kernels, and so whether the forward writes the image (and in which format), depends on
+// the shape and the mode alone.  (np, the width, changes neither: the image is split whole.)
+inline WGemm dq_proj_job(int B, int T, int d, int L, int bf16, int np) {
+  WGemm w = {};
+  w.a_sz = (long)B * T * d; w.a_sm = d; w.c_sm = d; w.M = B * T; w.N = d; w.K = d; w.batch = L;
+  w.bf16 = bf16; w.np = np;
+  return w;
+}
 inline int launch_gemm_wx(const WGemm* d, int n, hipStream_t s, const RowFlagJob* rows = nullptr) {
   if (n == 2 && gemm_wx_kernel(d[0]) != gemm_wx_kernel(d[1])) {   // one job on each kernel: two launches
     const int rc = launch_gemm_wx(&d[0], 1, s);
@@ -346,7 +358,9 @@ struct TnDyn { const unsigned* bits; int words, levels, P, K0;           // bits
                const TnDynPlan* plan; };                                 // the plan, evaluated once (an extra workgroup of bwd_pre_kernel)
 // by ONE full wave (all 64 lanes active); the result is uniform.  (Loops over the levels are unrolled over kDynLevels with the
 // live ones selected by a compare: a run-time index into the arrays would put them in scratch.)
-__device__ __forceinline__ TnDynPlan tn_dyn_plan(const TnDyn& d) {
+// src: the forward's bitmap in `saved` -- only when the forward's tag says it wrote one (kRowTag) -- or NULL: all `rows` rows are
+// live.  The words counted are stored to d.bits (the backward's workspace), which the launches behind read.
+__device__ __forceinline__ TnDynPlan tn_dyn_plan(const TnDyn& d, const unsigned* src, const int rows) {
   const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   TnDynPlan pl;
   int tot = 0;
@@ -354,7 +368,12 @@ __device__ __forceinline__ TnDynPlan tn_dyn_plan(const TnDyn& d) {
   for (int l = 0; l < kDynLevels; ++l) {
     int c = 0;
     if (l < d.levels) {
-      for (int i = lane; i < d.words; i += 64) c += __builtin_popcount(d.bits[(long)l * d.words + i]);
+      for (int i = lane; i < d.words; i += 64) {
+        const int r = rows - 32 * i;
+        const unsigned w = src ? src[(long)l * d.words + i] : (r >= 32 ? ~0u : (1u << r) - 1u);
+        const_cast<unsigned*>(d.bits)[(long)l * d.words + i] = w;
+        c += __builtin_popcount(w);
+      }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
     }
@@ -610,10 +629,16 @@ inline SavedOff saved_off(int B, int N, int T, int d, int L) {   // the one layo
   p.total = o;
   return p;
 }
+// Tag of that bitmap: three words at rowcnt + kRowTagWord (behind the eight counters), {kRowTag, B T, L} when the call's forward
+// wrote the bitmap and zeros when it did not -- set or cleared by every forward that computes the projections, in the launch
+// that writes its status header.  The backward reads the bitmap only under this tag, never because its own arguments (their
+// addresses included) would have let the forward write one (include/coattn.h: the backward needs the same values only).
+constexpr int kRowTagWord = 8;
+constexpr unsigned kRowTag = 0x54574f52u;   // "ROWT"
 
 // workspace of the fused backward (floats)
 struct FusedBwdOff {
-  size_t dsv, dsq, dPq, dPv, dA, dwv_part, dbv_part, dbq_part, dwq_part, dcs_part, dynplan, part, total;
+  size_t dsv, dsq, dPq, dPv, dA, dwv_part, dbv_part, dbq_part, dwq_part, dcs_part, dynplan, rowbits, part, total;
 };
 constexpr int kMaxParts = 40;   // split-K parts of the weight-gradient GEMMs (32 shared by dW_v and dW_q, rounded up per level)
 inline FusedBwdOff fused_bwd_off(int B, int N, int T, int d, int L) {
@@ -630,6 +655,7 @@ inline FusedBwdOff fused_bwd_off(int B, int N, int T, int d, int L) {
   p.dwq_part = o; o += fal64((size_t)L * B * d);
   p.dcs_part = o; o += fal64((size_t)L * B * 2);
   p.dynplan = o; o += 64;                          // TnDynPlan of a device-planned weight-gradient launch
+  p.rowbits = o; o += fal64(rowbits_words(B * T, L));   // the bitmap that plan counted (the forward's, or all rows live)
   // shared scratch: split-K partials of the weight-gradient GEMMs (<= kMaxParts x d x d) and, before them, the da_v
   // partials of bwd_dav_kernel ([B][d/64][3][N]), which outgrow the former at large B
   const size_t part_gemm = (size_t)kMaxParts * d * d, part_dav = (size_t)B * (d / 64) * 3 * N;

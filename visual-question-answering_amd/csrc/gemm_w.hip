@@ -31,7 +31,8 @@ using namespace gw;
 struct WJobs { WArgs job[2]; int first1; RowFlagJob rows; int nflag; };   // blocks [0, nflag): the row-flag job; then [0, first1) of the rest work on job 0, the others on job 1
 
 struct SplitJob { const float* W; void* out; int N, K, trans, ld, pieces; float* amax; };
-struct SplitArgs { SplitJob job[3]; int njobs; float* status_hdr; float f16; RowFlagJob rows; int row_blocks, cb; unsigned* zero8; };   // grid: [row_blocks][njobs x cb]
+struct SplitArgs { SplitJob job[3]; int njobs; float* status_hdr; float f16; RowFlagJob rows; int row_blocks, cb; unsigned* zero8;
+                   unsigned* row_tag; unsigned tag[3]; };   // grid: [row_blocks][njobs x cb]
 
 // The RowFlagJob's workgroups (the FIRST row_blocks of the launch: they have the most to wait for): workgroup x takes 32 rows of one batch entry, a wave 8 of them, all
 // requested before the first test (one memory latency per wave, not per row); a row is read in whole 1 KB segments (a lane
@@ -117,6 +118,7 @@ __global__ __launch_bounds__(256) void wsplit_kernel(const SplitArgs a) {
   f16_saturating_conversions();                      // (only the pieces = 16 jobs convert to fp16)
   // header of the call's status words (fused.h kStatusHdr): the projection launch behind this one raises [0]
   if (a.status_hdr && bx == 0 && by == 0 && threadIdx.x == 0) { a.status_hdr[0] = 0.f; a.status_hdr[1] = a.f16; }
+  if (a.row_tag && bx == 0 && by == 0 && threadIdx.x == 0) { a.row_tag[0] = a.tag[0]; a.row_tag[1] = a.tag[1]; a.row_tag[2] = a.tag[2]; }
   const int lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
   const int ks16 = (j.K + 15) / 16, nt32 = (j.N + 31) / 32;
   const int chunk = bx * 4 + (threadIdx.x >> 6);
@@ -199,7 +201,8 @@ static int check_rowflag_job(const RowFlagJob* rows) {
   return 0;
 }
 
-int launch_wsplit(const WSplit* jobs, int njobs, hipStream_t s, float* status_hdr, int f16, const RowFlagJob* rows, unsigned* zero8) {
+int launch_wsplit(const WSplit* jobs, int njobs, hipStream_t s, float* status_hdr, int f16, const RowFlagJob* rows, unsigned* zero8,
+                  unsigned* row_tag, const RowFlagJob* tag_rows) {
   CA_CHECK_ARG(njobs >= 1 && njobs <= 3, "wsplit: 1 to 3 jobs per launch");
   SplitArgs a = {};
   int row_blocks = 0;
@@ -220,6 +223,8 @@ int launch_wsplit(const WSplit* jobs, int njobs, hipStream_t s, float* status_hd
     chunks = c > chunks ? c : chunks;
   }
   a.row_blocks = row_blocks; a.cb = (chunks + 3) / 4; a.zero8 = zero8;
+  a.row_tag = row_tag;
+  if (const RowFlagJob* t = rows ? rows : tag_rows) { a.tag[0] = kRowTag; a.tag[1] = (unsigned)t->M; a.tag[2] = (unsigned)t->batch; }
   hipLaunchKernelGGL(wsplit_kernel, dim3(row_blocks + njobs * a.cb), dim3(256), 0, s, a);
   CA_CHECK_LAUNCH("wsplit");
   return 0;
