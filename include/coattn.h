@@ -31,7 +31,8 @@
  *            any other strides take the general-shape kernels.  dV is described the same way.
  *   Q[l]   : [B, T, d]  contiguous, l = 0..L-1 (word, phrase, sentence; model.py:298).
  *   W_v,W_q: [d, d] (nn.Linear.weight, out x in); b_v,b_q: [d]; w_v,w_q: [d]; c_v,c_q: [1]
- *            (model.py:350-354).  W_b (model.py:347) is dead in the reference and not passed.
+ *            (model.py:350-354).  W_b (model.py:347) is dead in the reference; it is read only under
+ *            COATTN_FLAG_BILINEAR (below).
  *   v_out,q_out,gv,gq : [L, B, d].
  */
 #ifndef COATTN_H
@@ -92,16 +93,46 @@ extern "C" {
  * in; no range report: that is coattn_forward's); the weight image written under this flag is read under this flag only. */
 #define COATTN_FLAG_F16PAIR 64
 #define COATTN_FLAG_FAST16 128
+/* ---- bilinear affinity (v0.10.0) ---------------------------------------------------------------------------------
+ * flags bit 8, on every co-attention entry point (coattn_forward, _infer, _attention_forward, _backward, their _len and
+ * _maps forms, coattn_workspace_bytes): the affinity of the published model (Lu et al. 2016, eq. 3) in place of the
+ * reference's C = tanh(Q V^T) (model.py:377).  Per sample and level, row-vector convention:
+ *     K = Q W_b^T + b_b   [T,d]   (the module's own self.W_b(Q), model.py:347)
+ *     A = K V^T,  C = tanh(A)     [T,N]
+ * Everything else is unchanged: P_v, P_q, H_v, H_q, both softmaxes, v = a_v^T V and q = a_q^T Q (Q, not K).  Backward, with
+ * dA = dC (.) (1 - C^2) as before:
+ *     dK = dA V;  dQ = dP_q W_q + dK W_b + a_q (x) g_q;  dV = dP_v W_v + dA^T K + a_v (x) g_v;
+ *     dW_b = sum_l sum_b dK^T Q;  db_b = sum_l sum_b sum_t dK[t]   (one W_b for all levels; `accumulate` as for the rest).
+ * Unmasked, a pad row of Q (zeros) gives K = b_b: it holds weight in C and its dK is not zero (db_b sums every row).  Under
+ * the length mask the rows t >= len_b of C are zero as before, so dK is zero there and the rule "the contents of pad rows do
+ * not matter" holds unchanged.  The maps entry points take G_av / G_aq on top of this form as on the reference one.
+ *   - coattn_params.W_b / b_b and coattn_param_grads.dW_b / db_b (the fields appended in v0.10.0) are read only under this
+ *     flag; a caller built against 0.9 passes the 8-field structs and is not affected.  NULL W_b / b_b (any call) or NULL
+ *     dW_b / db_b (a backward) under the flag: -1, nothing launched.
+ *   - `saved` of a bilinear forward also holds K (coattn_workspace_bytes reports the larger buffers when given the flag);
+ *     the backward and coattn_attention_forward read it there.  Same contract as above: same inputs, parameter values and
+ *     flags.
+ *   - Paths: the same as without the flag.  On fused shapes K is one more job on the pre-split-weight projection kernels, the
+ *     fused forward streams K through phase 1 (BIL instantiations), and the backward forms dQ with ONE projection
+ *     [dP_q | dK] [W_q; W_b] and dW_b on the hand-scheduled weight-gradient kernel (gemm_tn.hip); other shapes run the same math
+ *     on the general-shape kernels.
+ *   - COATTN_FLAG_FAST16: K replaces Q as phase 1's FP16-piece operand and the projection launch that stores it range-checks it,
+ *     and W_b's image follows the |256 W| rule of W_q's: coattn_status / coattn_status_accumulate cover both (-4 when |K| >
+ *     65,504 or |W_b| > 255.87).  Pad rows get K = b_b densely (the live-row bitmap serves P_q and dW_q only).
+ *   - Refused (-1): the flag together with COATTN_FLAG_BF16_PROJ. */
+#define COATTN_FLAG_BILINEAR 256
 typedef struct coattn_params {
   const void* W_v; const void* b_v;   /* model.py:350 */
   const void* W_q; const void* b_q;   /* model.py:351 */
   const void* w_v; const void* c_v;   /* model.py:353 */
   const void* w_q; const void* c_q;   /* model.py:354 */
+  const void* W_b; const void* b_b;   /* model.py:347; read only under COATTN_FLAG_BILINEAR (v0.10.0) */
 } coattn_params;
 
 typedef struct coattn_param_grads {
   void* dW_v; void* db_v; void* dW_q; void* db_q;
   void* dw_v; void* dc_v; void* dw_q; void* dc_q;
+  void* dW_b; void* db_b;             /* written only under COATTN_FLAG_BILINEAR (v0.10.0) */
 } coattn_param_grads;
 
 /* library version: major*10000 + minor*100 + patch */

@@ -33,6 +33,8 @@ FLAG_SPLIT2 = 32          # linear entry points: the two-piece width (hi + mid, 
 FLAG_F16PAIR = 64        # coattn_linear_forward: two FP16 pieces (the form the tolerance mode runs its projections in)
 FLAG_FAST16 = 128        # coattn_forward / coattn_backward / coattn_phrase_*: the tolerance mode (forward products on two FP16
                          # pieces = 22 bits, backward on two bf16 pieces = 16 bits; range report: coattn_status)
+FLAG_BILINEAR = 256      # every co-attention entry point: the affinity tanh((Q W_b^T + b_b) V^T) (v0.10.0; reads Params.W_b / b_b,
+                         # writes ParamGrads.dW_b / db_b)
 
 
 def precision_flag(fast: bool) -> int:
@@ -46,11 +48,12 @@ def default_fast() -> bool:
 
 
 class Params(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("W_v", "b_v", "W_q", "b_q", "w_v", "c_v", "w_q", "c_q")]
+    # (W_b, b_b: appended in v0.10.0, read only under FLAG_BILINEAR; an 8-pointer Params(...) leaves them NULL)
+    _fields_ = [(n, C.c_void_p) for n in ("W_v", "b_v", "W_q", "b_q", "w_v", "c_v", "w_q", "c_q", "W_b", "b_b")]
 
 
 class ParamGrads(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("dW_v", "db_v", "dW_q", "db_q", "dw_v", "dc_v", "dw_q", "dc_q")]
+    _fields_ = [(n, C.c_void_p) for n in ("dW_v", "db_v", "dW_q", "db_q", "dw_v", "dc_v", "dw_q", "dc_q", "dW_b", "db_b")]
 
 
 class PhraseParams(C.Structure):

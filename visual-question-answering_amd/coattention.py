@@ -6,7 +6,9 @@ in the HIP library through the C-ABI of ``include/coattn.h`` on the caller's cur
 Opt-in beyond the reference: ``question_mask=True`` restricts the question-side attention to the
 first ``x_ques_lens[b]`` tokens of every question (the C-ABI's ``*_len`` entry points), and
 ``forward(..., return_attention=True)`` also returns the attention maps a_v, a_q as differentiable
-tensors (the C-ABI's ``coattn_forward_maps`` / ``coattn_backward_maps``), for losses on the maps.
+tensors (the C-ABI's ``coattn_forward_maps`` / ``coattn_backward_maps``), for losses on the maps, and
+``affinity="bilinear"`` uses the constructed-but-dead ``W_b`` as the published model does, C = tanh(W_b(Q) V^T)
+(the C-ABI's ``COATTN_FLAG_BILINEAR``), so that it trains.
 """
 from __future__ import annotations
 
@@ -135,7 +137,7 @@ class _CoAttentionFn(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
-    def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques):
+    def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl, q_len, *x_ques):
         if not x_img.is_cuda:
             raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
         if x_img.dtype != torch.float32 or any(q.dtype != torch.float32 for q in x_ques):
@@ -149,7 +151,7 @@ class _CoAttentionFn(torch.autograd.Function):
                 raise RuntimeError("question features must all be [B,T,d] = %s, got %s" % ((B, T, d), tuple(q.shape)))
         V = _native_layout(x_img)
         Qs = [q.contiguous() for q in x_ques]
-        params = [t.contiguous() for t in (W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q)]
+        params = _param_list(W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl)
         need_grad = any(ctx.needs_input_grad)
         sb, fb, _ = _lib.workspace_bytes(B, N, T, d, L, impl)
         dev = x_img.device
@@ -174,6 +176,7 @@ class _CoAttentionFn(torch.autograd.Function):
             _lib.note_status("coattn", saved if saved is not None else ws, (B, N, T, d, L), dev)
         if need_grad:
             ctx.save_for_backward(V, saved, *params, *Qs)
+            ctx.nparams = len(params)
             ctx.dims = (B, N, T, d, L, impl)
             ctx.q_len = q_len                         # (the backward must see the forward's lengths)
         return out_v, out_q
@@ -184,7 +187,8 @@ class _CoAttentionFn(torch.autograd.Function):
         lib = _lib.load()
         B, N, T, d, L, impl = ctx.dims
         sv = ctx.saved_tensors
-        V, saved, params, Qs = sv[0], sv[1], sv[2:10], sv[10:]
+        npar = ctx.nparams
+        V, saved, params, Qs = sv[0], sv[1], sv[2:2 + npar], sv[2 + npar:]
         dev = V.device
         g_v = g_v.contiguous() if g_v is not None else torch.zeros((L, B, d), device=dev)
         g_q = g_q.contiguous() if g_q is not None else torch.zeros((L, B, d), device=dev)
@@ -209,6 +213,8 @@ class _CoAttentionFn(torch.autograd.Function):
                 _lib.check(lib.coattn_backward(_ptr(V), *_strides(V), qptr, *args), "coattn_backward")
             else:
                 _lib.check(lib.coattn_backward_len(_ptr(V), *_strides(V), qptr, _ptr(ctx.q_len), *args), "coattn_backward_len")
+        if npar == 8:                       # (the reference's affinity: W_b, b_b take no part)
+            grads += [None, None]
         return (dV, *grads, None, None, *dQs)
 
 
@@ -221,7 +227,7 @@ class _CoAttentionMapsFn(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
-    def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques):
+    def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl, q_len, *x_ques):
         if not x_img.is_cuda:
             raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
         if x_img.dtype != torch.float32 or any(q.dtype != torch.float32 for q in x_ques):
@@ -235,7 +241,7 @@ class _CoAttentionMapsFn(torch.autograd.Function):
                 raise RuntimeError("question features must all be [B,T,d] = %s, got %s" % ((B, T, d), tuple(q.shape)))
         V = _native_layout(x_img)
         Qs = [q.contiguous() for q in x_ques]
-        params = [t.contiguous() for t in (W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q)]
+        params = _param_list(W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl)
         need_grad = any(ctx.needs_input_grad)
         sb, fb, _ = _lib.workspace_bytes(B, N, T, d, L, impl)
         dev = x_img.device
@@ -265,6 +271,7 @@ class _CoAttentionMapsFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)              # (an unused map's gradient stays None: NULL for the C-ABI)
         if need_grad:
             ctx.save_for_backward(V, saved, *params, *Qs)
+            ctx.nparams = len(params)
             ctx.dims = (B, N, T, d, L, impl)
             ctx.q_len = q_len                         # (the backward must see the forward's lengths)
         return out_v, out_q, a_v, a_q
@@ -275,7 +282,8 @@ class _CoAttentionMapsFn(torch.autograd.Function):
         lib = _lib.load()
         B, N, T, d, L, impl = ctx.dims
         sv = ctx.saved_tensors
-        V, saved, params, Qs = sv[0], sv[1], sv[2:10], sv[10:]
+        npar = ctx.nparams
+        V, saved, params, Qs = sv[0], sv[1], sv[2:2 + npar], sv[2 + npar:]
         dev = V.device
         g_v = g_v.contiguous() if g_v is not None else torch.zeros((L, B, d), device=dev)
         g_q = g_q.contiguous() if g_q is not None else torch.zeros((L, B, d), device=dev)
@@ -304,22 +312,41 @@ class _CoAttentionMapsFn(torch.autograd.Function):
             else:
                 _lib.check(lib.coattn_backward_maps_len(_ptr(V), *_strides(V), qptr, _ptr(ctx.q_len), *args),
                            "coattn_backward_maps_len")
+        if npar == 8:                       # (the reference's affinity: W_b, b_b take no part)
+            grads += [None, None]
         return (dV, *grads, None, None, *dQs)
 
 
+def _param_list(W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl):
+    """The parameters in the order of coattn_params: eight, or ten with W_b, b_b under FLAG_BILINEAR."""
+    ps = [W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q]
+    if impl & _lib.FLAG_BILINEAR:
+        if W_b is None or b_b is None:
+            raise ValueError("the bilinear affinity needs W_b and b_b")
+        ps += [W_b, b_b]
+    return [t.contiguous() for t in ps]
+
+
 def coattention(x_img: torch.Tensor, x_ques: Sequence[torch.Tensor], W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q,
-                impl: int | None = None, q_len: torch.Tensor | None = None, return_attention: bool = False):
+                impl: int | None = None, q_len: torch.Tensor | None = None, return_attention: bool = False,
+                W_b=None, b_b=None):
     """Functional form: returns (v, q), each [L,B,d].  q_len: None (the reference's unmasked softmax over the T tokens), or
     the question lengths (see `question_lengths`): attention over the first q_len[b] tokens of question b.
     return_attention=True: returns (v, q, a_v [L,B,N], a_q [L,B,T]), the maps differentiable (a loss on them reaches every
-    input through coattn_backward_maps)."""
+    input through coattn_backward_maps).
+    W_b, b_b given: the bilinear affinity C = tanh((Q W_b^T + b_b) V^T) (FLAG_BILINEAR is added to `impl`), and W_b, b_b
+    receive gradients; None (the default): the reference's C = tanh(Q V^T)."""
     if impl is None:
         impl = _impl_flag()
+    if (W_b is None) != (b_b is None):
+        raise ValueError("the bilinear affinity needs both W_b and b_b")
+    if W_b is not None:
+        impl |= _lib.FLAG_BILINEAR
     if q_len is not None:
         q_len = question_lengths(q_len, x_img.shape[0], x_img.device)
     if return_attention:
-        return _CoAttentionMapsFn.apply(x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques)
-    return _CoAttentionFn.apply(x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, impl, q_len, *x_ques)
+        return _CoAttentionMapsFn.apply(x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl, q_len, *x_ques)
+    return _CoAttentionFn.apply(x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl, q_len, *x_ques)
 
 
 class ParallelCoAttention(nn.Module):
@@ -335,12 +362,23 @@ class ParallelCoAttention(nn.Module):
     alone: a_q is 0 past the length and sums to 1 before it, the affinity rows there count as zero, their gradients are zero
     (include/coattn.h, "length-masked question attention").  With the default (False) the lengths are ignored, as the
     reference ignores them.  The flag is not part of the ``state_dict``: a checkpoint does not say which form trained it.
+
+    ``affinity="bilinear"`` (opt-in; the published model, Lu et al. 2016 eq. 3): the affinity is
+    C = tanh(W_b(Q) V^T) = tanh((Q W_b^T + b_b) V^T) instead of the reference's tanh(Q V^T), and ``W_b`` receives gradients
+    (include/coattn.h, COATTN_FLAG_BILINEAR).  The ``state_dict`` keys are the same for both forms -- a reference checkpoint
+    loads unchanged -- and, as for ``question_mask``, a checkpoint does not record the form.  Not available together with
+    ``bf16_projections``.
     """
 
-    def __init__(self, hidden_dim: int, question_mask: bool = False):
+    AFFINITIES = ("reference", "bilinear")
+
+    def __init__(self, hidden_dim: int, question_mask: bool = False, affinity: str = "reference"):
         super().__init__()
+        if affinity not in self.AFFINITIES:
+            raise ValueError("affinity must be one of %s, got %r" % (self.AFFINITIES, affinity))
         self.hidden_dim = hidden_dim
         self.question_mask = bool(question_mask)
+        self.affinity = affinity
         self.W_b = nn.Linear(hidden_dim, hidden_dim)     # dead in the reference's forward
         self.W_v = nn.Linear(hidden_dim, hidden_dim)
         self.W_q = nn.Linear(hidden_dim, hidden_dim)
@@ -353,6 +391,19 @@ class ParallelCoAttention(nn.Module):
         # 22 significand bits, backward on two bf16 pieces = 16; inside the 1e-4 contract for operands below 65,504 in
         # magnitude; `vqa_amd.check_range()` reports an operand that was not): what train.Trainer(precision="fast") sets.
         self.fast_products = _lib.default_fast()
+
+    def _impl(self) -> int:
+        impl = _impl_flag() | (_lib.FLAG_BF16_PROJ if self.bf16_projections else 0) | _lib.precision_flag(self.fast_products)
+        if self.affinity == "bilinear":
+            if impl & _lib.FLAG_BF16_PROJ:
+                raise RuntimeError("ParallelCoAttention(affinity='bilinear') is not available in the reduced-precision mode "
+                                   "(bf16_projections / COATTN_BF16_PROJ)")
+            impl |= _lib.FLAG_BILINEAR
+        return impl
+
+    def _wb(self):
+        """(W_b, b_b) when the bilinear affinity is on, else (None, None)."""
+        return (self.W_b.weight, self.W_b.bias) if self.affinity == "bilinear" else (None, None)
 
     def _lengths(self, x_img: torch.Tensor, x_ques_lens):
         """int32 [B] lengths on the features' device when the mask is on (required then), else None (ignored)."""
@@ -374,16 +425,17 @@ class ParallelCoAttention(nn.Module):
         if return_attention:
             ques = list(x_ques_hierarchy)
             params = (self.W_v.weight, self.W_v.bias, self.W_q.weight, self.W_q.bias, self.w_v.weight, self.w_v.bias,
-                      self.w_q.weight, self.w_q.bias)
+                      self.w_q.weight, self.w_q.bias, *[t for t in self._wb() if t is not None])
             if not (torch.is_grad_enabled() and any(t.requires_grad for t in (x_img, *ques, *params))):
                 return self.forward_with_attention(x_img, ques, x_ques_lens)
-        impl = _impl_flag() | (_lib.FLAG_BF16_PROJ if self.bf16_projections else 0) | _lib.precision_flag(self.fast_products)
+        impl = self._impl()
+        W_b, b_b = self._wb()
         q_len = self._lengths(x_img, x_ques_lens)
         if x_img.is_cuda and not (x_img.requires_grad and torch.is_grad_enabled()):
             x_img = native_features(x_img)           # frozen encoder: bf16 / non-native strides in one library pass
         out = coattention(x_img, list(x_ques_hierarchy), self.W_v.weight, self.W_v.bias, self.W_q.weight,
                           self.W_q.bias, self.w_v.weight, self.w_v.bias, self.w_q.weight, self.w_q.bias, impl=impl,
-                          q_len=q_len, return_attention=return_attention)
+                          q_len=q_len, return_attention=return_attention, W_b=W_b, b_b=b_b)
         v, q = out[0], out[1]
         n = v.shape[0]
         if return_attention:
@@ -398,13 +450,13 @@ class ParallelCoAttention(nn.Module):
         a_q[l, b, t] is 0 for t >= x_ques_lens[b].  Raises if a gradient would be needed."""
         ques = list(x_ques_hierarchy)
         params = (self.W_v.weight, self.W_v.bias, self.W_q.weight, self.W_q.bias, self.w_v.weight, self.w_v.bias,
-                  self.w_q.weight, self.w_q.bias)
+                  self.w_q.weight, self.w_q.bias, *[t for t in self._wb() if t is not None])
         if torch.is_grad_enabled() and any(t.requires_grad for t in (x_img, *ques, *params)):
             raise RuntimeError("forward_with_attention is forward only: run it under torch.no_grad() (the maps come from "
                                "the inference path, which keeps no state for a backward)")
         if not x_img.is_cuda:
             raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
-        impl = _impl_flag() | (_lib.FLAG_BF16_PROJ if self.bf16_projections else 0) | _lib.precision_flag(self.fast_products)
+        impl = self._impl()
         q_len = self._lengths(x_img, x_ques_lens)
         V = native_features(x_img)
         if V.dtype != torch.float32 or any(q.dtype != torch.float32 for q in ques):

@@ -16,7 +16,7 @@ void coattn_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int coattn_version(void) { return 900; }   // 0.9.0: coattn_forward_maps(_len) / coattn_backward_maps(_len) (differentiable attention maps); 0.8.0: the length-masked forms coattn_forward_len / _infer_len / _attention_forward_len / _backward_len; 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
+extern "C" int coattn_version(void) { return 1000; }   // 0.10.0: COATTN_FLAG_BILINEAR (the affinity tanh(Q W_b^T + b_b) V^T; W_b / b_b, dW_b / db_b appended to the parameter structs); 0.9.0: coattn_forward_maps(_len) / coattn_backward_maps(_len) (differentiable attention maps); 0.8.0: the length-masked forms coattn_forward_len / _infer_len / _attention_forward_len / _backward_len; 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
 
 // ---------------------------------------------------------------------------------------
 // per-kernel timing (bench.py's backward roofline legs): HIP events recorded between the launches of the calls made
@@ -105,16 +105,30 @@ static BwdPlan plan_bwd(int B, int N, int T, int d, int L) {
   return p;
 }
 
-static size_t fwd_ws_floats(int B, int N, int T, int d, int L) {
-  return plan_saved(B, N, T, d, L).total + al64((size_t)B * N * d);
+// COATTN_FLAG_BILINEAR: behind the common layout of `saved` (at plan_saved(..).total) lie K = Q W_b^T + b_b of all levels
+// [L][B][T][d] and the range words of W_b's FP16 image (tolerance mode); behind the backward's workspace its BilBwd buffers
+static bool bilinear(int flags) { return (flags & COATTN_FLAG_BILINEAR) != 0; }
+static size_t wchunks(int d) { return (size_t)((d + 31) / 32) * ((d + 15) / 16); }
+static size_t bil_floats(int B, int T, int d, int L, bool bil) {
+  return bil ? al64((size_t)L * B * T * d) + al64(wchunks(d)) : 0;
 }
-static size_t bwd_ws_floats(int B, int N, int T, int d, int L) {
+static size_t saved_floats(int B, int N, int T, int d, int L, bool bil) {
+  return plan_saved(B, N, T, d, L).total + bil_floats(B, T, d, L, bil);
+}
+static size_t bil_bwd_floats(int B, int T, int d, int L) {
+  const size_t k = al64((size_t)L * B * T * d);
+  return 3 * k + al64((size_t)2 * d * d) + al64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1) + al64((size_t)L * B * d);
+}
+static size_t fwd_ws_floats(int B, int N, int T, int d, int L, bool bil = false) {
+  return saved_floats(B, N, T, d, L, bil) + al64((size_t)B * N * d);
+}
+static size_t bwd_ws_floats(int B, int N, int T, int d, int L, bool bil = false) {
   size_t bw = plan_bwd(B, N, T, d, L).total;
   if (fused_supported(B, N, T, d, L)) {
     const size_t fb = fused_bwd_ws_floats(B, N, T, d, L);
     if (fb > bw) bw = fb;
   }
-  return bw;
+  return bw + (bil ? bil_bwd_floats(B, T, d, L) : 0);
 }
 
 static int check_shape(int B, int N, int T, int d, int L, int dtype) {
@@ -133,13 +147,12 @@ extern "C" int coattn_fused_supported(int B, int N, int T, int d, int L, int dty
 
 extern "C" int coattn_workspace_bytes(int B, int N, int T, int d, int L, int dtype, int flags, size_t* saved,
                                       size_t* ws_fwd, size_t* ws_bwd) {
-  (void)flags;
   CA_TRY(check_shape(B, N, T, d, L, dtype));
-  const SavedPlan sp = plan_saved(B, N, T, d, L);
-  if (saved) *saved = sp.total * sizeof(float);
+  const bool bil = bilinear(flags);                   // (K in `saved`, dK in the backward's workspace)
+  if (saved) *saved = saved_floats(B, N, T, d, L, bil) * sizeof(float);
   // the forward workspace ends with room for two pre-split weight images (gemm_w.hip)
-  if (ws_fwd) *ws_fwd = fwd_ws_floats(B, N, T, d, L) * sizeof(float) + 2 * wsplit_bytes(d, d);
-  if (ws_bwd) *ws_bwd = bwd_ws_floats(B, N, T, d, L) * sizeof(float);
+  if (ws_fwd) *ws_fwd = fwd_ws_floats(B, N, T, d, L, bil) * sizeof(float) + (bil ? 3 : 2) * wsplit_bytes(d, d);   // (+ W_b's)
+  if (ws_bwd) *ws_bwd = bwd_ws_floats(B, N, T, d, L, bil) * sizeof(float);
   return 0;
 }
 
@@ -292,6 +305,11 @@ struct Ctx {
   bool f16_proj = false;      // fp32 mode: both projections on two FP16 pieces (fused.h kF16WScale)
   float pscale = 1.f;         // factor on P_v, P_q as stored (fused path: kPScale, fused.h)
   const int* qlen = nullptr;  // [B] question lengths (the *_len entry points), NULL: unmasked
+  // COATTN_FLAG_BILINEAR (NULL W_b: the reference's affinity): W_b, b_b and K = Q W_b^T + b_b of all levels [L][B][T][d]
+  const float* Wb = nullptr;
+  const float* bb = nullptr;
+  float* K = nullptr;
+  float* dK = nullptr;        // (backward) dK = dA V of all levels, in the workspace
 };
 
 int launch_proj(const Ctx& c, const coattn_gemm_desc& g) {
@@ -318,6 +336,17 @@ int proj_q(const Ctx& c, const float* Q, const float* Wq, const float* bq, float
   g.b_sk = 1; g.b_sn = c.d;
   g.c_sm = c.d; g.c_sn = 1;
   return launch_proj(c, g);
+}
+// K_l = Q_l W_b^T + b_b of all levels in one launch (batch z = level, A from the pointer table; COATTN_FLAG_BILINEAR)
+int proj_k(const Ctx& c, const float* const* Q) {
+  coattn_gemm_desc g = {};
+  for (int l = 0; l < c.L; ++l) g.a_ptrs[l] = Q[l];
+  g.B = c.Wb; g.C = c.K; g.c_sz = (int64_t)c.B * c.T * c.d; g.bias_n = c.bb;
+  g.M = c.B * c.T; g.N = c.d; g.K = c.d; g.batch = c.L;
+  g.a_sm = c.d; g.a_sk = 1;
+  g.b_sk = 1; g.b_sn = c.d;
+  g.c_sm = c.d; g.c_sn = 1;
+  return launch_gemm_f32(g, c.s);
 }
 // C = tanh(Q V)   (model.py:377)
 int affinity(const Ctx& c, const float* Q, const float* V, float* C) {
@@ -516,6 +545,30 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
   return launch_proj(c, g);
 }
 
+// COATTN_FLAG_BILINEAR: K = Q W_b^T + b_b of all levels.  On the pre-split-weight kernels whenever P_q runs there -- the same
+// kernel, width and FP16-piece mode as P_q (the tolerance mode range-checks the stored K: it is phase 1's FP16-piece operand), W_b
+// split by a launch of its own into the third image of the forward workspace, whose |256 W| words are folded into W_q's (the
+// range report covers both weights) -- else on the general GEMM.  Dense: pad rows take b_b, not the P_q bitmap's bias path.
+int bilinear_projection(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, float* sv, char* wimg_b) {
+  const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
+  WGemm wv, wq;
+  bool v_w, q_w;
+  const bool f16 = c.f16_proj && !c.bf16_proj;
+  projection_jobs(c, V, Q, p, sv, nullptr, wv, wq, v_w, q_w, f16);
+  if (!q_w) return proj_k(c, Q);
+  WGemm wk = wq;
+  wk.Wf = wimg_b; wk.C = c.K; wk.bias_n = c.bb; wk.out_scale = 1.f; wk.rowbits = nullptr;
+  float* status = sv + sp.status;
+  float* wb_words = c.K + al64((size_t)c.L * c.B * c.T * c.d);
+  wk.status = f16 ? status : nullptr;
+  const WSplit job{c.Wb, wimg_b, c.d, c.d, 0, c.d, wimg_pieces(wk), f16 ? wb_words : nullptr};
+  CA_TRY(launch_wsplit(&job, 1, c.s));
+  if (f16) CA_TRY(launch_max_words(status + kStatusHdr + wchunks(c.d), wb_words, (int)wchunks(c.d), c.s));
+  CA_TRY(launch_gemm_wx(&wk, 1, c.s));
+  prof_mark(c.s, "bilinear_projection");
+  return 0;
+}
+
 // everything after the projections: affinity, H_v / H_q, scores, softmax, attended reductions
 // av_out / aq_out: the caller's map buffers [L][B][N] / [L][B][T] (coattn_infer), else NULL: the maps go to `sv`;
 // dual (coattn_forward_maps): the maps go to `sv` AND to av_out / aq_out, from the same softmax launches
@@ -532,7 +585,7 @@ int general_attention(const Ctx& c, const float* V, const float* const* Q, const
     float* aq = (aq_out && !dual ? aq_out : sv + sp.aq) + (size_t)l * c.B * c.T;
     float* av2 = dual ? av_out + (size_t)l * c.B * c.N : nullptr;
     float* aq2 = dual ? aq_out + (size_t)l * c.B * c.T : nullptr;
-    CA_TRY(affinity(c, Q[l], V, C));
+    CA_TRY(affinity(c, c.K ? c.K + l * BTd : Q[l], V, C));   // (bilinear: A = K V^T; q below stays a_q^T Q)
     if (c.qlen) CA_TRY(launch_mask_rows(C, c.qlen, c.B, c.T, c.N, c.s));   // length mask: C rows t >= len_b are zero
     CA_TRY(ct_times(c, C, Pq, Pv, Hv, 1));
     CA_TRY(c_times(c, C, Pv, Pq, Hq, 1));
@@ -613,22 +666,32 @@ int backward_general(const Ctx& c, const float* V, const float* const* Q, const 
     // dP_v(level) = dZ_v + C^T dZ_q   (in place), accumulate over levels
     CA_TRY(ct_times(c, C, dZq, Hv, Hv, 0));
     CA_TRY(launch_add_inplace(dPv, Hv, (int64_t)BNd, l > 0 ? 1 : 0, c.s));
-    // dQ_l = a_q (x) gq + dA V^T   (+ dP_q W_q below)
+    // dQ_l = a_q (x) gq + dA V^T   (+ dP_q W_q below);  bilinear: dK_l = dA V^T, dQ_l = a_q (x) gq + dK_l W_b (+ dP_q W_q)
     CA_TRY(launch_rank1(aq, gq + l * Bd, dQ[l], B, T, d, (int64_t)T * d, d, 1, 0, c.s));
+    float* dKl = c.K ? c.dK + l * BTd : nullptr;
     {
       coattn_gemm_desc g = {};
       g.A = dC; g.a_sz = (int64_t)T * N; g.a_sm = N; g.a_sk = 1;
       g.B = V; g.b_sz = c.vl.sB; g.b_sk = c.vl.sN; g.b_sn = c.vl.sD;
-      g.Cin = dQ[l]; g.cin_sz = (int64_t)T * d; g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f;
-      g.C = dQ[l]; g.c_sz = (int64_t)T * d; g.c_sm = d; g.c_sn = 1;
+      if (!dKl) { g.Cin = dQ[l]; g.cin_sz = (int64_t)T * d; g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f; }
+      g.C = dKl ? dKl : dQ[l]; g.c_sz = (int64_t)T * d; g.c_sm = d; g.c_sn = 1;
       g.M = T; g.N = d; g.K = N; g.batch = B;
       CA_TRY(launch_gemm_f32(g, c.s));
     }
-    // dV (+)= a_v (x) gv + Q^T dA
+    if (dKl) {
+      coattn_gemm_desc g = {};
+      g.A = dKl; g.a_sm = d; g.a_sk = 1;
+      g.B = c.Wb; g.b_sk = d; g.b_sn = 1;
+      g.Cin = dQ[l]; g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f;
+      g.C = dQ[l]; g.c_sm = d; g.c_sn = 1;
+      g.M = B * T; g.N = d; g.K = d; g.batch = 1;
+      CA_TRY(launch_gemm_f32(g, c.s));
+    }
+    // dV (+)= a_v (x) gv + Q^T dA   (bilinear: K^T dA)
     if (dV) CA_TRY(launch_rank1(av, gv + l * Bd, dV, B, N, d, dvl.sB, dvl.sN, dvl.sD, l > 0 ? 1 : 0, c.s));
     if (dV) {
       coattn_gemm_desc g = {};
-      g.A = Q[l]; g.a_sz = (int64_t)T * d; g.a_sm = 1; g.a_sk = d;
+      g.A = c.K ? c.K + l * BTd : Q[l]; g.a_sz = (int64_t)T * d; g.a_sm = 1; g.a_sk = d;
       g.B = dC; g.b_sz = (int64_t)T * N; g.b_sk = N; g.b_sn = 1;
       g.Cin = dV; g.cin_sz = dvl.sB; g.cin_sm = dvl.sD; g.cin_sn = dvl.sN; g.beta = 1.f;
       g.C = dV; g.c_sz = dvl.sB; g.c_sm = dvl.sD; g.c_sn = dvl.sN;
@@ -693,6 +756,26 @@ int backward_general(const Ctx& c, const float* V, const float* const* Q, const 
     CA_TRY(launch_colsum_partial(nullptr, ws + bp.dPq, part, R, d, rpc, &nch, c.s));
     CA_TRY(launch_reduce_partials(part, (float*)pg->db_q, nch, d, accumulate, c.s));
   }
+  if (c.K) {
+    // bilinear: dW_b[j][k] += sum_m dK_l[m][j] Q_l[m][k] (split-K, as dW_q);  db_b = sum of every row of dK
+    for (int l = 0; l < L; ++l) {
+      const int K = B * T;
+      int ks = (K + kMaxSplits - 1) / kMaxSplits;
+      ks = (ks + 15) / 16 * 16;
+      const int S = (K + ks - 1) / ks;
+      coattn_gemm_desc g = {};
+      g.A = c.dK + l * BTd; g.a_sm = 1; g.a_sk = d;
+      g.B = Q[l]; g.b_sk = d; g.b_sn = 1;
+      g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
+      g.M = d; g.N = d; g.K = K; g.batch = S; g.ksplit = ks;
+      CA_TRY(launch_gemm_f32(g, c.s));
+      CA_TRY(launch_reduce_partials(part, (float*)pg->dW_b, S, (int64_t)d * d, (accumulate || l > 0) ? 1 : 0, c.s));
+    }
+    const int R = L * B * T;
+    const int rpc = (R + 255) / 256 > 32 ? (R + 255) / 256 : 32;
+    CA_TRY(launch_colsum_partial(nullptr, c.dK, part, R, d, rpc, &nch, c.s));
+    CA_TRY(launch_reduce_partials(part, (float*)pg->db_b, nch, d, accumulate, c.s));
+  }
   return 0;
 }
 
@@ -728,6 +811,15 @@ static Ctx call_ctx(int B, int N, int T, int d, int L, void* stream, const VLayo
   return c;
 }
 
+// COATTN_FLAG_BILINEAR: the refusals of include/coattn.h (pg: the backward's gradients, NULL in a forward)
+static int check_bilinear(int flags, const coattn_params* p, const coattn_param_grads* pg) {
+  if (!bilinear(flags)) return 0;
+  CA_CHECK_ARG(!(flags & COATTN_FLAG_BF16_PROJ), "COATTN_FLAG_BILINEAR is not available in the reduced-precision mode (COATTN_FLAG_BF16_PROJ)");
+  CA_CHECK_ARG(p->W_b && p->b_b, "COATTN_FLAG_BILINEAR: null W_b / b_b");
+  CA_CHECK_ARG(!pg || (pg->dW_b && pg->db_b), "COATTN_FLAG_BILINEAR: null dW_b / db_b");
+  return 0;
+}
+
 static int check_vlayout(const VLayout& v, int B, int N, int d, const char* what) {
   (void)B;
   CA_CHECK_ARG(v.sN > 0 && v.sD > 0 && v.sB > 0, "%s: strides must be positive (sB=%ld sN=%ld sD=%ld)", what, v.sB, v.sN, v.sD);
@@ -749,22 +841,27 @@ static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, 
   for (int l = 0; l < L; ++l) CA_CHECK_ARG(Q[l] != nullptr, "forward: Q[%d] is null", l);
   CA_CHECK_ARG(p->W_v && p->b_v && p->W_q && p->b_q && p->w_v && p->c_v && p->w_q && p->c_q,
                "forward: null parameter pointer");
+  const bool bil = bilinear(flags);
+  CA_TRY(check_bilinear(flags, p, nullptr));
   int fused = 0;
   CA_TRY(pick_impl(flags, B, N, T, d, L, vl, &fused));
   const SavedPlan sp = plan_saved(B, N, T, d, L);
   float* sv = saved ? (float*)saved : (float*)ws;      // inference: state lives in the workspace
-  float* tail = (float*)ws + sp.total;
-  const Ctx c = call_ctx(B, N, T, d, L, stream, vl, q_len, V, Q, flags, fused);
-  if (do_proj)
-    CA_TRY(general_projections(c, (const float*)V, (const float* const*)Q, p, sv,
-                               (char*)ws + fwd_ws_floats(B, N, T, d, L) * sizeof(float), saved != nullptr));
+  float* tail = (float*)ws + saved_floats(B, N, T, d, L, bil);
+  Ctx c = call_ctx(B, N, T, d, L, stream, vl, q_len, V, Q, flags, fused);
+  if (bil) { c.Wb = (const float*)p->W_b; c.bb = (const float*)p->b_b; c.K = sv + sp.total; }
+  if (do_proj) {
+    char* wimg = (char*)ws + fwd_ws_floats(B, N, T, d, L, bil) * sizeof(float);
+    CA_TRY(general_projections(c, (const float*)V, (const float* const*)Q, p, sv, wimg, saved != nullptr));
+    if (bil) CA_TRY(bilinear_projection(c, (const float*)V, (const float* const*)Q, p, sv, wimg + 2 * wsplit_bytes(d, d)));
+  }
   if (!do_attn) return 0;
   const bool dual = saved && av_out;                  // coattn_forward_maps
   if (fused)
     return fused_attention_forward(B, N, T, d, L, (const float*)V, vl, (const float* const*)Q, p, (float*)v_out,
                                    (float*)q_out, sv, tail, c.s, c.bf16_proj ? 1 : 0, np_fwd(flags, c.f16_proj),
                                    dual ? nullptr : (float*)av_out, dual ? nullptr : (float*)aq_out, saved != nullptr ? 1 : 0,
-                                   q_len, dual ? (float*)av_out : nullptr, dual ? (float*)aq_out : nullptr);
+                                   q_len, dual ? (float*)av_out : nullptr, dual ? (float*)aq_out : nullptr, c.K);
   return general_attention(c, (const float*)V, (const float* const*)Q, p, (float*)v_out, (float*)q_out, sv, tail,
                            (float*)av_out, (float*)aq_out, dual);
 }
@@ -844,9 +941,23 @@ static int backward_impl(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD
   for (int l = 0; l < L; ++l) CA_CHECK_ARG(Q[l] && dQ[l], "backward: Q[%d]/dQ[%d] is null", l, l);
   CA_CHECK_ARG(pg->dW_v && pg->db_v && pg->dW_q && pg->db_q && pg->dw_v && pg->dc_v && pg->dw_q && pg->dc_q,
                "backward: null parameter-gradient pointer");
+  CA_TRY(check_bilinear(flags, p, pg));
   int fused = 0;
   CA_TRY(pick_impl(flags, B, N, T, d, L, vl, &fused));
-  const Ctx c = call_ctx(B, N, T, d, L, stream, vl, q_len, V, Q, flags, fused);
+  Ctx c = call_ctx(B, N, T, d, L, stream, vl, q_len, V, Q, flags, fused);
+  if (bilinear(flags)) {                              // K from the forward's `saved`, dK into the workspace
+    c.Wb = (const float*)p->W_b; c.bb = (const float*)p->b_b;
+    c.K = (float*)saved + plan_saved(B, N, T, d, L).total;
+    c.dK = (float*)ws + bwd_ws_floats(B, N, T, d, L, false);
+  }
+  BilBwd bb = {};
+  if (c.K) {
+    const size_t k = al64((size_t)L * B * T * d);
+    bb.Wb = c.Wb; bb.K = c.K; bb.dK = c.dK; bb.dpk = c.dK + k; bb.wstack = c.dK + 3 * k;
+    bb.wimg = c.dK + 3 * k + al64((size_t)2 * d * d);
+    bb.zeros = (float*)bb.wimg + al64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1);
+    bb.dWb = (float*)pg->dW_b; bb.dbb = (float*)pg->db_b;
+  }
   // (`saved` of the fused forward holds P_v, P_q scaled by kPScale: only the fused backward may read it)
   CA_CHECK_ARG(!fused || fused_backward_supported(B, N, T, d, L), "backward: the fused forward's saved state has no fused backward for this shape");
   if (fused)
@@ -855,7 +966,7 @@ static int backward_impl(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD
                           (float*)ws, c.s, c.bf16_proj ? 1 : 0,
                           gemm_w_enabled() ? 1 : 0, np_bwd(flags),
                           rowbits_in_saved(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, flags, fused) ? 1 : 0,
-                          q_len, (const float*)g_av, (const float*)g_aq);
+                          q_len, (const float*)g_av, (const float*)g_aq, c.K ? &bb : nullptr);
   return backward_general(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, (const float*)gv,
                           (const float*)gq, (float*)dV, dvl, (float* const*)dQ, pg, accumulate, (float*)ws, (const float*)g_av,
                           (const float*)g_aq);

@@ -59,7 +59,7 @@ int fused_supported(int B, int N, int T, int d, int L) {
 int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl,
                             const float* const* Q, const coattn_params* p, float* v_out, float* q_out, float* saved,
                             float* ws, hipStream_t s, int bf16, int np, float* av, float* aq, int keep, const int* qlen,
-                            float* av_copy, float* aq_copy) {
+                            float* av_copy, float* aq_copy, const float* K) {
   CA_CHECK_ARG(fused_supported(B, N, T, d, L), "fused forward: unsupported shape");
   const bool lm = v_is_lm(vl, N, d);
   CA_CHECK_ARG(lm || v_is_cm(vl, N, d), "fused forward: image features must be channel-major [B,d,N] or location-major [B,N,d]");
@@ -71,7 +71,8 @@ int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, c
   a.wv = (const float*)p->w_v; a.cv = (const float*)p->c_v; a.wq = (const float*)p->w_q; a.cq = (const float*)p->c_q;
   a.C = saved + so.C; a.Hq = saved + so.Hq;
   a.av = av ? av : saved + so.av; a.aq = aq ? aq : saved + so.aq;   // the caller's map buffers (coattn_infer), else `saved`
-  a.av2 = av_copy; a.aq2 = aq_copy;                  // (coattn_forward_maps: a second store of both maps, same epilogue)
+  a.av2 = av_copy; a.aq2 = aq_copy;
+  a.K = K;                                           // (bilinear: phase 1 streams K, phase 3 still reads Q)                  // (coattn_forward_maps: a second store of both maps, same epilogue)
   a.keep = keep ? 1 : 0;
   a.qlen = qlen;
   a.q_out = q_out;

@@ -329,7 +329,7 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
                    const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
                    const VLayout& dvl, float* const* dQ, const coattn_param_grads* pg, int accumulate, float* ws,
                    hipStream_t s, int bf16_proj, int wgemm, int np, int live_rows, const int* qlen, const float* g_av,
-                   const float* g_aq) {
+                   const float* g_aq, const BilBwd* bil) {
   // np: width of the fp32 mode's contractions (fused.h): 2 = hi + mid in the three fused kernels and in the GEMM launch
   // (dW_v, dW_q, dQ = dP_q W_q), 3 = the exact split everywhere; dV (general GEMM) is always exact
   np = (np == 2 && !bf16_proj) ? 2 : 3;
@@ -423,8 +423,10 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
   // 123.2 combined at N = 196, 41.8 + 26.6 against 63.7 at N = 49: inside the weight-gradient launch its tiles fill the CUs
   // the last parts leave, which is worth as much as the faster kernel.
   static const int own_dq_env = dev_env_int("COATTN_OWN_DQ", 0);
-  const bool own_dq = own_dq_env && dq32 && wdq_ok && tn_v && tn_q && !gemm_bf_supported(wdq) && gemm_h2_supported(wdq) && !no_combine;
-  const bool combine = dq32 && wdq_ok && tn_v && tn_q && !gemm_bf_supported(wdq) && !no_combine && !own_dq;
+  const bool own_dq = own_dq_env && !bil && dq32 && wdq_ok && tn_v && tn_q && !gemm_bf_supported(wdq) && gemm_h2_supported(wdq) && !no_combine;
+  // (bilinear: dQ comes from its own projection [dP_q | dK] [W_q; W_b] below, so the dQ tiles do not ride in the weight-gradient
+  //  launch -- which keeps the static split-K plan)
+  const bool combine = dq32 && wdq_ok && tn_v && tn_q && !gemm_bf_supported(wdq) && !no_combine && !own_dq && !bil;
   const bool late_dq = combine || own_dq;           // the dA V kernel (and, before it, the projection) run after the weight gradients
   // Reduced-precision mode with a frozen image encoder (no dV) and all three consumers of dP_v / dP_q on gemm_bf.hip:
   // bwd_nat32 stores both as bf16 -- the GEMMs would round them on their way in anyway -- halving what it writes and
@@ -478,23 +480,20 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
   //    accumulate input); channel-major features with unaligned rows (N % 4 != 0): the exact-f32 kernel first, then
   //    the projection onto it.
   //    When the projection shares the weight-gradient launch (step 5), the dA V kernel runs after that launch.
-  if (dq32 && !late_dq) {
-    CA_TRY(dq_projection(false));
-    prof_mark(s, "bwd_gemm_dq_projection");
-  }
   // (red: the two weight gradients' partial sums, handed to the dQ kernel's launch when it is the bf16-MFMA one)
   struct RedJob { const float* part[2]; float* out[2]; int np[2]; long n; int acc; bool on; TnDyn dyn; } red = {};
   static const int red_in_dq = dev_env_int("COATTN_RED_IN_DQ", 1);   // developer switch
-  auto run_dq = [&]() -> int {
+  // dst / gq_ / acc (bilinear's dK pass: dK = dA V + a_q (x) 0, overwritten): the dQ pointers, gq and the accumulate of the plain call
+  auto run_dq = [&](float* const* dst = nullptr, const float* gq_ = nullptr, int acc = -1) -> int {
     DqArgs da = {};
-    da.accumulate = dq32 ? 1 : 0;
+    da.accumulate = acc >= 0 ? acc : (dq32 ? 1 : 0);
     if (red.on && dq32) {
       for (int i = 0; i < 2; ++i) { da.red_part[i] = red.part[i]; da.red_out[i] = red.out[i]; da.red_np[i] = red.np[i]; }
       da.red_n = red.n; da.red_acc = red.acc; da.red_jobs = 2; da.red_blocks = (int)((red.n / 4 + 255) / 256);
       da.red_dyn = red.dyn;
     }
-    da.V = V; da.v_sB = vl.sB; da.dA = ws + wo.dA; da.aq = saved + so.aq; da.gq = gq;
-    for (int l = 0; l < 8; ++l) da.dQ[l] = l < L ? dQ[l] : nullptr;
+    da.V = V; da.v_sB = vl.sB; da.dA = ws + wo.dA; da.aq = saved + so.aq; da.gq = gq_ ? gq_ : gq;
+    for (int l = 0; l < 8; ++l) da.dQ[l] = l < L ? (dst ? dst[l] : dQ[l]) : nullptr;
     da.B = B; da.N = N; da.T = T; da.d = d; da.L = L;
     da.bf16 = bf16_proj; da.np = np;
     const bool al = (N % 4) == 0;
@@ -526,14 +525,81 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
     prof_mark(s, "bwd_dq");
     return 0;
   };
-  if (!late_dq) CA_TRY(run_dq());
+  if (bil) {
+    // The bilinear affinity: dK = dA V (the dA V pass, into dK), then ONE projection dQ = [dP_q | dK] [W_q; W_b] (K = 2d) on the
+    // pre-split-weight kernel, + a_q (x) gq; dW_b = sum_l dK_l^T Q_l on the weight-gradient kernel, db_b = column sums of dK.
+    float* dk_ptrs[8] = {};
+    for (int l = 0; l < L; ++l) dk_ptrs[l] = bil->dK + l * BTd;
+    if (hipMemsetAsync(bil->zeros, 0, (size_t)L * Bd * sizeof(float), s) != hipSuccess) {
+      coattn_set_error("fused backward: hipMemsetAsync failed");
+      return -3;
+    }
+    CA_TRY(run_dq(dk_ptrs, bil->zeros, 0));
+    CA_TRY(launch_concat_cols(ws + wo.dPq, d, bil->dK, d, bil->dpk, (int64_t)L * B * T, s));
+    CA_TRY(launch_concat_cols((const float*)p->W_q, d * d, bil->Wb, d * d, bil->wstack, 1, s));
+    WGemm wj = dq_proj_job(B, T, d, L, 0, np);
+    wj.K = 2 * d; wj.a_sm = 2 * d; wj.a_sz = 2 * (long)BTd; wj.A = bil->dpk; wj.Wf = bil->wimg;
+    for (int l = 0; l < L; ++l) wj.c_ptrs[l] = dQ[l];
+    if (wgemm && gemm_w_supported(wj)) {
+      const WSplit job{bil->wstack, bil->wimg, d, 2 * d, 1, d, wimg_pieces(wj), nullptr};
+      CA_TRY(launch_wsplit(&job, 1, s));
+      CA_TRY(launch_gemm_wx(&wj, 1, s));
+    } else {
+      coattn_gemm_desc g = {};
+      g.A = bil->dpk; g.a_sz = 2 * (int64_t)BTd; g.a_sm = 2 * d; g.a_sk = 1;
+      g.B = bil->wstack; g.b_sk = d; g.b_sn = 1;
+      for (int l = 0; l < L; ++l) g.c_ptrs[l] = dQ[l];
+      g.c_sm = d; g.c_sn = 1;
+      g.M = B * T; g.N = d; g.K = 2 * d; g.batch = L;
+      CA_TRY(launch_gemm_f32(g, s));
+    }
+    for (int l = 0; l < L; ++l)
+      CA_TRY(launch_rank1(saved + so.aq + (size_t)l * B * T, gq + l * Bd, dQ[l], B, T, d, (int64_t)T * d, d, 1, 1, s));
+    prof_mark(s, "bwd_bilinear_dq");
+    TnGemm tnb = tnq;
+    tnb.A = bil->dK; tnb.a_bf16 = 0; tnb.C = part;
+    if (tn_q) {
+      int ks, S;
+      const int parts = gemm_tn_plan(tnb, 32, &ks, &S);
+      CA_TRY(launch_gemm_tn(&tnb, &ks, &S, 1, s));
+      CA_TRY(launch_reduce_partials(part, bil->dWb, parts, (int64_t)d * d, accumulate, s));
+    } else {
+      for (int l = 0; l < L; ++l) {
+        const int K = B * T;
+        int ks = (K + 31) / 32;
+        ks = (ks + 15) / 16 * 16;
+        const int S = (K + ks - 1) / ks;
+        coattn_gemm_desc g = {};
+        g.A = bil->dK + l * BTd; g.a_sm = 1; g.a_sk = d;
+        g.B = Q[l]; g.b_sk = d; g.b_sn = 1;
+        g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
+        g.M = d; g.N = d; g.K = K; g.batch = S; g.ksplit = ks;
+        CA_TRY(launch_gemm_f32(g, s));
+        CA_TRY(launch_reduce_partials(part, bil->dWb, S, (int64_t)d * d, (accumulate || l > 0) ? 1 : 0, s));
+      }
+    }
+    {
+      const int R = L * B * T;
+      const int rpc = (R + 255) / 256 > 32 ? (R + 255) / 256 : 32;
+      int nch = 0;
+      CA_TRY(launch_colsum_partial(nullptr, bil->dK, part, R, d, rpc, &nch, s));
+      CA_TRY(launch_reduce_partials(part, bil->dbb, nch, d, accumulate, s));
+    }
+    prof_mark(s, "bwd_bilinear_dwb");
+  } else {
+    if (dq32 && !late_dq) {
+      CA_TRY(dq_projection(false));
+      prof_mark(s, "bwd_gemm_dq_projection");
+    }
+    if (!late_dq) CA_TRY(run_dq());
+  }
   if (dV) {
     for (int l = 0; l < L; ++l) {
       const float* dA = ws + wo.dA + l * BTN;
       const float* av = saved + so.av + (size_t)l * B * N;
       CA_TRY(launch_rank1(av, gv + l * Bd, dV, B, N, d, dvl.sB, dvl.sN, dvl.sD, l > 0 ? 1 : 0, s));
       coattn_gemm_desc g = {};
-      g.A = Q[l]; g.a_sz = (int64_t)T * d; g.a_sm = 1; g.a_sk = d;
+      g.A = bil ? bil->K + l * BTd : Q[l]; g.a_sz = (int64_t)T * d; g.a_sm = 1; g.a_sk = d;   // (bilinear: dA^T K)
       g.B = dA; g.b_sz = (int64_t)T * N; g.b_sk = N; g.b_sn = 1;
       g.Cin = dV; g.cin_sz = dvl.sB; g.cin_sm = dvl.sD; g.cin_sn = dvl.sN; g.beta = 1.f;
       g.C = dV; g.c_sz = dvl.sB; g.c_sm = dvl.sD; g.c_sn = dvl.sN;
@@ -541,7 +607,7 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
       CA_TRY(launch_gemm_f32(g, s));
     }
   }
-  if (!dq32) CA_TRY(dq_projection(true));
+  if (!dq32 && !bil) CA_TRY(dq_projection(true));
   // sum dP_v over the levels in place into level 0 (one streaming pass for L = 3; folding the sum into
   // the weight-gradient GEMM's operand loads was measured slower: 302 vs 170 + 50 us)
   // (the frozen-encoder default needs no dV: the weight-gradient kernel then adds the three levels while staging them)

@@ -79,7 +79,9 @@ __device__ __forceinline__ void vmcnt_wait(int n) {
 // MASK: the length-masked form (coattn_forward_len, FwdArgs::qlen); a template flag so that the unmasked code objects stay
 // what they were (the runtime test alone moved the tolerance instantiations by 2 - 4 VGPRs).
 // MAPS: the maps are stored twice from the same epilogue (coattn_forward_maps, FwdArgs::av2 / aq2) -- a template flag too.
-template <int NT, int NW, bool LM, int NP_, bool FV = false, bool MASK = false, bool MAPS = false>
+// BIL: the bilinear affinity (COATTN_FLAG_BILINEAR): phase 1 streams K = Q W_b^T + b_b (FwdArgs::K, a resource of its own that
+// ends at row tl like the Q one) in place of Q; phase 3's q = a_q^T Q keeps reading Q.  Without it the K resource IS the Q one.
+template <int NT, int NW, bool LM, int NP_, bool FV = false, bool MASK = false, bool MAPS = false, bool BIL = false>
 __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs a) {
   static_assert(!FV || (LM && NT == 2 && NW == 4), "the fused v pass: location-major features, N <= 64, 256 threads");
   constexpr bool HF = NP_ == 4;
@@ -126,6 +128,7 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
   const float* Pqp = a.Pq + pair * (size_t)T * d;
   // buffer resources over exactly this sample's tensors: rows beyond T / N (Q: beyond tl) read as 0, stores there are dropped
   const __amdgpu_buffer_rsrc_t rs_q = make_rsrc(Qp, (unsigned)tl * d * 4u);
+  const __amdgpu_buffer_rsrc_t rs_k = BIL ? make_rsrc(a.K + pair * (size_t)T * d, (unsigned)tl * d * 4u) : rs_q;
   const __amdgpu_buffer_rsrc_t rs_v = make_rsrc(Vp, (unsigned)d * N * 4u);
   const __amdgpu_buffer_rsrc_t rs_pq = make_rsrc(Pqp, (unsigned)T * d * 4u);
   const int nsl = d / (128 * NW);                    // 128-channel slices per wave (1 at d = 512)
@@ -185,7 +188,7 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           if (j == 0)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_q, (lds_ptr)(dst + 1024 * i), 16, dvoff, so + 8 * i * d * 4, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (lds_ptr)(dst + 1024 * i), 16, dvoff, so + 8 * i * d * 4, 0, 0);
           else
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (lds_ptr)(dst + 1024 * i), 16, dvoff, so + 8 * i * d * 4, 0, 0);
         }
@@ -290,8 +293,8 @@ __global__ __launch_bounds__(NW * 64, 2) void coattn_fwd32_kernel(const FwdArgs 
         if (j == 0) {                                  // Q fragment
           // (the +32 bytes of the second piece go into the scalar offset: an instruction offset would also move the
           // LDS address)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_q, (lds_ptr)dst, 16, q_voff, k0 * 4, 0, 0);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_q, (lds_ptr)(dst + 1024), 16, q_voff, k0 * 4 + 32, 0, 0);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (lds_ptr)dst, 16, q_voff, k0 * 4, 0, 0);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (lds_ptr)(dst + 1024), 16, q_voff, k0 * 4 + 32, 0, 0);
         } else {
           // channel-major V [d][N]: a unit is 16 channel rows x 32 locations (128 B per row), fetched by two 16-byte
           // DMAs of 8 rows each (a lane per 16 bytes of a row segment) into a row-major image [16][32]
@@ -886,7 +889,7 @@ __global__ __launch_bounds__(256) void attend_v_lm_kernel(const float* V, long v
   }
 }
 
-template <int NT, int NW, bool LM, int NP, bool FV = false, bool MASK = false, bool MAPS = false>
+template <int NT, int NW, bool LM, int NP, bool FV = false, bool MASK = false, bool MAPS = false, bool BIL = false>
 int launch_fwd32(const FwdArgs& a, hipStream_t s) {
   constexpr int NPAD = 32 * NT;
   constexpr int RING_SLOTS = (NT + 1) * ((NT + 1 >= 6) ? 1 : 2);
@@ -895,17 +898,17 @@ int launch_fwd32(const FwdArgs& a, hipStream_t s) {
   const size_t lds = lds_p2 > lds_p1 ? lds_p2 : lds_p1;
   static DeviceOnce once;                            // the attribute is per device
   CA_TRY(once.run([&] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK, MAPS>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK, MAPS, BIL>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }, "coattn_fwd32"));
   const int groups = (a.B + 7) / 8;
   dim3 grid(groups * a.L * 8), block(NW * 64);
-  hipLaunchKernelGGL((coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK, MAPS>), grid, block, lds, s, a);
+  hipLaunchKernelGGL((coattn_fwd32_kernel<NT, NW, LM, NP, FV, MASK, MAPS, BIL>), grid, block, lds, s, a);
   CA_CHECK_LAUNCH("coattn_fwd32");
   return 0;
 }
 
-template <bool LM, bool M, bool MP>
+template <bool LM, bool M, bool MP, bool BL>
 int dispatch_fwd32(const FwdArgs& a, hipStream_t s) {
   const bool small_n = a.N <= 64;
   const bool w2 = a.np == 2;                         // phase 2 on two bf16 pieces
@@ -913,19 +916,28 @@ int dispatch_fwd32(const FwdArgs& a, hipStream_t s) {
   if (a.d % 512 == 0) {
     if constexpr (LM) {
       if (small_n && a.v_out) {                      // the kernel attends the image features too (FwdArgs::v_out)
-        if (a.bf16) return launch_fwd32<2, 4, true, 1, true, M, MP>(a, s);
-        if (hf) return launch_fwd32<2, 4, true, 4, true, M, MP>(a, s);
-        return w2 ? launch_fwd32<2, 4, true, 2, true, M, MP>(a, s) : launch_fwd32<2, 4, true, 3, true, M, MP>(a, s);
+        if (a.bf16) return launch_fwd32<2, 4, true, 1, true, M, MP, BL>(a, s);
+        if (hf) return launch_fwd32<2, 4, true, 4, true, M, MP, BL>(a, s);
+        return w2 ? launch_fwd32<2, 4, true, 2, true, M, MP, BL>(a, s) : launch_fwd32<2, 4, true, 3, true, M, MP, BL>(a, s);
       }
     }
-    if (a.bf16) return small_n ? launch_fwd32<2, 4, LM, 1, false, M, MP>(a, s) : launch_fwd32<7, 4, LM, 1, false, M, MP>(a, s);
-    if (hf) return small_n ? launch_fwd32<2, 4, LM, 4, false, M, MP>(a, s) : launch_fwd32<7, 4, LM, 4, false, M, MP>(a, s);
-    if (w2) return small_n ? launch_fwd32<2, 4, LM, 2, false, M, MP>(a, s) : launch_fwd32<7, 4, LM, 2, false, M, MP>(a, s);
-    return small_n ? launch_fwd32<2, 4, LM, 3, false, M, MP>(a, s) : launch_fwd32<7, 4, LM, 3, false, M, MP>(a, s);
+    if (a.bf16) return small_n ? launch_fwd32<2, 4, LM, 1, false, M, MP, BL>(a, s) : launch_fwd32<7, 4, LM, 1, false, M, MP, BL>(a, s);
+    if (hf) return small_n ? launch_fwd32<2, 4, LM, 4, false, M, MP, BL>(a, s) : launch_fwd32<7, 4, LM, 4, false, M, MP, BL>(a, s);
+    if (w2) return small_n ? launch_fwd32<2, 4, LM, 2, false, M, MP, BL>(a, s) : launch_fwd32<7, 4, LM, 2, false, M, MP, BL>(a, s);
+    return small_n ? launch_fwd32<2, 4, LM, 3, false, M, MP, BL>(a, s) : launch_fwd32<7, 4, LM, 3, false, M, MP, BL>(a, s);
   }
-  if (hf) return small_n ? launch_fwd32<2, 2, LM, 4, false, M, MP>(a, s) : launch_fwd32<7, 2, LM, 4, false, M, MP>(a, s);
-  if (w2) return small_n ? launch_fwd32<2, 2, LM, 2, false, M, MP>(a, s) : launch_fwd32<7, 2, LM, 2, false, M, MP>(a, s);
-  return small_n ? launch_fwd32<2, 2, LM, 3, false, M, MP>(a, s) : launch_fwd32<7, 2, LM, 3, false, M, MP>(a, s);   // (the fp32 mode at these widths)
+  if (hf) return small_n ? launch_fwd32<2, 2, LM, 4, false, M, MP, BL>(a, s) : launch_fwd32<7, 2, LM, 4, false, M, MP, BL>(a, s);
+  if (w2) return small_n ? launch_fwd32<2, 2, LM, 2, false, M, MP, BL>(a, s) : launch_fwd32<7, 2, LM, 2, false, M, MP, BL>(a, s);
+  return small_n ? launch_fwd32<2, 2, LM, 3, false, M, MP, BL>(a, s) : launch_fwd32<7, 2, LM, 3, false, M, MP, BL>(a, s);   // (the fp32 mode at these widths)
+}
+
+int fused32_forward_bil(const FwdArgs& a, hipStream_t s) {
+  if (a.av2) {
+    if (a.qlen) return a.lm ? dispatch_fwd32<true, true, true, true>(a, s) : dispatch_fwd32<false, true, true, true>(a, s);
+    return a.lm ? dispatch_fwd32<true, false, true, true>(a, s) : dispatch_fwd32<false, false, true, true>(a, s);
+  }
+  if (a.qlen) return a.lm ? dispatch_fwd32<true, true, false, true>(a, s) : dispatch_fwd32<false, true, false, true>(a, s);
+  return a.lm ? dispatch_fwd32<true, false, false, true>(a, s) : dispatch_fwd32<false, false, false, true>(a, s);
 }
 
 }  // namespace
@@ -933,12 +945,13 @@ int dispatch_fwd32(const FwdArgs& a, hipStream_t s) {
 int fused32_forward(const FwdArgs& a, hipStream_t s) {
   CA_CHECK_ARG(!a.v_out || (a.lm && a.N <= 64 && a.d % 512 == 0), "fused forward: the in-kernel v pass needs location-major features, N <= 64, d %% 512 == 0");
   CA_CHECK_ARG(!a.av2 == !a.aq2, "fused forward: both map copies or neither");
+  if (a.K) return fused32_forward_bil(a, s);          // the bilinear affinity: instantiations of their own (BIL)
   if (a.av2) {                                       // coattn_forward_maps: the maps to `saved` and to the caller's buffers
-    if (a.qlen) return a.lm ? dispatch_fwd32<true, true, true>(a, s) : dispatch_fwd32<false, true, true>(a, s);
-    return a.lm ? dispatch_fwd32<true, false, true>(a, s) : dispatch_fwd32<false, false, true>(a, s);
+    if (a.qlen) return a.lm ? dispatch_fwd32<true, true, true, false>(a, s) : dispatch_fwd32<false, true, true, false>(a, s);
+    return a.lm ? dispatch_fwd32<true, false, true, false>(a, s) : dispatch_fwd32<false, false, true, false>(a, s);
   }
-  if (a.qlen) return a.lm ? dispatch_fwd32<true, true, false>(a, s) : dispatch_fwd32<false, true, false>(a, s);   // length-masked
-  return a.lm ? dispatch_fwd32<true, false, false>(a, s) : dispatch_fwd32<false, false, false>(a, s);
+  if (a.qlen) return a.lm ? dispatch_fwd32<true, true, false, false>(a, s) : dispatch_fwd32<false, true, false, false>(a, s);   // length-masked
+  return a.lm ? dispatch_fwd32<true, false, false, false>(a, s) : dispatch_fwd32<false, false, false, false>(a, s);
 }
 
 int launch_attend_v_lm(const float* V, long v_sB, const float* av, float* v_out, int B, int N, int d, int L, hipStream_t s) {

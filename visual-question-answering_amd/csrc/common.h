@@ -275,6 +275,12 @@ int launch_dtanh(const float* dC, const float* C, float* out, int64_t n, hipStre
 int launch_add_inplace(float* y, const float* x, int64_t n, int accumulate, hipStream_t s);
 // y += x1 + x2 in one pass
 int launch_add3_inplace(float* y, const float* x1, const float* x2, int64_t n, hipStream_t s);
+// out[r][0 .. w0) = x0[r][..], out[r][w0 .. w0 + w1) = x1[r][..] for r < R (rows of x0 / x1 / out w0 / w1 / w0 + w1 floats apart):
+// the bilinear backward's [dP_q | dK] operand and the stacked [W_q; W_b] weight (R = 1)
+int launch_concat_cols(const float* x0, int w0, const float* x1, int w1, float* out, int64_t R, hipStream_t s);
+// dst[i] = max(dst[i], src[i]) on the bit patterns of non-negative floats (NaN wins), i < n: folds the range words of one weight
+// image into another's (status words of the tolerance mode)
+int launch_max_words(float* dst, const float* src, int n, hipStream_t s);
 // out[z][i][j] (+)= a[z][i] * g[z][j] with strides (o_sz, o_si, o_sj)
 int launch_rank1(const float* a, const float* g, float* out, int Z, int I, int J,
                  int64_t o_sz, int64_t o_si, int64_t o_sj, int accumulate, hipStream_t s);

@@ -21,14 +21,28 @@ int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, c
                             float* ws, hipStream_t s, int bf16 = 0, int np = 3,   // bf16: reduced precision, one MFMA per product; np: width of phase 2
                             float* av = nullptr, float* aq = nullptr, int keep = 1,
                             const int* qlen = nullptr,    // qlen: [B] question lengths (coattn_forward_len), NULL = unmasked
-                            float* av_copy = nullptr, float* aq_copy = nullptr);   // (coattn_forward_maps) the maps ALSO go here
+                            float* av_copy = nullptr, float* aq_copy = nullptr,   // (coattn_forward_maps) the maps ALSO go here
+                            const float* K = nullptr);    // (COATTN_FLAG_BILINEAR) K [L][B][T][d], the affinity's question operand
 int fused_backward_supported(int B, int N, int T, int d, int L);
+// The bilinear affinity's backward state (COATTN_FLAG_BILINEAR; NULL: the reference's affinity).  K comes from `saved`; the rest
+// lives in the backward's workspace behind everything else.
+struct BilBwd {
+  const float* Wb;       // [d][d]
+  const float* K;        // [L][B][T][d] (saved)
+  float* dK;             // [L][B][T][d]  dK = dA V
+  float* dpk;            // [L][B][T][2d] [dP_q | dK], the A operand of the dQ projection
+  float* wstack;         // [2d][d] [W_q; W_b]
+  void* wimg;            // wsplit image of [W_q; W_b] (wsplit_bytes(d, 2d))
+  float* zeros;          // [L][B][d] (the dK pass adds a_q (x) 0)
+  float* dWb; float* dbb;
+};
 int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl, const float* const* Q,
                    const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
                    const VLayout& dvl, float* const* dQ, const coattn_param_grads* pg, int accumulate, float* ws,
                    hipStream_t s, int bf16_proj, int wgemm, int np = 3, int live_rows = 0,   // wgemm: gemm_w / gemm_tn enabled; np: width of the contractions (3 | 2); live_rows: `saved` holds the forward's bitmap of the non-zero question rows
                    const int* qlen = nullptr,    // qlen: the forward's question lengths (NULL = unmasked)
-                   const float* g_av = nullptr, const float* g_aq = nullptr);   // (coattn_backward_maps) upstream gradients of the maps, NULL = 0
+                   const float* g_av = nullptr, const float* g_aq = nullptr,   // (coattn_backward_maps) upstream gradients of the maps, NULL = 0
+                   const BilBwd* bil = nullptr);   // (COATTN_FLAG_BILINEAR) see BilBwd
 
 // Diagnostic build only (tools/probe_stamps.py, -DCOATTN_STAMPS=1): wave 0 of every workgroup writes the
 // 100 MHz constant clock at its phase boundaries into the (otherwise unused) forward workspace tail.
@@ -467,6 +481,7 @@ struct FwdArgs {
   const int* qlen;       // [B] question lengths (coattn_forward_len), clamped into [1, T]; NULL: every row counts (the reference)
   float* av2;            // (MAPS instantiations, coattn_forward_maps) a second store of a_v [L][B][N] / a_q [L][B][T] from the same
   float* aq2;            // epilogue: the caller's map buffers, while av / aq stay the copies in `saved` the backward reads
+  const float* K;        // (BIL instantiations, COATTN_FLAG_BILINEAR) K = Q W_b^T + b_b [L][B][T][d]: phase 1's question operand
 };
 
 // arguments of the two big fused backward kernels (coattn_fused_bwd.hip, coattn_bwd32.hip)

@@ -494,3 +494,37 @@ extern "C" int coattn_features_native(const void* x, int x_dtype, int64_t sB, in
   CA_CHECK_LAUNCH("features_native");
   return 0;
 }
+
+// ---- bilinear affinity (COATTN_FLAG_BILINEAR): operand packing and range-word folding ---------------------------------
+__global__ __launch_bounds__(256) void concat_cols_kernel(const float* __restrict__ x0, int w0, const float* __restrict__ x1, int w1,
+                                                          float* __restrict__ out, int64_t R) {
+  const int64_t W = (int64_t)w0 + w1;
+  const int64_t n = R * W;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t r = i / W, c = i - r * W;
+    out[i] = c < w0 ? x0[r * w0 + c] : x1[r * w1 + (c - w0)];
+  }
+}
+
+int launch_concat_cols(const float* x0, int w0, const float* x1, int w1, float* out, int64_t R, hipStream_t s) {
+  const int64_t n = R * ((int64_t)w0 + w1);
+  int64_t blocks = (n + 255) / 256;
+  blocks = blocks > 8192 ? 8192 : (blocks < 1 ? 1 : blocks);
+  hipLaunchKernelGGL(concat_cols_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x0, w0, x1, w1, out, R);
+  CA_CHECK_LAUNCH("concat_cols");
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void max_words_kernel(float* __restrict__ dst, const float* __restrict__ src, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const unsigned a = __builtin_bit_cast(unsigned, dst[i]), b = __builtin_bit_cast(unsigned, src[i]);
+  dst[i] = __builtin_bit_cast(float, a > b ? a : b);
+}
+
+int launch_max_words(float* dst, const float* src, int n, hipStream_t s) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(max_words_kernel, dim3((n + 255) / 256), dim3(256), 0, s, dst, src, n);
+  CA_CHECK_LAUNCH("max_words");
+  return 0;
+}

@@ -8,6 +8,8 @@ model shards naturally by QA pair, so the only exchange step is the gradient mea
 * ``co_attention.W_b`` is constructed but never used (model.py:347 vs :377), so it never gets a
   gradient; stock DDP (find_unused_parameters=False) fails on step 2.  The reducer learns the
   set of parameters that actually receive gradients on the first step and buckets only those.
+  Under ``ParallelCoAttention(affinity="bilinear")`` W_b trains: it receives a gradient on the
+  first step and is bucketed like every other parameter.
 * buffers (frozen-VGG BatchNorm statistics, model.py:239-241) are never broadcast.
 * buckets are filled in reverse registration order (~ backward order) and each all-reduce is
   launched asynchronously as soon as its bucket is complete, overlapping with the rest of

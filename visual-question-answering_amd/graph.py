@@ -32,6 +32,9 @@ buffer, it raises instead of dropping the earlier gradient.
 reading a static int32 [B] length buffer, which every call of the node refills from its ``q_len`` argument before the
 forward is issued or replayed -- captured graphs read the lengths of the step they run.
 
+The co-attention module's ``affinity="bilinear"``: the calls carry ``COATTN_FLAG_BILINEAR`` and ``W_b`` (weight and bias) joins
+the static parameters and gradients (18 instead of 16), eager and captured alike.
+
 ``logits`` is returned as a fresh tensor (``alias_outputs=True``: the static buffer itself, overwritten by the next
 step).  A gradient arriving for ``logits`` is added by the head's backward in eager mode; under graph capture it raises.
 """
@@ -69,6 +72,10 @@ class HotPathGraph:
         self.dims = (B, N, T, d, mlp, K)
         dev = co_attention.W_v.weight.device
         self.device = dev
+        if getattr(co_attention, "affinity", "reference") == "bilinear":   # (W_b joins the parameters: _param_lists)
+            if flags & _lib.FLAG_BF16_PROJ:
+                raise RuntimeError("HotPathGraph: the bilinear affinity is not available in the reduced-precision mode")
+            flags |= _lib.FLAG_BILINEAR
         self.flags = flags
         self.head_flags = _lib.FLAG_BF16_PROJ if getattr(mlp_classify, "bf16_products", False) else 0
         f32 = dict(device=dev, dtype=torch.float32)
@@ -112,7 +119,9 @@ class HotPathGraph:
 
     @staticmethod
     def _param_lists(co, mlp):
-        return ([co.W_v.weight, co.W_v.bias, co.W_q.weight, co.W_q.bias, co.w_v.weight, co.w_v.bias, co.w_q.weight, co.w_q.bias],
+        bil = [co.W_b.weight, co.W_b.bias] if getattr(co, "affinity", "reference") == "bilinear" else []
+        return ([co.W_v.weight, co.W_v.bias, co.W_q.weight, co.W_q.bias, co.w_v.weight, co.w_v.bias, co.w_q.weight, co.w_q.bias,
+                 *bil],
                 [mlp.W_w.weight, mlp.W_w.bias, mlp.W_p.weight, mlp.W_p.bias, mlp.W_s.weight, mlp.W_s.bias, mlp.W_h.weight, mlp.W_h.bias])
 
     def stale(self) -> bool:

@@ -391,7 +391,8 @@ class HierarchicalCoAttentionNet(nn.Module):
         T = x_ques_features[0].shape[1]
         key = (B, N, T, bool(x_img_features.requires_grad), bool(self.co_attention.bf16_projections),
                bool(self.mlp_classify.bf16_products), bool(self.hot_path_graph), bool(self.hot_path_direct_grads),
-               bool(self.co_attention.fast_products), self._question_mask())
+               bool(self.co_attention.fast_products), self._question_mask(),
+               getattr(self.co_attention, "affinity", "reference"))
         hp = self._graphs.get(key)
         # (the node reads the parameters where they lie: one built before the module was moved -- .to(), .cuda(), new
         #  Parameter objects -- would read the old storage)

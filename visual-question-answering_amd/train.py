@@ -111,22 +111,56 @@ def set_question_mask(model: nn.Module, question_mask: bool) -> None:
     co.question_mask = bool(question_mask)
 
 
-def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, **kw) -> nn.Module:
-    """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`."""
+def check_affinity(model_name: str, affinity: str, opt_lvl: int = 0) -> None:
+    """--affinity: "reference" (the default: C = tanh(Q V^T), model.py:377, W_b untrained) or "bilinear" (the published model's
+    C = tanh(W_b(Q) V^T), W_b trained; ParallelCoAttention(affinity=...)).  The bilinear form exists for the co-attention
+    models only and not in the reduced-precision mode (--opt_lvl >= 1): both are errors."""
+    if affinity not in ("reference", "bilinear"):
+        raise ValueError("--affinity must be 'reference' or 'bilinear', got %r" % (affinity,))
+    if affinity == "reference":
+        return
+    if not model_name.startswith("attention"):
+        raise ValueError("--affinity bilinear applies to the co-attention models (--model attention*), not to %s" % model_name)
+    if opt_lvl > 0:
+        raise ValueError("--affinity bilinear is not available with --opt_lvl >= 1 (the reduced-precision mode)")
+
+
+def set_affinity(model: nn.Module, affinity: str) -> None:
+    """The co-attention's affinity form (see `check_affinity`): a module attribute, not part of the state_dict."""
+    co = getattr(model, "co_attention", None)
+    if co is None or not hasattr(co, "affinity"):
+        if affinity != "reference":
+            raise ValueError("--affinity bilinear applies to the co-attention models (--model attention*), not to %s"
+                             % type(model).__name__)
+        return
+    if affinity not in co.AFFINITIES:
+        raise ValueError("affinity must be one of %s, got %r" % (co.AFFINITIES, affinity))
+    co.affinity = affinity
+
+
+def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, affinity: str = "reference",
+                **kw) -> nn.Module:
+    """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`; affinity: see
+    `check_affinity`."""
+    check_affinity(model_name, affinity)
     cfg = setup_model_configs(model_name, vocab_size, **kw)
     model = cfg["model"](cfg["question_params"], cfg["image_params"], K=num_cls + 1)
     set_question_mask(model, question_mask)
+    set_affinity(model, affinity)
     return model
 
 
 def model_from_args(args):
     """The model of a parsed command line, as main.py:388 builds it: (model, registry entry).  attention_bert: the token ids
     are BERT's, so args.vocab_size becomes BERT's vocabulary.  --question_mask is applied to the co-attention (the Trainer's
-    steps and `validate` then pass the lengths through).  (train.main, predict.main)"""
+    steps and `validate` then pass the lengths through), --affinity likewise.  (train.main, predict.main)"""
+    affinity = getattr(args, "affinity", "reference")
+    check_affinity(args.model, affinity, getattr(args, "opt_lvl", 0))
     cfg = setup_model_configs(args, args.vocab_size)             # (as main.py:388)
     args.vocab_size = cfg.get("vocab_size", args.vocab_size)
     model = cfg["model"](cfg["question_params"], cfg["image_params"], K=args.num_cls + 1)
     set_question_mask(model, getattr(args, "question_mask", False))
+    set_affinity(model, affinity)
     return model, cfg
 
 
@@ -546,6 +580,11 @@ def build_parser():
     ap.add_argument("--question_mask", type=str2bool, default="false",
                     help="co-attention over each question's first ques_len tokens only (a_q = 0 on pad tokens); default: "
                          "unmasked, as the reference (model.py:388).  Checkpoints hold only the state_dict, so the flag is not "
+                         "recorded: give prediction the value the checkpoint was trained with (a mismatch goes undetected)")
+    ap.add_argument("--affinity", default="reference", choices=["reference", "bilinear"],
+                    help="co-attention affinity: 'reference' = tanh(Q V^T) as model.py:377 (W_b constructed, never trained); "
+                         "'bilinear' = tanh(W_b(Q) V^T) as the published model, W_b trained.  Co-attention models only, not with "
+                         "--opt_lvl >= 1.  Checkpoints hold only the state_dict (same keys for both), so the flag is not "
                          "recorded: give prediction the value the checkpoint was trained with (a mismatch goes undetected)")
     return ap
 
