@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Parallel Co-Attention path.
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -305,6 +305,61 @@ int coattn_backward_maps_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t 
                              const void* g_av, const void* g_aq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD,
                              void* const* dQ, const coattn_param_grads* pg, int accumulate,
                              void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+
+/* ---- alternating co-attention (v0.11.0) --------------------------------------------------------------------------
+ * The paper's second co-attention form (Lu et al. 2016, section 3.3, eq. 6): no T x N affinity, three chained guided-attention
+ * steps.  Per sample b and level l, row-vector convention, one parameter set shared by the L levels, its own per step:
+ *     guided(X, g):  H = tanh(X W_x^T + b_x + g)   [R,d]   (g broadcast over the R rows)
+ *                    a = softmax_R(H w_h^T + c_h)  [R]
+ *                    x^ = a^T X                    [d]
+ *     step 1:  s^, a_s = guided(Q, 0)                            (W_x1, w_h1)      R = T
+ *     step 2:  v^, a_v = guided(V, s^ W_g2^T + b_g2)             (W_x2, W_g2, w_h2) R = N
+ *     step 3:  q^, a_q = guided(Q, v^ W_g3^T + b_g3)             (W_x3, W_g3, w_h3) R = T
+ *     v_out = v^, q_out = q^  [L,B,d]   (the shapes and meaning of coattn_forward's outputs)
+ * W_x*, W_g* are [d,d] (nn.Linear(d, d)), b_* [d]; w_h* [d] (nn.Linear(d, 1).weight), c_h* [1].
+ *   q_len : DEVICE int32 [B] or NULL (unmasked: the softmaxes of steps 1 and 3 run over all T tokens).  With it, the semantics of
+ *           v0.8.0: steps 1 and 3 run over the rows t < clamp(len_b, 1, T) alone; a_s, a_q are exactly 0 beyond, those rows of
+ *           Q are not read for their values and dQ is 0 there.  The backward must receive the same q_len.
+ * V, Q, strides, buffers, streams, errors: as coattn_forward (V by its three strides, Q a host array of L device pointers, the
+ * caller owns every buffer, nothing is allocated, asynchronous on `stream`, no CPU fallback).  Limits: N, T <= 512, d <= 1024,
+ * L <= 4.
+ * EXACT MODE ONLY: flags must be 0 (COATTN_FLAG_FAST16, COATTN_FLAG_BF16_PROJ, COATTN_FLAG_BILINEAR, the impl selectors: -1).
+ * Paths: [X1 | X3] = Q_l [W_x1; W_x3]^T + [b_x1; b_x3] for every level in ONE projection, X2 = V W_x2^T + b_x2 once per sample,
+ * the guide vectors (M = L B) -- on the pre-split-weight kernels where they take the shape (gemm_w.hip), else on the general
+ * GEMM; the weight gradients on the split-K weight-gradient kernel (gemm_tn.hip) with a fixed-order reduce.  The guided steps
+ * run on their own kernels (coattn_alt.hip); step 2 takes the L levels of a sample in one workgroup.  No float atomics: two
+ * runs are bitwise identical. */
+typedef struct coattn_alt_params {
+  const void* W_x1; const void* b_x1; const void* w_h1; const void* c_h1;
+  const void* W_x2; const void* b_x2; const void* W_g2; const void* b_g2; const void* w_h2; const void* c_h2;
+  const void* W_x3; const void* b_x3; const void* W_g3; const void* b_g3; const void* w_h3; const void* c_h3;
+} coattn_alt_params;
+typedef struct coattn_alt_param_grads {
+  void* dW_x1; void* db_x1; void* dw_h1; void* dc_h1;
+  void* dW_x2; void* db_x2; void* dW_g2; void* db_g2; void* dw_h2; void* dc_h2;
+  void* dW_x3; void* db_x3; void* dW_g3; void* db_g3; void* dw_h3; void* dc_h3;
+} coattn_alt_param_grads;
+/* saved: forward -> backward state (X1 | X3, X2, both guide vectors, s^, v^, a_s, a_v, a_q); ws_fwd / ws_bwd: scratch.  H is not
+ * stored: the backward recomputes it from X and g. */
+int coattn_alt_workspace_bytes(int B, int N, int T, int d, int L, int dtype, int flags, size_t* saved, size_t* ws_fwd,
+                               size_t* ws_bwd);
+/* av_out [L,B,N] (a_v of step 2) and aq_out [L,B,T] (a_q of step 3) may each be NULL.  saved NULL: inference, nothing kept (the
+ * state lives in ws), and v_out / q_out are bit-identical to a call with `saved`. */
+int coattn_alt_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const int32_t* q_len,
+                       const coattn_alt_params* p, void* v_out, void* q_out, void* av_out, void* aq_out, void* saved, void* ws,
+                       int B, int N, int T, int d, int L, int dtype, int flags, void* stream);
+/* gv, gq [L,B,d]: upstream gradients of v_out, q_out.  g_av [L,B,N], g_aq [L,B,T]: upstream gradients of the maps, or NULL (= 0);
+ * as in v0.9.0 they enter before the softmax backward (da = X g + G) and under the mask g_aq is read as 0 past the length.
+ * dV (its own strides; overwritten) may be NULL for a frozen encoder; dQ: host array of L device pointers (overwritten).
+ * pg: accumulate = 0 overwrites, 1 adds; the gradients of the L levels are summed.  Per step the backward forms, row by row,
+ *     da_r = x_r . gx^ (+ G_a),  ds = a (.) (da - sum a da),  dH_r = ds_r w_h (.) (1 - H_r^2),  dg = sum_r dH_r,
+ * and the gradient into v^ is gv + dg3 W_g3, into s^ dg2 W_g2.  `saved`: of a coattn_alt_forward with the same inputs, parameter
+ * values, flags and q_len. */
+int coattn_alt_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const int32_t* q_len,
+                        const coattn_alt_params* p, const void* saved, const void* gv, const void* gq, const void* g_av,
+                        const void* g_aq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                        const coattn_alt_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d, int L,
+                        int dtype, int flags, void* stream);
 
 /* Range report of the tolerance mode (COATTN_FLAG_FAST16).  SYNCHRONISES `stream`, reads the status words the last
  * coattn_forward left in `saved` (or in `ws`, when that call was given saved = NULL) and returns

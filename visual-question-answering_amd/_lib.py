@@ -21,7 +21,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_profile_begin", "coattn_profile_end", "coattn_features_native", "coattn_status",
            "coattn_phrase_status", "coattn_status_accumulate", "coattn_phrase_status_accumulate", "coattn_infer",
            "coattn_forward_len", "coattn_infer_len", "coattn_attention_forward_len", "coattn_backward_len",
-           "coattn_forward_maps", "coattn_forward_maps_len", "coattn_backward_maps", "coattn_backward_maps_len")
+           "coattn_forward_maps", "coattn_forward_maps_len", "coattn_backward_maps", "coattn_backward_maps_len",
+           "coattn_alt_workspace_bytes", "coattn_alt_forward", "coattn_alt_backward")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -54,6 +55,19 @@ class Params(C.Structure):
 
 class ParamGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dW_v", "db_v", "dW_q", "db_q", "dw_v", "dc_v", "dw_q", "dc_q", "dW_b", "db_b")]
+
+
+# alternating co-attention (v0.11.0): the three guided-attention steps' parameters, in the header's order
+ALT_PARAM_NAMES = ("W_x1", "b_x1", "w_h1", "c_h1", "W_x2", "b_x2", "W_g2", "b_g2", "w_h2", "c_h2",
+                   "W_x3", "b_x3", "W_g3", "b_g3", "w_h3", "c_h3")
+
+
+class AltParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ALT_PARAM_NAMES]
+
+
+class AltParamGrads(C.Structure):
+    _fields_ = [("d" + n, C.c_void_p) for n in ALT_PARAM_NAMES]
 
 
 class PhraseParams(C.Structure):
@@ -138,6 +152,13 @@ def load() -> C.CDLL:
     lib.coattn_backward_maps.argtypes = lib.coattn_backward.argtypes[:9] + [C.c_void_p, C.c_void_p] + lib.coattn_backward.argtypes[9:]
     lib.coattn_forward_maps_len.argtypes = _with_len(lib.coattn_forward_maps.argtypes)
     lib.coattn_backward_maps_len.argtypes = _with_len(lib.coattn_backward_maps.argtypes)
+    lib.coattn_alt_workspace_bytes.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_size_t)] * 3
+    lib.coattn_alt_forward.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.c_void_p,
+                                        C.POINTER(AltParams)] + [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p])
+    lib.coattn_alt_backward.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.c_void_p,
+                                         C.POINTER(AltParams)] + [C.c_void_p] * 6 + [C.c_int64] * 3
+                                        + [C.POINTER(C.c_void_p), C.POINTER(AltParamGrads), C.c_int, C.c_void_p]
+                                        + [C.c_int] * 7 + [C.c_void_p])
     lib.coattn_gemm_f32.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
     lib.coattn_gemm_bf16.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
     lib.coattn_phrase_workspace_bytes.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_size_t)] * 3
@@ -299,6 +320,22 @@ def workspace_bytes(B, N, T, d, L, flags=0):
           "coattn_workspace_bytes")
     _ws_cache[key] = (s.value, f.value, b.value)
     return _ws_cache[key]
+
+
+_alt_ws_cache = {}
+
+
+def alt_workspace_bytes(B, N, T, d, L):
+    """(saved, ws_fwd, ws_bwd) in bytes of the alternating co-attention (coattn_alt_workspace_bytes; exact mode)."""
+    key = (B, N, T, d, L)
+    hit = _alt_ws_cache.get(key)
+    if hit is not None:
+        return hit
+    s, f, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    check(load().coattn_alt_workspace_bytes(B, N, T, d, L, F32, 0, C.byref(s), C.byref(f), C.byref(b)),
+          "coattn_alt_workspace_bytes")
+    _alt_ws_cache[key] = (s.value, f.value, b.value)
+    return _alt_ws_cache[key]
 
 
 _scratch = {}

@@ -27,6 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 
+from .alternating import AlternatingCoAttention
 from .coattention import ParallelCoAttention
 from .head import answer_head
 
@@ -304,9 +305,13 @@ class MLPClassifier(nn.Module):
 
 
 class HierarchicalCoAttentionNet(nn.Module):
-    """question encoder -> image encoder -> parallel co-attention (HIP) -> MLP logits [B, K]."""
+    """question encoder -> image encoder -> co-attention (HIP) -> MLP logits [B, K].
+    co_attention: "parallel" (the default: ParallelCoAttention, the reference's form) or "alternating"
+    (AlternatingCoAttention, Lu et al. 2016 section 3.3; it always takes the per-module path, never the hot-path node)."""
 
-    def __init__(self, ques_enc_params, img_enc_params, K, mlp_dim=1024):
+    CO_ATTENTIONS = ("parallel", "alternating")
+
+    def __init__(self, ques_enc_params, img_enc_params, K, mlp_dim=1024, co_attention="parallel"):
         super().__init__()
         self.hidden_dim = ques_enc_params["hidden_dim"]
         img_enc_params = dict(img_enc_params)
@@ -318,7 +323,11 @@ class HierarchicalCoAttentionNet(nn.Module):
             self.question_encoder = QuestionBertCoAttentionEncoder(**ques_enc_params)
         else:
             self.question_encoder = QuestionCoAttentionEncoder(**ques_enc_params)
-        self.co_attention = ParallelCoAttention(self.hidden_dim)
+        if co_attention not in self.CO_ATTENTIONS:
+            raise ValueError("co_attention must be one of %s, got %r" % (self.CO_ATTENTIONS, co_attention))
+        self.co_attention_form = co_attention
+        self.co_attention = (AlternatingCoAttention(self.hidden_dim) if co_attention == "alternating"
+                             else ParallelCoAttention(self.hidden_dim))
         self.mlp_classify = MLPClassifier(self.hidden_dim, mlp_dim, K)
         self.hot_path_graph = False                   # opt-in: replay the hot path from a captured HIP graph (graph.py)
         # train.Trainer's default on CUDA: the hot path as ONE autograd node over static buffers, its C-ABI calls issued
@@ -350,7 +359,7 @@ class HierarchicalCoAttentionNet(nn.Module):
                 return (*self.mlp_classify.forward_loss(v, q, labels), a_v, a_q)
             return self.mlp_classify(v, q), a_v, a_q
         if (labels is not None and (self.hot_path_graph or self.hot_path_static) and x_img_features.is_cuda
-                and torch.is_grad_enabled()):
+                and torch.is_grad_enabled() and self.co_attention_form == "parallel"):     # (the node is parallel-only)
             return self._graphed(x_img_features, x_ques_features, labels, x_ques_lens if masked else None)
         if masked:
             x_img_attn, x_ques_attn = self.co_attention(x_img_features, x_ques_features, x_ques_lens)
@@ -387,6 +396,8 @@ class HierarchicalCoAttentionNet(nn.Module):
         default)."""
         from . import _lib
         from .graph import HotPathGraph
+        if self.co_attention_form != "parallel":
+            raise RuntimeError("the hot-path node (graph.HotPathGraph) serves the parallel co-attention only")
         B, N, _ = x_img_features.shape
         T = x_ques_features[0].shape[1]
         key = (B, N, T, bool(x_img_features.requires_grad), bool(self.co_attention.bf16_projections),

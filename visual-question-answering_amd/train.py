@@ -125,6 +125,31 @@ def check_affinity(model_name: str, affinity: str, opt_lvl: int = 0) -> None:
         raise ValueError("--affinity bilinear is not available with --opt_lvl >= 1 (the reduced-precision mode)")
 
 
+def check_co_attention(model_name: str, co_attention: str, affinity: str = "reference", opt_lvl: int = 0,
+                       precision: str = "exact") -> None:
+    """--co_attention: "parallel" (the default: the reference's ParallelCoAttention) or "alternating" (AlternatingCoAttention,
+    Lu et al. 2016 section 3.3).  The alternating form exists for the co-attention models only and in the exact mode only:
+    with --affinity bilinear (a parallel-form option), --opt_lvl >= 1 or --precision fast it is an error."""
+    if co_attention not in ("parallel", "alternating"):
+        raise ValueError("--co_attention must be 'parallel' or 'alternating', got %r" % (co_attention,))
+    if co_attention == "parallel":
+        return
+    if not model_name.startswith("attention"):
+        raise ValueError("--co_attention alternating applies to the co-attention models (--model attention*), not to %s"
+                         % model_name)
+    if affinity != "reference":
+        raise ValueError("--co_attention alternating has no affinity matrix: --affinity %s applies to the parallel form only"
+                         % affinity)
+    if opt_lvl >= 1:
+        raise ValueError("--co_attention alternating is not available with --opt_lvl >= 1 (the reduced-precision mode)")
+    if precision == "fast":
+        raise ValueError("--co_attention alternating runs in the exact mode only, not with --precision fast")
+
+
+def _net_kwargs(co_attention: str) -> dict:
+    return {} if co_attention == "parallel" else {"co_attention": co_attention}
+
+
 def set_affinity(model: nn.Module, affinity: str) -> None:
     """The co-attention's affinity form (see `check_affinity`): a module attribute, not part of the state_dict."""
     co = getattr(model, "co_attention", None)
@@ -139,12 +164,13 @@ def set_affinity(model: nn.Module, affinity: str) -> None:
 
 
 def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, affinity: str = "reference",
-                **kw) -> nn.Module:
+                co_attention: str = "parallel", **kw) -> nn.Module:
     """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`; affinity: see
-    `check_affinity`."""
+    `check_affinity`; co_attention: see `check_co_attention`."""
     check_affinity(model_name, affinity)
+    check_co_attention(model_name, co_attention, affinity)
     cfg = setup_model_configs(model_name, vocab_size, **kw)
-    model = cfg["model"](cfg["question_params"], cfg["image_params"], K=num_cls + 1)
+    model = cfg["model"](cfg["question_params"], cfg["image_params"], K=num_cls + 1, **_net_kwargs(co_attention))
     set_question_mask(model, question_mask)
     set_affinity(model, affinity)
     return model
@@ -156,9 +182,11 @@ def model_from_args(args):
     steps and `validate` then pass the lengths through), --affinity likewise.  (train.main, predict.main)"""
     affinity = getattr(args, "affinity", "reference")
     check_affinity(args.model, affinity, getattr(args, "opt_lvl", 0))
+    co_attention = getattr(args, "co_attention", "parallel")
+    check_co_attention(args.model, co_attention, affinity, getattr(args, "opt_lvl", 0), getattr(args, "precision", "exact"))
     cfg = setup_model_configs(args, args.vocab_size)             # (as main.py:388)
     args.vocab_size = cfg.get("vocab_size", args.vocab_size)
-    model = cfg["model"](cfg["question_params"], cfg["image_params"], K=args.num_cls + 1)
+    model = cfg["model"](cfg["question_params"], cfg["image_params"], K=args.num_cls + 1, **_net_kwargs(co_attention))
     set_question_mask(model, getattr(args, "question_mask", False))
     set_affinity(model, affinity)
     return model, cfg
@@ -586,6 +614,11 @@ def build_parser():
                          "'bilinear' = tanh(W_b(Q) V^T) as the published model, W_b trained.  Co-attention models only, not with "
                          "--opt_lvl >= 1.  Checkpoints hold only the state_dict (same keys for both), so the flag is not "
                          "recorded: give prediction the value the checkpoint was trained with (a mismatch goes undetected)")
+    ap.add_argument("--co_attention", default="parallel", choices=["parallel", "alternating"],
+                    help="co-attention form (Lu et al. 2016 section 3.3): 'parallel' = the reference's ParallelCoAttention; "
+                         "'alternating' = three chained guided-attention steps (AlternatingCoAttention; its own state_dict "
+                         "keys).  Co-attention models only, exact mode only: not with --affinity bilinear, --opt_lvl >= 1 or "
+                         "--precision fast")
     return ap
 
 
