@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -481,6 +481,44 @@ int coattn_head_backward(const void* const* v, const void* const* q, const coatt
                          const void* g_loss, const void* g_logits, void* const* dv, void* const* dq,
                          const coattn_head_param_grads* pg, int accumulate, void* ws, int B, int d, int mlp, int K,
                          int dtype, int flags, void* stream);
+
+/* ---- soft answer targets (v0.12.0): the VQA annotations' ten human answers instead of one majority label ----------
+ * A VQA sample has up to A (answer, score) pairs; the task's own metric scores an answer min(1, humans who gave it / 3).
+ * The targets are passed sparse, as the annotations are:
+ *   ans_idx   : int32 [B,A], a class index in [0,K), or -1 for an empty slot;
+ *   ans_score : fp32  [B,A], the slot's score; NOT READ for an empty slot (a NaN there changes no bit);
+ *   1 <= A <= 16.
+ * They stand for the dense target t[b][k] = sum over the slots a with ans_idx[b][a] == k of ans_score[b][a] (duplicate
+ * indices in a row add; a row of empty slots is legal: t[b][:] = 0), which is never formed in memory.  An index >= K or
+ * < -1 makes the loss NaN and raises the status word of the hard-label loss: coattn_ce_status / coattn_head_status
+ * return -2 and name the row; the call stays asynchronous.
+ * Loss kinds, with S_b = sum_k t[b][k] and the mean taken over the B rows (loss = (1/B) sum_b row):
+ *   COATTN_LOSS_SOFT_CE: row = S_b logsumexp(z_b) - sum_k t z           d loss / d z = (S_b softmax(z) - t) / B
+ *                        (for a row whose only slot is (label, 1.0) this IS coattn_ce_forward's cross entropy, bit for bit)
+ *   COATTN_LOSS_BCE    : row = sum_k (softplus(z) - min(t, 1) z)        d loss / d z = (sigmoid(z) - min(t, 1)) / B
+ *                        (binary cross entropy with logits summed over the classes; the target is clamped to 1, and
+ *                        softplus is max(z, 0) + log1p(exp(-|z|)): finite for every finite logit)
+ * One launch, no float atomics, bitwise repeatable -- as coattn_ce_forward. */
+#define COATTN_LOSS_SOFT_CE 1
+#define COATTN_LOSS_BCE 2
+/* loss [1], dlogits [B,K] or NULL; ws: coattn_ce_workspace_bytes (its contents need no initialisation), read by
+ * coattn_ce_status.  Argument errors (A outside 1..16, unknown kind, NULL pointers): -1 before anything is launched. */
+int coattn_soft_loss_forward(const void* logits, const void* ans_idx, const void* ans_score, int A, int kind,
+                             void* loss, void* dlogits, void* ws, int B, int K, int dtype, void* stream);
+/* Evaluation: pred[b] = argmax_k z[b][k] (the lowest index among equal maxima), row_score[b] = min(1, t[b][pred[b]]) -- the
+ * VQA accuracy of the predicted answer -- and score_sum[0] = their sum in a fixed order, in one launch.
+ * pred: int32 [B]; row_score: fp32 [B], may be NULL; score_sum: fp32 [1]; ws as above (K <= 2^24). */
+int coattn_vqa_score(const void* logits, const void* ans_idx, const void* ans_score, int A,
+                     void* pred, void* row_score, void* score_sum,
+                     void* ws, int B, int K, int dtype, void* stream);
+/* coattn_head_forward with (ans_idx, ans_score, A, kind) in place of `labels` (loss must be given).  It writes the SAME
+ * `saved` layout as coattn_head_forward, so coattn_head_backward and coattn_head_status serve both unchanged, and it
+ * accepts the same flags (COATTN_HEAD_PERSISTENT, COATTN_FLAG_BF16_PROJ: the loss is fp32 in all of them).  The launch
+ * count is coattn_head_forward's: four layers + ONE launch for the loss. */
+int coattn_head_forward_soft(const void* const* v, const void* const* q, const coattn_head_params* p,
+                             const void* ans_idx, const void* ans_score, int A, int kind,
+                             void* logits, void* loss, void* saved, int B, int d, int mlp, int K, int dtype, int flags,
+                             void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

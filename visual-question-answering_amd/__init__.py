@@ -10,8 +10,9 @@ from . import _lib  # noqa: F401
 from ._lib import RangeError, check_range  # noqa: F401
 from .coattention import ParallelCoAttention, coattention, native_features  # noqa: F401
 from .alternating import AlternatingCoAttention  # noqa: F401
-from .loss import CrossEntropyLoss, cross_entropy  # noqa: F401
+from .loss import CrossEntropyLoss, SoftTargetLoss, cross_entropy, soft_target_loss, vqa_score  # noqa: F401
 from .head import answer_head  # noqa: F401
 
-__all__ = ["ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "_lib",
+__all__ = ["ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
+           "SoftTargetLoss", "vqa_score", "_lib",
            "check_range", "RangeError"]

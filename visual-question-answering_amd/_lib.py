@@ -22,7 +22,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_phrase_status", "coattn_status_accumulate", "coattn_phrase_status_accumulate", "coattn_infer",
            "coattn_forward_len", "coattn_infer_len", "coattn_attention_forward_len", "coattn_backward_len",
            "coattn_forward_maps", "coattn_forward_maps_len", "coattn_backward_maps", "coattn_backward_maps_len",
-           "coattn_alt_workspace_bytes", "coattn_alt_forward", "coattn_alt_backward")
+           "coattn_alt_workspace_bytes", "coattn_alt_forward", "coattn_alt_backward",
+           "coattn_soft_loss_forward", "coattn_vqa_score", "coattn_head_forward_soft")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -34,6 +35,9 @@ FLAG_SPLIT2 = 32          # linear entry points: the two-piece width (hi + mid, 
 FLAG_F16PAIR = 64        # coattn_linear_forward: two FP16 pieces (the form the tolerance mode runs its projections in)
 FLAG_FAST16 = 128        # coattn_forward / coattn_backward / coattn_phrase_*: the tolerance mode (forward products on two FP16
                          # pieces = 22 bits, backward on two bf16 pieces = 16 bits; range report: coattn_status)
+LOSS_SOFT_CE, LOSS_BCE = 1, 2   # loss kinds of the soft-answer-target calls (v0.12.0: COATTN_LOSS_*)
+MAX_ANSWERS = 16         # answer slots per sample the soft-target kernels take
+LOSS_KINDS = {"soft_ce": LOSS_SOFT_CE, "bce": LOSS_BCE}
 FLAG_BILINEAR = 256      # every co-attention entry point: the affinity tanh((Q W_b^T + b_b) V^T) (v0.10.0; reads Params.W_b / b_b,
                          # writes ParamGrads.dW_b / db_b)
 
@@ -197,6 +201,12 @@ def load() -> C.CDLL:
                                          + [C.c_void_p] * 3 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                                                C.POINTER(HeadParamGrads), C.c_int, C.c_void_p]
                                          + [C.c_int] * 6 + [C.c_void_p])
+    # soft answer targets (v0.12.0): (ans_idx, ans_score, A, kind) where the hard-label calls take `labels`
+    lib.coattn_soft_loss_forward.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]
+    lib.coattn_vqa_score.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]
+    lib.coattn_head_forward_soft.argtypes = ([C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(HeadParams)]
+                                             + [C.c_void_p] * 2 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 6
+                                             + [C.c_void_p])
     _lib = lib
     return lib
 

@@ -620,7 +620,14 @@ int launch_bwd(BwdLayer& L, bool want_dx, bool vec, bool bf, hipStream_t s) {
 
 // cross entropy rows + mean (ce.hip)
 int launch_ce_rows(const float* logits, const void* labels, float* row_loss, float* dlogits, float* loss, int B, int K, int* status, hipStream_t s, int ldd, bool zeroed);
+int launch_soft_rows(const float* logits, const void* ans_idx, const void* ans_score, int A, int kind, float* row_loss, float* dlogits, float* loss, int B, int K, int* status, hipStream_t s, int ldd, bool zeroed);
+int check_soft_targets(const char* what, const void* ans_idx, const void* ans_score, int A, int kind);
 int head_status_check(const int* status_dev, void* stream);
+
+namespace {
+// what the loss behind the logits is computed against: int64 labels (kind 0), soft answer targets (COATTN_LOSS_*), or nothing
+struct HeadTarget { const void* labels; const void* ans_idx; const void* ans_score; int A, kind; };
+}  // namespace
 
 extern "C" int coattn_head_workspace_bytes(int B, int d, int mlp, int K, int dtype, size_t* saved, size_t* ws_bwd) {
   CA_TRY(check_dims(B, d, mlp, K, dtype));
@@ -629,9 +636,10 @@ extern "C" int coattn_head_workspace_bytes(int B, int d, int mlp, int K, int dty
   return 0;
 }
 
-extern "C" int coattn_head_forward(const void* const* v, const void* const* q, const coattn_head_params* p, const void* labels,
-                                   void* logits, void* loss, void* saved, int B, int d, int mlp, int K, int dtype, int flags,
-                                   void* stream) {
+static int head_forward(const void* const* v, const void* const* q, const coattn_head_params* p, const HeadTarget& tg,
+                        void* logits, void* loss, void* saved, int B, int d, int mlp, int K, int dtype, int flags,
+                        void* stream) {
+  const void* labels = tg.kind ? tg.ans_idx : tg.labels;     // (non-NULL: a loss follows the logits)
   CA_TRY(check_dims(B, d, mlp, K, dtype));
   CA_CHECK_ARG(v && q && p && logits && saved, "head_forward: null argument");
   for (int l = 0; l < 3; ++l) CA_CHECK_ARG(v[l] && q[l], "head_forward: v[%d] / q[%d] is null", l, l);
@@ -676,8 +684,25 @@ extern "C" int coattn_head_forward(const void* const* v, const void* const* q, c
     if (labels) { Ls[3].zero2 = reinterpret_cast<int*>(sv + hs.st); ce_zeroed = true; }   // (the logits layer clears the loss's two words)
     for (int l = 0; l < 4; ++l) CA_TRY(launch_fwd(Ls[l], vec, bf, s));
   }
-  if (labels) CA_TRY(launch_ce_rows((const float*)logits, labels, sv + hs.rl, sv + hs.dl, (float*)loss, B, K, reinterpret_cast<int*>(sv + hs.st), s, kpad(K), ce_zeroed));
+  if (tg.kind) CA_TRY(launch_soft_rows((const float*)logits, tg.ans_idx, tg.ans_score, tg.A, tg.kind, sv + hs.rl, sv + hs.dl, (float*)loss, B, K, reinterpret_cast<int*>(sv + hs.st), s, kpad(K), ce_zeroed));
+  else if (labels) CA_TRY(launch_ce_rows((const float*)logits, labels, sv + hs.rl, sv + hs.dl, (float*)loss, B, K, reinterpret_cast<int*>(sv + hs.st), s, kpad(K), ce_zeroed));
   return 0;
+}
+
+extern "C" int coattn_head_forward(const void* const* v, const void* const* q, const coattn_head_params* p, const void* labels,
+                                   void* logits, void* loss, void* saved, int B, int d, int mlp, int K, int dtype, int flags,
+                                   void* stream) {
+  return head_forward(v, q, p, HeadTarget{labels, nullptr, nullptr, 0, 0}, logits, loss, saved, B, d, mlp, K, dtype, flags, stream);
+}
+
+// as coattn_head_forward with soft answer targets: the same four layers, the same `saved` layout (d loss / d logits with padded
+// rows, row losses, status word), the soft-target rows kernel (ce.hip) as the one launch behind the logits
+extern "C" int coattn_head_forward_soft(const void* const* v, const void* const* q, const coattn_head_params* p,
+                                        const void* ans_idx, const void* ans_score, int A, int kind, void* logits, void* loss,
+                                        void* saved, int B, int d, int mlp, int K, int dtype, int flags, void* stream) {
+  CA_TRY(check_soft_targets("head_forward_soft", ans_idx, ans_score, A, kind));
+  CA_CHECK_ARG(loss, "head_forward_soft: null loss");
+  return head_forward(v, q, p, HeadTarget{nullptr, ans_idx, ans_score, A, kind}, logits, loss, saved, B, d, mlp, K, dtype, flags, stream);
 }
 
 extern "C" int coattn_head_status(const void* saved, int B, int d, int mlp, int K, void* stream) {

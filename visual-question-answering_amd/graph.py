@@ -35,6 +35,10 @@ forward is issued or replayed -- captured graphs read the lengths of the step th
 The co-attention module's ``affinity="bilinear"``: the calls carry ``COATTN_FLAG_BILINEAR`` and ``W_b`` (weight and bias) joins
 the static parameters and gradients (18 instead of 16), eager and captured alike.
 
+``loss="soft_ce" | "bce"`` (fixed at construction, with ``num_answers=A``): the head's forward is ``coattn_head_forward_soft`` and
+the third argument of a call is the pair ``(ans_idx int32 [B,A], ans_score fp32 [B,A])`` -- read where it lies like ``labels``,
+or copied into the node's static ``ans_idx`` / ``ans_score`` buffers.  The default ``loss="ce"`` builds the node described above.
+
 ``logits`` is returned as a fresh tensor (``alias_outputs=True``: the static buffer itself, overwritten by the next
 step).  A gradient arriving for ``logits`` is added by the head's backward in eager mode; under graph capture it raises.
 """
@@ -63,8 +67,13 @@ class HotPathGraph:
 
     def __init__(self, co_attention, mlp_classify, B: int, N: int, T: int, need_dv: bool = False, flags: int = 0,
                  capture: bool = True, direct_grads: bool = False, alias_outputs: bool = False,
-                 question_mask: bool = False):
+                 question_mask: bool = False, loss: str = "ce", num_answers: int = 10):
         self.co, self.mlp = co_attention, mlp_classify
+        if loss != "ce" and loss not in _lib.LOSS_KINDS:
+            raise ValueError("HotPathGraph: loss must be 'ce', 'soft_ce' or 'bce', got %r" % (loss,))
+        if loss != "ce" and not 1 <= int(num_answers) <= _lib.MAX_ANSWERS:
+            raise ValueError("HotPathGraph: num_answers must be in 1..%d, got %r" % (_lib.MAX_ANSWERS, num_answers))
+        self.loss_name, self.num_answers = loss, (int(num_answers) if loss != "ce" else 0)
         self.capture, self.direct_grads, self.alias_outputs = capture, direct_grads, alias_outputs
         self._warned_accumulate = False                          # (one warning when a backward adds into held gradients)
         d = co_attention.hidden_dim
@@ -83,6 +92,9 @@ class HotPathGraph:
         self.V = torch.zeros((B, N, d), **f32)
         self.Q = [torch.zeros((B, T, d), **f32) for _ in range(3)]
         self.labels = torch.zeros((B,), device=dev, dtype=torch.int64)
+        if loss != "ce":                                             # soft answer targets: static where `labels` is static
+            self.ans_idx = torch.full((B, self.num_answers), -1, device=dev, dtype=torch.int32)
+            self.ans_score = torch.zeros((B, self.num_answers), **f32)
         # question lengths of the masked form (static: the plans / graphs hold its address), None when unmasked
         self.q_len = torch.full((B,), T, device=dev, dtype=torch.int32) if question_mask else None
         # static outputs
@@ -111,8 +123,11 @@ class HotPathGraph:
         self._pairs = {}                                             # input addresses -> (forward graph, backward graph)
         self._plans = {}                                             # input addresses -> argument blocks of the four calls
         self._warm = False
-        self._static = (self.V, self.Q[0], self.Q[1], self.Q[2], self.labels)
+        self._static = ((self.V, self.Q[0], self.Q[1], self.Q[2], self.labels) if loss == "ce"
+                        else (self.V, self.Q[0], self.Q[1], self.Q[2], self.ans_idx, self.ans_score))
         self._lib = _lib.load()
+        self._head_fwd, self._head_fwd_name = ((self._lib.coattn_head_forward, "coattn_head_forward") if loss == "ce" else
+                                               (self._lib.coattn_head_forward_soft, "coattn_head_forward_soft"))
         self._co_fwd = self._lib.coattn_forward_len if question_mask else self._lib.coattn_forward
         self._co_bwd = self._lib.coattn_backward_len if question_mask else self._lib.coattn_backward
         self.pair(self._static)
@@ -134,7 +149,7 @@ class HotPathGraph:
 
     def _key(self, ins):
         V = ins[0]
-        return (V.data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), ins[3].data_ptr(), ins[4].data_ptr(), V.stride(0), V.stride(1), V.stride(2))
+        return (V.data_ptr(), *[t.data_ptr() for t in ins[1:]], V.stride(0), V.stride(1), V.stride(2))
 
     def _plan(self, ins, key=None):
         """Argument blocks of the four C-ABI calls for the inputs `ins` = (V [B,N,d] in a native layout, Q_w, Q_p, Q_s,
@@ -147,7 +162,10 @@ class HotPathGraph:
         if len(self._plans) >= 8 * self.MAX_KEYS:                # (eager mode has no graph to keep: drop the oldest)
             self._plans.pop(next(iter(self._plans)))
         B, N, T, d, mlp, K = self.dims
-        V, Qs, labels = ins[0], ins[1:4], ins[4]
+        V, Qs = ins[0], ins[1:4]
+        # the head's target arguments: int64 labels, or (ans_idx, ans_score, A, kind) of the soft-target call
+        target = ((_ptr(ins[4]),) if self.loss_name == "ce"
+                  else (_ptr(ins[4]), _ptr(ins[5]), self.num_answers, _lib.LOSS_KINDS[self.loss_name]))
         qptr = (C.c_void_p * 3)(*[t.data_ptr() for t in Qs])
         dqptr = (C.c_void_p * 3)(*[t.data_ptr() for t in self.dQ])
         rows = lambda t: (C.c_void_p * 3)(*[t[l].data_ptr() for l in range(3)])   # noqa: E731
@@ -163,7 +181,7 @@ class HotPathGraph:
             "keep": (qptr, dqptr, p, pg, hp, hg, rv, rq, rdx),
             "co_fwd": (_ptr(V), *vs, qptr, *ql, C.byref(p), _ptr(self.v), _ptr(self.q), _ptr(self.saved), _ptr(self.ws),
                        B, N, T, d, 3, _lib.F32, self.flags),
-            "head_fwd": (rv, rq, C.byref(hp), _ptr(labels), _ptr(self.logits), _ptr(self.loss), _ptr(self.hsaved),
+            "head_fwd": (rv, rq, C.byref(hp), *target, _ptr(self.logits), _ptr(self.loss), _ptr(self.hsaved),
                          B, d, mlp, K, _lib.F32, self.head_flags),
             "head_bwd": (rv, rq, C.byref(hp), _ptr(self.hsaved), _ptr(self.g_loss), None, rdx, None, C.byref(hg), 0,
                          _ptr(self.hws), B, d, mlp, K, _lib.F32, self.head_flags),
@@ -187,18 +205,19 @@ class HotPathGraph:
         st = C.c_void_p(stream)
         if fwd:
             _lib.check(self._co_fwd(*plan["co_fwd"], st), "coattn_forward")
-            _lib.check(lib.coattn_head_forward(*plan["head_fwd"], st), "coattn_head_forward")
+            _lib.check(self._head_fwd(*plan["head_fwd"], st), self._head_fwd_name)
         if bwd:
             _lib.check(lib.coattn_head_backward(*plan["head_bwd"], st), "coattn_head_backward")
             _lib.check(self._co_bwd(*plan["co_bwd"], st), "coattn_backward")
 
     def usable_in_place(self, ins) -> bool:
         B, N, T, d, _, _ = self.dims
-        V, labels = ins[0], ins[4]
+        V = ins[0]
         # (labels: the kernels read `const long long*` at the captured address -- anything but contiguous int64 on this
-        #  device goes through the static copy, which converts)
+        #  device goes through the static copy, which converts; the soft targets likewise: int32 indices, fp32 scores)
+        want = (torch.int64,) if self.loss_name == "ce" else (torch.int32, torch.float32)
         return (V.dtype == torch.float32 and V.device == self.device and _native_layout(V) is V
-                and labels.is_contiguous() and labels.dtype == torch.int64 and labels.device == self.device
+                and all(t.is_contiguous() and t.dtype == dt and t.device == self.device for t, dt in zip(ins[4:], want))
                 and all(q.is_contiguous() and q.dtype == torch.float32 and q.data_ptr() % 16 == 0 and q.device == self.device
                         for q in ins[1:4]))
 
@@ -258,7 +277,7 @@ class HotPathGraph:
             with _lib.on_device(self.device):
                 if fwd:
                     _lib.check(self._co_fwd(*plan["co_fwd"], st), "coattn_forward")
-                    _lib.check(lib.coattn_head_forward(*plan["head_fwd"], st), "coattn_head_forward")
+                    _lib.check(self._head_fwd(*plan["head_fwd"], st), self._head_fwd_name)
                 else:
                     _lib.check(lib.coattn_head_backward(*plan["head_bwd"], st), "coattn_head_backward")
                     _lib.check(self._co_bwd(*plan["co_bwd"], st), "coattn_backward")
@@ -271,7 +290,8 @@ class HotPathGraph:
         self.run(pair, ins, True)
         self.run(pair, ins, False)
 
-    def __call__(self, x_img: torch.Tensor, x_ques: Sequence[torch.Tensor], labels: torch.Tensor, q_len=None):
+    def __call__(self, x_img: torch.Tensor, x_ques: Sequence[torch.Tensor], labels, q_len=None):
+        # labels: int64 [B] -- or, for a node built with loss="soft_ce" | "bce", the pair (ans_idx [B,A], ans_score [B,A])
         # With direct gradients the parameters need not be inputs of the autograd node (their gradients do not travel through
         # autograd) as long as some input keeps the node alive -- the question levels of a trainable question encoder do;
         # 6 arguments instead of 22 through the Function machinery on every step.
@@ -298,23 +318,36 @@ class _HotPathFn(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, hp: HotPathGraph, x_img, labels, Qw, Qp, Qs, *params):
         B, N, T, d, mlp, K = hp.dims
-        if tuple(x_img.shape) != (B, N, d) or any(tuple(q.shape) != (B, T, d) for q in (Qw, Qp, Qs)) or tuple(labels.shape) != (B,):
+        if tuple(x_img.shape) != (B, N, d) or any(tuple(q.shape) != (B, T, d) for q in (Qw, Qp, Qs)):
             raise RuntimeError("HotPathGraph: captured for x_img %s, questions %s" % ((B, N, d), (B, T, d)))
-        if labels.dtype.is_floating_point or labels.dtype == torch.bool:
-            raise RuntimeError("HotPathGraph: labels must be integer class indices (int64 [B]), got %s" % labels.dtype)
+        if hp.loss_name == "ce":
+            if not torch.is_tensor(labels) or tuple(labels.shape) != (B,):
+                raise RuntimeError("HotPathGraph: captured for x_img %s, questions %s" % ((B, N, d), (B, T, d)))
+            if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+                raise RuntimeError("HotPathGraph: labels must be integer class indices (int64 [B]), got %s" % labels.dtype)
+            tgt = (labels,)
+        else:
+            if torch.is_tensor(labels) or len(labels) != 2:
+                raise RuntimeError("HotPathGraph(loss=%r): targets (ans_idx, ans_score) expected, not labels" % hp.loss_name)
+            tgt = tuple(labels)
+            if (any(tuple(t.shape) != (B, hp.num_answers) for t in tgt) or tgt[0].dtype.is_floating_point
+                    or tgt[0].dtype == torch.bool or not tgt[1].dtype.is_floating_point):
+                raise RuntimeError("HotPathGraph: built for targets ans_idx int32 / ans_score fp32 of shape %s"
+                                   % ((B, hp.num_answers),))
         if ctx.needs_input_grad[1] and hp.dV is None:
             raise RuntimeError("HotPathGraph: built with need_dv=False but the image features require a gradient")
         # (features in a layout the kernels do not run on -- e.g. the channel-major view at N = 49, whose rows are not
         #  16-byte multiples -- are re-laid once, as on the eager path; the allocator hands that buffer's block back step
         #  after step, so it is one more address set, not a copy into the static input on top)
-        ins = (_native_layout(x_img), Qw, Qp, Qs, labels)
+        ins = (_native_layout(x_img), Qw, Qp, Qs, *tgt)
         key = hp._key(ins)
         pair = hp.pair(ins, key) if hp.usable_in_place(ins) else None
         if pair is None:                                         # other dtype / too many address sets: static inputs
             if x_img.data_ptr() != hp.V.data_ptr():
                 hp.V.copy_(x_img)
             torch._foreach_copy_(hp.Q, [Qw, Qp, Qs])
-            hp.labels.copy_(labels)
+            for dst, src in zip(hp._static[4:], tgt):               # (labels, or ans_idx and ans_score; copy_ converts)
+                dst.copy_(src)
             ins = hp._static
             key = hp._key(ins)
             pair = hp.pair(ins, key)

@@ -116,6 +116,57 @@ class _HeadFn(torch.autograd.Function):
         return (dx if ctx.needs_input_grad[0] else None, dx if ctx.needs_input_grad[1] else None, *grads, None, None)
 
 
+class _HeadSoftFn(torch.autograd.Function):
+    """(v [3,B,d], q [3,B,d], 8 parameters, ans_idx int32 [B,A], ans_score fp32 [B,A], kind) -> (logits [B,K], loss []):
+    ``coattn_head_forward_soft``.  It writes ``_HeadFn``'s saved state, so the backward is ``_HeadFn``'s."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
+    def forward(ctx, v, q, W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h, ans_idx, ans_score, kind, bf16=False):
+        ctx.flags = _flags() | (_lib.FLAG_BF16_PROJ if bf16 else 0)
+        if not v.is_cuda:
+            raise RuntimeError("answer_head (HIP) needs tensors on the GPU; there is no CPU fallback")
+        if v.dtype != torch.float32 or q.dtype != torch.float32:
+            raise RuntimeError("answer_head (HIP) computes in fp32; got %s" % v.dtype)
+        if v.dim() != 3 or v.shape[0] != 3 or v.shape != q.shape:
+            raise RuntimeError("answer_head: v and q must both be [3,B,d], got %s / %s" % (tuple(v.shape), tuple(q.shape)))
+        _, B, d = v.shape
+        mlp, K = W_s.shape[0], W_h.shape[0]
+        if (tuple(W_w.shape) != (d, d) or tuple(W_p.shape) != (d, 2 * d) or tuple(W_s.shape) != (mlp, 2 * d)
+                or tuple(W_h.shape) != (K, mlp)):
+            raise RuntimeError("answer_head: weight shapes do not match MLPClassifier(hidden_dim=%d, mlp_dim, K)" % d)
+        if (ans_idx.dtype != torch.int32 or ans_score.dtype != torch.float32 or ans_idx.dim() != 2 or ans_idx.shape[0] != B
+                or ans_idx.shape != ans_score.shape or not 1 <= ans_idx.shape[1] <= _lib.MAX_ANSWERS):
+            raise RuntimeError("answer_head: targets must be (ans_idx int32 [B,A], ans_score fp32 [B,A]) with 1 <= A <= %d"
+                               % _lib.MAX_ANSWERS)
+        lib = _lib.load()
+        v, q = v.contiguous(), q.contiguous()
+        ps = [t.contiguous() for t in (W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h)]
+        ai, sc = ans_idx.contiguous(), ans_score.contiguous()
+        dev = v.device
+        sb, _ = _workspace_bytes(B, d, mlp, K)
+        saved = torch.empty(sb // 4, device=dev, dtype=torch.float32)
+        logits = torch.empty((B, K), device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        p = _lib.HeadParams(*[t.data_ptr() for t in ps])
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with _lib.on_device(dev):
+            _lib.check(lib.coattn_head_forward_soft(_rows(v), _rows(q), C.byref(p), _ptr(ai), _ptr(sc), ai.shape[1], kind,
+                                                    _ptr(logits), _ptr(loss), _ptr(saved), B, d, mlp, K, _lib.F32, ctx.flags,
+                                                    stream), "coattn_head_forward_soft")
+        global _last
+        _last = (saved, B, d, mlp, K, dev)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(v, q, saved, *ps)
+            ctx.dims = (B, d, mlp, K)
+            ctx.has_loss = True
+        return logits, loss
+
+    @staticmethod
+    def backward(ctx, g_logits, g_loss):
+        return _HeadFn.backward(ctx, g_logits, g_loss) + (None, None)    # (ans_score, kind beyond _HeadFn's twelve inputs)
+
+
 def check_labels() -> None:
     """nn.CrossEntropyLoss raises on a label outside [0, K); the HIP head stays asynchronous, makes the loss NaN and
     sets a status word instead.  This SYNCHRONISES the current stream and raises IndexError if the last forward with
@@ -148,10 +199,21 @@ def _as_3bd(x) -> torch.Tensor:
     return torch.stack(x)
 
 
-def answer_head(v, q, W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h, labels: Optional[torch.Tensor] = None, bf16: bool = False):
+def answer_head(v, q, W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h, labels: Optional[torch.Tensor] = None, bf16: bool = False,
+                targets=None, loss_kind: str = "soft_ce"):
     """v, q: [3,B,d] tensors or sequences of three [B,d] tensors (attended image / question features of the word,
     phrase and sentence levels).  Returns logits [B,K] -- and, with int64 labels [B], (logits, mean cross entropy).
     bf16: the reduced-precision mode (operands of the four products and of their gradients rounded to bf16, one bf16 MFMA
-    where the exact head issues eight f32 ones; fp32 accumulation, biases, tanh and loss) -- the apex-O1 analogue."""
+    where the exact head issues eight f32 ones; fp32 accumulation, biases, tanh and loss) -- the apex-O1 analogue.
+    targets = (ans_idx int32 [B,A], ans_score fp32 [B,A]) instead of labels: (logits, soft-target loss of `loss_kind`
+    "soft_ce" | "bce") -- loss.soft_target_loss's definitions, out of the head's own forward call."""
+    if targets is not None:
+        if labels is not None:
+            raise ValueError("answer_head: give labels or targets, not both")
+        if loss_kind not in _lib.LOSS_KINDS:
+            raise ValueError("answer_head: loss_kind must be one of %s, got %r" % (tuple(_lib.LOSS_KINDS), loss_kind))
+        ans_idx, ans_score = targets
+        return _HeadSoftFn.apply(_as_3bd(v), _as_3bd(q), W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h, ans_idx, ans_score,
+                                 _lib.LOSS_KINDS[loss_kind], bf16)
     logits, loss = _HeadFn.apply(_as_3bd(v), _as_3bd(q), W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h, labels, bf16)
     return logits if labels is None else (logits, loss)

@@ -296,11 +296,21 @@ class MLPClassifier(nn.Module):
         h_s = torch.tanh(self.W_s(torch.cat([q_s + v_s, h_p], dim=1)))
         return self.W_h(h_s)
 
-    def forward_loss(self, x_img_feats, x_ques_feats, labels):
-        """(logits, nn.CrossEntropyLoss()(logits, labels)) -- main.py:211 + :214 -- in one call of the HIP head."""
+    def forward_loss(self, x_img_feats, x_ques_feats, labels=None, targets=None, loss_kind="soft_ce"):
+        """(logits, nn.CrossEntropyLoss()(logits, labels)) -- main.py:211 + :214 -- in one call of the HIP head.
+        targets = (ans_idx int32 [B,A], ans_score fp32 [B,A]) instead of labels: (logits, the soft-target loss `loss_kind`
+        of loss.soft_target_loss) -- VQA's ten human answers instead of the majority answer."""
+        if (labels is None) == (targets is None):
+            raise ValueError("forward_loss: give labels or targets (one of the two)")
         if self._hip(x_img_feats):
+            if targets is not None:
+                return answer_head(x_img_feats, x_ques_feats, *self._params(), bf16=self.bf16_products, targets=targets,
+                                   loss_kind=loss_kind)
             return answer_head(x_img_feats, x_ques_feats, *self._params(), labels=labels, bf16=self.bf16_products)
         logits = self.forward(x_img_feats, x_ques_feats)
+        if targets is not None:
+            from .loss import soft_target_loss_stock
+            return logits, soft_target_loss_stock(logits.float(), targets[0], targets[1], loss_kind)
         return logits, F.cross_entropy(logits.float(), labels)
 
 
@@ -336,10 +346,12 @@ class HierarchicalCoAttentionNet(nn.Module):
         self.hot_path_direct_grads = False
         self._graphs = {}
 
-    def forward(self, x_img, x_ques, x_ques_lens, return_attention=False):
-        return self.forward_features(self.image_encoder(x_img), x_ques, x_ques_lens, return_attention=return_attention)
+    def forward(self, x_img, x_ques, x_ques_lens, return_attention=False, targets=None, loss_kind="soft_ce"):
+        return self.forward_features(self.image_encoder(x_img), x_ques, x_ques_lens, return_attention=return_attention,
+                                     targets=targets, loss_kind=loss_kind)
 
-    def forward_features(self, x_img_features, x_ques, x_ques_lens, labels=None, return_attention=False):
+    def forward_features(self, x_img_features, x_ques, x_ques_lens, labels=None, return_attention=False, targets=None,
+                         loss_kind="soft_ce"):
         """The forward pass from already-encoded image features [B,N,d] (model.py:171-187 minus the
         image encoder call): lets a frozen encoder run ahead on its own stream (train.Trainer).
         `x_img_features` may be a zero-argument callable returning the features.  With `labels` (int64 [B]) the
@@ -347,7 +359,15 @@ class HierarchicalCoAttentionNet(nn.Module):
         `x_ques_lens` reaches the co-attention too when its ``question_mask`` is on (ParallelCoAttention).
         return_attention=True: the co-attention maps a_v [3,B,N], a_q [3,B,T] come out as well -- (logits, a_v, a_q), or
         (logits, loss, a_v, a_q) with `labels` -- differentiable, for a loss on them (ParallelCoAttention.forward).  This
-        takes the per-module path, never the hot-path node (`hot_path_static` / `hot_path_graph`)."""
+        takes the per-module path, never the hot-path node (`hot_path_static` / `hot_path_graph`).
+        targets = (ans_idx int32 [B,A], ans_score fp32 [B,A]) in place of `labels`: the loss is the soft-target loss
+        `loss_kind` ("soft_ce" | "bce", loss.soft_target_loss); everything above holds with "labels" read as "targets"."""
+        if labels is not None and targets is not None:
+            raise ValueError("forward_features: give labels or targets, not both")
+        if targets is not None and loss_kind not in ("soft_ce", "bce"):
+            raise ValueError("loss_kind must be 'soft_ce' or 'bce', got %r" % (loss_kind,))
+        has_loss = labels is not None or targets is not None
+        tk = dict(targets=targets, loss_kind=loss_kind) if targets is not None else dict(labels=labels)
         x_ques_features = list(self.question_encoder(x_ques, x_ques_lens))
         if callable(x_img_features):            # resolved only now: the question side is queued first
             x_img_features = x_img_features()
@@ -355,18 +375,19 @@ class HierarchicalCoAttentionNet(nn.Module):
         if return_attention:
             lens = (x_ques_lens,) if masked else ()
             v, q, a_v, a_q = self.co_attention(x_img_features, x_ques_features, *lens, return_attention=True)
-            if labels is not None:
-                return (*self.mlp_classify.forward_loss(v, q, labels), a_v, a_q)
+            if has_loss:
+                return (*self.mlp_classify.forward_loss(v, q, **tk), a_v, a_q)
             return self.mlp_classify(v, q), a_v, a_q
-        if (labels is not None and (self.hot_path_graph or self.hot_path_static) and x_img_features.is_cuda
+        if (has_loss and (self.hot_path_graph or self.hot_path_static) and x_img_features.is_cuda
                 and torch.is_grad_enabled() and self.co_attention_form == "parallel"):     # (the node is parallel-only)
-            return self._graphed(x_img_features, x_ques_features, labels, x_ques_lens if masked else None)
+            return self._graphed(x_img_features, x_ques_features, labels, x_ques_lens if masked else None, targets=targets,
+                                 loss_kind=loss_kind)
         if masked:
             x_img_attn, x_ques_attn = self.co_attention(x_img_features, x_ques_features, x_ques_lens)
         else:
             x_img_attn, x_ques_attn = self.co_attention(x_img_features, x_ques_features)
-        if labels is not None:
-            return self.mlp_classify.forward_loss(x_img_attn, x_ques_attn, labels)
+        if has_loss:
+            return self.mlp_classify.forward_loss(x_img_attn, x_ques_attn, **tk)
         return self.mlp_classify(x_img_attn, x_ques_attn)
 
     def forward_with_attention(self, x_img, x_ques, x_ques_lens):
@@ -389,7 +410,7 @@ class HierarchicalCoAttentionNet(nn.Module):
     def _question_mask(self) -> bool:
         return bool(getattr(self.co_attention, "question_mask", False))
 
-    def _graphed(self, x_img_features, x_ques_features, labels, x_ques_lens=None):
+    def _graphed(self, x_img_features, x_ques_features, labels, x_ques_lens=None, targets=None, loss_kind="soft_ce"):
         """co-attention + answer head + loss, forward AND backward, as one autograd node over static buffers (graph.py),
         built per (B, N, T) on first use: replayed from captured HIP graphs (``net.hot_path_graph = True``,
         ``Trainer(graph=True)``) or with its four C-ABI calls issued eagerly (``net.hot_path_static``, the Trainer's
@@ -403,6 +424,7 @@ class HierarchicalCoAttentionNet(nn.Module):
         key = (B, N, T, bool(x_img_features.requires_grad), bool(self.co_attention.bf16_projections),
                bool(self.mlp_classify.bf16_products), bool(self.hot_path_graph), bool(self.hot_path_direct_grads),
                bool(self.co_attention.fast_products), self._question_mask(),
+               ("ce", 0) if targets is None else (loss_kind, int(targets[0].shape[1])),
                getattr(self.co_attention, "affinity", "reference"))
         hp = self._graphs.get(key)
         # (the node reads the parameters where they lie: one built before the module was moved -- .to(), .cuda(), new
@@ -412,8 +434,9 @@ class HierarchicalCoAttentionNet(nn.Module):
         if hp is None:
             hp = self._graphs[key] = HotPathGraph(self.co_attention, self.mlp_classify, B, N, T, need_dv=key[3],
                                                   flags=(_lib.FLAG_BF16_PROJ if key[4] else 0) | _lib.precision_flag(key[8] and not key[4]),
-                                                  capture=key[6], direct_grads=key[7], question_mask=key[9])
-        return hp(x_img_features, x_ques_features, labels, q_len=x_ques_lens)
+                                                  capture=key[6], direct_grads=key[7], question_mask=key[9],
+                                                  **({} if targets is None else dict(loss=key[10][0], num_answers=key[10][1])))
+        return hp(x_img_features, x_ques_features, labels if targets is None else targets, q_len=x_ques_lens)
 
 
 # ---- baseline model (BASELINE config 1: CPU plumbing, no custom kernels) ------------------

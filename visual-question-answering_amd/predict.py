@@ -16,6 +16,11 @@ README roadmap.  Same command line as ``train.py`` (the reference's flags) plus 
 * stdout: one JSON line ``{samples, accuracy, top{K}_accuracy, loss, pairs_per_s}`` (accuracies in percent, as
   ``Trainer.validate``; loss = mean cross entropy per sample).
 
+* ``--loss soft_ce | bce`` (the value the checkpoint was trained with; the checkpoint does not record it): the test split
+  carries soft answer targets (``--num_answers`` slots), every record gains ``score`` -- min(1, target of its top answer), the
+  VQA accuracy of the prediction -- and the summary ``vqa_score``, their mean; ``loss`` is then that loss kind's mean.  With
+  ``bce`` the reported probabilities are per-class sigmoids (they do not sum to 1), else softmax probabilities.
+
 The maps come from the forward-only co-attention (``coattn_infer``): no state for a backward is written.  One process:
 multi-GPU prediction is not offered.  Data: the synthetic test split (its own seed), every sample (no drop_last).
 """
@@ -31,6 +36,7 @@ import torch
 import torch.nn.functional as F
 import torch.utils.data
 
+from . import loss as L
 from . import train as T
 
 TEST_SEED = 555555
@@ -61,6 +67,10 @@ def main(argv=None):
                  % os.environ["WORLD_SIZE"])
     if not args.synthetic:
         raise SystemExit("only --synthetic true is available: the VQA dataset is not present in this environment")
+    try:
+        T.check_loss(args.loss, args.num_answers)
+    except ValueError as e:
+        ap.error(str(e))
 
     if torch.cuda.is_available():
         device = torch.device("cuda", args.gpu_id)
@@ -77,11 +87,13 @@ def main(argv=None):
         model.image_encoder.to(memory_format=torch.channels_last)
     T.set_products(model, args.precision)                       # the settings Trainer applies for --precision / --opt_lvl
     T.set_reduced_precision(model, args.opt_lvl)
-    criterion = T.CrossEntropyLoss()
+    soft = args.loss != "ce"                                    # the split then carries soft answer targets
+    criterion = T.SoftTargetLoss(args.loss) if soft else T.CrossEntropyLoss()
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
     k = min(args.topk, n_cls)
-    ds = T.SyntheticVQADataset(args.test_size, size, args.max_seq_length, args.vocab_size, n_cls, TEST_SEED)
+    ds = T.SyntheticVQADataset(args.test_size, size, args.max_seq_length, args.vocab_size, n_cls, TEST_SEED,
+                               num_answers=args.num_answers if soft else 0)
     loader = torch.utils.data.DataLoader(ds, args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
     maps = bool(args.attention_maps)
 
@@ -90,6 +102,7 @@ def main(argv=None):
     prob = torch.zeros((S, k), dtype=torch.float32)
     labels = torch.zeros(S, dtype=torch.int64)
     lens = torch.zeros(S, dtype=torch.int64)
+    scores = torch.zeros(S, dtype=torch.float32) if soft else None
     a_v = a_q = None
     loss_sum = 0.0
     model.eval()
@@ -101,8 +114,10 @@ def main(argv=None):
             index = torch.arange(start, start + n)
             start += n
             # sorted by question length for packing (main.py:196-202); the index rides along as a second label column
-            image, question, il, ques_len = T.sort_batch(b["image"], b["question"], torch.stack([index, b["label"]], 1),
-                                                         b["ques_len"])
+            extras = (b["answers"], b["answer_scores"]) if soft else ()
+            image, question, il, ques_len, *extras = T.sort_batch(b["image"], b["question"], torch.stack([index, b["label"]], 1),
+                                                                  b["ques_len"], *extras)
+            targets = [e.to(device) for e in extras]
             idx, label = il[:, 0], il[:, 1]
             image = image.to(device)
             if cl:
@@ -113,8 +128,13 @@ def main(argv=None):
                     logits, av, aq = model.forward_with_attention(image, question, ques_len)
                 else:
                     logits = model(image, question, ques_len)
-            loss_sum += float(criterion(logits.float(), label_d)) * n
-            pv, pi = F.softmax(logits.float(), dim=1).topk(k, dim=1)
+            if soft:
+                loss_sum += float(criterion(logits.float(), *targets)) * n
+                scores[idx] = L.vqa_score(logits.float(), *targets)[1].cpu()
+            else:
+                loss_sum += float(criterion(logits.float(), label_d)) * n
+            probs = torch.sigmoid(logits.float()) if args.loss == "bce" else F.softmax(logits.float(), dim=1)
+            pv, pi = probs.topk(k, dim=1)
             top[idx], prob[idx], labels[idx], lens[idx] = pi.cpu(), pv.cpu(), label, ques_len
             if maps:
                 if a_v is None:
@@ -134,8 +154,10 @@ def main(argv=None):
     if args.predictions:
         with open(args.predictions, "w") as fh:
             for i in range(S):
-                fh.write(json.dumps({"index": i, "label": int(labels[i]), "top": top[i].tolist(),
-                                     "prob": [float(x) for x in prob[i]]}) + "\n")
+                rec = {"index": i, "label": int(labels[i]), "top": top[i].tolist(), "prob": [float(x) for x in prob[i]]}
+                if soft:
+                    rec["score"] = float(scores[i])
+                fh.write(json.dumps(rec) + "\n")
     if maps:
         N = a_v.shape[-1]
         H = int(round(math.sqrt(N)))
@@ -146,6 +168,8 @@ def main(argv=None):
     summary = {"samples": S, "accuracy": round(100.0 * float(hit1.float().mean()), 4),
                "top%d_accuracy" % k: round(100.0 * float(hitk.float().mean()), 4),
                "loss": round(loss_sum / S, 6), "pairs_per_s": round(S / max(elapsed, 1e-9), 2)}
+    if soft:
+        summary["vqa_score"] = round(float(scores.mean()), 6)
     print(json.dumps(summary))
     return summary
 

@@ -22,7 +22,7 @@ import torch.nn as nn
 import torch.utils.data
 
 from . import dist as vdist
-from .loss import CrossEntropyLoss
+from .loss import CrossEntropyLoss, SoftTargetLoss
 from .modules import HierarchicalCoAttentionNet, VQABaselineNet
 
 PATH_VGG_WEIGHTS = None      # the reference hard-codes a local .pth (utils.py:15); none ships here
@@ -232,17 +232,50 @@ def autocast_for(opt_lvl: int, device):
     return contextlib.nullcontext()
 
 
-def sort_batch(images, questions, answers, ques_seq_lens):
-    """Descending by question length, as packing requires (utils.py:33-45)."""
+def sort_batch(images, questions, answers, ques_seq_lens, *extras):
+    """Descending by question length, as packing requires (utils.py:33-45).  `extras` (e.g. the soft answer targets
+    `answers`, `answer_scores` of a batch) are reordered alike and appended to the result."""
     ques_seq_lens, order = ques_seq_lens.sort(dim=0, descending=True)
-    return images[order], questions[order], answers[order], ques_seq_lens
+    return (images[order], questions[order], answers[order], ques_seq_lens, *[e[order] for e in extras])
+
+
+LOSSES = ("ce", "soft_ce", "bce")
+ANSWER_SCORES = (0.3, 0.6, 0.9, 1.0)      # min(1, n / 3) for n = 1, 2, 3, >= 4 humans, as VQA v2's annotations are commonly scored
+
+
+def check_loss(loss: str, num_answers: int = 10) -> None:
+    """--loss: "ce" (the default: the reference's nn.CrossEntropyLoss on the majority answer), "soft_ce" or "bce" on the soft
+    answer targets (loss.soft_target_loss); --num_answers: answer slots per sample, 1..16."""
+    if loss not in LOSSES:
+        raise ValueError("--loss must be one of %s, got %r" % (LOSSES, loss))
+    if not 1 <= int(num_answers) <= 16:
+        raise ValueError("--num_answers must be in 1..16, got %r" % (num_answers,))
+
+
+def synthetic_answers(labels: torch.Tensor, num_answers: int, num_classes: int, seed: int):
+    """Soft answer targets for `labels` (shape [...]): answers int32 [..., A] and answer_scores fp32 [..., A].  Slot 0 is
+    (label, 1.0); every further slot is empty (-1) with probability 1/3, else a class U{0..num_classes-1} with a score from
+    ANSWER_SCORES.  Drawn from a generator of its OWN (seeded by `seed`), so that asking for answers changes no bit of the
+    image, question, length or label of any seed."""
+    g = torch.Generator().manual_seed((seed * 2654435761 + 97) % (2 ** 63))
+    shape = tuple(labels.shape) + (num_answers,)
+    idx = torch.randint(0, num_classes, shape, generator=g)
+    empty = torch.randint(0, 3, shape, generator=g) == 0
+    score = torch.tensor(ANSWER_SCORES)[torch.randint(0, len(ANSWER_SCORES), shape, generator=g)]
+    idx = torch.where(empty, torch.full_like(idx, -1), idx)
+    score = torch.where(empty, torch.zeros_like(score), score)
+    idx[..., 0] = labels
+    score[..., 0] = 1.0
+    return idx.to(torch.int32), score.to(torch.float32)
 
 
 def synthetic_batch(batch_size: int, image_size, max_seq_len: int, vocab_size: int, num_classes: int,
-                    seed: int) -> Dict[str, torch.Tensor]:
+                    seed: int, num_answers: int = 0) -> Dict[str, torch.Tensor]:
     """One batch shaped like VQADataset's output (dataloader.py:72): images N(0,1), token ids
     U{2..vocab-1} zero-padded to max_seq_len, lengths U{3..max} with at least one full-length
-    question, labels U{0..num_classes-1}.  CPU tensors; lengths are NOT sorted (sort_batch does)."""
+    question, labels U{0..num_classes-1}.  CPU tensors; lengths are NOT sorted (sort_batch does).
+    num_answers = A > 0: also `answers` int32 [B,A] and `answer_scores` fp32 [B,A] (synthetic_answers; the other four keys
+    keep their bits)."""
     g = torch.Generator().manual_seed(seed)
     H, W = image_size
     image = torch.randn(batch_size, 3, H, W, generator=g)
@@ -251,7 +284,10 @@ def synthetic_batch(batch_size: int, image_size, max_seq_len: int, vocab_size: i
     question = torch.randint(2, vocab_size, (batch_size, max_seq_len), generator=g)
     question = question * (torch.arange(max_seq_len)[None, :] < lens[:, None])
     label = torch.randint(0, num_classes, (batch_size,), generator=g)
-    return {"image": image, "question": question, "ques_len": lens, "label": label}
+    out = {"image": image, "question": question, "ques_len": lens, "label": label}
+    if num_answers:
+        out["answers"], out["answer_scores"] = synthetic_answers(label, num_answers, num_classes, seed)
+    return out
 
 
 class DevicePrefetcher:
@@ -285,7 +321,7 @@ class DevicePrefetcher:
         try:
             torch.cuda.set_device(self.device)
             ring = [{}, {}]                                       # pinned staging buffers + their last copy event
-            for i, (image, question, ques_len, label) in enumerate(it):
+            for i, (image, question, ques_len, label, *extras) in enumerate(it):
                 slot = ring[i & 1]
                 if slot.get("event") is not None:
                     slot["event"].synchronize()                  # the previous copy out of this set is done
@@ -304,10 +340,11 @@ class DevicePrefetcher:
                         im = im.contiguous(memory_format=torch.channels_last)
                     qu = pin("question", question).to(self.device, non_blocking=True)
                     la = pin("label", label).to(self.device, non_blocking=True)
+                    ex = [pin("extra%d" % j, e).to(self.device, non_blocking=True) for j, e in enumerate(extras)]
                     ev = torch.cuda.Event()
                     ev.record(self.stream)
                 slot["event"] = ev
-                self._q.put((im, qu, ques_len, la, ev))
+                self._q.put((im, qu, ques_len, la, ev, *ex))
         except BaseException as e:                                # surfaced in the consumer thread
             self._err = e
         finally:
@@ -316,8 +353,8 @@ class DevicePrefetcher:
     def _advance(self):
         if self._q is None:
             try:
-                image, question, ques_len, label = next(self._it)
-                self.next = (image, question, ques_len, label, None)
+                image, question, ques_len, label, *extras = next(self._it)
+                self.next = (image, question, ques_len, label, None, *extras)
             except StopIteration:
                 self.next = None
             return
@@ -342,14 +379,14 @@ class DevicePrefetcher:
     def __next__(self):
         if self.next is None:
             raise StopIteration
-        im, qu, ln, la, ev = self.next
+        im, qu, ln, la, ev, *extras = self.next          # (extras: the soft answer targets, when the batches carry them)
         if ev is not None:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
-            for t in (im, qu, la):
+            for t in (im, qu, la, *extras):
                 t.record_stream(cur)
         self._advance()
-        return im, qu, ln, la
+        return (im, qu, ln, la, *extras)
 
 
 class Trainer:
@@ -366,7 +403,9 @@ class Trainer:
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, device=None, opt_lvl: int = 0,
                  bucket_mb: float = 16.0, encoder_runahead: bool = True, graph: bool = False, static_hot_path: bool = True,
-                 precision: str = "exact"):
+                 precision: str = "exact", loss: str = "ce"):
+        check_loss(loss)
+        self.loss = loss                                         # "ce": int64 labels; "soft_ce" | "bce": step(..., targets=...)
         self.device = device or next(model.parameters()).device
         self.model = model
         # Precision of the HIP path's fp32 products (include/coattn.h "Widths of the fp32 mode"): "exact" -- the default, the
@@ -379,6 +418,7 @@ class Trainer:
             raise ValueError("precision must be 'fast' or 'exact'")
         self.set_precision(precision)
         self.criterion = CrossEntropyLoss()      # nn.CrossEntropyLoss() semantics (main.py:94); fused HIP kernel on CUDA
+        self.soft_criterion = SoftTargetLoss(loss) if loss != "ce" else None
         self.optimizer = torch.optim.Adam(model.parameters(), lr)
         self.opt_lvl = opt_lvl
         set_reduced_precision(model, opt_lvl)                    # AMP: projections on the bf16 MFMA as well
@@ -432,10 +472,16 @@ class Trainer:
         feats.record_stream(main)
         return feats
 
-    def step(self, image, question, ques_len, label, next_image=None, next_ready=None) -> torch.Tensor:
+    def step(self, image, question, ques_len, label, next_image=None, next_ready=None, targets=None) -> torch.Tensor:
         """One optimisation step on device-resident, length-sorted tensors; returns the loss.
         `next_image`: the following step's image batch (device-resident), if known; `next_ready`: the
-        event that marks its host->device copy complete (DevicePrefetcher.peek_image)."""
+        event that marks its host->device copy complete (DevicePrefetcher.peek_image).
+        `targets` = (ans_idx int32 [B,A], ans_score fp32 [B,A]): what a Trainer(loss="soft_ce" | "bce") trains against
+        (`label` is then not read); a Trainer(loss="ce") takes none."""
+        if (targets is not None) != (self.loss != "ce"):
+            raise ValueError("Trainer(loss=%r).step: %s" % (self.loss, "targets=(ans_idx, ans_score) needed" if targets is None
+                                                           else "takes labels, not targets"))
+        tk = dict(labels=label) if targets is None else dict(targets=tuple(targets), loss_kind=self.loss)
         if self.runahead:
             with self._autocast():
                 mine, self._ahead = self._ahead, None
@@ -456,11 +502,11 @@ class Trainer:
                 # the question side is queued before the current stream waits for the image features; the loss comes
                 # out of the answer head's own call (main.py:211 + :214 in one)
                 logits, loss = self.model.forward_features((lambda: self._claim(mine)) if mine is not None else inline,
-                                                           question, ques_len, labels=label)
+                                                           question, ques_len, **tk)
         else:
             with self._autocast():
                 logits = self.model(image, question, ques_len)
-            loss = self.criterion(logits.float(), label)
+            loss = self.criterion(logits.float(), label) if targets is None else self.soft_criterion(logits.float(), *targets)
         self.optimizer.zero_grad()
         if self.reducer is not None:
             self.reducer.prepare()
@@ -516,19 +562,38 @@ class Trainer:
         """Accuracy / mean CE under eval() (main.py:290-351, without its n_iters+1 / n_iters slip).
         With encoder run-ahead, an encoder pass queued for the next training batch is waited for first
         (its BatchNorm running-statistics update is then already included, i.e. one batch earlier than
-        in the serial schedule); pass next_image=None on the step before validating to avoid that."""
+        in the serial schedule); pass next_image=None on the step before validating to avoid that.
+        Batches are (image, question, ques_len, label) or, with soft answer targets, (..., label, ans_idx, ans_score): the
+        dict then gains `vqa_score` (the mean of min(1, t[pred]) over all samples, in [0, 1]: with one-hot targets it is
+        `accuracy` / 100; on the GPU through coattn_vqa_score, summed on the device and read once), and `loss` is this trainer's own loss kind."""
         if self.enc_stream is not None:
             torch.cuda.current_stream(self.device).wait_stream(self.enc_stream)
         self.model.eval()
         n_ok = n = 0
         loss = 0.0
-        for image, question, ques_len, label in batches:
+        score = None
+        for image, question, ques_len, label, *targets in batches:
             logits = self.model(image, question, ques_len)
-            loss += float(self.criterion(logits.float(), label))
+            if self.loss != "ce":
+                if not targets:
+                    raise ValueError("Trainer(loss=%r).validate: the batches carry no answer targets" % self.loss)
+                loss += float(self.soft_criterion(logits.float(), *targets))
+            else:
+                loss += float(self.criterion(logits.float(), label))
             n_ok += int((logits.argmax(1) == label).sum())
             n += label.numel()
+            if targets:
+                from . import loss as _loss
+                if logits.is_cuda:
+                    part = _loss.vqa_score_sum(logits.float(), *targets, row_score=False)[2]
+                else:
+                    part = _loss.vqa_score(logits.float(), *targets)[1].sum()
+                score = part if score is None else score + part
         self.model.train()
-        return {"accuracy": 100.0 * n_ok / max(n, 1), "loss": loss / max(len(batches), 1)}
+        out = {"accuracy": 100.0 * n_ok / max(n, 1), "loss": loss / max(len(batches), 1)}
+        if score is not None:
+            out["vqa_score"] = float(score) / max(n, 1)          # (the one host read of the scores)
+        return out
 
 
 class SyntheticVQADataset(torch.utils.data.Dataset):
@@ -537,8 +602,9 @@ class SyntheticVQADataset(torch.utils.data.Dataset):
     in for the dataset files this environment does not have; feeds the same DataLoader(batch_size, shuffle, drop_last,
     num_workers) as main.py:129-130."""
 
-    def __init__(self, n_samples, image_size, max_seq_len, vocab_size, num_classes, seed):
+    def __init__(self, n_samples, image_size, max_seq_len, vocab_size, num_classes, seed, num_answers: int = 0):
         self.n, self.size, self.T, self.vocab, self.K, self.seed = n_samples, image_size, max_seq_len, vocab_size, num_classes, seed
+        self.A = num_answers          # > 0: samples also carry `answers` int32 [A], `answer_scores` fp32 [A] (synthetic_answers)
 
     def __len__(self):
         return self.n
@@ -547,8 +613,11 @@ class SyntheticVQADataset(torch.utils.data.Dataset):
         g = torch.Generator().manual_seed(self.seed * 1000003 + i)
         n = int(torch.randint(min(3, self.T), self.T + 1, (1,), generator=g))
         q = torch.randint(2, self.vocab, (self.T,), generator=g) * (torch.arange(self.T) < n)
-        return {"image": torch.randn(3, *self.size, generator=g), "question": q, "ques_len": torch.tensor(n),
-                "label": torch.randint(0, self.K, (), generator=g)}
+        out = {"image": torch.randn(3, *self.size, generator=g), "question": q, "ques_len": torch.tensor(n),
+               "label": torch.randint(0, self.K, (), generator=g)}
+        if self.A:
+            out["answers"], out["answer_scores"] = synthetic_answers(out["label"], self.A, self.K, self.seed * 1000003 + i)
+        return out
 
 
 def build_parser():
@@ -619,11 +688,18 @@ def build_parser():
                          "'alternating' = three chained guided-attention steps (AlternatingCoAttention; its own state_dict "
                          "keys).  Co-attention models only, exact mode only: not with --affinity bilinear, --opt_lvl >= 1 or "
                          "--precision fast")
+    ap.add_argument("--loss", default="ce", choices=list(LOSSES),
+                    help="'ce' = the reference's cross entropy on the majority answer; 'soft_ce' / 'bce' = soft cross entropy / "
+                         "binary cross entropy with logits on the soft answer targets (up to --num_answers (answer, score) pairs "
+                         "per sample; validation then reports the VQA score).  The checkpoint does not record it: give "
+                         "prediction the value the checkpoint was trained with (with 'bce' its probabilities are sigmoids)")
+    ap.add_argument("--num_answers", type=int, default=10, help="answer slots per sample of the soft targets (1..16)")
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    check_loss(args.loss, args.num_answers)
     if args.mode == "test":
         raise NotImplementedError("TODO: test mode")          # as the reference, main.py:286-287
     if not args.synthetic:
@@ -651,18 +727,21 @@ def main(argv=None):
     cl = args.channels_last and device.type == "cuda" and args.model.startswith("attention")
     if cl:
         model.image_encoder.to(memory_format=torch.channels_last)
-    trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision)
+    trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss)
+    n_ans = args.num_answers if args.loss != "ce" else 0
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
 
     def loader(n_samples, seed):
-        ds = SyntheticVQADataset(n_samples, size, args.max_seq_length, args.vocab_size, n_cls, seed)
+        ds = SyntheticVQADataset(n_samples, size, args.max_seq_length, args.vocab_size, n_cls, seed, num_answers=n_ans)
         return torch.utils.data.DataLoader(ds, args.batch_size, shuffle=True, drop_last=True, num_workers=args.num_workers,
                                            generator=torch.Generator().manual_seed(seed))
 
     def sorted_host(batch):                                      # main.py:196-202
-        image, question, label, ques_len = sort_batch(batch["image"], batch["question"], batch["label"], batch["ques_len"])
-        return image, question, ques_len, label
+        extras = (batch["answers"], batch["answer_scores"]) if n_ans else ()
+        image, question, label, ques_len, *extras = sort_batch(batch["image"], batch["question"], batch["label"],
+                                                               batch["ques_len"], *extras)
+        return (image, question, ques_len, label, *extras)
 
     train_loader = loader(args.num_steps * args.batch_size, 1234 + rank)
     steps_per_epoch = len(train_loader)
@@ -670,22 +749,23 @@ def main(argv=None):
     n_val = args.val_batches or args.val_size // args.batch_size
     if n_val > 0:
         for b in loader(n_val * args.batch_size, 987654 + rank):
-            image, question, ques_len, label = sorted_host(b)
+            image, question, ques_len, label, *extras = sorted_host(b)
             image = image.to(device)
             if cl:
                 image = image.contiguous(memory_format=torch.channels_last)
-            val.append((image, question.to(device), ques_len, label.to(device)))
+            val.append((image, question.to(device), ques_len, label.to(device), *[e.to(device) for e in extras]))
     val_every = args.val_interval or (args.log_interval if val else 0)
 
     t0 = time.time()
     step = 0
     for epoch in range(args.num_epochs):
         batches = DevicePrefetcher((sorted_host(b) for b in train_loader), device, cl)
-        for image, question, ques_len, label in batches:
+        for image, question, ques_len, label, *extras in batches:
             validate_now = bool(val) and val_every > 0 and (step + 1) % val_every == 0
             # no encoder run-ahead across a validation: its BatchNorm statistics must be those of this step
             nxt, ready = (None, None) if validate_now else batches.peek_image()
-            loss = trainer.step(image, question, ques_len, label, next_image=nxt, next_ready=ready)
+            loss = trainer.step(image, question, ques_len, label, next_image=nxt, next_ready=ready,
+                                targets=tuple(extras) if extras else None)
             if (step + 1) % args.log_interval == 0:
                 trainer.check_labels()                           # (the host synchronises here anyway to read the loss)
                 trainer.check_range()
@@ -696,7 +776,8 @@ def main(argv=None):
             if validate_now:
                 m = trainer.validate(val)
                 if rank == 0:
-                    print(json.dumps({"step": step + 1, "val_accuracy": round(m["accuracy"], 3), "val_loss": round(m["loss"], 5)}))
+                    print(json.dumps({"step": step + 1, "val_accuracy": round(m["accuracy"], 3), "val_loss": round(m["loss"], 5),
+                                      **({"val_vqa_score": round(m["vqa_score"], 5)} if "vqa_score" in m else {})}))
             if (step + 1) % args.save_interval == 0 and log_dir and rank == 0:   # main.py:260-263
                 torch.save(model.state_dict(), os.path.join(log_dir, "model_%d.pth" % (step + 1)))
             step += 1
