@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -519,6 +519,36 @@ int coattn_head_forward_soft(const void* const* v, const void* const* q, const c
                              const void* ans_idx, const void* ans_score, int A, int kind,
                              void* logits, void* loss, void* saved, int B, int d, int mlp, int K, int dtype, int flags,
                              void* stream);
+
+/* ---- the optimiser step (v0.13.0): Adam / AdamW with gradient clipping by global norm, fp32 ------------------------
+ * The reference ends its step in torch.optim.Adam(...).step() (main.py:180, :222): eight or nine multi-tensor launches.  Here
+ * one call updates a whole list of tensors in ONE launch (lists of more than 64 non-empty tensors: one launch per 64), with
+ * torch.optim.Adam's arithmetic for the caller's step number `step` >= 1 (bc1 = 1 - beta1^step, bc2 = 1 - beta2^step):
+ *     g' = g * clip                                        (max_grad_norm > 0 only)
+ *     p  = p * (1 - lr * weight_decay)                     (weight_decay != 0 only: decoupled decay, torch.optim.AdamW)
+ *     m  = beta1 m + (1 - beta1) g'       v = beta2 v + (1 - beta2) g'^2
+ *     p  = p - (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+ * p, m (exp_avg), v (exp_avg_sq) are updated in place, g is only read; each is n contiguous fp32 elements, 4-byte aligned
+ * (16-byte accesses where all four pointers of a tensor are 16-byte aligned, dword accesses otherwise).  n = 0 entries are
+ * skipped.  NaN / inf propagate as in the stock optimiser: nothing is skipped.
+ * The hyper-parameters are doubles: 1 - beta, lr / bc1, sqrt(bc2) and 1 - lr * weight_decay are formed on the host in double
+ * and rounded to fp32 once, as torch forms them from Python floats (1 - (float)0.999 is 1.3e-5 off 0.001).
+ * max_grad_norm > 0: a launch ahead of the update (one per 64 tensors) sums g^2 over the whole list -- per-workgroup partials
+ * in `ws`, added in a fixed order by the workgroup that takes the last integer ticket; accumulation in double, no float
+ * atomics: bitwise repeatable -- and leaves norm = sqrt(sum) and clip = min(1, max_grad_norm / (norm + 1e-6))
+ * (torch.nn.utils.clip_grad_norm_) in `ws`, where the update reads clip; the host never waits.  norm_out (device fp32 [1], may
+ * be NULL) receives norm.  max_grad_norm <= 0: no clipping, no norm pass, `ws` and norm_out are not touched (ws may be NULL).
+ * ws: coattn_adam_workspace_bytes(t, n_tensors) bytes (0 = bad list, see coattn_last_error), 8-byte aligned, contents need no
+ * initialisation; t is a HOST array, read before the call returns.
+ * Argument errors (n_tensors <= 0, a NULL pointer in an entry, n < 0, step < 1, a beta outside [0, 1), a clipped call whose
+ * workspace is too small): -1 before anything is launched. */
+typedef struct coattn_adam_tensor {
+  void* p; const void* g; void* m; void* v; int64_t n;
+} coattn_adam_tensor;
+size_t coattn_adam_workspace_bytes(const coattn_adam_tensor* t, int n_tensors);
+int coattn_adam_step(const coattn_adam_tensor* t, int n_tensors, int step, double lr, double beta1, double beta2,
+                     double eps, double weight_decay, double max_grad_norm, void* norm_out, void* ws, size_t ws_bytes,
+                     void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

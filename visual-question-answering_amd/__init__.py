@@ -12,7 +12,8 @@ from .coattention import ParallelCoAttention, coattention, native_features  # no
 from .alternating import AlternatingCoAttention  # noqa: F401
 from .loss import CrossEntropyLoss, SoftTargetLoss, cross_entropy, soft_target_loss, vqa_score  # noqa: F401
 from .head import answer_head  # noqa: F401
+from .optim import HipAdam  # noqa: F401
 
 __all__ = ["ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
-           "SoftTargetLoss", "vqa_score", "_lib",
+           "SoftTargetLoss", "vqa_score", "HipAdam", "_lib",
            "check_range", "RangeError"]

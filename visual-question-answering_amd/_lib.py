@@ -23,7 +23,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_forward_len", "coattn_infer_len", "coattn_attention_forward_len", "coattn_backward_len",
            "coattn_forward_maps", "coattn_forward_maps_len", "coattn_backward_maps", "coattn_backward_maps_len",
            "coattn_alt_workspace_bytes", "coattn_alt_forward", "coattn_alt_backward",
-           "coattn_soft_loss_forward", "coattn_vqa_score", "coattn_head_forward_soft")
+           "coattn_soft_loss_forward", "coattn_vqa_score", "coattn_head_forward_soft",
+           "coattn_adam_workspace_bytes", "coattn_adam_step")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -88,6 +89,11 @@ class HeadParams(C.Structure):
 
 class HeadParamGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dW_w", "db_w", "dW_p", "db_p", "dW_s", "db_s", "dW_h", "db_h")]
+
+
+class AdamTensor(C.Structure):
+    # one entry of the optimiser step's list (v0.13.0): parameter, gradient, exp_avg, exp_avg_sq, elements
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
 
 
 class GemmDesc(C.Structure):
@@ -207,6 +213,12 @@ def load() -> C.CDLL:
     lib.coattn_head_forward_soft.argtypes = ([C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(HeadParams)]
                                              + [C.c_void_p] * 2 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 6
                                              + [C.c_void_p])
+    # the optimiser step (v0.13.0): (list, n_tensors, step, lr, beta1, beta2, eps, weight_decay, max_grad_norm, norm_out, ws,
+    # ws_bytes, stream)
+    lib.coattn_adam_workspace_bytes.argtypes = [C.POINTER(AdamTensor), C.c_int]
+    lib.coattn_adam_workspace_bytes.restype = C.c_size_t
+    lib.coattn_adam_step.argtypes = ([C.POINTER(AdamTensor), C.c_int, C.c_int] + [C.c_double] * 6
+                                     + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
     _lib = lib
     return lib
 

@@ -252,6 +252,23 @@ def check_loss(loss: str, num_answers: int = 10) -> None:
         raise ValueError("--num_answers must be in 1..16, got %r" % (num_answers,))
 
 
+OPTIMIZERS = ("torch", "hip")
+
+
+def check_optimizer(optimizer: str, weight_decay: float = 0.0, clip_grad_norm=None) -> None:
+    """--optimizer: "torch" (the default: the reference's torch.optim.Adam, main.py:180, untouched) or "hip" (optim.HipAdam: the
+    fused HIP step).  --weight_decay (decoupled, AdamW) and --clip_grad_norm (global norm) exist on the HIP step only: the stock
+    path stays what it is and does not grow a second implementation."""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError("--optimizer must be one of %s, got %r" % (OPTIMIZERS, optimizer))
+    if weight_decay < 0:
+        raise ValueError("--weight_decay must be non-negative, got %r" % (weight_decay,))
+    if clip_grad_norm is not None and not clip_grad_norm > 0:
+        raise ValueError("--clip_grad_norm must be positive, got %r" % (clip_grad_norm,))
+    if optimizer == "torch" and (weight_decay != 0 or clip_grad_norm is not None):
+        raise ValueError("--weight_decay / --clip_grad_norm need --optimizer hip (the stock Adam path takes neither)")
+
+
 def synthetic_answers(labels: torch.Tensor, num_answers: int, num_classes: int, seed: int):
     """Soft answer targets for `labels` (shape [...]): answers int32 [..., A] and answer_scores fp32 [..., A].  Slot 0 is
     (label, 1.0); every further slot is empty (-1) with probability 1/3, else a class U{0..num_classes-1} with a score from
@@ -392,6 +409,11 @@ class DevicePrefetcher:
 class Trainer:
     """Owns model, Adam (lr, PyTorch defaults: main.py:180), loss and the gradient reducer.
 
+    optimizer="torch" (default) is exactly ``torch.optim.Adam(model.parameters(), lr)``; optimizer="hip" is ``optim.HipAdam``
+    -- the same arithmetic in one HIP launch on the step's stream -- and is what `weight_decay` (decoupled, AdamW) and
+    `clip_grad_norm` (by the global norm of the averaged gradients: it runs behind the reducer; the norm of the last step stays
+    on the device as ``trainer.optimizer.grad_norm``) need.
+
     Encoder run-ahead: when the image encoder is frozen (the reference default, main.py:67 /
     model.py:239-241) its output does not depend on the optimiser state, so ``step(...,
     next_image=...)`` launches the stock encoder for the NEXT batch on a second, high-priority HIP
@@ -403,8 +425,10 @@ class Trainer:
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, device=None, opt_lvl: int = 0,
                  bucket_mb: float = 16.0, encoder_runahead: bool = True, graph: bool = False, static_hot_path: bool = True,
-                 precision: str = "exact", loss: str = "ce"):
+                 precision: str = "exact", loss: str = "ce", optimizer: str = "torch", weight_decay: float = 0.0,
+                 clip_grad_norm=None):
         check_loss(loss)
+        check_optimizer(optimizer, weight_decay, clip_grad_norm)
         self.loss = loss                                         # "ce": int64 labels; "soft_ce" | "bce": step(..., targets=...)
         self.device = device or next(model.parameters()).device
         self.model = model
@@ -419,7 +443,13 @@ class Trainer:
         self.set_precision(precision)
         self.criterion = CrossEntropyLoss()      # nn.CrossEntropyLoss() semantics (main.py:94); fused HIP kernel on CUDA
         self.soft_criterion = SoftTargetLoss(loss) if loss != "ce" else None
-        self.optimizer = torch.optim.Adam(model.parameters(), lr)
+        if optimizer == "hip":
+            if self.device.type != "cuda":
+                raise ValueError("Trainer(optimizer='hip') needs a model on the GPU (HipAdam has no CPU fallback)")
+            from .optim import HipAdam
+            self.optimizer = HipAdam(model.parameters(), lr, weight_decay=weight_decay, max_grad_norm=clip_grad_norm)
+        else:
+            self.optimizer = torch.optim.Adam(model.parameters(), lr)
         self.opt_lvl = opt_lvl
         set_reduced_precision(model, opt_lvl)                    # AMP: projections on the bf16 MFMA as well
         # graph=True: co-attention + answer head + loss, forward and backward, replayed from one captured HIP graph
@@ -694,12 +724,19 @@ def build_parser():
                          "per sample; validation then reports the VQA score).  The checkpoint does not record it: give "
                          "prediction the value the checkpoint was trained with (with 'bce' its probabilities are sigmoids)")
     ap.add_argument("--num_answers", type=int, default=10, help="answer slots per sample of the soft targets (1..16)")
+    ap.add_argument("--optimizer", default="torch", choices=list(OPTIMIZERS),
+                    help="'torch' = torch.optim.Adam as the reference (main.py:180); 'hip' = the fused HIP Adam step (one launch "
+                         "for all parameters; same arithmetic), which also takes --weight_decay and --clip_grad_norm")
+    ap.add_argument("--weight_decay", type=float, default=0.0, help="decoupled weight decay (AdamW); --optimizer hip only")
+    ap.add_argument("--clip_grad_norm", type=float, default=None,
+                    help="clip the gradients to this global norm ahead of the update; --optimizer hip only")
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_loss(args.loss, args.num_answers)
+    check_optimizer(args.optimizer, args.weight_decay, args.clip_grad_norm)
     if args.mode == "test":
         raise NotImplementedError("TODO: test mode")          # as the reference, main.py:286-287
     if not args.synthetic:
@@ -727,7 +764,8 @@ def main(argv=None):
     cl = args.channels_last and device.type == "cuda" and args.model.startswith("attention")
     if cl:
         model.image_encoder.to(memory_format=torch.channels_last)
-    trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss)
+    trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss,
+                      optimizer=args.optimizer, weight_decay=args.weight_decay, clip_grad_norm=args.clip_grad_norm)
     n_ans = args.num_answers if args.loss != "ce" else 0
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
