@@ -63,7 +63,9 @@ __global__ __launch_bounds__(256) void phrase_pack_w_kernel(const float* __restr
   Wcat[idx] = v;
 }
 
-// out[bt][e] = tanh(max_j Z[bt][3e+j]); idx[bt][e] = argmax (first of equals, like MaxPool2d)
+// out[bt][e] = tanh(max_j Z[bt][3e+j]); idx[bt][e] = argmax (first of equals, like MaxPool2d; a NaN channel is taken
+// -- the last one of several -- so that max(finite, NaN) = NaN as MaxPool2d's: a group may straddle two n-grams, a finite
+// first channel then sits beside NaN ones.  Finite groups: the same bits as a plain `>` chain.)
 __global__ __launch_bounds__(256) void phrase_pool_kernel(const float* __restrict__ Z, float* __restrict__ out,
                                                           unsigned char* __restrict__ amax, long n) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -71,8 +73,8 @@ __global__ __launch_bounds__(256) void phrase_pool_kernel(const float* __restric
   const float a = Z[3 * idx], b = Z[3 * idx + 1], c = Z[3 * idx + 2];
   int k = 0;
   float m = a;
-  if (b > m) { m = b; k = 1; }
-  if (c > m) { m = c; k = 2; }
+  if (b > m || b != b) { m = b; k = 1; }
+  if (c > m || c != c) { m = c; k = 2; }
   out[idx] = tanhf(m);
   if (amax) amax[idx] = (unsigned char)k;
 }
