@@ -442,12 +442,15 @@ int coattn_ce_status(const void* ws, int B, void* stream);
  *     logits = W_h h_s + b_h;  loss = mean cross entropy.
  * coattn_head_backward replaces their autograd graph (main.py:219-220).  The adds, the concatenations, bias + tanh and
  * tanh' are folded into the operand addressing / epilogues of 32 x 32-tile products on the exact-fp32 MFMA (head.hip):
- * 4 launches + 2 for the loss forward, 4 launches backward.
+ * 4 launches + ONE for the loss (rows and their mean: the last workgroup's ticket, ce.hip) forward, 4 launches backward.
  *   v, q   : host arrays of 3 device pointers [B,d] each (word, phrase, sentence: the rows of co-attention's v_out /
  *            q_out, or any three tensors);  W_w [d,d], W_p [d,2d], W_s [mlp,2d], W_h [K,mlp] as nn.Linear stores them.
  *   labels : int64 [B] or NULL (then loss must be NULL too: logits only, e.g. validation's argmax).
  *   logits : [B,K] (written);  loss: [1] (written).  A label outside [0,K) makes the loss NaN and sets the status
  *            word coattn_head_status(saved, ...) reports (-2; it synchronises the stream, like coattn_ce_status).
+ *            Every forward WITH a loss clears the word first, so `saved` may be reused call after call without a memset;
+ *            a logits-only forward (labels NULL) leaves it alone: coattn_head_status then still reports the last
+ *            forward on this `saved` that had a loss.
  *   saved  : forward -> backward state (h_w, h_p, h_s, d loss / d logits, row losses): coattn_head_workspace_bytes.
  * Backward: g_loss [1] (device) scales the saved d loss / d logits; g_logits [B,K] (may be NULL) is added to it -- the two
  * upstream gradients autograd can hand over; at least one must be given.  dv, dq: host arrays of 3 device pointers [B,d]
