@@ -74,13 +74,8 @@ extern "C" int coattn_profile_end(float* us, char* names, int names_bytes, int m
 extern "C" const char* coattn_last_error(void) { return g_err; }
 
 // ---------------------------------------------------------------------------------------
-// buffer plans (in floats, every region aligned to 64 floats = 256 B)
+// buffer plans (in floats, every region aligned to 64 floats = 256 B: fused.h fal64)
 // ---------------------------------------------------------------------------------------
-static inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
-
-typedef SavedOff SavedPlan;
-static SavedPlan plan_saved(int B, int N, int T, int d, int L) { return saved_off(B, N, T, d, L); }
-
 static const int kMaxSplits = 32;
 
 struct BwdPlan {
@@ -89,38 +84,38 @@ struct BwdPlan {
 static BwdPlan plan_bwd(int B, int N, int T, int d, int L) {
   BwdPlan p;
   size_t o = 0;
-  p.Hv = o;  o += al64((size_t)B * N * d);
-  p.dPv = o; o += al64((size_t)B * N * d);
-  p.dZq = o; o += al64((size_t)B * T * d);
-  p.dPq = o; o += al64((size_t)L * B * T * d);
-  p.dC = o;  o += al64((size_t)L * B * T * N);
-  p.dav = o; o += al64((size_t)L * B * N);
-  p.dsv = o; o += al64((size_t)L * B * N);
-  p.daq = o; o += al64((size_t)L * B * T);
-  p.dsq = o; o += al64((size_t)L * B * T);
+  p.Hv = o;  o += fal64((size_t)B * N * d);
+  p.dPv = o; o += fal64((size_t)B * N * d);
+  p.dZq = o; o += fal64((size_t)B * T * d);
+  p.dPq = o; o += fal64((size_t)L * B * T * d);
+  p.dC = o;  o += fal64((size_t)L * B * T * N);
+  p.dav = o; o += fal64((size_t)L * B * N);
+  p.dsv = o; o += fal64((size_t)L * B * N);
+  p.daq = o; o += fal64((size_t)L * B * T);
+  p.dsq = o; o += fal64((size_t)L * B * T);
   size_t part = (size_t)kMaxSplits * d * d;
   size_t cs = (size_t)260 * d;
-  p.part = o; o += al64(part > cs ? part : cs);
+  p.part = o; o += fal64(part > cs ? part : cs);
   p.total = o;
   return p;
 }
 
-// COATTN_FLAG_BILINEAR: behind the common layout of `saved` (at plan_saved(..).total) lie K = Q W_b^T + b_b of all levels
+// COATTN_FLAG_BILINEAR: behind the common layout of `saved` (at saved_off(..).total) lie K = Q W_b^T + b_b of all levels
 // [L][B][T][d] and the range words of W_b's FP16 image (tolerance mode); behind the backward's workspace its BilBwd buffers
 static bool bilinear(int flags) { return (flags & COATTN_FLAG_BILINEAR) != 0; }
 static size_t wchunks(int d) { return (size_t)((d + 31) / 32) * ((d + 15) / 16); }
 static size_t bil_floats(int B, int T, int d, int L, bool bil) {
-  return bil ? al64((size_t)L * B * T * d) + al64(wchunks(d)) : 0;
+  return bil ? fal64((size_t)L * B * T * d) + fal64(wchunks(d)) : 0;
 }
 static size_t saved_floats(int B, int N, int T, int d, int L, bool bil) {
-  return plan_saved(B, N, T, d, L).total + bil_floats(B, T, d, L, bil);
+  return saved_off(B, N, T, d, L).total + bil_floats(B, T, d, L, bil);
 }
 static size_t bil_bwd_floats(int B, int T, int d, int L) {
-  const size_t k = al64((size_t)L * B * T * d);
-  return 3 * k + al64((size_t)2 * d * d) + al64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1) + al64((size_t)L * B * d);
+  const size_t k = fal64((size_t)L * B * T * d);
+  return 3 * k + fal64((size_t)2 * d * d) + fal64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1) + fal64((size_t)L * B * d);
 }
 static size_t fwd_ws_floats(int B, int N, int T, int d, int L, bool bil = false) {
-  return saved_floats(B, N, T, d, L, bil) + al64((size_t)B * N * d);
+  return saved_floats(B, N, T, d, L, bil) + fal64((size_t)B * N * d);
 }
 static size_t bwd_ws_floats(int B, int N, int T, int d, int L, bool bil = false) {
   size_t bw = plan_bwd(B, N, T, d, L).total;
@@ -242,7 +237,6 @@ int read_status_words(const float* status, int n_words, hipStream_t s, float* am
                      "re-run with flags = 0 (exact)", what,
                      act ? "an activation (feature or stored projection) of magnitude > 65504" : "", act && wgt ? " and " : "",
                      wgt ? "a projection weight of magnitude > 255.87" : "");
-    if (amax) { /* magnitudes are in amax */ }
     return -4;
   }
   return 0;
@@ -273,7 +267,7 @@ int fold_status_words(const float* status, int n_words, float* acc, hipStream_t 
 extern "C" int coattn_status_accumulate(const void* saved, int B, int N, int T, int d, int L, int dtype, void* acc, void* stream) {
   CA_TRY(check_shape(B, N, T, d, L, dtype));
   CA_CHECK_ARG(saved != nullptr, "status_accumulate: null `saved`");
-  const SavedPlan sp = plan_saved(B, N, T, d, L);
+  const SavedOff sp = saved_off(B, N, T, d, L);
   return fold_status_words((const float*)saved + sp.status, (int)status_floats(d, d, 2), (float*)acc, (hipStream_t)stream,
                            "coattn_status_accumulate");
 }
@@ -281,7 +275,7 @@ extern "C" int coattn_status_accumulate(const void* saved, int B, int N, int T, 
 extern "C" int coattn_status(const void* saved, int B, int N, int T, int d, int L, int dtype, void* stream, float* amax) {
   CA_TRY(check_shape(B, N, T, d, L, dtype));
   CA_CHECK_ARG(saved != nullptr, "status: null `saved`");
-  const SavedPlan sp = plan_saved(B, N, T, d, L);
+  const SavedOff sp = saved_off(B, N, T, d, L);
   return read_status_words((const float*)saved + sp.status, (int)status_floats(d, d, 2), (hipStream_t)stream, amax, "coattn_status");
 }
 
@@ -294,27 +288,73 @@ int bf_tn_rounds() {
   return r < 1 ? 1 : r;
 }
 
-namespace {
-
-struct Ctx {
-  int B, N, T, d, L;
-  hipStream_t s;
-  VLayout vl;                 // element strides of x_img[B,N,d]
-  bool bf16_proj = false;     // COATTN_FLAG_BF16_PROJ: the projections and their gradients on the bf16 MFMA
-  int np_pq = 3;              // width of the P_q projection in the fp32 mode (3 | 2)
-  bool f16_proj = false;      // fp32 mode: both projections on two FP16 pieces (fused.h kF16WScale)
-  float pscale = 1.f;         // factor on P_v, P_q as stored (fused path: kPScale, fused.h)
-  const int* qlen = nullptr;  // [B] question lengths (the *_len entry points), NULL: unmasked
-  // COATTN_FLAG_BILINEAR (NULL W_b: the reference's affinity): W_b, b_b and K = Q W_b^T + b_b of all levels [L][B][T][d]
-  const float* Wb = nullptr;
-  const float* bb = nullptr;
-  float* K = nullptr;
-  float* dK = nullptr;        // (backward) dK = dA V of all levels, in the workspace
-};
-
-int launch_proj(const Ctx& c, const coattn_gemm_desc& g) {
-  return c.bf16_proj ? launch_gemm_bf16in(g, c.s) : launch_gemm_f32(g, c.s);
+// ---------------------------------------------------------------------------------------
+// gradient jobs on the general GEMM (fused.h), shared by backward_general and the fallback branches of fused_backward
+// ---------------------------------------------------------------------------------------
+int grad_dw_splitk(const float* dY, const float* X, int K, int d, float* part, float* dW, int accumulate, bool bf16, hipStream_t s,
+                   const float* const* Xl, int L, long dy_sl) {
+  const SplitK k = splitk_plan(K);
+  coattn_gemm_desc g = {};
+  g.A = dY; g.a_sm = 1; g.a_sk = d;
+  g.B = X; g.b_sk = d; g.b_sn = 1;
+  if (!X) {                                          // levels as the inner loop (B from the pointer table)
+    g.a_si = (int64_t)dy_sl; g.ptr_by_inner = 1; g.inner = L;
+    for (int l = 0; l < L; ++l) g.b_ptrs[l] = Xl[l];
+  }
+  g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
+  g.M = d; g.N = d; g.K = K; g.batch = k.S; g.ksplit = k.ks;
+  CA_TRY(launch_gemm_mode(g, bf16, s));
+  return launch_reduce_partials(part, dW, k.S, (int64_t)d * d, accumulate, s);
 }
+
+int grad_dw_sample_groups(const float* dPv, const float* V, const VLayout& vl, int B, int N, int d, float* part, float* dW,
+                          int accumulate, bool bf16, hipStream_t s) {
+  const int G = (B + 31) / 32;                       // inner index = sample, in <= 32 groups
+  const int S = (B + G - 1) / G;
+  coattn_gemm_desc g = {};
+  g.A = dPv; g.a_sm = 1; g.a_sk = d; g.a_si = (int64_t)N * d; g.a_sz = (int64_t)G * N * d;
+  g.B = V; g.b_sk = vl.sN; g.b_sn = vl.sD; g.b_si = vl.sB; g.b_sz = (int64_t)G * vl.sB;
+  g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
+  g.M = d; g.N = d; g.K = N; g.batch = S; g.inner = G; g.inner_total = B;
+  CA_TRY(launch_gemm_mode(g, bf16, s));
+  return launch_reduce_partials(part, dW, S, (int64_t)d * d, accumulate, s);
+}
+
+int grad_colsum(const float* w, const float* X, int R, int d, float* part, float* out, int accumulate, hipStream_t s) {
+  const int rpc = (R + 255) / 256 > 32 ? (R + 255) / 256 : 32;
+  int nch = 0;
+  CA_TRY(launch_colsum_partial(w, X, part, R, d, rpc, &nch, s));
+  return launch_reduce_partials(part, out, nch, d, accumulate, s);
+}
+
+int grad_dv_kt_da(const float* Kq, const float* dA, float* dV, const VLayout& dvl, int B, int N, int T, int d, hipStream_t s) {
+  coattn_gemm_desc g = {};
+  g.A = Kq; g.a_sz = (int64_t)T * d; g.a_sm = 1; g.a_sk = d;
+  g.B = dA; g.b_sz = (int64_t)T * N; g.b_sk = N; g.b_sn = 1;
+  g.Cin = dV; g.cin_sz = dvl.sB; g.cin_sm = dvl.sD; g.cin_sn = dvl.sN; g.beta = 1.f;
+  g.C = dV; g.c_sz = dvl.sB; g.c_sm = dvl.sD; g.c_sn = dvl.sN;
+  g.M = d; g.N = N; g.K = T; g.batch = B;
+  return launch_gemm_f32(g, s);
+}
+
+int grad_dv_wv(const void* Wv, const float* dPv, float* dV, const VLayout& dvl, int B, int N, int d, bool bf16, hipStream_t s) {
+  coattn_gemm_desc g = {};
+  g.A = Wv; g.a_sm = 1; g.a_sk = d; g.a_sz = 0;
+  g.B = dPv; g.b_sz = (int64_t)N * d; g.b_sk = 1; g.b_sn = d;
+  g.Cin = dV; g.cin_sz = dvl.sB; g.cin_sm = dvl.sD; g.cin_sn = dvl.sN; g.beta = 1.f;
+  g.C = dV; g.c_sz = dvl.sB; g.c_sm = dvl.sD; g.c_sn = dvl.sN;
+  g.M = d; g.N = N; g.K = d; g.batch = B;
+  return launch_gemm_mode(g, bf16, s);
+}
+
+int grad_bilinear_wb(const float* dK, const float* const* Q, int B, int T, int d, int L, float* part, float* dWb, float* dbb,
+                     int accumulate, hipStream_t s) {
+  for (int l = 0; l < L; ++l)
+    CA_TRY(grad_dw_splitk(dK + (size_t)l * B * T * d, Q[l], B * T, d, part, dWb, (accumulate || l > 0) ? 1 : 0, false, s));
+  return grad_colsum(nullptr, dK, L * B * T, d, part, dbb, accumulate, s);
+}
+
+namespace {
 
 // P_v = V W_v^T + b_v   (model.py:380/384, evaluated once per sample)
 int proj_v(const Ctx& c, const float* V, const float* Wv, const float* bv, float* Pv) {
@@ -325,17 +365,7 @@ int proj_v(const Ctx& c, const float* V, const float* Wv, const float* bv, float
   if (c.vl.sB != (int64_t)c.N * c.vl.sN) { g.a_mdiv = c.N; g.a_sdiv = c.vl.sB; }
   g.b_sk = 1; g.b_sn = c.d;
   g.c_sm = c.d; g.c_sn = 1;
-  return launch_proj(c, g);
-}
-// P_q = Q W_q^T + b_q   (model.py:381/383)
-int proj_q(const Ctx& c, const float* Q, const float* Wq, const float* bq, float* Pq) {
-  coattn_gemm_desc g = {};
-  g.A = Q; g.B = Wq; g.C = Pq; g.bias_n = bq;
-  g.M = c.B * c.T; g.N = c.d; g.K = c.d; g.batch = 1;
-  g.a_sm = c.d; g.a_sk = 1;
-  g.b_sk = 1; g.b_sn = c.d;
-  g.c_sm = c.d; g.c_sn = 1;
-  return launch_proj(c, g);
+  return launch_gemm_mode(g, c.bf16_proj, c.s);
 }
 // K_l = Q_l W_b^T + b_b of all levels in one launch (batch z = level, A from the pointer table; COATTN_FLAG_BILINEAR)
 int proj_k(const Ctx& c, const float* const* Q) {
@@ -378,28 +408,38 @@ int c_times(const Ctx& c, const float* C, const float* Y, const float* X, float*
   return launch_gemm_f32(g, c.s);
 }
 
+// out (+)= X W: X, out [B T][d], W [d][d]   (the projections backward: dQ_l += dP_q,l W_q, dK_l W_b)
+int add_rows_times_w(const Ctx& c, const float* X, const float* W, float* out, bool bf16 = false) {
+  coattn_gemm_desc g = {};
+  g.A = X; g.a_sm = c.d; g.a_sk = 1;
+  g.B = W; g.b_sk = c.d; g.b_sn = 1;
+  g.Cin = out; g.cin_sm = c.d; g.cin_sn = 1; g.beta = 1.f;
+  g.C = out; g.c_sm = c.d; g.c_sn = 1;
+  g.M = c.B * c.T; g.N = c.d; g.K = c.d; g.batch = 1;
+  return launch_gemm_mode(g, bf16, c.s);
+}
+
 // Width of the fp32 mode's contractions (fused.h, include/coattn.h "Widths of the fp32 mode").  flags = 0: every
 // contraction on the exact three-piece split.  COATTN_FLAG_FAST16: the forward-side contractions on two FP16 pieces, the
 // backward's on two bf16 pieces.  Developer switches (builds with -DCOATTN_DEV_SWITCHES only): COATTN_SPLIT=3 forces the exact
 // split, COATTN_FWD_F16=0 / COATTN_FWD_F16_KERNEL=0 / COATTN_SPLIT_FWD=3 / COATTN_SPLIT_PQ=3 the bf16 widths of round 4's A/B runs.
-static int env_int(const char* name, int dflt) { return dev_env_int(name, dflt); }
 static bool fast16(int flags) {
-  static const int split = env_int("COATTN_SPLIT", 2);
+  static const int split = dev_env_int("COATTN_SPLIT", 2);
   return (flags & COATTN_FLAG_FAST16) && !(flags & COATTN_FLAG_EXACT3) && split != 3;
 }
 static int np_bwd(int flags) { return fast16(flags) ? 2 : 3; }
 static int np_projq(int flags) {                    // P_q = Q W_q^T: its error reaches H_v summed over T <= 28 tokens only
-  static const int pq = env_int("COATTN_SPLIT_PQ", 2);
+  static const int pq = dev_env_int("COATTN_SPLIT_PQ", 2);
   return fast16(flags) ? (pq == 2 ? 2 : 3) : 3;
 }
 // The forward's projections P_v, P_q on two FP16 pieces (fused.h; tests/test_split_emulation.py: less error than the exact
 // split of P_v next to two bf16 pieces of P_q, at half the MFMAs of the former).
 static bool f16_fwd(int flags) {
-  static const int on = env_int("COATTN_FWD_F16", 1);
+  static const int on = dev_env_int("COATTN_FWD_F16", 1);
   return fast16(flags) && on != 0;
 }
 static int np_fwd(int flags, bool f16) {            // 4: both phases of the forward kernel on two FP16 pieces (coattn_fwd32.hip)
-  static const int fwd = env_int("COATTN_SPLIT_FWD", 2), hk = env_int("COATTN_FWD_F16_KERNEL", 1);
+  static const int fwd = dev_env_int("COATTN_SPLIT_FWD", 2), hk = dev_env_int("COATTN_FWD_F16_KERNEL", 1);
   if (!fast16(flags)) return 3;
   if (f16) return (hk != 0 && fwd == 2) ? 4 : (fwd == 2 ? 2 : 3);
   return f16_fwd(flags) ? 3 : (fwd == 2 ? 2 : 3);   // FP16 pieces wanted but not available for this shape: exact
@@ -413,16 +453,16 @@ static bool gemm_w_enabled() {
 
 // The two projection jobs of a forward call on the pre-split-weight kernel (gemm_w.hip): P_v from the image features in
 // either layout, P_q of all levels from the pointer table.  Returns through v_w / q_w which of them that kernel takes.
-void projection_jobs(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, float* sv, char* wimg,
-                     WGemm& wv, WGemm& wq, bool& v_w, bool& q_w, bool want_f16) {
-  const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
+void projection_jobs(const Ctx& c, float* sv, char* wimg, WGemm& wv, WGemm& wq, bool& v_w, bool& q_w, bool want_f16) {
+  const coattn_params* p = c.p;
+  const SavedOff sp = saved_off(c.B, c.N, c.T, c.d, c.L);
   const size_t BTd = (size_t)c.B * c.T * c.d;
   wv = WGemm{}; wq = WGemm{};
-  wv.A = V; wv.a_sm = (int)c.vl.sN; wv.Wf = wimg; wv.C = sv + sp.Pv; wv.c_sm = c.d;
-  wv.bias_n = p ? (const float*)p->b_v : nullptr; wv.out_scale = c.pscale; wv.M = c.B * c.N; wv.N = c.d; wv.K = c.d; wv.batch = 1;
-  for (int l = 0; l < c.L; ++l) wq.a_ptrs[l] = Q[l];
+  wv.A = c.V; wv.a_sm = (int)c.vl.sN; wv.Wf = wimg; wv.C = sv + sp.Pv; wv.c_sm = c.d;
+  wv.bias_n = (const float*)p->b_v; wv.out_scale = c.pscale; wv.M = c.B * c.N; wv.N = c.d; wv.K = c.d; wv.batch = 1;
+  for (int l = 0; l < c.L; ++l) wq.a_ptrs[l] = c.Q[l];
   wq.a_sm = c.d; wq.Wf = wimg + wsplit_bytes(c.d, c.d); wq.C = sv + sp.Pq; wq.c_sz = (long)BTd; wq.c_sm = c.d;
-  wq.bias_n = p ? (const float*)p->b_q : nullptr; wq.out_scale = c.pscale; wq.M = c.B * c.T; wq.N = c.d; wq.K = c.d; wq.batch = c.L;
+  wq.bias_n = (const float*)p->b_q; wq.out_scale = c.pscale; wq.M = c.B * c.T; wq.N = c.d; wq.K = c.d; wq.batch = c.L;
   wv.bf16 = wq.bf16 = c.bf16_proj ? 1 : 0;          // reduced precision: the same kernels, hi pieces only, one MFMA per product
   wv.np = 3; wq.np = c.np_pq;
   if (want_f16 && !c.bf16_proj) { wv.np = wq.np = 2; wv.f16 = wq.f16 = 1; }   // two FP16 pieces (any M runs on gemm_w then)
@@ -439,45 +479,45 @@ void projection_jobs(const Ctx& c, const float* V, const float* const* Q, const 
 // Tolerance mode: FP16 pieces are used only when BOTH projections run on the pre-split-weight kernel -- it is that launch
 // which range-checks the image and question features and the stored projections for the fused kernel behind it
 // (coattn_status); any other shape computes exactly.
-bool f16_path(const Ctx& c, const float* V, const float* const* Q, int flags, int fused) {
+bool f16_path(const Ctx& c, int flags, int fused) {
   if (!fused || c.bf16_proj || !f16_fwd(flags)) return false;
   WGemm wv, wq;
   bool v_w, q_w;
-  projection_jobs(c, V, Q, nullptr, nullptr, nullptr, wv, wq, v_w, q_w, true);
+  projection_jobs(c, nullptr, nullptr, wv, wq, v_w, q_w, true);
   return v_w && q_w;
 }
 
 // Does the forward write the bitmap of the live question rows (and run P_q over them alone)?  A function of the call's shapes,
 // pointers and mode.  The backward asks it of its own arguments (rowbits_in_saved) to learn whether it MAY use a bitmap; whether
 // there is one it learns from the tag the forward left beside it (fused.h kRowTag).
-static bool rowbits_predicate(const Ctx& c, const WGemm& wq, const coattn_params* p, const float* sv, bool f16) {
+static bool rowbits_predicate(const Ctx& c, const WGemm& wq, const float* sv, bool f16) {
+  const coattn_params* p = c.p;
   static const int rows_env = dev_env_int("COATTN_SKIP_ZERO_ROWS", 1);   // developer switch
-  const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
+  const SavedOff sp = saved_off(c.B, c.N, c.T, c.d, c.L);
   return rows_env && !f16 && !c.bf16_proj && gemm_wx_kernel(wq) == 0 && wq.a_sk == 0 && p->b_q &&
          (wq.M + 31) / 32 <= kRowBitsMaxWords && c.d % 256 == 0 && c.d <= 1024 &&
          ((((uintptr_t)p->b_q) | ((uintptr_t)(sv + sp.Pq))) & 15) == 0;      // (16-byte accesses of the flag job)
 }
-bool rowbits_in_saved(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, const float* sv, int flags, int fused) {
+bool rowbits_in_saved(const Ctx& c) {              // (the backward's Ctx: call_ctx answered f16_path for the same call)
   WGemm wv, wq;
   bool v_w, q_w;
-  Ctx cc = c;
-  cc.f16_proj = f16_path(c, V, Q, flags, fused);
-  const bool f16 = cc.f16_proj && !cc.bf16_proj;
-  projection_jobs(cc, V, Q, p, const_cast<float*>(sv), nullptr, wv, wq, v_w, q_w, f16);
-  return q_w && rowbits_predicate(cc, wq, p, sv, f16);
+  const bool f16 = c.f16_proj && !c.bf16_proj;
+  projection_jobs(c, const_cast<float*>(c.saved), nullptr, wv, wq, v_w, q_w, f16);
+  return q_w && rowbits_predicate(c, wq, c.saved, f16);
 }
 
 // wimg: room for two pre-split weight images (wsplit_bytes(d, d) each) at the end of the forward workspace
-// keep_wqT: also split W_q the other way round into the saved state (sp.wqT) for the backward's dQ projection
-int general_projections(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, float* sv, char* wimg,
-                        bool keep_wqT) {
-  const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
+// c.keep: also split W_q the other way round into the saved state (sp.wqT) for the backward's dQ projection
+int general_projections(const Ctx& c, char* wimg) {
+  const coattn_params* p = c.p;
+  float* sv = c.state;
+  const SavedOff sp = saved_off(c.B, c.N, c.T, c.d, c.L);
   const size_t BTd = (size_t)c.B * c.T * c.d;
   // fp32 projections of row-major activations: the weight is split once, the GEMM reads it as MFMA fragments
   WGemm wv, wq;
   bool v_w, q_w;
   const bool f16 = c.f16_proj && !c.bf16_proj;        // (forward_impl: only when both projections run on gemm_w)
-  projection_jobs(c, V, Q, p, sv, wimg, wv, wq, v_w, q_w, f16);
+  projection_jobs(c, sv, wimg, wv, wq, v_w, q_w, f16);
   float* status = sv + sp.status;
   if (f16) wv.status = wq.status = status;            // both on two FP16 pieces, range-checked
   RowFlagJob rj = {};
@@ -485,7 +525,7 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
   // the image of W_q^T for the backward's dQ projection: whenever that job runs on the pre-split-weight kernels -- a question of
   // the shape and the mode alone, the backward asks the same one (fused.h dq_proj_job), whatever the alignment of Q here
   const WGemm wdq = dq_proj_job(c.B, c.T, c.d, c.L, c.bf16_proj ? 1 : 0, 3);
-  const bool wqT = keep_wqT && gemm_w_enabled() && gemm_w_supported(wdq);
+  const bool wqT = c.keep && gemm_w_enabled() && gemm_w_supported(wdq);
   unsigned* row_tag = reinterpret_cast<unsigned*>(sv + sp.rowcnt) + kRowTagWord;
   if (v_w || q_w || wqT) {
     WSplit jobs[3];
@@ -500,10 +540,10 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
     // workgroups flag the rows of Q_l that hold anything, write (0 + b_q) * scale into the others' rows of P_q, and the exact
     // four-wave GEMM runs over the flagged rows only (same values bit for bit; 44 % fewer rows on BASELINE's synthetic
     // questions, lengths U{3..26} of 26).  Row-major A on gemm_w_kernel only: the other kernels compute every row.
-    const bool skip_rows = q_w && rowbits_predicate(c, wq, p, sv, f16);
+    const bool skip_rows = q_w && rowbits_predicate(c, wq, sv, f16);
     if (skip_rows) {
       unsigned* bits = reinterpret_cast<unsigned*>(sv + sp.rowbits);        // (kept in `saved`: the backward's dW_q reads it)
-      for (int l = 0; l < c.L; ++l) rj.a_ptrs[l] = Q[l];
+      for (int l = 0; l < c.L; ++l) rj.a_ptrs[l] = c.Q[l];
       rj.a_sm = c.d; rj.C = sv + sp.Pq; rj.c_sz = (long)BTd; rj.c_sm = c.d;
       rj.bias_n = (const float*)p->b_q; rj.out_scale = c.pscale; rj.M = c.B * c.T; rj.N = c.d; rj.K = c.d; rj.batch = c.L;
       rj.rowbits = bits;
@@ -532,34 +572,35 @@ int general_projections(const Ctx& c, const float* V, const float* const* Q, con
     return 0;
   }
   if (v_w) CA_TRY(launch_gemm_wx(&wv, 1, c.s));
-  else CA_TRY(proj_v(c, V, (const float*)p->W_v, (const float*)p->b_v, sv + sp.Pv));
+  else CA_TRY(proj_v(c, c.V, (const float*)p->W_v, (const float*)p->b_v, sv + sp.Pv));
   if (q_w) return launch_gemm_wx(&wq, 1, c.s, rows_in_gemm ? &rj : nullptr);
   // P_q of all levels in one launch: batch z = level, A from the pointer table
   coattn_gemm_desc g = {};
-  for (int l = 0; l < c.L; ++l) g.a_ptrs[l] = Q[l];
+  for (int l = 0; l < c.L; ++l) g.a_ptrs[l] = c.Q[l];
   g.B = p->W_q; g.C = sv + sp.Pq; g.c_sz = (int64_t)BTd; g.bias_n = p->b_q; g.out_scale = c.pscale;
   g.M = c.B * c.T; g.N = c.d; g.K = c.d; g.batch = c.L;
   g.a_sm = c.d; g.a_sk = 1;
   g.b_sk = 1; g.b_sn = c.d;
   g.c_sm = c.d; g.c_sn = 1;
-  return launch_proj(c, g);
+  return launch_gemm_mode(g, c.bf16_proj, c.s);
 }
 
 // COATTN_FLAG_BILINEAR: K = Q W_b^T + b_b of all levels.  On the pre-split-weight kernels whenever P_q runs there -- the same
 // kernel, width and FP16-piece mode as P_q (the tolerance mode range-checks the stored K: it is phase 1's FP16-piece operand), W_b
 // split by a launch of its own into the third image of the forward workspace, whose |256 W| words are folded into W_q's (the
 // range report covers both weights) -- else on the general GEMM.  Dense: pad rows take b_b, not the P_q bitmap's bias path.
-int bilinear_projection(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, float* sv, char* wimg_b) {
-  const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
+int bilinear_projection(const Ctx& c, char* wimg_b) {
+  float* sv = c.state;
+  const SavedOff sp = saved_off(c.B, c.N, c.T, c.d, c.L);
   WGemm wv, wq;
   bool v_w, q_w;
   const bool f16 = c.f16_proj && !c.bf16_proj;
-  projection_jobs(c, V, Q, p, sv, nullptr, wv, wq, v_w, q_w, f16);
-  if (!q_w) return proj_k(c, Q);
+  projection_jobs(c, sv, nullptr, wv, wq, v_w, q_w, f16);
+  if (!q_w) return proj_k(c, c.Q);
   WGemm wk = wq;
   wk.Wf = wimg_b; wk.C = c.K; wk.bias_n = c.bb; wk.out_scale = 1.f; wk.rowbits = nullptr;
   float* status = sv + sp.status;
-  float* wb_words = c.K + al64((size_t)c.L * c.B * c.T * c.d);
+  float* wb_words = c.K + fal64((size_t)c.L * c.B * c.T * c.d);
   wk.status = f16 ? status : nullptr;
   const WSplit job{c.Wb, wimg_b, c.d, c.d, 0, c.d, wimg_pieces(wk), f16 ? wb_words : nullptr};
   CA_TRY(launch_wsplit(&job, 1, c.s));
@@ -570,81 +611,74 @@ int bilinear_projection(const Ctx& c, const float* V, const float* const* Q, con
 }
 
 // everything after the projections: affinity, H_v / H_q, scores, softmax, attended reductions
-// av_out / aq_out: the caller's map buffers [L][B][N] / [L][B][T] (coattn_infer), else NULL: the maps go to `sv`;
-// dual (coattn_forward_maps): the maps go to `sv` AND to av_out / aq_out, from the same softmax launches
-int general_attention(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, float* v_out,
-                      float* q_out, float* sv, float* Hv, float* av_out = nullptr, float* aq_out = nullptr, bool dual = false) {
-  const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
+int general_attention(const Ctx& c) {
+  const SavedOff sp = saved_off(c.B, c.N, c.T, c.d, c.L);
+  const coattn_params* p = c.p;
+  float* sv = c.state;
   float* Pv = sv + sp.Pv;
+  float* Hv = c.tail;
   const size_t BTd = (size_t)c.B * c.T * c.d, BTN = (size_t)c.B * c.T * c.N;
   for (int l = 0; l < c.L; ++l) {
     float* Pq = sv + sp.Pq + l * BTd;
     float* C = sv + sp.C + l * BTN;
     float* Hq = sv + sp.Hq + l * BTd;
-    float* av = (av_out && !dual ? av_out : sv + sp.av) + (size_t)l * c.B * c.N;
-    float* aq = (aq_out && !dual ? aq_out : sv + sp.aq) + (size_t)l * c.B * c.T;
-    float* av2 = dual ? av_out + (size_t)l * c.B * c.N : nullptr;
-    float* aq2 = dual ? aq_out + (size_t)l * c.B * c.T : nullptr;
-    CA_TRY(affinity(c, c.K ? c.K + l * BTd : Q[l], V, C));   // (bilinear: A = K V^T; q below stays a_q^T Q)
+    const size_t lBN = (size_t)l * c.B * c.N, lBT = (size_t)l * c.B * c.T;
+    const MapDst av = map_dst(c, sv + sp.av + lBN, c.av_out ? c.av_out + lBN : nullptr);
+    const MapDst aq = map_dst(c, sv + sp.aq + lBT, c.aq_out ? c.aq_out + lBT : nullptr);
+    CA_TRY(affinity(c, c.K ? c.K + l * BTd : c.Q[l], c.V, C));   // (bilinear: A = K V^T; q below stays a_q^T Q)
     if (c.qlen) CA_TRY(launch_mask_rows(C, c.qlen, c.B, c.T, c.N, c.s));   // length mask: C rows t >= len_b are zero
     CA_TRY(ct_times(c, C, Pq, Pv, Hv, 1));
     CA_TRY(c_times(c, C, Pv, Pq, Hq, 1));
-    CA_TRY(launch_score_softmax(Hv, (const float*)p->w_v, (const float*)p->c_v, av, c.B, c.N, c.d, c.s, nullptr, av2));
-    CA_TRY(launch_score_softmax(Hq, (const float*)p->w_q, (const float*)p->c_q, aq, c.B, c.T, c.d, c.s, c.qlen, aq2));
+    CA_TRY(launch_score_softmax(Hv, (const float*)p->w_v, (const float*)p->c_v, av.to, c.B, c.N, c.d, c.s, nullptr, av.copy));
+    CA_TRY(launch_score_softmax(Hq, (const float*)p->w_q, (const float*)p->c_q, aq.to, c.B, c.T, c.d, c.s, c.qlen, aq.copy));
     // v = sum_n a_v[n] V[:,n]   (model.py:391);  q = sum_t a_q[t] Q[t,:]   (model.py:392)
-    CA_TRY(launch_gemv(V, av, v_out + (size_t)l * c.B * c.d, c.B, c.d, c.N, c.vl.sB, c.vl.sD, c.vl.sN, c.N, c.d, c.s));
-    CA_TRY(launch_gemv(Q[l], aq, q_out + (size_t)l * c.B * c.d, c.B, c.d, c.T, (int64_t)c.T * c.d, 1, c.d, c.T, c.d, c.s));
+    CA_TRY(launch_gemv(c.V, av.to, c.v_out + (size_t)l * c.B * c.d, c.B, c.d, c.N, c.vl.sB, c.vl.sD, c.vl.sN, c.N, c.d, c.s));
+    CA_TRY(launch_gemv(c.Q[l], aq.to, c.q_out + (size_t)l * c.B * c.d, c.B, c.d, c.T, (int64_t)c.T * c.d, 1, c.d, c.T, c.d, c.s));
   }
   return 0;
 }
 
-int backward_general(const Ctx& c, const float* V, const float* const* Q, const coattn_params* p, const float* sv,
-                     const float* gv, const float* gq, float* dV, const VLayout& dvl, float* const* dQ,
-                     const coattn_param_grads* pg, int accumulate, float* ws, const float* g_av = nullptr,
-                     const float* g_aq = nullptr) {
-  const SavedPlan sp = plan_saved(c.B, c.N, c.T, c.d, c.L);
+int backward_general(const Ctx& c) {
+  const SavedOff sp = saved_off(c.B, c.N, c.T, c.d, c.L);
   const BwdPlan bp = plan_bwd(c.B, c.N, c.T, c.d, c.L);
-  const int B = c.B, N = c.N, T = c.T, d = c.d, L = c.L;
+  const int B = c.B, N = c.N, T = c.T, d = c.d, L = c.L, accumulate = c.accumulate;
   const size_t BTd = (size_t)B * T * d, BTN = (size_t)B * T * N, BNd = (size_t)B * N * d, Bd = (size_t)B * d;
-  const float* Pv = sv + sp.Pv;
-  const float* wv = (const float*)p->w_v;
-  const float* wq = (const float*)p->w_q;
-  float* Hv = ws + bp.Hv;
-  float* dPv = ws + bp.dPv;
-  float* dZq = ws + bp.dZq;
-  float* dC = ws + bp.dC;
-  float* dav = ws + bp.dav;
-  float* dsv = ws + bp.dsv;
-  float* daq = ws + bp.daq;
-  float* dsq = ws + bp.dsq;
-  float* part = ws + bp.part;
-  int nch = 0;
+  const float* Pv = c.saved + sp.Pv;
+  const float* wv = (const float*)c.p->w_v;
+  const float* wq = (const float*)c.p->w_q;
+  float* Hv = c.ws + bp.Hv;
+  float* dPv = c.ws + bp.dPv;
+  float* dZq = c.ws + bp.dZq;
+  float* dC = c.ws + bp.dC;
+  float* dav = c.ws + bp.dav;
+  float* dsv = c.ws + bp.dsv;
+  float* daq = c.ws + bp.daq;
+  float* dsq = c.ws + bp.dsq;
+  float* part = c.ws + bp.part;
   for (int l = 0; l < L; ++l) {
-    const float* Pq = sv + sp.Pq + l * BTd;
-    const float* C = sv + sp.C + l * BTN;
-    const float* Hq = sv + sp.Hq + l * BTd;
-    const float* av = sv + sp.av + (size_t)l * B * N;
-    const float* aq = sv + sp.aq + (size_t)l * B * T;
-    float* dPq = ws + bp.dPq + l * BTd;
+    const float* Pq = c.saved + sp.Pq + l * BTd;
+    const float* C = c.saved + sp.C + l * BTN;
+    const float* Hq = c.saved + sp.Hq + l * BTd;
+    const float* av = c.saved + sp.av + (size_t)l * B * N;
+    const float* aq = c.saved + sp.aq + (size_t)l * B * T;
+    const float* gv = c.gv + l * Bd;
+    const float* gq = c.gq + l * Bd;
+    float* dPq = c.ws + bp.dPq + l * BTd;
     const int acc_l = (accumulate || l > 0) ? 1 : 0;
     // recompute H_v = tanh(P_v + C^T P_q)
     CA_TRY(ct_times(c, C, Pq, Pv, Hv, 1));
     // softmax backward of a_v, a_q
-    CA_TRY(launch_gemv(V, gv + l * Bd, dav, B, N, d, c.vl.sB, c.vl.sN, c.vl.sD, d, N, c.s));
+    CA_TRY(launch_gemv(c.V, gv, dav, B, N, d, c.vl.sB, c.vl.sN, c.vl.sD, d, N, c.s));
     // (coattn_backward_maps: da + G, the map's own upstream gradient -- G_aq read as 0 past a question's length)
-    CA_TRY(launch_softmax_bwd(av, dav, dsv, B, N, c.s, g_av ? g_av + (size_t)l * B * N : nullptr));
-    CA_TRY(launch_gemv(Q[l], gq + l * Bd, daq, B, T, d, (int64_t)T * d, d, 1, d, T, c.s));
+    CA_TRY(launch_softmax_bwd(av, dav, dsv, B, N, c.s, c.g_av ? c.g_av + (size_t)l * B * N : nullptr));
+    CA_TRY(launch_gemv(c.Q[l], gq, daq, B, T, d, (int64_t)T * d, d, 1, d, T, c.s));
     if (c.qlen) CA_TRY(launch_mask_rows(daq, c.qlen, B, T, 1, c.s));   // (a_q = 0 there: ds_q = 0 whatever the pad rows hold)
-    CA_TRY(launch_softmax_bwd(aq, daq, dsq, B, T, c.s, g_aq ? g_aq + (size_t)l * B * T : nullptr, c.qlen));
+    CA_TRY(launch_softmax_bwd(aq, daq, dsq, B, T, c.s, c.g_aq ? c.g_aq + (size_t)l * B * T : nullptr, c.qlen));
     // dw_v += ds_v^T H_v ; dc_v += sum ds_v ; same for q
-    const int rpc_v = (B * N + 255) / 256 > 32 ? (B * N + 255) / 256 : 32;
-    CA_TRY(launch_colsum_partial(dsv, Hv, part, B * N, d, rpc_v, &nch, c.s));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->dw_v, nch, d, acc_l, c.s));
-    CA_TRY(launch_sum_all(dsv, (float*)pg->dc_v, (int64_t)B * N, acc_l, c.s));
-    const int rpc_q = (B * T + 255) / 256 > 32 ? (B * T + 255) / 256 : 32;
-    CA_TRY(launch_colsum_partial(dsq, Hq, part, B * T, d, rpc_q, &nch, c.s));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->dw_q, nch, d, acc_l, c.s));
-    CA_TRY(launch_sum_all(dsq, (float*)pg->dc_q, (int64_t)B * T, acc_l, c.s));
+    CA_TRY(grad_colsum(dsv, Hv, B * N, d, part, (float*)c.pg->dw_v, acc_l, c.s));
+    CA_TRY(launch_sum_all(dsv, (float*)c.pg->dc_v, (int64_t)B * N, acc_l, c.s));
+    CA_TRY(grad_colsum(dsq, Hq, B * T, d, part, (float*)c.pg->dw_q, acc_l, c.s));
+    CA_TRY(launch_sum_all(dsq, (float*)c.pg->dc_q, (int64_t)B * T, acc_l, c.s));
     // dZ_v (in place over H_v), dZ_q
     CA_TRY(launch_dz(dsv, wv, Hv, Hv, (int64_t)B * N, d, c.s));
     CA_TRY(launch_dz(dsq, wq, Hq, dZq, (int64_t)B * T, d, c.s));
@@ -667,115 +701,33 @@ int backward_general(const Ctx& c, const float* V, const float* const* Q, const 
     CA_TRY(ct_times(c, C, dZq, Hv, Hv, 0));
     CA_TRY(launch_add_inplace(dPv, Hv, (int64_t)BNd, l > 0 ? 1 : 0, c.s));
     // dQ_l = a_q (x) gq + dA V^T   (+ dP_q W_q below);  bilinear: dK_l = dA V^T, dQ_l = a_q (x) gq + dK_l W_b (+ dP_q W_q)
-    CA_TRY(launch_rank1(aq, gq + l * Bd, dQ[l], B, T, d, (int64_t)T * d, d, 1, 0, c.s));
+    CA_TRY(launch_rank1(aq, gq, c.dQ[l], B, T, d, (int64_t)T * d, d, 1, 0, c.s));
     float* dKl = c.K ? c.dK + l * BTd : nullptr;
     {
       coattn_gemm_desc g = {};
       g.A = dC; g.a_sz = (int64_t)T * N; g.a_sm = N; g.a_sk = 1;
-      g.B = V; g.b_sz = c.vl.sB; g.b_sk = c.vl.sN; g.b_sn = c.vl.sD;
-      if (!dKl) { g.Cin = dQ[l]; g.cin_sz = (int64_t)T * d; g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f; }
-      g.C = dKl ? dKl : dQ[l]; g.c_sz = (int64_t)T * d; g.c_sm = d; g.c_sn = 1;
+      g.B = c.V; g.b_sz = c.vl.sB; g.b_sk = c.vl.sN; g.b_sn = c.vl.sD;
+      if (!dKl) { g.Cin = c.dQ[l]; g.cin_sz = (int64_t)T * d; g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f; }
+      g.C = dKl ? dKl : c.dQ[l]; g.c_sz = (int64_t)T * d; g.c_sm = d; g.c_sn = 1;
       g.M = T; g.N = d; g.K = N; g.batch = B;
       CA_TRY(launch_gemm_f32(g, c.s));
     }
-    if (dKl) {
-      coattn_gemm_desc g = {};
-      g.A = dKl; g.a_sm = d; g.a_sk = 1;
-      g.B = c.Wb; g.b_sk = d; g.b_sn = 1;
-      g.Cin = dQ[l]; g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f;
-      g.C = dQ[l]; g.c_sm = d; g.c_sn = 1;
-      g.M = B * T; g.N = d; g.K = d; g.batch = 1;
-      CA_TRY(launch_gemm_f32(g, c.s));
-    }
+    if (dKl) CA_TRY(add_rows_times_w(c, dKl, c.Wb, c.dQ[l]));
     // dV (+)= a_v (x) gv + Q^T dA   (bilinear: K^T dA)
-    if (dV) CA_TRY(launch_rank1(av, gv + l * Bd, dV, B, N, d, dvl.sB, dvl.sN, dvl.sD, l > 0 ? 1 : 0, c.s));
-    if (dV) {
-      coattn_gemm_desc g = {};
-      g.A = c.K ? c.K + l * BTd : Q[l]; g.a_sz = (int64_t)T * d; g.a_sm = 1; g.a_sk = d;
-      g.B = dC; g.b_sz = (int64_t)T * N; g.b_sk = N; g.b_sn = 1;
-      g.Cin = dV; g.cin_sz = dvl.sB; g.cin_sm = dvl.sD; g.cin_sn = dvl.sN; g.beta = 1.f;
-      g.C = dV; g.c_sz = dvl.sB; g.c_sm = dvl.sD; g.c_sn = dvl.sN;
-      g.M = d; g.N = N; g.K = T; g.batch = B;
-      CA_TRY(launch_gemm_f32(g, c.s));
-    }
+    if (c.dV) CA_TRY(launch_rank1(av, gv, c.dV, B, N, d, c.dvl.sB, c.dvl.sN, c.dvl.sD, l > 0 ? 1 : 0, c.s));
+    if (c.dV) CA_TRY(grad_dv_kt_da(c.K ? c.K + l * BTd : c.Q[l], dC, c.dV, c.dvl, B, N, T, d, c.s));
   }
   // projections backward
-  for (int l = 0; l < L; ++l) {
-    const float* dPq = ws + bp.dPq + l * BTd;
-    coattn_gemm_desc g = {};
-    g.A = dPq; g.a_sm = d; g.a_sk = 1;
-    g.B = p->W_q; g.b_sk = d; g.b_sn = 1;
-    g.Cin = dQ[l]; g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f;
-    g.C = dQ[l]; g.c_sm = d; g.c_sn = 1;
-    g.M = B * T; g.N = d; g.K = d; g.batch = 1;
-    CA_TRY(c.bf16_proj ? launch_gemm_bf16in(g, c.s) : launch_gemm_f32(g, c.s));
-  }
-  if (dV) {
-    // dV[b][k][n] += sum_j W_v[j][k] dP_v[b][n][j]
-    coattn_gemm_desc g = {};
-    g.A = p->W_v; g.a_sm = 1; g.a_sk = d; g.a_sz = 0;
-    g.B = dPv; g.b_sz = (int64_t)N * d; g.b_sk = 1; g.b_sn = d;
-    g.Cin = dV; g.cin_sz = dvl.sB; g.cin_sm = dvl.sD; g.cin_sn = dvl.sN; g.beta = 1.f;
-    g.C = dV; g.c_sz = dvl.sB; g.c_sm = dvl.sD; g.c_sn = dvl.sN;
-    g.M = d; g.N = N; g.K = d; g.batch = B;
-    CA_TRY(c.bf16_proj ? launch_gemm_bf16in(g, c.s) : launch_gemm_f32(g, c.s));
-  }
-  {
-    // dW_v[j][k] = sum_b sum_n dP_v[b][n][j] V[b][k][n]  -> split over sample groups
-    const int G = (B + kMaxSplits - 1) / kMaxSplits;
-    const int S = (B + G - 1) / G;
-    coattn_gemm_desc g = {};
-    g.A = dPv; g.a_sm = 1; g.a_sk = d; g.a_si = (int64_t)N * d; g.a_sz = (int64_t)G * N * d;
-    g.B = V; g.b_sk = c.vl.sN; g.b_sn = c.vl.sD; g.b_si = c.vl.sB; g.b_sz = (int64_t)G * c.vl.sB;
-    g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
-    g.M = d; g.N = d; g.K = N; g.batch = S; g.inner = G; g.inner_total = B;
-    CA_TRY(c.bf16_proj ? launch_gemm_bf16in(g, c.s) : launch_gemm_f32(g, c.s));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->dW_v, S, (int64_t)d * d, accumulate, c.s));
-    const int rpc = (B * N + 255) / 256 > 32 ? (B * N + 255) / 256 : 32;
-    CA_TRY(launch_colsum_partial(nullptr, dPv, part, B * N, d, rpc, &nch, c.s));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->db_v, nch, d, accumulate, c.s));
-  }
-  for (int l = 0; l < L; ++l) {
-    // dW_q[j][k] += sum_m dP_q[m][j] Q_l[m][k],  m over (b,t): split-K
-    const float* dPq = ws + bp.dPq + l * BTd;
-    const int K = B * T;
-    int ks = (K + kMaxSplits - 1) / kMaxSplits;
-    ks = (ks + 15) / 16 * 16;
-    const int S = (K + ks - 1) / ks;
-    coattn_gemm_desc g = {};
-    g.A = dPq; g.a_sm = 1; g.a_sk = d;
-    g.B = Q[l]; g.b_sk = d; g.b_sn = 1;
-    g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
-    g.M = d; g.N = d; g.K = K; g.batch = S; g.ksplit = ks;
-    CA_TRY(c.bf16_proj ? launch_gemm_bf16in(g, c.s) : launch_gemm_f32(g, c.s));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->dW_q, S, (int64_t)d * d, (accumulate || l > 0) ? 1 : 0, c.s));
-  }
-  {
-    const int R = L * B * T;
-    const int rpc = (R + 255) / 256 > 32 ? (R + 255) / 256 : 32;
-    CA_TRY(launch_colsum_partial(nullptr, ws + bp.dPq, part, R, d, rpc, &nch, c.s));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->db_q, nch, d, accumulate, c.s));
-  }
-  if (c.K) {
-    // bilinear: dW_b[j][k] += sum_m dK_l[m][j] Q_l[m][k] (split-K, as dW_q);  db_b = sum of every row of dK
-    for (int l = 0; l < L; ++l) {
-      const int K = B * T;
-      int ks = (K + kMaxSplits - 1) / kMaxSplits;
-      ks = (ks + 15) / 16 * 16;
-      const int S = (K + ks - 1) / ks;
-      coattn_gemm_desc g = {};
-      g.A = c.dK + l * BTd; g.a_sm = 1; g.a_sk = d;
-      g.B = Q[l]; g.b_sk = d; g.b_sn = 1;
-      g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
-      g.M = d; g.N = d; g.K = K; g.batch = S; g.ksplit = ks;
-      CA_TRY(launch_gemm_f32(g, c.s));
-      CA_TRY(launch_reduce_partials(part, (float*)pg->dW_b, S, (int64_t)d * d, (accumulate || l > 0) ? 1 : 0, c.s));
-    }
-    const int R = L * B * T;
-    const int rpc = (R + 255) / 256 > 32 ? (R + 255) / 256 : 32;
-    CA_TRY(launch_colsum_partial(nullptr, c.dK, part, R, d, rpc, &nch, c.s));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->db_b, nch, d, accumulate, c.s));
-  }
+  for (int l = 0; l < L; ++l) CA_TRY(add_rows_times_w(c, c.ws + bp.dPq + l * BTd, (const float*)c.p->W_q, c.dQ[l], c.bf16_proj));
+  if (c.dV) CA_TRY(grad_dv_wv(c.p->W_v, dPv, c.dV, c.dvl, B, N, d, c.bf16_proj, c.s));
+  CA_TRY(grad_dw_sample_groups(dPv, c.V, c.vl, B, N, d, part, (float*)c.pg->dW_v, accumulate, c.bf16_proj, c.s));
+  CA_TRY(grad_colsum(nullptr, dPv, B * N, d, part, (float*)c.pg->db_v, accumulate, c.s));
+  // dW_q[j][k] += sum_m dP_q[m][j] Q_l[m][k],  m over (b,t): split-K, level by level
+  for (int l = 0; l < L; ++l)
+    CA_TRY(grad_dw_splitk(c.ws + bp.dPq + l * BTd, c.Q[l], B * T, d, part, (float*)c.pg->dW_q, (accumulate || l > 0) ? 1 : 0,
+                          c.bf16_proj, c.s));
+  CA_TRY(grad_colsum(nullptr, c.ws + bp.dPq, L * B * T, d, part, (float*)c.pg->db_q, accumulate, c.s));
+  if (c.K) CA_TRY(grad_bilinear_wb(c.dK, c.Q, B, T, d, L, part, (float*)c.pg->dW_b, (float*)c.pg->db_b, accumulate, c.s));
   return 0;
 }
 
@@ -796,19 +748,26 @@ int pick_impl(int flags, int B, int N, int T, int d, int L, const VLayout& vl, i
 
 }  // namespace
 
-// The context of a call, built alike by the forward and by the backward of its state: the backward re-asks the forward's
+// The call descriptor (fused.h Ctx) of the arguments every entry point shares; the wrappers add their own.
+static Ctx call_args(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const int32_t* q_len,
+                     const coattn_params* p, int B, int N, int T, int d, int L, void* stream) {
+  Ctx c{B, N, T, d, L, (hipStream_t)stream, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}};
+  c.V = (const float*)V; c.Q = (const float* const*)Q; c.p = p; c.qlen = q_len;
+  return c;
+}
+
+// The modes of a call, derived alike by the forward and by the backward of its state: the backward re-asks the forward's
 // questions about the same call (rowbits_in_saved), on the same Ctx.
-static Ctx call_ctx(int B, int N, int T, int d, int L, void* stream, const VLayout& vl, const int32_t* q_len, const void* V,
-                    const void* const* Q, int flags, int fused) {
-  Ctx c{B, N, T, d, L, (hipStream_t)stream, vl};
-  c.qlen = q_len;
+static void call_modes(Ctx& c, int flags, int fused) {
   c.bf16_proj = (flags & COATTN_FLAG_BF16_PROJ) != 0;
-  c.f16_proj = f16_path(c, (const float*)V, (const float* const*)Q, flags, fused);
+  c.f16_proj = f16_path(c, flags, fused);
   // (the general-shape path stays exact throughout; a fused shape without the FP16 path too -- unless the developer switch
   //  COATTN_FWD_F16=0 asks for round 4's bf16 widths)
   c.np_pq = (fused && fast16(flags) && !f16_fwd(flags)) ? np_projq(flags) : 3;
+  c.np_fwd = np_fwd(flags, c.f16_proj);
+  c.np_bwd = np_bwd(flags);
   c.pscale = fused ? kPScale : 1.f;
-  return c;
+  c.wgemm = gemm_w_enabled();
 }
 
 // COATTN_FLAG_BILINEAR: the refusals of include/coattn.h (pg: the backward's gradients, NULL in a forward)
@@ -820,57 +779,47 @@ static int check_bilinear(int flags, const coattn_params* p, const coattn_param_
   return 0;
 }
 
-static int check_vlayout(const VLayout& v, int B, int N, int d, const char* what) {
-  (void)B;
+static int check_vlayout(const VLayout& v, int N, int d, const char* what) {
   CA_CHECK_ARG(v.sN > 0 && v.sD > 0 && v.sB > 0, "%s: strides must be positive (sB=%ld sN=%ld sD=%ld)", what, v.sB, v.sN, v.sD);
   // the extent of one sample must not reach into the next one
   CA_CHECK_ARG((long)(N - 1) * v.sN + (long)(d - 1) * v.sD < v.sB, "%s: sample stride %ld is smaller than a sample's extent", what, v.sB);
   return 0;
 }
 
-// saved == NULL: forward only -- the state lives in the workspace, and the fused kernel stores no C / H_q (nothing reads
-// them); av_out / aq_out (may be NULL): the attention maps go straight to the caller's buffers -- with `saved` as well
-// (coattn_forward_maps) the maps go to both, from the same epilogue
-static int forward_impl(const void* V, const VLayout& vl, const void* const* Q, const coattn_params* p, void* v_out,
-                        void* q_out, void* saved, void* ws, int B, int N, int T, int d, int L, int dtype, int flags,
-                        void* stream, bool do_proj, bool do_attn, void* av_out = nullptr, void* aq_out = nullptr,
-                        const int32_t* q_len = nullptr) {
+// c: the call as its wrapper filled it -- c.state = `saved` (NULL: forward only -- the state lives in the workspace, and the
+// fused kernel stores no C / H_q: nothing reads them), c.av_out / c.aq_out the caller's map buffers (may be NULL)
+static int forward_impl(Ctx c, void* ws, int dtype, int flags, bool do_proj) {
+  const int B = c.B, N = c.N, T = c.T, d = c.d, L = c.L;
+  const coattn_params* p = c.p;
   CA_TRY(check_shape(B, N, T, d, L, dtype));
-  CA_CHECK_ARG(V && Q && p && v_out && q_out && ws, "forward: null argument");
-  CA_TRY(check_vlayout(vl, B, N, d, "forward: V"));
-  for (int l = 0; l < L; ++l) CA_CHECK_ARG(Q[l] != nullptr, "forward: Q[%d] is null", l);
+  CA_CHECK_ARG(c.V && c.Q && p && c.v_out && c.q_out && ws, "forward: null argument");
+  CA_TRY(check_vlayout(c.vl, N, d, "forward: V"));
+  for (int l = 0; l < L; ++l) CA_CHECK_ARG(c.Q[l] != nullptr, "forward: Q[%d] is null", l);
   CA_CHECK_ARG(p->W_v && p->b_v && p->W_q && p->b_q && p->w_v && p->c_v && p->w_q && p->c_q,
                "forward: null parameter pointer");
   const bool bil = bilinear(flags);
   CA_TRY(check_bilinear(flags, p, nullptr));
   int fused = 0;
-  CA_TRY(pick_impl(flags, B, N, T, d, L, vl, &fused));
-  const SavedPlan sp = plan_saved(B, N, T, d, L);
-  float* sv = saved ? (float*)saved : (float*)ws;      // inference: state lives in the workspace
-  float* tail = (float*)ws + saved_floats(B, N, T, d, L, bil);
-  Ctx c = call_ctx(B, N, T, d, L, stream, vl, q_len, V, Q, flags, fused);
-  if (bil) { c.Wb = (const float*)p->W_b; c.bb = (const float*)p->b_b; c.K = sv + sp.total; }
+  CA_TRY(pick_impl(flags, B, N, T, d, L, c.vl, &fused));
+  c.keep = c.state != nullptr;
+  if (!c.keep) c.state = (float*)ws;                  // inference: state lives in the workspace
+  c.tail = (float*)ws + saved_floats(B, N, T, d, L, bil);
+  call_modes(c, flags, fused);
+  if (bil) { c.Wb = (const float*)p->W_b; c.bb = (const float*)p->b_b; c.K = c.state + saved_off(B, N, T, d, L).total; }
   if (do_proj) {
     char* wimg = (char*)ws + fwd_ws_floats(B, N, T, d, L, bil) * sizeof(float);
-    CA_TRY(general_projections(c, (const float*)V, (const float* const*)Q, p, sv, wimg, saved != nullptr));
-    if (bil) CA_TRY(bilinear_projection(c, (const float*)V, (const float* const*)Q, p, sv, wimg + 2 * wsplit_bytes(d, d)));
+    CA_TRY(general_projections(c, wimg));
+    if (bil) CA_TRY(bilinear_projection(c, wimg + 2 * wsplit_bytes(d, d)));
   }
-  if (!do_attn) return 0;
-  const bool dual = saved && av_out;                  // coattn_forward_maps
-  if (fused)
-    return fused_attention_forward(B, N, T, d, L, (const float*)V, vl, (const float* const*)Q, p, (float*)v_out,
-                                   (float*)q_out, sv, tail, c.s, c.bf16_proj ? 1 : 0, np_fwd(flags, c.f16_proj),
-                                   dual ? nullptr : (float*)av_out, dual ? nullptr : (float*)aq_out, saved != nullptr ? 1 : 0,
-                                   q_len, dual ? (float*)av_out : nullptr, dual ? (float*)aq_out : nullptr, c.K);
-  return general_attention(c, (const float*)V, (const float* const*)Q, p, (float*)v_out, (float*)q_out, sv, tail,
-                           (float*)av_out, (float*)aq_out, dual);
+  return fused ? fused_attention_forward(c) : general_attention(c);
 }
 
 extern "C" int coattn_forward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
                                   const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* saved, void* ws,
                                   int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
-  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
-                      dtype, flags, stream, true, true, nullptr, nullptr, q_len);
+  Ctx c = call_args(V, v_sB, v_sN, v_sD, Q, q_len, p, B, N, T, d, L, stream);
+  c.v_out = (float*)v_out; c.q_out = (float*)q_out; c.state = (float*)saved;
+  return forward_impl(c, ws, dtype, flags, true);
 }
 
 extern "C" int coattn_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -885,8 +834,10 @@ extern "C" int coattn_forward_maps_len(const void* V, int64_t v_sB, int64_t v_sN
                                        void* stream) {
   CA_CHECK_ARG(saved != nullptr, "forward_maps: null `saved` (the backward state is required; coattn_infer keeps none)");
   CA_CHECK_ARG(av_out && aq_out, "forward_maps: null map buffer (av_out [L,B,N] and aq_out [L,B,T] are required)");
-  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
-                      dtype, flags, stream, true, true, av_out, aq_out, q_len);
+  Ctx c = call_args(V, v_sB, v_sN, v_sD, Q, q_len, p, B, N, T, d, L, stream);
+  c.v_out = (float*)v_out; c.q_out = (float*)q_out; c.state = (float*)saved;
+  c.av_out = (float*)av_out; c.aq_out = (float*)aq_out;
+  return forward_impl(c, ws, dtype, flags, true);
 }
 
 extern "C" int coattn_forward_maps(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -899,8 +850,10 @@ extern "C" int coattn_forward_maps(const void* V, int64_t v_sB, int64_t v_sN, in
 extern "C" int coattn_infer_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
                                 const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* av_out,
                                 void* aq_out, void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
-  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, nullptr, ws, B, N, T, d, L,
-                      dtype, flags, stream, true, true, av_out, aq_out, q_len);
+  Ctx c = call_args(V, v_sB, v_sN, v_sD, Q, q_len, p, B, N, T, d, L, stream);
+  c.v_out = (float*)v_out; c.q_out = (float*)q_out;
+  c.av_out = (float*)av_out; c.aq_out = (float*)aq_out;
+  return forward_impl(c, ws, dtype, flags, true);
 }
 
 extern "C" int coattn_infer(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -914,8 +867,9 @@ extern "C" int coattn_attention_forward_len(const void* V, int64_t v_sB, int64_t
                                             const int32_t* q_len, const coattn_params* p, void* v_out, void* q_out, void* saved,
                                             void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
   CA_CHECK_ARG(saved != nullptr, "attention_forward: needs the saved buffer of a previous coattn_forward");
-  return forward_impl(V, VLayout{(long)v_sB, (long)v_sN, (long)v_sD}, Q, p, v_out, q_out, saved, ws, B, N, T, d, L,
-                      dtype, flags, stream, false, true, nullptr, nullptr, q_len);
+  Ctx c = call_args(V, v_sB, v_sN, v_sD, Q, q_len, p, B, N, T, d, L, stream);
+  c.v_out = (float*)v_out; c.q_out = (float*)q_out; c.state = (float*)saved;
+  return forward_impl(c, ws, dtype, flags, false);
 }
 
 extern "C" int coattn_attention_forward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -925,60 +879,40 @@ extern "C" int coattn_attention_forward(const void* V, int64_t v_sB, int64_t v_s
                                       flags, stream);
 }
 
-// g_av / g_aq (may be NULL = 0; coattn_backward_maps): the upstream gradients of the maps [L][B][N] / [L][B][T]
-static int backward_impl(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q, const int32_t* q_len,
-                         const coattn_params* p, const void* saved, const void* gv, const void* gq, const void* g_av,
-                         const void* g_aq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
-                         const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d, int L, int dtype,
-                         int flags, void* stream) {
+// c: the call as coattn_backward_maps_len filled it (c.g_av / c.g_aq may be NULL = 0, c.dV may be NULL)
+static int backward_impl(Ctx c, int dtype, int flags) {
+  const int B = c.B, N = c.N, T = c.T, d = c.d, L = c.L;
+  const coattn_params* p = c.p;
+  const coattn_param_grads* pg = c.pg;
   CA_TRY(check_shape(B, N, T, d, L, dtype));
-  CA_CHECK_ARG(V && Q && p && saved && gv && gq && dQ && pg && ws, "backward: null argument");  // dV may be NULL
-  const VLayout vl{(long)v_sB, (long)v_sN, (long)v_sD};
-  VLayout dvl{(long)dv_sB, (long)dv_sN, (long)dv_sD};
-  CA_TRY(check_vlayout(vl, B, N, d, "backward: V"));
-  if (dV) CA_TRY(check_vlayout(dvl, B, N, d, "backward: dV"));
-  else dvl = vl;
-  for (int l = 0; l < L; ++l) CA_CHECK_ARG(Q[l] && dQ[l], "backward: Q[%d]/dQ[%d] is null", l, l);
+  CA_CHECK_ARG(c.V && c.Q && p && c.saved && c.gv && c.gq && c.dQ && pg && c.ws, "backward: null argument");  // dV may be NULL
+  CA_TRY(check_vlayout(c.vl, N, d, "backward: V"));
+  if (c.dV) CA_TRY(check_vlayout(c.dvl, N, d, "backward: dV"));
+  else c.dvl = c.vl;
+  for (int l = 0; l < L; ++l) CA_CHECK_ARG(c.Q[l] && c.dQ[l], "backward: Q[%d]/dQ[%d] is null", l, l);
   CA_CHECK_ARG(pg->dW_v && pg->db_v && pg->dW_q && pg->db_q && pg->dw_v && pg->dc_v && pg->dw_q && pg->dc_q,
                "backward: null parameter-gradient pointer");
   CA_TRY(check_bilinear(flags, p, pg));
   int fused = 0;
-  CA_TRY(pick_impl(flags, B, N, T, d, L, vl, &fused));
-  Ctx c = call_ctx(B, N, T, d, L, stream, vl, q_len, V, Q, flags, fused);
+  CA_TRY(pick_impl(flags, B, N, T, d, L, c.vl, &fused));
+  call_modes(c, flags, fused);
+  BilBwd bb = {};
   if (bilinear(flags)) {                              // K from the forward's `saved`, dK into the workspace
     c.Wb = (const float*)p->W_b; c.bb = (const float*)p->b_b;
-    c.K = (float*)saved + plan_saved(B, N, T, d, L).total;
-    c.dK = (float*)ws + bwd_ws_floats(B, N, T, d, L, false);
-  }
-  BilBwd bb = {};
-  if (c.K) {
-    const size_t k = al64((size_t)L * B * T * d);
+    c.K = const_cast<float*>(c.saved) + saved_off(B, N, T, d, L).total;
+    c.dK = c.ws + bwd_ws_floats(B, N, T, d, L, false);
+    const size_t k = fal64((size_t)L * B * T * d);
     bb.Wb = c.Wb; bb.K = c.K; bb.dK = c.dK; bb.dpk = c.dK + k; bb.wstack = c.dK + 3 * k;
-    bb.wimg = c.dK + 3 * k + al64((size_t)2 * d * d);
-    bb.zeros = (float*)bb.wimg + al64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1);
+    bb.wimg = c.dK + 3 * k + fal64((size_t)2 * d * d);
+    bb.zeros = (float*)bb.wimg + fal64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1);
     bb.dWb = (float*)pg->dW_b; bb.dbb = (float*)pg->db_b;
+    c.bil = &bb;
   }
   // (`saved` of the fused forward holds P_v, P_q scaled by kPScale: only the fused backward may read it)
   CA_CHECK_ARG(!fused || fused_backward_supported(B, N, T, d, L), "backward: the fused forward's saved state has no fused backward for this shape");
-  if (fused)
-    return fused_backward(B, N, T, d, L, (const float*)V, vl, (const float* const*)Q, p, (const float*)saved,
-                          (const float*)gv, (const float*)gq, (float*)dV, dvl, (float* const*)dQ, pg, accumulate,
-                          (float*)ws, c.s, c.bf16_proj ? 1 : 0,
-                          gemm_w_enabled() ? 1 : 0, np_bwd(flags),
-                          rowbits_in_saved(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, flags, fused) ? 1 : 0,
-                          q_len, (const float*)g_av, (const float*)g_aq, c.K ? &bb : nullptr);
-  return backward_general(c, (const float*)V, (const float* const*)Q, p, (const float*)saved, (const float*)gv,
-                          (const float*)gq, (float*)dV, dvl, (float* const*)dQ, pg, accumulate, (float*)ws, (const float*)g_av,
-                          (const float*)g_aq);
-}
-
-extern "C" int coattn_backward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
-                                   const int32_t* q_len, const coattn_params* p, const void* saved, const void* gv,
-                                   const void* gq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
-                                   const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d,
-                                   int L, int dtype, int flags, void* stream) {
-  return backward_impl(V, v_sB, v_sN, v_sD, Q, q_len, p, saved, gv, gq, nullptr, nullptr, dV, dv_sB, dv_sN, dv_sD, dQ, pg,
-                       accumulate, ws, B, N, T, d, L, dtype, flags, stream);
+  if (!fused) return backward_general(c);
+  c.live_rows = rowbits_in_saved(c);
+  return fused_backward(c);
 }
 
 extern "C" int coattn_backward_maps_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -987,8 +921,21 @@ extern "C" int coattn_backward_maps_len(const void* V, int64_t v_sB, int64_t v_s
                                         int64_t dv_sN, int64_t dv_sD, void* const* dQ, const coattn_param_grads* pg,
                                         int accumulate, void* ws, int B, int N, int T, int d, int L, int dtype, int flags,
                                         void* stream) {
-  return backward_impl(V, v_sB, v_sN, v_sD, Q, q_len, p, saved, gv, gq, g_av, g_aq, dV, dv_sB, dv_sN, dv_sD, dQ, pg,
-                       accumulate, ws, B, N, T, d, L, dtype, flags, stream);
+  Ctx c = call_args(V, v_sB, v_sN, v_sD, Q, q_len, p, B, N, T, d, L, stream);
+  c.saved = (const float*)saved; c.gv = (const float*)gv; c.gq = (const float*)gq;
+  c.g_av = (const float*)g_av; c.g_aq = (const float*)g_aq;
+  c.dV = (float*)dV; c.dvl = VLayout{(long)dv_sB, (long)dv_sN, (long)dv_sD}; c.dQ = (float* const*)dQ;
+  c.pg = pg; c.accumulate = accumulate; c.ws = (float*)ws;
+  return backward_impl(c, dtype, flags);
+}
+
+extern "C" int coattn_backward_len(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
+                                   const int32_t* q_len, const coattn_params* p, const void* saved, const void* gv,
+                                   const void* gq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
+                                   const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d,
+                                   int L, int dtype, int flags, void* stream) {
+  return coattn_backward_maps_len(V, v_sB, v_sN, v_sD, Q, q_len, p, saved, gv, gq, nullptr, nullptr, dV, dv_sB, dv_sN, dv_sD, dQ,
+                                  pg, accumulate, ws, B, N, T, d, L, dtype, flags, stream);
 }
 
 extern "C" int coattn_backward_maps(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,
@@ -996,8 +943,8 @@ extern "C" int coattn_backward_maps(const void* V, int64_t v_sB, int64_t v_sN, i
                                     const void* g_aq, void* dV, int64_t dv_sB, int64_t dv_sN, int64_t dv_sD, void* const* dQ,
                                     const coattn_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d, int L,
                                     int dtype, int flags, void* stream) {
-  return backward_impl(V, v_sB, v_sN, v_sD, Q, nullptr, p, saved, gv, gq, g_av, g_aq, dV, dv_sB, dv_sN, dv_sD, dQ, pg,
-                       accumulate, ws, B, N, T, d, L, dtype, flags, stream);
+  return coattn_backward_maps_len(V, v_sB, v_sN, v_sD, Q, nullptr, p, saved, gv, gq, g_av, g_aq, dV, dv_sB, dv_sN, dv_sD, dQ, pg,
+                                  accumulate, ws, B, N, T, d, L, dtype, flags, stream);
 }
 
 extern "C" int coattn_backward(const void* V, int64_t v_sB, int64_t v_sN, int64_t v_sD, const void* const* Q,

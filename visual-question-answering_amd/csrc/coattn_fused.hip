@@ -8,7 +8,6 @@
 #include "fused.h"
 #include <stdlib.h>
 
-
 namespace {
 
 // v_l[b][k] = sum_n a_v[l][b][n] V[b][k][n]   (model.py:391), all L levels in one pass over V.
@@ -56,36 +55,41 @@ int fused_supported(int B, int N, int T, int d, int L) {
   return 1;
 }
 
-int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl,
-                            const float* const* Q, const coattn_params* p, float* v_out, float* q_out, float* saved,
-                            float* ws, hipStream_t s, int bf16, int np, float* av, float* aq, int keep, const int* qlen,
-                            float* av_copy, float* aq_copy, const float* K) {
+int fused_attention_forward(const Ctx& c) {
+  const int B = c.B, N = c.N, T = c.T, d = c.d, L = c.L;
+  const float* V = c.V;
+  const VLayout& vl = c.vl;
+  float* v_out = c.v_out;
+  hipStream_t s = c.s;
   CA_CHECK_ARG(fused_supported(B, N, T, d, L), "fused forward: unsupported shape");
   const bool lm = v_is_lm(vl, N, d);
   CA_CHECK_ARG(lm || v_is_cm(vl, N, d), "fused forward: image features must be channel-major [B,d,N] or location-major [B,N,d]");
   const SavedOff so = saved_off(B, N, T, d, L);
+  float* saved = c.state;
   FwdArgs a;
   a.V = V; a.v_sB = vl.sB; a.lm = lm ? 1 : 0;
-  for (int l = 0; l < 8; ++l) a.Q[l] = l < L ? Q[l] : nullptr;
+  for (int l = 0; l < 8; ++l) a.Q[l] = l < L ? c.Q[l] : nullptr;
   a.Pv = saved + so.Pv; a.Pq = saved + so.Pq;
-  a.wv = (const float*)p->w_v; a.cv = (const float*)p->c_v; a.wq = (const float*)p->w_q; a.cq = (const float*)p->c_q;
+  a.wv = (const float*)c.p->w_v; a.cv = (const float*)c.p->c_v; a.wq = (const float*)c.p->w_q; a.cq = (const float*)c.p->c_q;
   a.C = saved + so.C; a.Hq = saved + so.Hq;
-  a.av = av ? av : saved + so.av; a.aq = aq ? aq : saved + so.aq;   // the caller's map buffers (coattn_infer), else `saved`
-  a.av2 = av_copy; a.aq2 = aq_copy;
-  a.K = K;                                           // (bilinear: phase 1 streams K, phase 3 still reads Q)                  // (coattn_forward_maps: a second store of both maps, same epilogue)
-  a.keep = keep ? 1 : 0;
-  a.qlen = qlen;
-  a.q_out = q_out;
+  // the maps: into the state, to the caller's buffers (coattn_infer), or both from the same epilogue (coattn_forward_maps)
+  const MapDst av = map_dst(c, saved + so.av, c.av_out), aq = map_dst(c, saved + so.aq, c.aq_out);
+  a.av = av.to; a.aq = aq.to;
+  a.av2 = av.copy; a.aq2 = aq.copy;
+  a.K = c.K;                                         // (bilinear: phase 1 streams K, phase 3 still reads Q)
+  a.keep = c.keep ? 1 : 0;                           // 0: forward only, no C / H_q stored
+  a.qlen = c.qlen;
+  a.q_out = c.q_out;
   // Small grids (the 7 x 7 grid of 224 x 224 images: N = 49) on location-major features: the attended image feature
   // v_l = a_v^T V is computed by the affinity kernel's own workgroup -- its 100 KB of V come from L2, where phase 1 left
   // them, in less time than a second launch costs.  (At N = 196 the separate pass over V stays: DESIGN.md section 3.1.)
   static const int fuse_v_env = dev_env_int("COATTN_FUSE_V", 1);   // developer switch
   const bool fuse_v = lm && N <= 64 && d % 512 == 0 && fuse_v_env;
   a.v_out = fuse_v ? v_out : nullptr;
-  a.stamps = COATTN_STAMPS ? reinterpret_cast<unsigned long long*>(ws) : nullptr;
+  a.stamps = COATTN_STAMPS ? reinterpret_cast<unsigned long long*>(c.tail) : nullptr;
   a.B = B; a.N = N; a.T = T; a.d = d; a.L = L;
-  a.bf16 = bf16;
-  a.np = ((np == 2 || np == 4) && !bf16) ? np : 3;      // 4: both phases on two FP16 pieces (coattn_fwd32.hip)
+  a.bf16 = c.bf16_proj ? 1 : 0;
+  a.np = ((c.np_fwd == 2 || c.np_fwd == 4) && !c.bf16_proj) ? c.np_fwd : 3;   // 4: both phases on two FP16 pieces (coattn_fwd32.hip)
   CA_TRY(fused32_forward(a, s));
   prof_mark(s, "coattn_fwd32");
   if (fuse_v) return 0;

@@ -22,8 +22,6 @@
 #include "fused.h"
 #include <stdlib.h>
 
-
-
 namespace {
 
 // partial da_v over 64 channel rows: part[b][kc][l][n] = sum_{k in chunk kc} V[b][k][n] gv[l][b][k].
@@ -319,115 +317,92 @@ int launch_pre(const PreArgs& a, hipStream_t s) {
   return 0;
 }
 
-}  // namespace
+// ---- the host driver: fused_backward decides the route of a call once (decide_route), then runs its steps ---------------------
 
-size_t fused_bwd_ws_floats(int B, int N, int T, int d, int L) { return fused_bwd_off(B, N, T, d, L).total; }
+// where things lie in `saved` and in the workspace, and the sizes the steps share
+struct Off { SavedOff so; FusedBwdOff wo; size_t BTd, BTN, BNd, Bd; };
 
-int fused_backward_supported(int B, int N, int T, int d, int L) { return fused_supported(B, N, T, d, L); }
+// Every decision of a call, taken before its first launch, and the GEMM jobs the decisions are about.
+struct Route {
+  bool lm;                 // location-major image features (else channel-major)
+  int np;                  // width of the fp32 mode's contractions (fused.h): 2 = hi + mid in the three fused kernels and in the GEMM
+                           // launch (dW_v, dW_q, dQ = dP_q W_q), 3 = the exact split everywhere; dV (general GEMM) is always exact
+  int tn_budget;           // split-K parts dW_v and dW_q share
+  int ko_dpv, ko_sum3;     // developer knock-outs (wrong results)
+  TnDyn dyn_all;           // bits != NULL: the pre-pass plans the weight gradients over the live question rows (fused.h TnDyn)
+  TnGemm tnv, tnq;         // dW_v = (sum_l dP_v)^T V, dW_q = sum_l dP_q,l^T Q_l on the hand-scheduled A^T B kernels
+  WGemm wdq;               // dQ_l = dP_q,l W_q against the W_q image the forward left in `saved` (fused.h dq_proj_job)
+  bool tn_v, tn_q, wdq_ok; // which of the three those kernels take
+  bool dq32;               // dA V on the bf16-MFMA kernel (both layouts; channel-major: aligned rows), else the exact-f32 one
+  bool own_dq, combine;    // the dQ projection behind the weight gradients (COATTN_OWN_DQ) / its tiles inside their launch;
+  bool late_dq;            // either way the dA V kernel then runs after the weight gradients
+  bool dp_bf16;            // bwd_nat32 stores dP_v / dP_q as bf16
+  bool sum_in_gemm;        // the weight-gradient kernel adds the three levels of dP_v while staging them (no dV: the frozen encoder)
+  bool bf_tn, wide;        // both weight gradients on gemm_bf.hip's single-product kernel / on gemm_tn_wide.hip's 128 x 256 tiles
+  bool red_in_dq;          // their partial sums ride in the dQ kernel's launch (RedJob),
+  bool use_dyn;            // which then follows the device's plan (dyn_all)
+};
+struct RedJob { const float* part[2]; float* out[2]; int np[2]; long n; int acc; TnDyn dyn; };
 
-int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl, const float* const* Q,
-                   const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
-                   const VLayout& dvl, float* const* dQ, const coattn_param_grads* pg, int accumulate, float* ws,
-                   hipStream_t s, int bf16_proj, int wgemm, int np, int live_rows, const int* qlen, const float* g_av,
-                   const float* g_aq, const BilBwd* bil) {
-  // np: width of the fp32 mode's contractions (fused.h): 2 = hi + mid in the three fused kernels and in the GEMM launch
-  // (dW_v, dW_q, dQ = dP_q W_q), 3 = the exact split everywhere; dV (general GEMM) is always exact
-  np = (np == 2 && !bf16_proj) ? 2 : 3;
-  CA_CHECK_ARG(fused_backward_supported(B, N, T, d, L), "fused backward: unsupported shape");
-  const bool lm = v_is_lm(vl, N, d);
-  CA_CHECK_ARG(lm || v_is_cm(vl, N, d), "fused backward: image features must be channel-major [B,d,N] or location-major [B,N,d]");
-  // gradients of the two projections (d x d contractions): fp32 MFMA, or bf16 MFMA under COATTN_FLAG_BF16_PROJ
-  auto gemm_proj = [&](const coattn_gemm_desc& g) { return bf16_proj ? launch_gemm_bf16in(g, s) : launch_gemm_f32(g, s); };
-  const SavedOff so = saved_off(B, N, T, d, L);
-  const FusedBwdOff wo = fused_bwd_off(B, N, T, d, L);
-  const size_t BTd = (size_t)B * T * d, BTN = (size_t)B * T * N, BNd = (size_t)B * N * d, Bd = (size_t)B * d;
-  const bool small_n = N <= 64;
-  // 1. per-sample pre-pass: one launch for the question side and the da_v partials, a small one for the image side
-  CA_CHECK_ARG(N <= 256, "fused backward: N > 256");
-  PreArgs pa;
-  pa.V = V; pa.v_sB = vl.sB; pa.gv = gv; pa.dav_out = ws + wo.part; pa.dav_lm = lm ? 1 : 0;
-  pa.dav_gx = lm ? (N + 15) / 16 : d / 64;
-  pa.dav_part = ws + wo.part;
-  pa.nkc = lm ? 1 : d / 64;
-  for (int l = 0; l < 8; ++l) pa.Q[l] = l < L ? Q[l] : nullptr;
-  pa.gq = gq; pa.av = saved + so.av; pa.aq = saved + so.aq;
-  pa.dsq = ws + wo.dsq; pa.dcs_part = ws + wo.dcs_part; pa.qlen = qlen; pa.dA = ws + wo.dA;
-  pa.gaq = g_aq;                                     // (coattn_backward_maps; NULL: the plain pre-pass)
-  pa.B = B; pa.N = N; pa.T = T; pa.d = d; pa.L = L;
+void decide_route(const Ctx& c, const Off& o, Route& r) {
+  const int B = c.B, N = c.N, T = c.T, d = c.d, L = c.L;
+  // developer switches (builds with -DCOATTN_DEV_SWITCHES only; tools/ab_*.sh)
+  static const int tn_budget_env = dev_env_int("COATTN_TN_PARTS", 0);
+  static const int ko_dpv = dev_env_int("COATTN_KO_DPV", 0);      // knock-outs (wrong results): what would ONE sum_l dP_v array
+  static const int ko_sum3 = dev_env_int("COATTN_KO_SUM3", 0);    // save in bwd_nat32's stores / the GEMM's reads
+  static const int no_combine = dev_env_int("COATTN_NO_COMBINE", 0);
+  // COATTN_OWN_DQ=1 (round 5, measured and NOT kept): the dQ projection as a launch of its own on the persistent pipeline of
+  // gemm_h2.hip (bf16 pieces) between the weight gradients and the dA V kernel -- 98.9 + 28.5 us against 123.2 combined at
+  // N = 196, 41.8 + 26.6 against 63.7 at N = 49: inside the weight-gradient launch its tiles fill the CUs the last parts leave,
+  // which is worth as much as the faster kernel.
+  static const int own_dq_env = dev_env_int("COATTN_OWN_DQ", 0);
+  static const int dp_bf16_off = (dev_env_int("COATTN_DP_BF16", 1) == 0);
+  static const int red_in_dq = dev_env_int("COATTN_RED_IN_DQ", 1);
+  static const int live_env = dev_env_int("COATTN_DW_LIVE_ROWS", 1);   // 0: the host's static plan over all rows
+  r = Route{};
+  r.lm = v_is_lm(c.vl, N, d);
+  r.np = (c.np_bwd == 2 && !c.bf16_proj) ? 2 : 3;
+  r.tn_budget = tn_budget_env > 0 ? tn_budget_env : 32;
+  r.ko_dpv = ko_dpv; r.ko_sum3 = ko_sum3;
+  const int budget = r.tn_budget;
+  float* part = c.ws + o.wo.part;
   // (exact mode: the forward's bitmap of the live question rows may be in `saved` -- live_rows: the shape and mode allow one,
   //  its tag says whether the forward wrote it; the plan of the weight gradients over those rows is a function of it and of
-  //  shapes known here -- evaluated once, by an extra workgroup of this launch, which copies the words it counted to `ws`)
-  static const int tn_budget_env = dev_env_int("COATTN_TN_PARTS", 0);   // developer switch
-  const int tn_budget = tn_budget_env > 0 ? tn_budget_env : 32;
-  TnDyn dyn_all = {};
-  pa.dyn = dyn_all; pa.plan_out = nullptr; pa.saved_bits = nullptr; pa.row_tag = nullptr;
-  if (live_rows && L <= kDynLevels && (B * T + 31) / 32 <= kRowBitsMaxWords && tn_budget > L) {
-    dyn_all.bits = reinterpret_cast<const unsigned*>(ws + wo.rowbits);
-    pa.saved_bits = reinterpret_cast<const unsigned*>(saved + so.rowbits);
-    pa.row_tag = reinterpret_cast<const unsigned*>(saved + so.rowcnt) + kRowTagWord;
-    dyn_all.words = (B * T + 31) / 32; dyn_all.levels = L; dyn_all.P = tn_budget; dyn_all.K0 = B * N;
-    dyn_all.plan = reinterpret_cast<const TnDynPlan*>(ws + wo.dynplan);
-    pa.dyn = dyn_all; pa.plan_out = reinterpret_cast<TnDynPlan*>(ws + wo.dynplan);
+  //  shapes known here -- evaluated once, by an extra workgroup of the pre-pass, which copies the words it counted to `ws`)
+  if (c.live_rows && L <= kDynLevels && (B * T + 31) / 32 <= kRowBitsMaxWords && budget > L) {
+    r.dyn_all.bits = reinterpret_cast<const unsigned*>(c.ws + o.wo.rowbits);
+    r.dyn_all.words = (B * T + 31) / 32; r.dyn_all.levels = L; r.dyn_all.P = budget; r.dyn_all.K0 = B * N;
+    r.dyn_all.plan = reinterpret_cast<const TnDynPlan*>(c.ws + o.wo.dynplan);
   }
-  CA_TRY(launch_pre(pa, s));
-  prof_mark(s, "bwd_pre");
-  // 2. the two recompute kernels
-  BwdArgs ba;
-  ba.Pv = saved + so.Pv; ba.Pq = saved + so.Pq; ba.C = saved + so.C;
-  ba.Hq = saved + so.Hq; ba.dsq = ws + wo.dsq; ba.wq = (const float*)p->w_q; ba.dwq_part = ws + wo.dwq_part;
-  ba.dav_part = ws + wo.part; ba.nkc = pa.nkc; ba.av = saved + so.av; ba.dcs_part = ws + wo.dcs_part;
-  ba.wv = (const float*)p->w_v;
-  ba.dPv = ws + wo.dPv; ba.dPq = ws + wo.dPq; ba.dA = ws + wo.dA; ba.dwv_part = ws + wo.dwv_part;
-  ba.dbv_part = ws + wo.dbv_part; ba.dbq_part = ws + wo.dbq_part;
-  ba.B = B; ba.N = N; ba.T = T; ba.d = d; ba.L = L;
-  ba.bf16 = bf16_proj;
-  ba.np = np;
-  static const int ko_dpv = dev_env_int("COATTN_KO_DPV", 0);      // developer knock-outs (DEV builds; wrong results): what would
-  static const int ko_sum3 = dev_env_int("COATTN_KO_SUM3", 0);    // ONE sum_l dP_v array save in bwd_nat32's stores / the GEMM's reads
-  ba.ko_dpv = ko_dpv;
-  ba.dp_bf16 = 0;
-  ba.qlen = qlen;
-  ba.gav = g_av;                                     // (coattn_backward_maps; NULL: the kernels without the G_av operand)
-  CA_TRY(launch_bwd_dc32(ba, s));                    // dC, dA                       (coattn_bwd32.hip)
-  prof_mark(s, "bwd_dc32");
-  // which of the backward's GEMMs take the hand-scheduled kernels (decided here: when all three do, they share ONE
-  // launch in step 5 -- weight gradients, the dQ projection's tiles and the small reductions)
-  float* dPv = ws + wo.dPv;
-  float* part = ws + wo.part;
-  TnGemm tnv = {};
-  tnv.A = dPv; tnv.a_ld = d; tnv.B = V; tnv.b_ld = (int)vl.sN; tnv.C = part; tnv.M = d; tnv.N = d; tnv.K = B * N; tnv.levels = 1;
-  bool tn_v = false;
-  tnv.bf16 = bf16_proj; tnv.np = np;
-  if (wgemm && lm && vl.sB == (long)N * vl.sN && vl.sN < (1L << 24)) {
-    tn_v = gemm_tn_supported(tnv) != 0;              // location-major rows, samples abutting
-  } else if (wgemm && !lm && vl.sD < (1L << 24)) {
-    tnv.b_ld = (int)vl.sD; tnv.b_kdiv = N; tnv.b_sdiv = vl.sB;          // channel-major, read in place
-    tn_v = gemm_tn_supported(tnv) != 0;
+  // which of the backward's GEMMs take the hand-scheduled kernels (when all three do, they share ONE launch)
+  TnGemm& tnv = r.tnv;
+  tnv.A = c.ws + o.wo.dPv; tnv.a_ld = d; tnv.B = c.V; tnv.b_ld = (int)c.vl.sN; tnv.C = part; tnv.M = d; tnv.N = d; tnv.K = B * N;
+  tnv.levels = 1; tnv.bf16 = c.bf16_proj; tnv.np = r.np;
+  if (c.wgemm && r.lm && c.vl.sB == (long)N * c.vl.sN && c.vl.sN < (1L << 24)) {
+    r.tn_v = gemm_tn_supported(tnv) != 0;            // location-major rows, samples abutting
+  } else if (c.wgemm && !r.lm && c.vl.sD < (1L << 24)) {
+    tnv.b_ld = (int)c.vl.sD; tnv.b_kdiv = N; tnv.b_sdiv = c.vl.sB;       // channel-major, read in place
+    r.tn_v = gemm_tn_supported(tnv) != 0;
   }
-  TnGemm tnq = {};
-  tnq.A = ws + wo.dPq; tnq.a_sl = (long)BTd; tnq.a_ld = d; tnq.b_ld = d; tnq.M = d; tnq.N = d; tnq.K = B * T; tnq.levels = L;
-  for (int l = 0; l < L; ++l) tnq.b_ptrs[l] = Q[l];
-  tnq.bf16 = bf16_proj; tnq.np = np;
-  const bool tn_q = wgemm && gemm_tn_supported(tnq);       // levels as extra split-K parts (gemm_tn.hip)
-  const bool dq32 = lm || (N % 4) == 0;              // the bf16 dA V kernel takes both layouts (channel-major: aligned rows)
-  // dQ_l = dP_q,l W_q against the W_q image the forward left in `saved` -- written whenever this job is supported (the same
-  // test, api.hip general_projections: fused.h dq_proj_job)
-  WGemm wdq = dq_proj_job(B, T, d, L, bf16_proj, np);
-  const bool wdq_ok = wgemm && gemm_w_supported(wdq);
-  wdq.A = ws + wo.dPq; wdq.Wf = saved + so.wqT;
-  for (int l = 0; l < L; ++l) wdq.c_ptrs[l] = dQ[l];
-  // (a dQ projection on gemm_bf.hip -- 512-thread workgroups -- cannot ride in the weight-gradient launch)
-  static const int no_combine = dev_env_int("COATTN_NO_COMBINE", 0);   // developer switch
-  // COATTN_OWN_DQ=1 (developer switch; round 5, measured and NOT kept): the dQ projection as a launch of its own on the
-  // persistent pipeline of gemm_h2.hip (bf16 pieces) between the weight gradients and the dA V kernel -- 98.9 + 28.5 us against
-  // 123.2 combined at N = 196, 41.8 + 26.6 against 63.7 at N = 49: inside the weight-gradient launch its tiles fill the CUs
-  // the last parts leave, which is worth as much as the faster kernel.
-  static const int own_dq_env = dev_env_int("COATTN_OWN_DQ", 0);
-  const bool own_dq = own_dq_env && !bil && dq32 && wdq_ok && tn_v && tn_q && !gemm_bf_supported(wdq) && gemm_h2_supported(wdq) && !no_combine;
-  // (bilinear: dQ comes from its own projection [dP_q | dK] [W_q; W_b] below, so the dQ tiles do not ride in the weight-gradient
-  //  launch -- which keeps the static split-K plan)
-  const bool combine = dq32 && wdq_ok && tn_v && tn_q && !gemm_bf_supported(wdq) && !no_combine && !own_dq && !bil;
-  const bool late_dq = combine || own_dq;           // the dA V kernel (and, before it, the projection) run after the weight gradients
+  TnGemm& tnq = r.tnq;
+  tnq.A = c.ws + o.wo.dPq; tnq.a_sl = (long)o.BTd; tnq.a_ld = d; tnq.b_ld = d; tnq.M = d; tnq.N = d; tnq.K = B * T; tnq.levels = L;
+  for (int l = 0; l < L; ++l) tnq.b_ptrs[l] = c.Q[l];
+  tnq.bf16 = c.bf16_proj; tnq.np = r.np;
+  r.tn_q = c.wgemm && gemm_tn_supported(tnq);        // levels as extra split-K parts (gemm_tn.hip)
+  r.dq32 = r.lm || (N % 4) == 0;
+  // the dQ projection's image is written by the forward whenever this job is supported (the same test, api.hip
+  // general_projections: fused.h dq_proj_job)
+  WGemm& wdq = r.wdq;
+  wdq = dq_proj_job(B, T, d, L, c.bf16_proj, r.np);
+  r.wdq_ok = c.wgemm && gemm_w_supported(wdq);
+  wdq.A = c.ws + o.wo.dPq; wdq.Wf = c.saved + o.so.wqT;
+  for (int l = 0; l < L; ++l) wdq.c_ptrs[l] = c.dQ[l];
+  // (a dQ projection on gemm_bf.hip -- 512-thread workgroups -- cannot ride in the weight-gradient launch; bilinear: dQ comes
+  //  from its own projection [dP_q | dK] [W_q; W_b], so the dQ tiles do not ride there either -- which keeps the static plan)
+  const bool all3 = r.dq32 && r.wdq_ok && r.tn_v && r.tn_q;
+  r.own_dq = own_dq_env && !c.bil && all3 && !gemm_bf_supported(wdq) && gemm_h2_supported(wdq) && !no_combine;
+  r.combine = all3 && !gemm_bf_supported(wdq) && !no_combine && !r.own_dq && !c.bil;
+  r.late_dq = r.combine || r.own_dq;
   // Reduced-precision mode with a frozen image encoder (no dV) and all three consumers of dP_v / dP_q on gemm_bf.hip:
   // bwd_nat32 stores both as bf16 -- the GEMMs would round them on their way in anyway -- halving what it writes and
   // what they fetch.
@@ -435,327 +410,369 @@ int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLay
     TnGemm tv = tnv, tq = tnq;
     WGemm wq = wdq;
     tv.a_bf16 = tq.a_bf16 = wq.a_bf16 = 1;
-    tv.a_term = L == 3 ? (long)BNd : 0;
-    static const int off = (dev_env_int("COATTN_DP_BF16", 1) == 0);   // developer switch
-    if (!off && bf16_proj && !dV && L == 3 && d % 512 == 0 && dq32 && wdq_ok && tn_v && tn_q && gemm_bf_tn_supported(tv) &&
-        gemm_bf_tn_supported(tq) && gemm_bf_supported(wq)) {
-      ba.dp_bf16 = 1;
-      tnv.a_bf16 = tnq.a_bf16 = wdq.a_bf16 = 1;
-      tnq.a_sl = (long)BTd; wdq.a_sz = (long)BTd;   // (elements, as before)
-    }
+    tv.a_term = L == 3 ? (long)o.BNd : 0;
+    r.dp_bf16 = !dp_bf16_off && c.bf16_proj && !c.dV && L == 3 && d % 512 == 0 && all3 && gemm_bf_tn_supported(tv) &&
+                gemm_bf_tn_supported(tq) && gemm_bf_supported(wq);
+    if (r.dp_bf16) tnv.a_bf16 = tnq.a_bf16 = wdq.a_bf16 = 1;   // (a_sl, a_sz stay in elements)
   }
-  CA_TRY(launch_bwd_nat32(ba, s));                   // dP_q, dP_v, dw_v, db_v, db_q (coattn_bwd32.hip)
-  prof_mark(s, "bwd_nat32");
-  // 3. small parameter gradients from the per-(sample, level) partials (dw_v, db_v, db_q, dw_q, and dc_v, dc_q as
-  //    whole-array sums): a few short workgroups -- riding along in the weight-gradient launch of step 5 when that
-  //    is the hand-scheduled one, else a launch of their own
+  r.sum_in_gemm = r.tn_v && L == 3 && !c.dV;
+  if (r.sum_in_gemm) tnv.a_term = ko_sum3 ? 0 : (long)o.BNd;
+  r.bf_tn = r.tn_v && r.tn_q && gemm_bf_tn_supported(tnv) && gemm_bf_tn_supported(tnq);
+  if (!r.tn_v || !r.tn_q || r.bf_tn) return;
+  // two-piece width: 128 x 256 tiles on 512-thread workgroups (gemm_tn_wide.hip) -- the same split-K partition, pieces and
+  // order of products, so the same bits as the 128 x 128 kernel
+  r.wide = gemm_tn_wide_supported(tnv) && gemm_tn_wide_supported(tnq) &&
+           (!r.combine || (wdq.N % 256 == 0 && !wdq.f16 && (wdq.np == 2) == (tnv.np == 2)));
+  const bool red_al = (((int64_t)d * d) & 3) == 0 &&
+                      ((((uintptr_t)part) | ((uintptr_t)c.pg->dW_v) | ((uintptr_t)c.pg->dW_q)) & 15) == 0;
+  r.red_in_dq = r.late_dq && r.dq32 && red_in_dq && red_al;
+  // The forward left the bitmap of the question rows that are not all zeros in `saved` (exact mode; api.hip rowbits_in_saved):
+  // dW_q = sum dP_q^T Q then contracts over those rows only, and the launch shares its `budget` parts between dW_v and the
+  // levels of dW_q ON THE DEVICE (fused.h TnDyn) -- the partial sums are added by the dQ kernel's extra workgroups, which
+  // evaluate the same plan.
+  r.use_dyn = live_env && r.dyn_all.bits && r.wide && r.red_in_dq && tnq.K <= 8192 && !tnq.a_bf16 &&
+              (tnq.K + 31) / 32 <= kRowBitsMaxWords && budget > L && budget <= kMaxParts && L <= kDynLevels;
+}
+
+// 1. per-sample pre-pass: one launch for the question side and the da_v partials (and the live-row plan)
+int run_pre(const Ctx& c, const Route& r, const Off& o) {
+  const int N = c.N, d = c.d, L = c.L;
+  PreArgs pa;
+  pa.V = c.V; pa.v_sB = c.vl.sB; pa.gv = c.gv; pa.dav_out = c.ws + o.wo.part; pa.dav_lm = r.lm ? 1 : 0;
+  pa.dav_gx = r.lm ? (N + 15) / 16 : d / 64;
+  pa.dav_part = c.ws + o.wo.part;
+  pa.nkc = r.lm ? 1 : d / 64;
+  for (int l = 0; l < 8; ++l) pa.Q[l] = l < L ? c.Q[l] : nullptr;
+  pa.gq = c.gq; pa.av = c.saved + o.so.av; pa.aq = c.saved + o.so.aq;
+  pa.dsq = c.ws + o.wo.dsq; pa.dcs_part = c.ws + o.wo.dcs_part; pa.qlen = c.qlen; pa.dA = c.ws + o.wo.dA;
+  pa.gaq = c.g_aq;                                   // (coattn_backward_maps; NULL: the plain pre-pass)
+  pa.B = c.B; pa.N = N; pa.T = c.T; pa.d = d; pa.L = L;
+  pa.dyn = r.dyn_all; pa.plan_out = nullptr; pa.saved_bits = nullptr; pa.row_tag = nullptr;
+  if (r.dyn_all.bits) {
+    pa.saved_bits = reinterpret_cast<const unsigned*>(c.saved + o.so.rowbits);
+    pa.row_tag = reinterpret_cast<const unsigned*>(c.saved + o.so.rowcnt) + kRowTagWord;
+    pa.plan_out = reinterpret_cast<TnDynPlan*>(c.ws + o.wo.dynplan);
+  }
+  CA_TRY(launch_pre(pa, c.s));
+  prof_mark(c.s, "bwd_pre");
+  return 0;
+}
+
+// 2. the two recompute kernels' arguments (coattn_bwd32.hip)
+BwdArgs recompute_args(const Ctx& c, const Route& r, const Off& o) {
+  const float* saved = c.saved;
+  float* ws = c.ws;
+  BwdArgs ba;
+  ba.Pv = saved + o.so.Pv; ba.Pq = saved + o.so.Pq; ba.C = saved + o.so.C;
+  ba.Hq = saved + o.so.Hq; ba.dsq = ws + o.wo.dsq; ba.wq = (const float*)c.p->w_q; ba.dwq_part = ws + o.wo.dwq_part;
+  ba.dav_part = ws + o.wo.part; ba.nkc = r.lm ? 1 : c.d / 64; ba.av = saved + o.so.av; ba.dcs_part = ws + o.wo.dcs_part;
+  ba.wv = (const float*)c.p->w_v;
+  ba.dPv = ws + o.wo.dPv; ba.dPq = ws + o.wo.dPq; ba.dA = ws + o.wo.dA; ba.dwv_part = ws + o.wo.dwv_part;
+  ba.dbv_part = ws + o.wo.dbv_part; ba.dbq_part = ws + o.wo.dbq_part;
+  ba.B = c.B; ba.N = c.N; ba.T = c.T; ba.d = c.d; ba.L = c.L;
+  ba.bf16 = c.bf16_proj;
+  ba.np = r.np;
+  ba.ko_dpv = r.ko_dpv;
+  ba.dp_bf16 = 0;                                    // (bwd_dc32 stores neither; bwd_nat32: Route::dp_bf16)
+  ba.qlen = c.qlen;
+  ba.gav = c.g_av;                                   // (coattn_backward_maps; NULL: the kernels without the G_av operand)
+  return ba;
+}
+
+// 3. small parameter gradients from the per-(sample, level) partials (dw_v, db_v, db_q, dw_q; dc_v, dc_q as whole-array sums):
+//    a few short workgroups in the hand-scheduled weight-gradient launch, else a launch of their own (run_small_reductions)
+TnReduce small_reductions(const Ctx& c, const Off& o) {
   TnReduce small = {};
-  {
-    const float* src[4] = {ws + wo.dwv_part, ws + wo.dbv_part, ws + wo.dbq_part, ws + wo.dwq_part};
-    float* dst[4] = {(float*)pg->dw_v, (float*)pg->db_v, (float*)pg->db_q, (float*)pg->dw_q};
-    for (int i = 0; i < 4; ++i) { small.src[i] = src[i]; small.dst[i] = dst[i]; }
-    small.njobs = 4; small.nparts = L * B; small.n = d; small.accumulate = accumulate;
-    small.sum_x[0] = ws + wo.dcs_part; small.sum_x[1] = ws + wo.dcs_part + (size_t)L * B;
-    small.sum_out[0] = (float*)pg->dc_v; small.sum_out[1] = (float*)pg->dc_q; small.sum_n = (long)L * B;
+  const float* src[4] = {c.ws + o.wo.dwv_part, c.ws + o.wo.dbv_part, c.ws + o.wo.dbq_part, c.ws + o.wo.dwq_part};
+  float* dst[4] = {(float*)c.pg->dw_v, (float*)c.pg->db_v, (float*)c.pg->db_q, (float*)c.pg->dw_q};
+  for (int i = 0; i < 4; ++i) { small.src[i] = src[i]; small.dst[i] = dst[i]; }
+  small.njobs = 4; small.nparts = c.L * c.B; small.n = c.d; small.accumulate = c.accumulate;
+  small.sum_x[0] = c.ws + o.wo.dcs_part; small.sum_x[1] = c.ws + o.wo.dcs_part + (size_t)c.L * c.B;
+  small.sum_out[0] = (float*)c.pg->dc_v; small.sum_out[1] = (float*)c.pg->dc_q; small.sum_n = (long)c.L * c.B;
+  return small;
+}
+int run_small_reductions(const Ctx& c, const Off& o) {
+  const TnReduce small = small_reductions(c, o);
+  return launch_reduce_jobs(small.src, small.dst, 4, c.L * c.B, c.d, c.accumulate, c.s, small.sum_x, small.sum_out, small.sum_n);
+}
+
+// dQ_l (+)= dP_q,l W_q for all levels in one launch (batch z = level, C through the pointer table)
+int run_dq_projection(const Ctx& c, const Route& r, const Off& o, bool onto_dq) {
+  // (W_q split once by the forward's launch -- the same shape test decided there, api.hip general_projections --
+  //  and read as MFMA fragments, gemm_w.hip)
+  if (!onto_dq && r.wdq_ok) return launch_gemm_wx(&r.wdq, 1, c.s);
+  const int d = c.d;
+  coattn_gemm_desc g = {};
+  g.A = c.ws + o.wo.dPq; g.a_sz = (int64_t)o.BTd; g.a_sm = d; g.a_sk = 1;
+  g.B = c.p->W_q; g.b_sk = d; g.b_sn = 1;
+  for (int l = 0; l < c.L; ++l) { g.c_ptrs[l] = c.dQ[l]; if (onto_dq) g.cin_ptrs[l] = c.dQ[l]; }
+  if (onto_dq) { g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f; }
+  g.c_sm = d; g.c_sn = 1;
+  g.M = c.B * c.T; g.N = d; g.K = d; g.batch = c.L;
+  return launch_gemm_mode(g, c.bf16_proj, c.s);
+}
+
+template <int NT>
+void launch_dq_f32(bool lm, bool al, dim3 grid, size_t lds, hipStream_t s, const DqArgs& da) {
+  if (lm && al) hipLaunchKernelGGL((bwd_dq_kernel<NT, true, true>), grid, dim3(256), lds, s, da);
+  else if (lm) hipLaunchKernelGGL((bwd_dq_kernel<NT, false, true>), grid, dim3(256), lds, s, da);
+  else if (al) hipLaunchKernelGGL((bwd_dq_kernel<NT, true>), grid, dim3(256), lds, s, da);
+  else hipLaunchKernelGGL((bwd_dq_kernel<NT, false>), grid, dim3(256), lds, s, da);
+}
+
+// dst_l (+)= a_q,l (x) gq_l + dA_l V^T: the bf16-MFMA kernel (coattn_bwd32.hip; red != NULL: with the weight gradients' partial
+// sums in its launch) or the exact-f32 bwd_dq_kernel above
+int run_dq(const Ctx& c, const Route& r, const Off& o, float* const* dst, const float* gq, int accumulate, const RedJob* red) {
+  const int B = c.B, N = c.N, d = c.d, L = c.L;
+  DqArgs da = {};
+  da.accumulate = accumulate;
+  if (red && r.dq32) {
+    for (int i = 0; i < 2; ++i) { da.red_part[i] = red->part[i]; da.red_out[i] = red->out[i]; da.red_np[i] = red->np[i]; }
+    da.red_n = red->n; da.red_acc = red->acc; da.red_jobs = 2; da.red_blocks = (int)((red->n / 4 + 255) / 256);
+    da.red_dyn = red->dyn;
   }
-  auto small_reductions = [&]() -> int {
-    return launch_reduce_jobs(small.src, small.dst, 4, L * B, d, accumulate, s, small.sum_x, small.sum_out, small.sum_n);
-  };
-  // dQ_l (+)= dP_q,l W_q for all levels in one launch (batch z = level, C through the pointer table)
-  auto dq_projection = [&](bool onto_dq) -> int {
-    // (W_q split once by the forward's launch -- the same shape test decided there, api.hip general_projections --
-    //  and read as MFMA fragments, gemm_w.hip)
-    if (!onto_dq && wdq_ok) return launch_gemm_wx(&wdq, 1, s);
+  da.V = c.V; da.v_sB = c.vl.sB; da.dA = c.ws + o.wo.dA; da.aq = c.saved + o.so.aq; da.gq = gq;
+  for (int l = 0; l < 8; ++l) da.dQ[l] = l < L ? dst[l] : nullptr;
+  da.B = B; da.N = N; da.T = c.T; da.d = d; da.L = L;
+  da.bf16 = c.bf16_proj; da.np = r.np;
+  const bool al = (N % 4) == 0, lm = r.lm;
+  const dim3 grid(d / 128, B);
+  if (r.dq32) {
+    CA_TRY(launch_bwd_dq32(da, lm ? 1 : 0, c.s));
+  } else if (N <= 64) {
+    launch_dq_f32<4>(lm, al, grid, (size_t)(3 * kTRows * (64 + 4) + 96) * sizeof(float), c.s, da);
+  } else {
+    const size_t lds = (size_t)(3 * kTRows * (208 + 4) + 96) * sizeof(float);
+    static DeviceOnce once;
+    CA_TRY(once.run([&] {
+      hipError_t e = set_lds(bwd_dq_kernel<13, true>, lds);
+      if (e == hipSuccess) e = set_lds(bwd_dq_kernel<13, false>, lds);
+      if (e == hipSuccess) e = set_lds(bwd_dq_kernel<13, true, true>, lds);
+      if (e == hipSuccess) e = set_lds(bwd_dq_kernel<13, false, true>, lds);
+      return e;
+    }, "bwd_dq"));
+    launch_dq_f32<13>(lm, al, grid, lds, c.s, da);
+  }
+  CA_CHECK_LAUNCH("bwd_dq");
+  prof_mark(c.s, "bwd_dq");
+  return 0;
+}
+// the call's own dQ: added onto the projection by the bf16 kernel, written first by the exact-f32 one
+int run_own_dq(const Ctx& c, const Route& r, const Off& o, const RedJob* red = nullptr) {
+  return run_dq(c, r, o, c.dQ, c.gq, r.dq32 ? 1 : 0, red);
+}
+
+// one weight gradient on the hand-scheduled A^T B kernel (gemm_tn.hip): <= 32 split-K parts in g.C, then their sum
+int run_dw_tn(const Ctx& c, const TnGemm& g, float* dW) {
+  int ks, S;
+  const int parts = gemm_tn_plan(g, 32, &ks, &S);
+  CA_TRY(launch_gemm_tn(&g, &ks, &S, 1, c.s));
+  return launch_reduce_partials(g.C, dW, parts, (int64_t)c.d * c.d, c.accumulate, c.s);
+}
+
+// The bilinear affinity: dK = dA V (the dA V pass, into dK), then ONE projection dQ = [dP_q | dK] [W_q; W_b] (K = 2d) on the
+// pre-split-weight kernel, + a_q (x) gq; dW_b = sum_l dK_l^T Q_l on the weight-gradient kernel, db_b = column sums of dK.
+int run_bilinear_dq_dwb(const Ctx& c, const Route& r, const Off& o) {
+  const int B = c.B, T = c.T, d = c.d, L = c.L;
+  const BilBwd* bil = c.bil;
+  float* part = c.ws + o.wo.part;
+  float* dk_ptrs[8] = {};
+  for (int l = 0; l < L; ++l) dk_ptrs[l] = bil->dK + l * o.BTd;
+  if (hipMemsetAsync(bil->zeros, 0, (size_t)L * o.Bd * sizeof(float), c.s) != hipSuccess) {
+    coattn_set_error("fused backward: hipMemsetAsync failed");
+    return -3;
+  }
+  CA_TRY(run_dq(c, r, o, dk_ptrs, bil->zeros, 0, nullptr));          // dK = dA V + a_q (x) 0, overwritten
+  CA_TRY(launch_concat_cols(c.ws + o.wo.dPq, d, bil->dK, d, bil->dpk, (int64_t)L * B * T, c.s));
+  CA_TRY(launch_concat_cols((const float*)c.p->W_q, d * d, bil->Wb, d * d, bil->wstack, 1, c.s));
+  WGemm wj = dq_proj_job(B, T, d, L, 0, r.np);
+  wj.K = 2 * d; wj.a_sm = 2 * d; wj.a_sz = 2 * (long)o.BTd; wj.A = bil->dpk; wj.Wf = bil->wimg;
+  for (int l = 0; l < L; ++l) wj.c_ptrs[l] = c.dQ[l];
+  if (c.wgemm && gemm_w_supported(wj)) {
+    const WSplit job{bil->wstack, bil->wimg, d, 2 * d, 1, d, wimg_pieces(wj), nullptr};
+    CA_TRY(launch_wsplit(&job, 1, c.s));
+    CA_TRY(launch_gemm_wx(&wj, 1, c.s));
+  } else {
     coattn_gemm_desc g = {};
-    g.A = ws + wo.dPq; g.a_sz = (int64_t)BTd; g.a_sm = d; g.a_sk = 1;
-    g.B = p->W_q; g.b_sk = d; g.b_sn = 1;
-    for (int l = 0; l < L; ++l) { g.c_ptrs[l] = dQ[l]; if (onto_dq) g.cin_ptrs[l] = dQ[l]; }
-    if (onto_dq) { g.cin_sm = d; g.cin_sn = 1; g.beta = 1.f; }
+    g.A = bil->dpk; g.a_sz = 2 * (int64_t)o.BTd; g.a_sm = 2 * d; g.a_sk = 1;
+    g.B = bil->wstack; g.b_sk = d; g.b_sn = 1;
+    for (int l = 0; l < L; ++l) g.c_ptrs[l] = c.dQ[l];
     g.c_sm = d; g.c_sn = 1;
-    g.M = B * T; g.N = d; g.K = d; g.batch = L;
-    return gemm_proj(g);
-  };
-  // 4. dQ_l = a_q (x) gq + dA V^T + dP_q W_q ;  dV = sum_l (a_v (x) gv + Q^T dA) + (sum_l dP_v) W_v
-  //    The projection writes dQ first and the bf16 dA V kernel adds onto it (the GEMM is 24 us faster without an
-  //    accumulate input); channel-major features with unaligned rows (N % 4 != 0): the exact-f32 kernel first, then
-  //    the projection onto it.
-  //    When the projection shares the weight-gradient launch (step 5), the dA V kernel runs after that launch.
-  // (red: the two weight gradients' partial sums, handed to the dQ kernel's launch when it is the bf16-MFMA one)
-  struct RedJob { const float* part[2]; float* out[2]; int np[2]; long n; int acc; bool on; TnDyn dyn; } red = {};
-  static const int red_in_dq = dev_env_int("COATTN_RED_IN_DQ", 1);   // developer switch
-  // dst / gq_ / acc (bilinear's dK pass: dK = dA V + a_q (x) 0, overwritten): the dQ pointers, gq and the accumulate of the plain call
-  auto run_dq = [&](float* const* dst = nullptr, const float* gq_ = nullptr, int acc = -1) -> int {
-    DqArgs da = {};
-    da.accumulate = acc >= 0 ? acc : (dq32 ? 1 : 0);
-    if (red.on && dq32) {
-      for (int i = 0; i < 2; ++i) { da.red_part[i] = red.part[i]; da.red_out[i] = red.out[i]; da.red_np[i] = red.np[i]; }
-      da.red_n = red.n; da.red_acc = red.acc; da.red_jobs = 2; da.red_blocks = (int)((red.n / 4 + 255) / 256);
-      da.red_dyn = red.dyn;
-    }
-    da.V = V; da.v_sB = vl.sB; da.dA = ws + wo.dA; da.aq = saved + so.aq; da.gq = gq_ ? gq_ : gq;
-    for (int l = 0; l < 8; ++l) da.dQ[l] = l < L ? (dst ? dst[l] : dQ[l]) : nullptr;
-    da.B = B; da.N = N; da.T = T; da.d = d; da.L = L;
-    da.bf16 = bf16_proj; da.np = np;
-    const bool al = (N % 4) == 0;
-    dim3 grid(d / 128, B), block(256);
-    if (dq32) {
-      CA_TRY(launch_bwd_dq32(da, lm ? 1 : 0, s));    // bf16 MFMA kernel (coattn_bwd32.hip)
-    } else if (small_n) {
-      const size_t lds = (size_t)(3 * kTRows * (64 + 4) + 96) * sizeof(float);
-      if (lm && al) hipLaunchKernelGGL((bwd_dq_kernel<4, true, true>), grid, block, lds, s, da);
-      else if (lm) hipLaunchKernelGGL((bwd_dq_kernel<4, false, true>), grid, block, lds, s, da);
-      else if (al) hipLaunchKernelGGL((bwd_dq_kernel<4, true>), grid, block, lds, s, da);
-      else hipLaunchKernelGGL((bwd_dq_kernel<4, false>), grid, block, lds, s, da);
-    } else {
-      const size_t lds = (size_t)(3 * kTRows * (208 + 4) + 96) * sizeof(float);
-      static DeviceOnce once;
-      CA_TRY(once.run([&] {
-        hipError_t e = set_lds(bwd_dq_kernel<13, true>, lds);
-        if (e == hipSuccess) e = set_lds(bwd_dq_kernel<13, false>, lds);
-        if (e == hipSuccess) e = set_lds(bwd_dq_kernel<13, true, true>, lds);
-        if (e == hipSuccess) e = set_lds(bwd_dq_kernel<13, false, true>, lds);
-        return e;
-      }, "bwd_dq"));
-      if (lm && al) hipLaunchKernelGGL((bwd_dq_kernel<13, true, true>), grid, block, lds, s, da);
-      else if (lm) hipLaunchKernelGGL((bwd_dq_kernel<13, false, true>), grid, block, lds, s, da);
-      else if (al) hipLaunchKernelGGL((bwd_dq_kernel<13, true>), grid, block, lds, s, da);
-      else hipLaunchKernelGGL((bwd_dq_kernel<13, false>), grid, block, lds, s, da);
-    }
-    CA_CHECK_LAUNCH("bwd_dq");
-    prof_mark(s, "bwd_dq");
-    return 0;
-  };
-  if (bil) {
-    // The bilinear affinity: dK = dA V (the dA V pass, into dK), then ONE projection dQ = [dP_q | dK] [W_q; W_b] (K = 2d) on the
-    // pre-split-weight kernel, + a_q (x) gq; dW_b = sum_l dK_l^T Q_l on the weight-gradient kernel, db_b = column sums of dK.
-    float* dk_ptrs[8] = {};
-    for (int l = 0; l < L; ++l) dk_ptrs[l] = bil->dK + l * BTd;
-    if (hipMemsetAsync(bil->zeros, 0, (size_t)L * Bd * sizeof(float), s) != hipSuccess) {
-      coattn_set_error("fused backward: hipMemsetAsync failed");
-      return -3;
-    }
-    CA_TRY(run_dq(dk_ptrs, bil->zeros, 0));
-    CA_TRY(launch_concat_cols(ws + wo.dPq, d, bil->dK, d, bil->dpk, (int64_t)L * B * T, s));
-    CA_TRY(launch_concat_cols((const float*)p->W_q, d * d, bil->Wb, d * d, bil->wstack, 1, s));
-    WGemm wj = dq_proj_job(B, T, d, L, 0, np);
-    wj.K = 2 * d; wj.a_sm = 2 * d; wj.a_sz = 2 * (long)BTd; wj.A = bil->dpk; wj.Wf = bil->wimg;
-    for (int l = 0; l < L; ++l) wj.c_ptrs[l] = dQ[l];
-    if (wgemm && gemm_w_supported(wj)) {
-      const WSplit job{bil->wstack, bil->wimg, d, 2 * d, 1, d, wimg_pieces(wj), nullptr};
-      CA_TRY(launch_wsplit(&job, 1, s));
-      CA_TRY(launch_gemm_wx(&wj, 1, s));
-    } else {
-      coattn_gemm_desc g = {};
-      g.A = bil->dpk; g.a_sz = 2 * (int64_t)BTd; g.a_sm = 2 * d; g.a_sk = 1;
-      g.B = bil->wstack; g.b_sk = d; g.b_sn = 1;
-      for (int l = 0; l < L; ++l) g.c_ptrs[l] = dQ[l];
-      g.c_sm = d; g.c_sn = 1;
-      g.M = B * T; g.N = d; g.K = 2 * d; g.batch = L;
-      CA_TRY(launch_gemm_f32(g, s));
-    }
-    for (int l = 0; l < L; ++l)
-      CA_TRY(launch_rank1(saved + so.aq + (size_t)l * B * T, gq + l * Bd, dQ[l], B, T, d, (int64_t)T * d, d, 1, 1, s));
-    prof_mark(s, "bwd_bilinear_dq");
-    TnGemm tnb = tnq;
+    g.M = B * T; g.N = d; g.K = 2 * d; g.batch = L;
+    CA_TRY(launch_gemm_f32(g, c.s));
+  }
+  for (int l = 0; l < L; ++l)
+    CA_TRY(launch_rank1(c.saved + o.so.aq + (size_t)l * B * T, c.gq + l * o.Bd, c.dQ[l], B, T, d, (int64_t)T * d, d, 1, 1, c.s));
+  prof_mark(c.s, "bwd_bilinear_dq");
+  if (r.tn_q) {
+    TnGemm tnb = r.tnq;
     tnb.A = bil->dK; tnb.a_bf16 = 0; tnb.C = part;
-    if (tn_q) {
-      int ks, S;
-      const int parts = gemm_tn_plan(tnb, 32, &ks, &S);
-      CA_TRY(launch_gemm_tn(&tnb, &ks, &S, 1, s));
-      CA_TRY(launch_reduce_partials(part, bil->dWb, parts, (int64_t)d * d, accumulate, s));
-    } else {
-      for (int l = 0; l < L; ++l) {
-        const int K = B * T;
-        int ks = (K + 31) / 32;
-        ks = (ks + 15) / 16 * 16;
-        const int S = (K + ks - 1) / ks;
-        coattn_gemm_desc g = {};
-        g.A = bil->dK + l * BTd; g.a_sm = 1; g.a_sk = d;
-        g.B = Q[l]; g.b_sk = d; g.b_sn = 1;
-        g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
-        g.M = d; g.N = d; g.K = K; g.batch = S; g.ksplit = ks;
-        CA_TRY(launch_gemm_f32(g, s));
-        CA_TRY(launch_reduce_partials(part, bil->dWb, S, (int64_t)d * d, (accumulate || l > 0) ? 1 : 0, s));
-      }
-    }
-    {
-      const int R = L * B * T;
-      const int rpc = (R + 255) / 256 > 32 ? (R + 255) / 256 : 32;
-      int nch = 0;
-      CA_TRY(launch_colsum_partial(nullptr, bil->dK, part, R, d, rpc, &nch, s));
-      CA_TRY(launch_reduce_partials(part, bil->dbb, nch, d, accumulate, s));
-    }
-    prof_mark(s, "bwd_bilinear_dwb");
+    CA_TRY(run_dw_tn(c, tnb, bil->dWb));
+    CA_TRY(grad_colsum(nullptr, bil->dK, L * B * T, d, part, bil->dbb, c.accumulate, c.s));
   } else {
-    if (dq32 && !late_dq) {
-      CA_TRY(dq_projection(false));
-      prof_mark(s, "bwd_gemm_dq_projection");
-    }
-    if (!late_dq) CA_TRY(run_dq());
+    CA_TRY(grad_bilinear_wb(bil->dK, c.Q, B, T, d, L, part, bil->dWb, bil->dbb, c.accumulate, c.s));
   }
-  if (dV) {
-    for (int l = 0; l < L; ++l) {
-      const float* dA = ws + wo.dA + l * BTN;
-      const float* av = saved + so.av + (size_t)l * B * N;
-      CA_TRY(launch_rank1(av, gv + l * Bd, dV, B, N, d, dvl.sB, dvl.sN, dvl.sD, l > 0 ? 1 : 0, s));
-      coattn_gemm_desc g = {};
-      g.A = bil ? bil->K + l * BTd : Q[l]; g.a_sz = (int64_t)T * d; g.a_sm = 1; g.a_sk = d;   // (bilinear: dA^T K)
-      g.B = dA; g.b_sz = (int64_t)T * N; g.b_sk = N; g.b_sn = 1;
-      g.Cin = dV; g.cin_sz = dvl.sB; g.cin_sm = dvl.sD; g.cin_sn = dvl.sN; g.beta = 1.f;
-      g.C = dV; g.c_sz = dvl.sB; g.c_sm = dvl.sD; g.c_sn = dvl.sN;
-      g.M = d; g.N = N; g.K = T; g.batch = B;
-      CA_TRY(launch_gemm_f32(g, s));
-    }
-  }
-  if (!dq32 && !bil) CA_TRY(dq_projection(true));
-  // sum dP_v over the levels in place into level 0 (one streaming pass for L = 3; folding the sum into
-  // the weight-gradient GEMM's operand loads was measured slower: 302 vs 170 + 50 us)
-  // (the frozen-encoder default needs no dV: the weight-gradient kernel then adds the three levels while staging them)
-  const bool sum_in_gemm = tn_v && L == 3 && !dV;
-  if (sum_in_gemm) {
-    tnv.a_term = ko_sum3 ? 0 : (long)BNd;
-  } else if (L == 3) {
-    CA_TRY(launch_add3_inplace(dPv, dPv + BNd, dPv + 2 * BNd, (int64_t)BNd, s));
-  } else {
-    for (int l = 1; l < L; ++l) CA_TRY(launch_add_inplace(dPv, dPv + l * BNd, (int64_t)BNd, 1, s));
-  }
-  if (dV) {
-    // dV[b][k][n] += sum_j W_v[j][k] dP_v[b][n][j]
-    coattn_gemm_desc g = {};
-    g.A = p->W_v; g.a_sm = 1; g.a_sk = d; g.a_sz = 0;
-    g.B = dPv; g.b_sz = (int64_t)N * d; g.b_sk = 1; g.b_sn = d;
-    g.Cin = dV; g.cin_sz = dvl.sB; g.cin_sm = dvl.sD; g.cin_sn = dvl.sN; g.beta = 1.f;
-    g.C = dV; g.c_sz = dvl.sB; g.c_sm = dvl.sD; g.c_sn = dvl.sN;
-    g.M = d; g.N = N; g.K = d; g.batch = B;
-    CA_TRY(gemm_proj(g));
-  }
-  // 5. weight gradients
-  if (tn_v && tn_q && gemm_bf_tn_supported(tnv) && gemm_bf_tn_supported(tnq)) {
-    // reduced-precision mode at wide shapes (config 4): the single-product kernel of gemm_bf.hip, 256 x 256 tiles; the
-    // parts of the two products share two rounds of workgroups in proportion to their contraction lengths
-    const int ntiles = (d / 256) * (d / 256);
-    int total = (bf_tn_rounds() * 256 + ntiles - 1) / ntiles;
-    total = total < 2 ? 2 : (total > kMaxParts ? kMaxParts : total);
-    const double kv = (double)B * N, kq = (double)L * B * T;
-    int pv = (int)(total * kv / (kv + kq) + 0.5);
-    pv = pv < 1 ? 1 : (pv > total - 1 ? total - 1 : pv);
-    int spp[2], parts[2];
-    parts[0] = gemm_bf_tn_plan(tnv, pv, &spp[0]);
-    tnq.C = part + (size_t)parts[0] * d * d;
-    parts[1] = gemm_bf_tn_plan(tnq, total - pv, &spp[1]);
-    CA_CHECK_ARG(parts[0] + parts[1] <= kMaxParts, "fused backward: %d split-K parts exceed the workspace", parts[0] + parts[1]);
-    CA_TRY(small_reductions());
-    const TnGemm both[2] = {tnv, tnq};
-    CA_TRY(launch_gemm_bf_tn(both, spp, parts, 2, s));
-    prof_mark(s, "bwd_gemm_dw");
-    if (combine) CA_TRY(run_dq());
-    CA_TRY(launch_reduce_partials2(part, (float*)pg->dW_v, parts[0], tnq.C, (float*)pg->dW_q, parts[1], (int64_t)d * d,
-                                   accumulate, s));
-    prof_mark(s, "reduce_partials");
-    return 0;
-  }
-  if (tn_v && tn_q) {
-    // both weight gradients in one launch: 32 split-K parts (x 16 tiles = the 512 workgroup slots) shared in
-    // proportion to the contraction lengths, so that all workgroups run about equally long
-    const double kv = (double)B * N, kq = (double)L * B * T;
-    const int budget = tn_budget;
-    int pv = (int)((double)budget * kv / (kv + kq) + 0.5);
-    pv = pv < 1 ? 1 : (pv > budget - 1 ? budget - 1 : pv);
-    const int pq = (budget - pv) / L > 0 ? (budget - pv) / L * L : L;
-    int ks[2], S[2];
-    // two-piece width: 128 x 256 tiles on 512-thread workgroups (gemm_tn_wide.hip) -- the same split-K partition, pieces and
-    // order of products, so the same bits as the 128 x 128 kernel
-    const bool wide = gemm_tn_wide_supported(tnv) && gemm_tn_wide_supported(tnq) && (!combine || (wdq.N % 256 == 0 && !wdq.f16 && (wdq.np == 2) == (tnv.np == 2)));
-    const bool red_al = (((int64_t)d * d) & 3) == 0 && ((((uintptr_t)part) | ((uintptr_t)pg->dW_v) | ((uintptr_t)pg->dW_q)) & 15) == 0;
-    // The forward left the bitmap of the question rows that are not all zeros in `saved` (exact mode; api.hip rowbits_in_saved):
-    // dW_q = sum dP_q^T Q then contracts over those rows only, and the launch shares its `budget` parts between dW_v and the
-    // levels of dW_q ON THE DEVICE (fused.h TnDyn) -- the partial sums are added by the dQ kernel's extra workgroups, which
-    // evaluate the same plan.  COATTN_DW_LIVE_ROWS=0 (developer switch): the host's static plan over all rows.
-    static const int live_env = dev_env_int("COATTN_DW_LIVE_ROWS", 1);
-    TnDyn dyn = {};
-    const bool use_dyn = live_env && dyn_all.bits && wide && late_dq && dq32 && red_in_dq && red_al && tnq.K <= 8192 && !tnq.a_bf16 &&
-                         (tnq.K + 31) / 32 <= kRowBitsMaxWords && budget > L && budget <= kMaxParts && L <= kDynLevels;
-    if (use_dyn) dyn = dyn_all;
-    const int parts_v = wide ? gemm_tn_wide_plan(tnv, pv, &ks[0], &S[0]) : gemm_tn_plan(tnv, pv, &ks[0], &S[0]);
-    tnq.C = use_dyn ? part : part + (size_t)parts_v * d * d;
-    const int parts_q = wide ? gemm_tn_wide_plan(tnq, pq, &ks[1], &S[1]) : gemm_tn_plan(tnq, pq, &ks[1], &S[1]);
-    CA_CHECK_ARG(parts_v + parts_q <= kMaxParts, "fused backward: %d split-K parts exceed the workspace", parts_v + parts_q);
-    const TnGemm both[2] = {tnv, tnq};
-    if (wide) CA_TRY(launch_gemm_tn_wide(both, ks, S, 2, s, &small, combine ? &wdq : nullptr, use_dyn ? &dyn : nullptr));
-    else CA_TRY(launch_gemm_tn(both, ks, S, 2, s, &small, combine ? &wdq : nullptr));
-    prof_mark(s, combine ? "bwd_gemm" : "bwd_gemm_dw");
-    if (own_dq) {
-      CA_TRY(dq_projection(false));
-      prof_mark(s, "bwd_gemm_dq_projection");
-    }
-    if (late_dq && dq32 && red_in_dq && red_al) {       // the partial sums ride in the dQ kernel's launch
-      red.part[0] = part; red.out[0] = (float*)pg->dW_v; red.np[0] = parts_v;
-      red.part[1] = tnq.C; red.out[1] = (float*)pg->dW_q; red.np[1] = parts_q;
-      red.n = (long)d * d; red.acc = accumulate; red.on = true; red.dyn = dyn;
-      return run_dq();
-    }
-    if (late_dq) CA_TRY(run_dq());
-    CA_TRY(launch_reduce_partials2(part, (float*)pg->dW_v, parts_v, tnq.C, (float*)pg->dW_q, parts_q, (int64_t)d * d,
-                                   accumulate, s));
-    prof_mark(s, "reduce_partials");
-    return 0;
-  }
-  tnq.C = part;
-  CA_TRY(small_reductions());
-  {
-    // dW_v[j][k] = sum_{b,n} dP_v[b][n][j] V[b][k][n]
-    coattn_gemm_desc g = {};
-    int S;
-    if (tn_v) {
-      // both operands row-major over the B*N contraction rows: the hand-scheduled A^T B kernel (gemm_tn.hip)
-      int ks;
-      const int parts = gemm_tn_plan(tnv, 32, &ks, &S);
-      CA_TRY(launch_gemm_tn(&tnv, &ks, &S, 1, s));
-      CA_TRY(launch_reduce_partials(part, (float*)pg->dW_v, parts, (int64_t)d * d, accumulate, s));
-    } else {
-    if (lm && vl.sB == (long)N * d) {
-      // location-major, samples abutting: one flat contraction over m = (b, n), split-K over the B*N rows
-      const int K = B * N;
-      int ks = (K + 31) / 32;
-      ks = (ks + 15) / 16 * 16;
-      S = (K + ks - 1) / ks;
-      g.A = dPv; g.a_sm = 1; g.a_sk = d;
-      g.B = V; g.b_sk = d; g.b_sn = 1;
-      g.M = d; g.N = d; g.K = K; g.batch = S; g.ksplit = ks;
-    } else {
-      // inner index = sample, split into <= 32 groups
-      const int G = (B + 31) / 32;
-      S = (B + G - 1) / G;
-      g.A = dPv; g.a_sm = 1; g.a_sk = d; g.a_si = (int64_t)N * d; g.a_sz = (int64_t)G * N * d;
-      g.B = V; g.b_sk = vl.sN; g.b_sn = vl.sD; g.b_si = vl.sB; g.b_sz = (int64_t)G * vl.sB;
-      g.M = d; g.N = d; g.K = N; g.batch = S; g.inner = G; g.inner_total = B;
-    }
-    g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
-    CA_TRY(gemm_proj(g));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->dW_v, S, (int64_t)d * d, accumulate, s));
-    }
-  }
-  {
-    // dW_q[j][k] = sum_l sum_m dP_q,l[m][j] Q_l[m][k]: levels as the inner loop (B from the pointer
-    // table), split-K over the B*T rows
-    const int K = B * T;
-    if (tn_q) {
-      int ks, S;
-      const int parts = gemm_tn_plan(tnq, 32, &ks, &S);
-      CA_TRY(launch_gemm_tn(&tnq, &ks, &S, 1, s));
-      return launch_reduce_partials(part, (float*)pg->dW_q, parts, (int64_t)d * d, accumulate, s);
-    }
-    int ks = (K + 31) / 32;
-    ks = (ks + 15) / 16 * 16;
-    const int S = (K + ks - 1) / ks;
-    coattn_gemm_desc g = {};
-    g.A = ws + wo.dPq; g.a_sm = 1; g.a_sk = d; g.a_si = (int64_t)BTd;
-    for (int l = 0; l < L; ++l) g.b_ptrs[l] = Q[l];
-    g.ptr_by_inner = 1; g.b_sk = d; g.b_sn = 1;
-    g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
-    g.M = d; g.N = d; g.K = K; g.batch = S; g.ksplit = ks; g.inner = L;
-    CA_TRY(gemm_proj(g));
-    CA_TRY(launch_reduce_partials(part, (float*)pg->dW_q, S, (int64_t)d * d, accumulate, s));
+  prof_mark(c.s, "bwd_bilinear_dwb");
+  return 0;
+}
+
+// dV = sum_l (a_v,l (x) gv_l + Q_l^T dA_l)   (bilinear: K_l^T dA_l);  (sum_l dP_v) W_v is added by run_sum_dpv
+int run_dv(const Ctx& c, const Off& o) {
+  for (int l = 0; l < c.L; ++l) {
+    const float* av = c.saved + o.so.av + (size_t)l * c.B * c.N;
+    CA_TRY(launch_rank1(av, c.gv + l * o.Bd, c.dV, c.B, c.N, c.d, c.dvl.sB, c.dvl.sN, c.dvl.sD, l > 0 ? 1 : 0, c.s));
+    CA_TRY(grad_dv_kt_da(c.bil ? c.bil->K + l * o.BTd : c.Q[l], c.ws + o.wo.dA + l * o.BTN, c.dV, c.dvl, c.B, c.N, c.T, c.d, c.s));
   }
   return 0;
+}
+
+// sum dP_v over the levels in place into level 0 (one streaming pass for L = 3; folding the sum into the weight-gradient
+// GEMM's operand loads was measured slower: 302 vs 170 + 50 us) -- unless the weight-gradient kernel adds them itself
+// (Route::sum_in_gemm) -- then dV += (sum_l dP_v) W_v
+int run_sum_dpv(const Ctx& c, const Route& r, const Off& o) {
+  float* dPv = c.ws + o.wo.dPv;
+  const int64_t BNd = (int64_t)o.BNd;
+  if (!r.sum_in_gemm && c.L == 3) CA_TRY(launch_add3_inplace(dPv, dPv + BNd, dPv + 2 * BNd, BNd, c.s));
+  if (!r.sum_in_gemm && c.L != 3)
+    for (int l = 1; l < c.L; ++l) CA_TRY(launch_add_inplace(dPv, dPv + l * BNd, BNd, 1, c.s));
+  if (c.dV) CA_TRY(grad_dv_wv(c.p->W_v, dPv, c.dV, c.dvl, c.B, c.N, c.d, c.bf16_proj, c.s));
+  return 0;
+}
+
+// 5a. weight gradients, reduced-precision mode at wide shapes (config 4): the single-product kernel of gemm_bf.hip, 256 x 256
+// tiles; the parts of the two products share two rounds of workgroups in proportion to their contraction lengths
+int run_dw_bf_tn(const Ctx& c, const Route& r, const Off& o) {
+  const int B = c.B, d = c.d;
+  float* part = c.ws + o.wo.part;
+  TnGemm both[2] = {r.tnv, r.tnq};
+  const int ntiles = (d / 256) * (d / 256);
+  int total = (bf_tn_rounds() * 256 + ntiles - 1) / ntiles;
+  total = total < 2 ? 2 : (total > kMaxParts ? kMaxParts : total);
+  const double kv = (double)B * c.N, kq = (double)c.L * B * c.T;
+  int pv = (int)(total * kv / (kv + kq) + 0.5);
+  pv = pv < 1 ? 1 : (pv > total - 1 ? total - 1 : pv);
+  int spp[2], parts[2];
+  parts[0] = gemm_bf_tn_plan(both[0], pv, &spp[0]);
+  both[1].C = part + (size_t)parts[0] * d * d;
+  parts[1] = gemm_bf_tn_plan(both[1], total - pv, &spp[1]);
+  CA_CHECK_ARG(parts[0] + parts[1] <= kMaxParts, "fused backward: %d split-K parts exceed the workspace", parts[0] + parts[1]);
+  CA_TRY(run_small_reductions(c, o));
+  CA_TRY(launch_gemm_bf_tn(both, spp, parts, 2, c.s));
+  prof_mark(c.s, "bwd_gemm_dw");
+  if (r.combine) CA_TRY(run_own_dq(c, r, o));
+  CA_TRY(launch_reduce_partials2(part, (float*)c.pg->dW_v, parts[0], both[1].C, (float*)c.pg->dW_q, parts[1], (int64_t)d * d,
+                                 c.accumulate, c.s));
+  prof_mark(c.s, "reduce_partials");
+  return 0;
+}
+
+// 5b. both weight gradients in one launch: 32 split-K parts (x 16 tiles = the 512 workgroup slots) shared in proportion to the
+// contraction lengths, so that all workgroups run about equally long; with them the small reductions and (Route::combine) the
+// dQ projection's tiles; behind them the late dQ pass, which adds the partial sums (Route::red_in_dq)
+int run_dw_tn_pair(const Ctx& c, const Route& r, const Off& o) {
+  const int B = c.B, d = c.d, L = c.L;
+  float* part = c.ws + o.wo.part;
+  TnGemm both[2] = {r.tnv, r.tnq};
+  const TnReduce small = small_reductions(c, o);
+  const double kv = (double)B * c.N, kq = (double)L * B * c.T;
+  const int budget = r.tn_budget;
+  int pv = (int)((double)budget * kv / (kv + kq) + 0.5);
+  pv = pv < 1 ? 1 : (pv > budget - 1 ? budget - 1 : pv);
+  const int pq = (budget - pv) / L > 0 ? (budget - pv) / L * L : L;
+  int ks[2], S[2];
+  const int parts_v = r.wide ? gemm_tn_wide_plan(both[0], pv, &ks[0], &S[0]) : gemm_tn_plan(both[0], pv, &ks[0], &S[0]);
+  both[1].C = r.use_dyn ? part : part + (size_t)parts_v * d * d;
+  const int parts_q = r.wide ? gemm_tn_wide_plan(both[1], pq, &ks[1], &S[1]) : gemm_tn_plan(both[1], pq, &ks[1], &S[1]);
+  CA_CHECK_ARG(parts_v + parts_q <= kMaxParts, "fused backward: %d split-K parts exceed the workspace", parts_v + parts_q);
+  const WGemm* wextra = r.combine ? &r.wdq : nullptr;
+  if (r.wide) CA_TRY(launch_gemm_tn_wide(both, ks, S, 2, c.s, &small, wextra, r.use_dyn ? &r.dyn_all : nullptr));
+  else CA_TRY(launch_gemm_tn(both, ks, S, 2, c.s, &small, wextra));
+  prof_mark(c.s, r.combine ? "bwd_gemm" : "bwd_gemm_dw");
+  if (r.own_dq) {
+    CA_TRY(run_dq_projection(c, r, o, false));
+    prof_mark(c.s, "bwd_gemm_dq_projection");
+  }
+  if (r.red_in_dq) {
+    RedJob red = {};
+    red.part[0] = part; red.out[0] = (float*)c.pg->dW_v; red.np[0] = parts_v;
+    red.part[1] = both[1].C; red.out[1] = (float*)c.pg->dW_q; red.np[1] = parts_q;
+    red.n = (long)d * d; red.acc = c.accumulate;
+    if (r.use_dyn) red.dyn = r.dyn_all;
+    return run_own_dq(c, r, o, &red);
+  }
+  if (r.late_dq) CA_TRY(run_own_dq(c, r, o));
+  CA_TRY(launch_reduce_partials2(part, (float*)c.pg->dW_v, parts_v, both[1].C, (float*)c.pg->dW_q, parts_q, (int64_t)d * d,
+                                 c.accumulate, c.s));
+  prof_mark(c.s, "reduce_partials");
+  return 0;
+}
+
+// 5c. the weight gradients one by one: each on the hand-scheduled A^T B kernel (gemm_tn.hip) if it takes the job, else on the
+// general GEMM
+int run_dw_separate(const Ctx& c, const Route& r, const Off& o) {
+  const int B = c.B, N = c.N, d = c.d;
+  float* part = c.ws + o.wo.part;
+  float* dPv = c.ws + o.wo.dPv;
+  CA_TRY(run_small_reductions(c, o));
+  // dW_v[j][k] = sum_{b,n} dP_v[b][n][j] V[b][k][n]
+  if (r.tn_v) {
+    CA_TRY(run_dw_tn(c, r.tnv, (float*)c.pg->dW_v));
+  } else if (r.lm && c.vl.sB == (long)N * d) {
+    // location-major, samples abutting: one flat contraction over m = (b, n), split-K over the B*N rows
+    CA_TRY(grad_dw_splitk(dPv, c.V, B * N, d, part, (float*)c.pg->dW_v, c.accumulate, c.bf16_proj, c.s));
+  } else {
+    CA_TRY(grad_dw_sample_groups(dPv, c.V, c.vl, B, N, d, part, (float*)c.pg->dW_v, c.accumulate, c.bf16_proj, c.s));
+  }
+  // dW_q[j][k] = sum_l sum_m dP_q,l[m][j] Q_l[m][k]: levels as the inner loop, split-K over the B*T rows
+  if (r.tn_q) {
+    TnGemm tnq = r.tnq;
+    tnq.C = part;
+    return run_dw_tn(c, tnq, (float*)c.pg->dW_q);
+  }
+  return grad_dw_splitk(c.ws + o.wo.dPq, nullptr, B * c.T, d, part, (float*)c.pg->dW_q, c.accumulate, c.bf16_proj, c.s, c.Q, c.L,
+                        (long)o.BTd);
+}
+
+}  // namespace
+
+size_t fused_bwd_ws_floats(int B, int N, int T, int d, int L) { return fused_bwd_off(B, N, T, d, L).total; }
+
+int fused_backward_supported(int B, int N, int T, int d, int L) { return fused_supported(B, N, T, d, L); }
+
+// dQ_l = a_q (x) gq + dA V^T + dP_q W_q ;  dV = sum_l (a_v (x) gv + Q^T dA) + (sum_l dP_v) W_v.  The projection writes dQ first
+// and the bf16 dA V kernel adds onto it (the GEMM is 24 us faster without an accumulate input); channel-major features with
+// unaligned rows (N % 4 != 0): the exact-f32 kernel first, then the projection onto it.  When the projection shares the
+// weight-gradient launch (Route::late_dq), the dA V kernel runs after that launch.
+int fused_backward(const Ctx& c) {
+  const int B = c.B, N = c.N, T = c.T, d = c.d, L = c.L;
+  CA_CHECK_ARG(fused_backward_supported(B, N, T, d, L), "fused backward: unsupported shape");
+  CA_CHECK_ARG(v_is_lm(c.vl, N, d) || v_is_cm(c.vl, N, d),
+               "fused backward: image features must be channel-major [B,d,N] or location-major [B,N,d]");
+  CA_CHECK_ARG(N <= 256, "fused backward: N > 256");
+  const Off o{saved_off(B, N, T, d, L), fused_bwd_off(B, N, T, d, L), (size_t)B * T * d, (size_t)B * T * N, (size_t)B * N * d,
+              (size_t)B * d};
+  Route r;
+  decide_route(c, o, r);
+  CA_TRY(run_pre(c, r, o));
+  BwdArgs ba = recompute_args(c, r, o);
+  CA_TRY(launch_bwd_dc32(ba, c.s));                  // dC, dA
+  prof_mark(c.s, "bwd_dc32");
+  ba.dp_bf16 = r.dp_bf16 ? 1 : 0;
+  CA_TRY(launch_bwd_nat32(ba, c.s));                 // dP_q, dP_v, dw_v, db_v, db_q
+  prof_mark(c.s, "bwd_nat32");
+  if (c.bil) {
+    CA_TRY(run_bilinear_dq_dwb(c, r, o));
+  } else if (!r.late_dq) {
+    if (r.dq32) {
+      CA_TRY(run_dq_projection(c, r, o, false));
+      prof_mark(c.s, "bwd_gemm_dq_projection");
+    }
+    CA_TRY(run_own_dq(c, r, o));
+  }
+  if (c.dV) CA_TRY(run_dv(c, o));
+  if (!r.dq32 && !c.bil) CA_TRY(run_dq_projection(c, r, o, true));
+  CA_TRY(run_sum_dpv(c, r, o));
+  if (r.bf_tn) return run_dw_bf_tn(c, r, o);
+  if (r.tn_v && r.tn_q) return run_dw_tn_pair(c, r, o);
+  return run_dw_separate(c, r, o);
 }

@@ -14,15 +14,6 @@ inline bool v_is_cm(const VLayout& v, int N, int d) { (void)d; return v.sN == 1 
 
 int fused_supported(int B, int N, int T, int d, int L);
 inline bool fused_layout_ok(const VLayout& v, int N, int d) { return v_is_lm(v, N, d) || v_is_cm(v, N, d); }
-// everything after the projections (P_v, P_q already in `saved`)
-// av / aq: where a_v [L][B][N] / a_q [L][B][T] go (NULL: into `saved`); keep = 0: forward only, no C / H_q stored
-int fused_attention_forward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl,
-                            const float* const* Q, const coattn_params* p, float* v_out, float* q_out, float* saved,
-                            float* ws, hipStream_t s, int bf16 = 0, int np = 3,   // bf16: reduced precision, one MFMA per product; np: width of phase 2
-                            float* av = nullptr, float* aq = nullptr, int keep = 1,
-                            const int* qlen = nullptr,    // qlen: [B] question lengths (coattn_forward_len), NULL = unmasked
-                            float* av_copy = nullptr, float* aq_copy = nullptr,   // (coattn_forward_maps) the maps ALSO go here
-                            const float* K = nullptr);    // (COATTN_FLAG_BILINEAR) K [L][B][T][d], the affinity's question operand
 int fused_backward_supported(int B, int N, int T, int d, int L);
 // The bilinear affinity's backward state (COATTN_FLAG_BILINEAR; NULL: the reference's affinity).  K comes from `saved`; the rest
 // lives in the backward's workspace behind everything else.
@@ -36,13 +27,73 @@ struct BilBwd {
   float* zeros;          // [L][B][d] (the dK pass adds a_q (x) 0)
   float* dWb; float* dbb;
 };
-int fused_backward(int B, int N, int T, int d, int L, const float* V, const VLayout& vl, const float* const* Q,
-                   const coattn_params* p, const float* saved, const float* gv, const float* gq, float* dV,
-                   const VLayout& dvl, float* const* dQ, const coattn_param_grads* pg, int accumulate, float* ws,
-                   hipStream_t s, int bf16_proj, int wgemm, int np = 3, int live_rows = 0,   // wgemm: gemm_w / gemm_tn enabled; np: width of the contractions (3 | 2); live_rows: `saved` holds the forward's bitmap of the non-zero question rows
-                   const int* qlen = nullptr,    // qlen: the forward's question lengths (NULL = unmasked)
-                   const float* g_av = nullptr, const float* g_aq = nullptr,   // (coattn_backward_maps) upstream gradients of the maps, NULL = 0
-                   const BilBwd* bil = nullptr);   // (COATTN_FLAG_BILINEAR) see BilBwd
+
+// One co-attention call as the C-ABI's wrappers (api.hip) fill it, read by both implementations: the fused kernels and the
+// general-shape composition (api.hip general_attention, backward_general).  The backward builds it from its own arguments
+// and so asks the forward's questions about the same call (api.hip rowbits_in_saved).
+struct Ctx {
+  int B, N, T, d, L;
+  hipStream_t s;
+  VLayout vl;                 // element strides of x_img[B,N,d]
+  const float* V = nullptr;
+  const float* const* Q = nullptr;   // [L] levels [B][T][d]
+  const coattn_params* p = nullptr;
+  const int* qlen = nullptr;  // [B] question lengths (the *_len entry points), NULL: unmasked
+  bool bf16_proj = false;     // COATTN_FLAG_BF16_PROJ: the projections and their gradients on the bf16 MFMA
+  bool f16_proj = false;      // fp32 mode: both projections on two FP16 pieces (kF16WScale)
+  int np_pq = 3, np_fwd = 3, np_bwd = 3;   // widths in the fp32 mode: the P_q projection (3 | 2), the fused forward kernel (3 | 2;
+                              // 4: both phases on two FP16 pieces), the backward's contractions (3 | 2)
+  float pscale = 1.f;         // factor on P_v, P_q as stored (fused path: kPScale)
+  bool wgemm = false;         // the pre-split-weight / weight-gradient kernels are enabled (COATTN_GEMM_W)
+  // COATTN_FLAG_BILINEAR (NULL W_b: the reference's affinity): W_b, b_b, K = Q W_b^T + b_b of all levels [L][B][T][d]; in the
+  // backward dK = dA V (general path) or the BilBwd buffers (fused path), in the workspace
+  const float* Wb = nullptr; const float* bb = nullptr; float* K = nullptr; float* dK = nullptr; const BilBwd* bil = nullptr;
+  // forward: the state (SavedOff) lives in `state` -- the caller's `saved` when keep, else the head of the workspace, and then
+  // nothing stores C / H_q.  The maps go to the state when keep and to av_out / aq_out where given (map_dst)
+  float* v_out = nullptr; float* q_out = nullptr;     // [L][B][d]
+  float* state = nullptr; bool keep = false;
+  float* av_out = nullptr; float* aq_out = nullptr;   // [L][B][N] / [L][B][T], each may be NULL
+  float* tail = nullptr;      // the forward workspace behind the state (general path: H_v)
+  // backward
+  const float* saved = nullptr;
+  const float* gv = nullptr; const float* gq = nullptr;       // [L][B][d] upstream gradients of v, q
+  const float* g_av = nullptr; const float* g_aq = nullptr;   // (coattn_backward_maps) upstream gradients of the maps, NULL = 0
+  float* dV = nullptr; VLayout dvl = {};                      // NULL: the image features need no gradient
+  float* const* dQ = nullptr;
+  const coattn_param_grads* pg = nullptr;
+  int accumulate = 0;
+  float* ws = nullptr;
+  bool live_rows = false;     // `saved` may hold the forward's bitmap of the non-zero question rows (api.hip rowbits_in_saved)
+};
+// where one attention map of a forward goes: `to`, and `copy` (may be NULL) from the same store
+struct MapDst { float* to; float* copy; };
+inline MapDst map_dst(const Ctx& c, float* in_state, float* out) {
+  return c.keep ? MapDst{in_state, out} : MapDst{out ? out : in_state, nullptr};
+}
+int fused_attention_forward(const Ctx& c);   // everything after the projections (P_v, P_q already in c.state)
+int fused_backward(const Ctx& c);
+
+// ---- gradient jobs on the general GEMM (api.hip), shared by backward_general and the fallback branches of fused_backward;
+// bf16: on launch_gemm_bf16in; `part`: room for the partial sums.  Split-K over K contraction rows: <= 32 parts of ks rows
+struct SplitK { int ks, S; };
+inline SplitK splitk_plan(int K) {
+  const int ks = ((K + 31) / 32 + 15) / 16 * 16;
+  return SplitK{ks, (K + ks - 1) / ks};
+}
+// dW[j][k] (+)= sum_m dY[m][j] X[m][k], dY / X [K][d]; X == NULL: summed over L levels in one launch, dY_l at dY + l * dy_sl, X_l = Xl[l]
+int grad_dw_splitk(const float* dY, const float* X, int K, int d, float* part, float* dW, int accumulate, bool bf16, hipStream_t s,
+                   const float* const* Xl = nullptr, int L = 0, long dy_sl = 0);
+// dW_v[j][k] (+)= sum_b sum_n dP_v[b][n][j] V[b][n][k] for any strides of V: the samples in <= 32 groups
+int grad_dw_sample_groups(const float* dPv, const float* V, const VLayout& vl, int B, int N, int d, float* part, float* dW,
+                          int accumulate, bool bf16, hipStream_t s);
+// out[j] (+)= sum_r w[r] X[r][j] (w NULL: 1), X [R][d]: a bias gradient, or dw = ds^T H
+int grad_colsum(const float* w, const float* X, int R, int d, float* part, float* out, int accumulate, hipStream_t s);
+// dV[b] += Kq[b]^T dA[b]  (Kq [B][T][d]: Q_l, or K_l of the bilinear affinity);  dV[b][n][k] += sum_j W_v[j][k] dP_v[b][n][j]
+int grad_dv_kt_da(const float* Kq, const float* dA, float* dV, const VLayout& dvl, int B, int N, int T, int d, hipStream_t s);
+int grad_dv_wv(const void* Wv, const float* dPv, float* dV, const VLayout& dvl, int B, int N, int d, bool bf16, hipStream_t s);
+// bilinear: dW_b (+)= sum_l dK_l^T Q_l level by level, db_b (+)= the column sums of dK [L][B][T][d]
+int grad_bilinear_wb(const float* dK, const float* const* Q, int B, int T, int d, int L, float* part, float* dWb, float* dbb,
+                     int accumulate, hipStream_t s);
 
 // Diagnostic build only (tools/probe_stamps.py, -DCOATTN_STAMPS=1): wave 0 of every workgroup writes the
 // 100 MHz constant clock at its phase boundaries into the (otherwise unused) forward workspace tail.
@@ -619,6 +670,7 @@ int launch_bwd_dq32(const DqArgs& a, int lm, hipStream_t s);
 int fused32_forward(const FwdArgs& a, hipStream_t s);
 int launch_attend_v_lm(const float* V, long v_sB, const float* av, float* v_out, int B, int N, int d, int L, hipStream_t s);
 
+// buffer plans are in floats, every region aligned to 64 floats = 256 B
 inline size_t fal64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 struct SavedOff {
