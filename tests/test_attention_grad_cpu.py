@@ -1,23 +1,14 @@
 """Differentiable attention maps (C-ABI 0.9.0: coattn_forward_maps(_len), coattn_backward_maps(_len)), on the CPU:
 declarations, exports, argument order, refusals and the Python surface's refusal of CPU tensors."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
+from tests._header import args as _args, header as _header
+
 NEW = ("coattn_forward_maps", "coattn_forward_maps_len", "coattn_backward_maps", "coattn_backward_maps_len")
-
-
-def _header():
-    from vqa_amd import _lib
-    return open(os.path.join(os.path.dirname(_lib.CSRC.rstrip("/")), "..", "include", "coattn.h")).read()
-
-
-def _args(hdr, name):
-    decl = re.search(r"^int %s\(([^;]*)\);" % name, hdr, re.M).group(1)
-    return [" ".join(a.split()) for a in decl.split(",")]
 
 
 def test_map_entry_points_declared_exported_and_versioned():

@@ -109,6 +109,125 @@ class GemmDesc(C.Structure):
                    ("kband_n", C.c_int), ("kband_lo", C.c_int * 3), ("kband_hi", C.c_int * 3),
                    ("out_scale", C.c_float)])
 
+# ---- the co-attention, alternating and head entry points, argument by argument ------------------------------------------
+# SIGNATURES[symbol] = ((argument name, ctype), ...) with the names and the order of include/coattn.h
+# (tests/test_call_layer_cpu.py holds every row against the header).  load() takes their argtypes from here, bind()
+# turns keyword arguments into the positional tuple.
+def _of(ctype):
+    return lambda names: tuple((n, ctype) for n in names.split())
+
+
+_void, _i64, _int, _ptrs = _of(C.c_void_p), _of(C.c_int64), _of(C.c_int), _of(C.POINTER(C.c_void_p))
+_V_Q = _void("V") + _i64("v_sB v_sN v_sD") + _ptrs("Q")
+_LEN, _MAPS, _MAP_GRADS = _void("q_len"), _void("av_out aq_out"), _void("g_av g_aq")
+_DIMS = _int("B N T d L dtype flags") + _void("stream")
+_HEAD = _ptrs("v q") + (("p", C.POINTER(HeadParams)),)
+_HEAD_DIMS = _int("B d mlp K dtype flags") + _void("stream")
+
+
+def _forward(lens=(), maps=(), saved=_void("saved"), params=Params):
+    return _V_Q + lens + (("p", C.POINTER(params)),) + _void("v_out q_out") + maps + saved + _void("ws") + _DIMS
+
+
+def _backward(lens=(), maps=(), params=Params, grads=ParamGrads):
+    return (_V_Q + lens + (("p", C.POINTER(params)),) + _void("saved gv gq") + maps + _void("dV") + _i64("dv_sB dv_sN dv_sD")
+            + _ptrs("dQ") + (("pg", C.POINTER(grads)),) + _int("accumulate") + _void("ws") + _DIMS)
+
+
+SIGNATURES = {
+    "coattn_forward": _forward(), "coattn_forward_len": _forward(_LEN),
+    "coattn_attention_forward": _forward(), "coattn_attention_forward_len": _forward(_LEN),
+    "coattn_forward_maps": _forward(maps=_MAPS), "coattn_forward_maps_len": _forward(_LEN, _MAPS),
+    "coattn_infer": _forward(maps=_MAPS, saved=()), "coattn_infer_len": _forward(_LEN, _MAPS, saved=()),
+    "coattn_backward": _backward(), "coattn_backward_len": _backward(_LEN),
+    "coattn_backward_maps": _backward(maps=_MAP_GRADS), "coattn_backward_maps_len": _backward(_LEN, _MAP_GRADS),
+    "coattn_alt_forward": _forward(_LEN, _MAPS, params=AltParams),
+    "coattn_alt_backward": _backward(_LEN, _MAP_GRADS, AltParams, AltParamGrads),
+    "coattn_head_forward": _HEAD + _void("labels logits loss saved") + _HEAD_DIMS,
+    "coattn_head_forward_soft": (_HEAD + _void("ans_idx ans_score") + _int("A kind") + _void("logits loss saved")
+                                 + _HEAD_DIMS),
+    "coattn_head_backward": (_HEAD + _void("saved g_loss g_logits") + _ptrs("dv dq") + (("pg", C.POINTER(HeadParamGrads)),)
+                             + _int("accumulate") + _void("ws") + _HEAD_DIMS),
+}
+_INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in SIGNATURES.items()}
+# what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
+_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq".split())
+_DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
+
+
+def ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def ptr_array(tensors):
+    """Host array of the tensors' device pointers (`Q`, `dQ`)."""
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def rows(t):
+    """Host array of the three [B,d] row-block pointers of a contiguous [3,B,d] tensor (the head's `v`, `q`, `dv`)."""
+    step = t.stride(0) * t.element_size()
+    return (C.c_void_p * 3)(*[t.data_ptr() + l * step for l in range(3)])
+
+
+def stream_ptr(dev) -> int:
+    """The hipStream_t of torch's current stream on `dev`."""
+    import torch
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _as_arg(value, ctype):
+    if hasattr(value, "data_ptr"):                       # a tensor: its device pointer
+        return C.c_void_p(value.data_ptr())
+    if isinstance(value, C.Structure):                   # (the byref object keeps the structure alive)
+        return C.byref(value)
+    if ctype is C.c_void_p and isinstance(value, int):
+        return C.c_void_p(value)
+    return value
+
+
+class Call(tuple):
+    """The positional arguments of the entry point `name`, as bind() lays them out.  call() issues it and raises on an error
+    code; a call bound without `stream` (always the last argument) takes it then: call(stream).  The tuple keeps the host
+    arrays and structures it points to alive."""
+
+    def __call__(self, *stream):
+        check(self.fn(*self, *stream), self.name)
+
+    def replace(self, **kw):
+        """The same call with the given arguments replaced (one list copy: cheap enough for every step)."""
+        sig, index, vals = SIGNATURES[self.name], _INDEX[self.name], list(self)
+        for n, v in kw.items():
+            if n not in index:
+                raise TypeError("%s has no argument %r" % (self.name, n))
+            i = index[n]
+            vals[i:i + 1] = [_as_arg(v, sig[i][1])]          # (i == len(vals): a `stream` left out so far)
+        return _call(self.name, vals)
+
+
+def _call(name, vals):
+    call = Call(vals)
+    call.name, call.fn = name, getattr(load(), name)
+    return call
+
+
+def bind(name: str, **kw) -> Call:
+    """The call of SIGNATURES[name] with its arguments given by name: tensors go in as their device pointers, ctypes
+    structures by reference, None as NULL; an omitted nullable pointer is NULL, an omitted dV stride 0, `stream` may be left
+    for the call itself.  Raises TypeError on a name the entry point does not have and on a missing required one."""
+    unknown = kw.keys() - _INDEX[name].keys()
+    if unknown:
+        raise TypeError("%s has no argument %s" % (name, ", ".join(sorted(unknown))))
+    vals = []
+    for n, ctype in SIGNATURES[name]:
+        if n in kw:
+            vals.append(_as_arg(kw[n], ctype))
+        elif n in _DEFAULTS:
+            vals.append(_DEFAULTS[n])
+        elif n != "stream":
+            raise TypeError("%s: missing argument %r" % (name, n))
+    return _call(name, vals)
+
 
 def build(verbose: bool = False) -> str:
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
@@ -139,36 +258,11 @@ def load() -> C.CDLL:
             raise RuntimeError("libcoattn_hip.so lacks symbol %s" % name)
     lib.coattn_version.restype = C.c_int
     lib.coattn_last_error.restype = C.c_char_p
+    for name, sig in SIGNATURES.items():                 # the co-attention, alternating and head calls: SIGNATURES
+        getattr(lib, name).argtypes = [ctype for _, ctype in sig]
     lib.coattn_fused_supported.argtypes = [C.c_int] * 6
     lib.coattn_workspace_bytes.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_size_t)] * 3
-    lib.coattn_forward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(Params),
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
-    lib.coattn_attention_forward.argtypes = lib.coattn_forward.argtypes
-    lib.coattn_infer.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(Params),
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
-    lib.coattn_backward.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(Params),
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                    C.POINTER(C.c_void_p), C.POINTER(ParamGrads), C.c_int,
-                                    C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]
-    # the length-masked forms: one more argument after Q, the device int32 [B] lengths (NULL = unmasked)
-    def _with_len(argtypes):
-        return argtypes[:5] + [C.c_void_p] + argtypes[5:]
-    lib.coattn_forward_len.argtypes = _with_len(lib.coattn_forward.argtypes)
-    lib.coattn_attention_forward_len.argtypes = _with_len(lib.coattn_attention_forward.argtypes)
-    lib.coattn_infer_len.argtypes = _with_len(lib.coattn_infer.argtypes)
-    lib.coattn_backward_len.argtypes = _with_len(lib.coattn_backward.argtypes)
-    # differentiable maps: the forward takes av_out, aq_out before `saved`; the backward g_av, g_aq right after gq
-    lib.coattn_forward_maps.argtypes = lib.coattn_forward.argtypes[:8] + [C.c_void_p, C.c_void_p] + lib.coattn_forward.argtypes[8:]
-    lib.coattn_backward_maps.argtypes = lib.coattn_backward.argtypes[:9] + [C.c_void_p, C.c_void_p] + lib.coattn_backward.argtypes[9:]
-    lib.coattn_forward_maps_len.argtypes = _with_len(lib.coattn_forward_maps.argtypes)
-    lib.coattn_backward_maps_len.argtypes = _with_len(lib.coattn_backward_maps.argtypes)
     lib.coattn_alt_workspace_bytes.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_size_t)] * 3
-    lib.coattn_alt_forward.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.c_void_p,
-                                        C.POINTER(AltParams)] + [C.c_void_p] * 6 + [C.c_int] * 7 + [C.c_void_p])
-    lib.coattn_alt_backward.argtypes = ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.c_void_p,
-                                         C.POINTER(AltParams)] + [C.c_void_p] * 6 + [C.c_int64] * 3
-                                        + [C.POINTER(C.c_void_p), C.POINTER(AltParamGrads), C.c_int, C.c_void_p]
-                                        + [C.c_int] * 7 + [C.c_void_p])
     lib.coattn_gemm_f32.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
     lib.coattn_gemm_bf16.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
     lib.coattn_phrase_workspace_bytes.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_size_t)] * 3
@@ -201,18 +295,9 @@ def load() -> C.CDLL:
                                            C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.coattn_head_status.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
     lib.coattn_head_workspace_bytes.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_size_t)] * 2
-    lib.coattn_head_forward.argtypes = ([C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(HeadParams)]
-                                        + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p])
-    lib.coattn_head_backward.argtypes = ([C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(HeadParams)]
-                                         + [C.c_void_p] * 3 + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                                               C.POINTER(HeadParamGrads), C.c_int, C.c_void_p]
-                                         + [C.c_int] * 6 + [C.c_void_p])
     # soft answer targets (v0.12.0): (ans_idx, ans_score, A, kind) where the hard-label calls take `labels`
     lib.coattn_soft_loss_forward.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]
     lib.coattn_vqa_score.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]
-    lib.coattn_head_forward_soft.argtypes = ([C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(HeadParams)]
-                                             + [C.c_void_p] * 2 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 6
-                                             + [C.c_void_p])
     # the optimiser step (v0.13.0): (list, n_tensors, step, lr, beta1, beta2, eps, weight_decay, max_grad_norm, norm_out, ws,
     # ws_bytes, stream)
     lib.coattn_adam_workspace_bytes.argtypes = [C.POINTER(AdamTensor), C.c_int]
@@ -328,36 +413,34 @@ def on_device(dev):
     return _NO_GUARD if dev.index is None or dev.index == torch.cuda.current_device() else torch.cuda.device(dev)
 
 
-_ws_cache = {}
+_bytes_cache = {}
+
+
+def _bytes(symbol, n_out, *dims):
+    """The n_out byte counts the *_workspace_bytes entry point `symbol` reports for `dims`; cached (the plan is a pure
+    function of the shape)."""
+    key = (symbol, *dims)
+    hit = _bytes_cache.get(key)
+    if hit is None:
+        out = [C.c_size_t() for _ in range(n_out)]
+        check(getattr(load(), symbol)(*dims, *[C.byref(o) for o in out]), symbol)
+        hit = _bytes_cache[key] = tuple(o.value for o in out)
+    return hit
 
 
 def workspace_bytes(B, N, T, d, L, flags=0):
-    """(saved, ws_fwd, ws_bwd) in bytes; cached per shape (the plan is a pure function of the shape)."""
-    key = (B, N, T, d, L, flags)
-    hit = _ws_cache.get(key)
-    if hit is not None:
-        return hit
-    s, f, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
-    check(load().coattn_workspace_bytes(B, N, T, d, L, F32, flags, C.byref(s), C.byref(f), C.byref(b)),
-          "coattn_workspace_bytes")
-    _ws_cache[key] = (s.value, f.value, b.value)
-    return _ws_cache[key]
-
-
-_alt_ws_cache = {}
+    """(saved, ws_fwd, ws_bwd) in bytes of the parallel co-attention."""
+    return _bytes("coattn_workspace_bytes", 3, B, N, T, d, L, F32, flags)
 
 
 def alt_workspace_bytes(B, N, T, d, L):
-    """(saved, ws_fwd, ws_bwd) in bytes of the alternating co-attention (coattn_alt_workspace_bytes; exact mode)."""
-    key = (B, N, T, d, L)
-    hit = _alt_ws_cache.get(key)
-    if hit is not None:
-        return hit
-    s, f, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
-    check(load().coattn_alt_workspace_bytes(B, N, T, d, L, F32, 0, C.byref(s), C.byref(f), C.byref(b)),
-          "coattn_alt_workspace_bytes")
-    _alt_ws_cache[key] = (s.value, f.value, b.value)
-    return _alt_ws_cache[key]
+    """(saved, ws_fwd, ws_bwd) in bytes of the alternating co-attention (exact mode)."""
+    return _bytes("coattn_alt_workspace_bytes", 3, B, N, T, d, L, F32, 0)
+
+
+def head_workspace_bytes(B, d, mlp, K):
+    """(saved, ws_bwd) in bytes of the answer head."""
+    return _bytes("coattn_head_workspace_bytes", 2, B, d, mlp, K, F32)
 
 
 _scratch = {}

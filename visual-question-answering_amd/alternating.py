@@ -7,14 +7,13 @@ image attended under s^ (step 2, v), the question attended under v (step 3, q). 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Sequence
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .coattention import _ptr, _strides, question_lengths
+from .coattention import _run_backward, _run_forward, _strides, question_lengths
 
 
 def _features(x_img: torch.Tensor) -> torch.Tensor:
@@ -34,9 +33,8 @@ class _AltFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
     def forward(ctx, x_img, q_len, *tensors):
-        L = len(tensors) - len(_lib.ALT_PARAM_NAMES)
-        params, x_ques = tensors[:len(_lib.ALT_PARAM_NAMES)], tensors[len(_lib.ALT_PARAM_NAMES):]
-        lib = _lib.load()
+        npar = len(_lib.ALT_PARAM_NAMES)
+        params, x_ques = tensors[:npar], tensors[npar:]
         B, N, d = x_img.shape
         T = x_ques[0].shape[1]
         for q in x_ques:
@@ -45,61 +43,25 @@ class _AltFn(torch.autograd.Function):
         V = _features(x_img)
         Qs = [q.contiguous() for q in x_ques]
         ps = [t.contiguous() for t in params]
-        need_grad = any(ctx.needs_input_grad)
-        sb, fb, _ = _lib.alt_workspace_bytes(B, N, T, d, L)
-        dev = x_img.device
-        out_v = torch.empty((L, B, d), device=dev, dtype=torch.float32)
-        out_q = torch.empty((L, B, d), device=dev, dtype=torch.float32)
-        a_v = torch.empty((L, B, N), device=dev, dtype=torch.float32)
-        a_q = torch.empty((L, B, T), device=dev, dtype=torch.float32)
-        saved = torch.empty(sb // 4, device=dev, dtype=torch.float32) if need_grad else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _lib.scratch(fb, dev, stream)
-        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
-        p = _lib.AltParams(*[t.data_ptr() for t in ps])
-        with _lib.on_device(dev):
-            _lib.check(lib.coattn_alt_forward(_ptr(V), *_strides(V), qptr, _ptr(q_len), C.byref(p), _ptr(out_v), _ptr(out_q),
-                                              _ptr(a_v), _ptr(a_q), _ptr(saved), _ptr(ws), B, N, T, d, L, _lib.F32, 0,
-                                              C.c_void_p(stream)), "coattn_alt_forward")
+        keep = any(ctx.needs_input_grad)
+        outs, saved, _ = _run_forward("coattn_alt_forward", V, Qs, q_len, _lib.AltParams(*[t.data_ptr() for t in ps]),
+                                      _lib.alt_workspace_bytes(B, N, T, d, len(Qs)), 0, keep, maps=True)
         ctx.set_materialize_grads(False)              # (an unused map's gradient stays None: NULL for the C-ABI)
-        if need_grad:
+        if keep:
             ctx.save_for_backward(V, saved, q_len, *ps, *Qs)
-            ctx.dims = (B, N, T, d, L)
             ctx.x_img_stride_d = x_img.stride(2)
-        return out_v, out_q, a_v, a_q
+        return outs
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_v, g_q, g_av, g_aq):
-        lib = _lib.load()
-        B, N, T, d, L = ctx.dims
         sv = ctx.saved_tensors
         npar = len(_lib.ALT_PARAM_NAMES)
         V, saved, q_len, params, Qs = sv[0], sv[1], sv[2], sv[3:3 + npar], sv[3 + npar:]
-        dev = V.device
-        g_v = g_v.contiguous() if g_v is not None else torch.zeros((L, B, d), device=dev)
-        g_q = g_q.contiguous() if g_q is not None else torch.zeros((L, B, d), device=dev)
-        g_av = g_av.contiguous() if g_av is not None else None
-        g_aq = g_aq.contiguous() if g_aq is not None else None
-        _, _, bb = _lib.alt_workspace_bytes(B, N, T, d, L)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _lib.scratch(bb, dev, stream)
-        need_dv = ctx.needs_input_grad[0]
-        dV = None
-        if need_dv:                         # gradient of x_img[B,N,d] in the layout of x_img itself
-            dV = (torch.empty((B, N, d), device=dev) if ctx.x_img_stride_d == 1
-                  else torch.empty((B, d, N), device=dev).permute(0, 2, 1))
-        dQs = [torch.empty_like(q) for q in Qs]
-        grads = [torch.empty_like(t) for t in params]
-        pg = _lib.AltParamGrads(*[t.data_ptr() for t in grads])
-        p = _lib.AltParams(*[t.data_ptr() for t in params])
-        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
-        dqptr = (C.c_void_p * L)(*[q.data_ptr() for q in dQs])
-        with _lib.on_device(dev):
-            _lib.check(lib.coattn_alt_backward(_ptr(V), *_strides(V), qptr, _ptr(q_len), C.byref(p), _ptr(saved), _ptr(g_v),
-                                               _ptr(g_q), _ptr(g_av), _ptr(g_aq), _ptr(dV),
-                                               *(_strides(dV) if need_dv else (0, 0, 0)), dqptr, C.byref(pg), 0, _ptr(ws),
-                                               B, N, T, d, L, _lib.F32, 0, C.c_void_p(stream)), "coattn_alt_backward")
+        (B, N, d), T = V.shape, Qs[0].shape[1]
+        dV, grads, dQs = _run_backward("coattn_alt_backward", (_lib.AltParams, _lib.AltParamGrads), V, Qs, q_len, params, saved,
+                                       _lib.alt_workspace_bytes(B, N, T, d, len(Qs)), 0, g_v, g_q, g_av, g_aq,
+                                       ctx.x_img_stride_d if ctx.needs_input_grad[0] else None)
         return (dV, None, *grads, *dQs)
 
 

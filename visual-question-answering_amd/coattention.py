@@ -14,12 +14,13 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Sequence, Tuple
+from typing import Sequence
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 
 def _impl_flag() -> int:
@@ -28,10 +29,6 @@ def _impl_flag() -> int:
     if os.environ.get("COATTN_BF16_PROJ", "0") not in ("0", ""):
         f |= _lib.FLAG_BF16_PROJ
     return f
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def _is_native(x_img: torch.Tensor, lm_only: bool = False) -> bool:
@@ -96,8 +93,7 @@ def native_features(x_img: torch.Tensor, out: torch.Tensor = None) -> torch.Tens
         raise RuntimeError("native_features: negative strides")
     with _lib.on_device(x_img.device):
         _lib.check(lib.coattn_features_native(_ptr(x_img), _lib.BF16 if x_img.dtype == torch.bfloat16 else _lib.F32,
-                                              sB, sN, sD, _ptr(out), B, N, d,
-                                              C.c_void_p(torch.cuda.current_stream(x_img.device).cuda_stream)),
+                                              sB, sN, sD, _ptr(out), B, N, d, C.c_void_p(_lib.stream_ptr(x_img.device))),
                    "coattn_features_native")
     return out
 
@@ -131,190 +127,134 @@ def _strides(x: torch.Tensor):
     return sB, sN, sD
 
 
+def _shared_args(V, Qs, q_len, p, ws, flags):
+    """The arguments every co-attention call takes, parallel or alternating, forward or backward, by the header's names
+    (all but `stream`)."""
+    (B, N, d), T = V.shape, Qs[0].shape[1]
+    sB, sN, sD = _strides(V)
+    return dict(V=V, v_sB=sB, v_sN=sN, v_sD=sD, Q=_lib.ptr_array(Qs), q_len=q_len, p=p, ws=ws, B=B, N=N, T=T, d=d,
+                L=len(Qs), dtype=_lib.F32, flags=flags)
+
+
+def _run_forward(symbol, V, Qs, q_len, p, sizes, flags, keep, maps):
+    """The forward `symbol` on the current stream, for V in a layout the kernels take and contiguous Qs: allocates v, q
+    [L,B,d], with `maps` also a_v [L,B,N] and a_q [L,B,T], with `keep` the backward's state (NULL otherwise: nothing is kept).
+    sizes: the family's (saved, ws_fwd, ws_bwd) bytes.  Returns (the outputs, saved or None, the workspace)."""
+    (B, N, d), T, L, dev = V.shape, Qs[0].shape[1], len(Qs), V.device
+    outs = tuple(torch.empty((L, B, n), device=dev, dtype=torch.float32) for n in ((d, d, N, T) if maps else (d, d)))
+    kw = dict(zip(("v_out", "q_out", "av_out", "aq_out"), outs))
+    saved = None
+    if keep:
+        saved = kw["saved"] = torch.empty(sizes[0] // 4, device=dev, dtype=torch.float32)
+    stream = _lib.stream_ptr(dev)
+    ws = _lib.scratch(sizes[1], dev, stream)             # per-stream scratch, reused from call to call
+    with _lib.on_device(dev):
+        _lib.bind(symbol, stream=stream, **_shared_args(V, Qs, q_len, p, ws, flags), **kw)()
+    return outs, saved, ws
+
+
+def _run_backward(symbol, structs, V, Qs, q_len, params, saved, sizes, flags, g_v, g_q, g_av, g_aq, dv_stride_d):
+    """The backward `symbol` on the current stream.  A missing g_v / g_q goes in as zeros, a missing map gradient as NULL.
+    structs: the family's (parameters, parameter gradients) structures; dv_stride_d: None when x_img needs no gradient, else
+    x_img's innermost stride -- dV takes the layout of x_img itself.  Returns (dV, parameter gradients, dQs)."""
+    (B, N, d), L, dev = V.shape, len(Qs), V.device
+    g_v = g_v.contiguous() if g_v is not None else torch.zeros((L, B, d), device=dev)
+    g_q = g_q.contiguous() if g_q is not None else torch.zeros((L, B, d), device=dev)
+    g_av = g_av.contiguous() if g_av is not None else None
+    g_aq = g_aq.contiguous() if g_aq is not None else None
+    stream = _lib.stream_ptr(dev)
+    ws = _lib.scratch(sizes[2], dev, stream)
+    dV, kw = None, {}
+    if dv_stride_d is not None:
+        dV = (torch.empty((B, N, d), device=dev) if dv_stride_d == 1
+              else torch.empty((B, d, N), device=dev).permute(0, 2, 1))
+        kw = dict(zip(("dV", "dv_sB", "dv_sN", "dv_sD"), (dV, *_strides(dV))))
+    dQs = [torch.empty_like(q) for q in Qs]
+    grads = [torch.empty_like(t) for t in params]
+    p, pg = structs[0](*[t.data_ptr() for t in params]), structs[1](*[t.data_ptr() for t in grads])
+    with _lib.on_device(dev):
+        _lib.bind(symbol, stream=stream, saved=saved, gv=g_v, gq=g_q, g_av=g_av, g_aq=g_aq, dQ=_lib.ptr_array(dQs), pg=pg,
+                  accumulate=0, **_shared_args(V, Qs, q_len, p, ws, flags), **kw)()
+    return dV, grads, dQs
+
+
+def _forward(ctx, x_img, x_ques, params, impl, q_len, maps):
+    """The parallel form's forward (params: the ten of `_param_list`): validate, lay out, call, note the tolerance mode's status words, and -- ctx: the autograd
+    context, None from forward_with_attention -- keep the backward's state when an input needs a gradient.  With state the
+    call is coattn_forward_len (coattn_forward_maps_len with `maps`), without it coattn_infer_len; q_len None = unmasked."""
+    if not x_img.is_cuda:
+        raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
+    if x_img.dtype != torch.float32 or any(q.dtype != torch.float32 for q in x_ques):
+        raise RuntimeError("ParallelCoAttention (HIP) computes in fp32; got %s" % x_img.dtype)
+    L = len(x_ques)
+    B, N, d = x_img.shape
+    T = x_ques[0].shape[1]
+    for q in x_ques:
+        if tuple(q.shape) != (B, T, d):
+            raise RuntimeError("question features must all be [B,T,d] = %s, got %s" % ((B, T, d), tuple(q.shape)))
+    V = _native_layout(x_img)
+    Qs = [q.contiguous() for q in x_ques]
+    params = _param_list(*params, impl)
+    keep = ctx is not None and any(ctx.needs_input_grad)
+    symbol = "coattn_infer_len" if not keep else "coattn_forward_maps_len" if maps else "coattn_forward_len"
+    outs, saved, ws = _run_forward(symbol, V, Qs, q_len, _lib.Params(*[t.data_ptr() for t in params]),
+                                   _lib.workspace_bytes(B, N, T, d, L, impl), impl, keep, maps)
+    if impl & _lib.FLAG_FAST16:                       # tolerance mode: where _lib.check_range() finds this call's status words
+        _lib.note_status("coattn", saved if keep else ws, (B, N, T, d, L), x_img.device)
+    if keep:
+        ctx.save_for_backward(V, saved, *params, *Qs)
+        ctx.nparams = len(params)
+        ctx.impl = impl
+        ctx.q_len = q_len                             # (the backward must see the forward's lengths)
+    return outs
+
+
+def _backward(ctx, g_v, g_q, g_av=None, g_aq=None):
+    """The parallel form's backward, coattn_backward_maps_len: NULL lengths = unmasked, NULL map gradients = coattn_backward's
+    bits."""
+    sv = ctx.saved_tensors
+    npar = ctx.nparams
+    V, saved, params, Qs = sv[0], sv[1], sv[2:2 + npar], sv[2 + npar:]
+    (B, N, d), T, L = V.shape, Qs[0].shape[1], len(Qs)
+    dV, grads, dQs = _run_backward("coattn_backward_maps_len", (_lib.Params, _lib.ParamGrads), V, Qs, ctx.q_len, params, saved,
+                                   _lib.workspace_bytes(B, N, T, d, L, ctx.impl), ctx.impl, g_v, g_q, g_av, g_aq,
+                                   V.stride(2) if ctx.needs_input_grad[0] else None)
+    if npar == 8:                           # (the reference's affinity: W_b, b_b take no part)
+        grads += [None, None]
+    return (dV, *grads, None, None, *dQs)
+
+
 class _CoAttentionFn(torch.autograd.Function):
-    """forward -> coattn_forward, backward -> coattn_backward (autograd of model.py:372-392); with question lengths
-    (int32 [B] on the device) coattn_forward_len / coattn_backward_len, both given the same lengths."""
+    """(v, q), each [L,B,d]: autograd of model.py:372-392.  q_len: the question lengths (int32 [B] on the device), given to
+    the forward and the backward alike, or None."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
     def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl, q_len, *x_ques):
-        if not x_img.is_cuda:
-            raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
-        if x_img.dtype != torch.float32 or any(q.dtype != torch.float32 for q in x_ques):
-            raise RuntimeError("ParallelCoAttention (HIP) computes in fp32; got %s" % x_img.dtype)
-        lib = _lib.load()
-        L = len(x_ques)
-        B, N, d = x_img.shape
-        T = x_ques[0].shape[1]
-        for q in x_ques:
-            if tuple(q.shape) != (B, T, d):
-                raise RuntimeError("question features must all be [B,T,d] = %s, got %s" % ((B, T, d), tuple(q.shape)))
-        V = _native_layout(x_img)
-        Qs = [q.contiguous() for q in x_ques]
-        params = _param_list(W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl)
-        need_grad = any(ctx.needs_input_grad)
-        sb, fb, _ = _lib.workspace_bytes(B, N, T, d, L, impl)
-        dev = x_img.device
-        out_v = torch.empty((L, B, d), device=dev, dtype=torch.float32)
-        out_q = torch.empty((L, B, d), device=dev, dtype=torch.float32)
-        saved = torch.empty(sb // 4, device=dev, dtype=torch.float32) if need_grad else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _lib.scratch(fb, dev, stream)            # per-stream scratch, reused from call to call
-        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
-        p = _lib.Params(*[t.data_ptr() for t in params])
-        with _lib.on_device(dev):
-            if q_len is None:
-                _lib.check(lib.coattn_forward(_ptr(V), *_strides(V), qptr, C.byref(p), _ptr(out_v), _ptr(out_q), _ptr(saved),
-                                              _ptr(ws), B, N, T, d, L, _lib.F32, impl, C.c_void_p(stream)),
-                           "coattn_forward")
-            else:
-                _lib.check(lib.coattn_forward_len(_ptr(V), *_strides(V), qptr, _ptr(q_len), C.byref(p), _ptr(out_v),
-                                                  _ptr(out_q), _ptr(saved), _ptr(ws), B, N, T, d, L, _lib.F32, impl,
-                                                  C.c_void_p(stream)),
-                           "coattn_forward_len")
-        if impl & _lib.FLAG_FAST16:                   # tolerance mode: where _lib.check_range() finds this call's status words
-            _lib.note_status("coattn", saved if saved is not None else ws, (B, N, T, d, L), dev)
-        if need_grad:
-            ctx.save_for_backward(V, saved, *params, *Qs)
-            ctx.nparams = len(params)
-            ctx.dims = (B, N, T, d, L, impl)
-            ctx.q_len = q_len                         # (the backward must see the forward's lengths)
-        return out_v, out_q
+        return _forward(ctx, x_img, x_ques, (W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b), impl, q_len, maps=False)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_v, g_q):
-        lib = _lib.load()
-        B, N, T, d, L, impl = ctx.dims
-        sv = ctx.saved_tensors
-        npar = ctx.nparams
-        V, saved, params, Qs = sv[0], sv[1], sv[2:2 + npar], sv[2 + npar:]
-        dev = V.device
-        g_v = g_v.contiguous() if g_v is not None else torch.zeros((L, B, d), device=dev)
-        g_q = g_q.contiguous() if g_q is not None else torch.zeros((L, B, d), device=dev)
-        _, _, bb = _lib.workspace_bytes(B, N, T, d, L, impl)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _lib.scratch(bb, dev, stream)
-        need_dv = ctx.needs_input_grad[0]
-        dV = None
-        if need_dv:                         # gradient of x_img[B,N,d] in the layout of x_img itself
-            dV = (torch.empty((B, N, d), device=dev) if V.stride(2) == 1
-                  else torch.empty((B, d, N), device=dev).permute(0, 2, 1))
-        dQs = [torch.empty_like(q) for q in Qs]
-        grads = [torch.empty_like(t) for t in params]
-        pg = _lib.ParamGrads(*[t.data_ptr() for t in grads])
-        p = _lib.Params(*[t.data_ptr() for t in params])
-        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
-        dqptr = (C.c_void_p * L)(*[q.data_ptr() for q in dQs])
-        args = (C.byref(p), _ptr(saved), _ptr(g_v), _ptr(g_q), _ptr(dV), *(_strides(dV) if need_dv else (0, 0, 0)), dqptr,
-                C.byref(pg), 0, _ptr(ws), B, N, T, d, L, _lib.F32, impl, C.c_void_p(stream))
-        with _lib.on_device(dev):
-            if ctx.q_len is None:
-                _lib.check(lib.coattn_backward(_ptr(V), *_strides(V), qptr, *args), "coattn_backward")
-            else:
-                _lib.check(lib.coattn_backward_len(_ptr(V), *_strides(V), qptr, _ptr(ctx.q_len), *args), "coattn_backward_len")
-        if npar == 8:                       # (the reference's affinity: W_b, b_b take no part)
-            grads += [None, None]
-        return (dV, *grads, None, None, *dQs)
+        return _backward(ctx, g_v, g_q)
 
 
 class _CoAttentionMapsFn(torch.autograd.Function):
-    """The co-attention with differentiable attention maps: forward -> coattn_forward_maps(_len), returning (v, q, a_v, a_q)
-    with v, q [L,B,d], a_v [L,B,N], a_q [L,B,T]; backward -> coattn_backward_maps(_len), which adds the maps' own upstream
-    gradients in the two softmax backward steps (include/coattn.h).  A map whose gradient autograd gives as None goes in as
-    NULL (the backward is then coattn_backward's bit for bit), a missing g_v / g_q as zeros.  With no input that needs a
-    gradient the forward is coattn_infer(_len): the same maps, no backward state."""
+    """The co-attention with differentiable attention maps: (v, q, a_v, a_q) with v, q [L,B,d], a_v [L,B,N], a_q [L,B,T]; the
+    backward adds the maps' own upstream gradients in the two softmax backward steps (include/coattn.h).  A map whose
+    gradient autograd gives as None goes in as NULL (the backward is then _CoAttentionFn's bit for bit), a missing g_v / g_q
+    as zeros.  With no input that needs a gradient the forward keeps no backward state: the same maps."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
     def forward(ctx, x_img, W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl, q_len, *x_ques):
-        if not x_img.is_cuda:
-            raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
-        if x_img.dtype != torch.float32 or any(q.dtype != torch.float32 for q in x_ques):
-            raise RuntimeError("ParallelCoAttention (HIP) computes in fp32; got %s" % x_img.dtype)
-        lib = _lib.load()
-        L = len(x_ques)
-        B, N, d = x_img.shape
-        T = x_ques[0].shape[1]
-        for q in x_ques:
-            if tuple(q.shape) != (B, T, d):
-                raise RuntimeError("question features must all be [B,T,d] = %s, got %s" % ((B, T, d), tuple(q.shape)))
-        V = _native_layout(x_img)
-        Qs = [q.contiguous() for q in x_ques]
-        params = _param_list(W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl)
-        need_grad = any(ctx.needs_input_grad)
-        sb, fb, _ = _lib.workspace_bytes(B, N, T, d, L, impl)
-        dev = x_img.device
-        out_v = torch.empty((L, B, d), device=dev, dtype=torch.float32)
-        out_q = torch.empty((L, B, d), device=dev, dtype=torch.float32)
-        a_v = torch.empty((L, B, N), device=dev, dtype=torch.float32)
-        a_q = torch.empty((L, B, T), device=dev, dtype=torch.float32)
-        saved = torch.empty(sb // 4, device=dev, dtype=torch.float32) if need_grad else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _lib.scratch(fb, dev, stream)
-        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
-        p = _lib.Params(*[t.data_ptr() for t in params])
-        lens = () if q_len is None else (_ptr(q_len),)
-        with _lib.on_device(dev):
-            if need_grad:
-                fn = "coattn_forward_maps" if q_len is None else "coattn_forward_maps_len"
-                _lib.check(getattr(lib, fn)(_ptr(V), *_strides(V), qptr, *lens, C.byref(p), _ptr(out_v), _ptr(out_q),
-                                            _ptr(a_v), _ptr(a_q), _ptr(saved), _ptr(ws), B, N, T, d, L, _lib.F32, impl,
-                                            C.c_void_p(stream)), fn)
-            else:
-                fn = "coattn_infer" if q_len is None else "coattn_infer_len"
-                _lib.check(getattr(lib, fn)(_ptr(V), *_strides(V), qptr, *lens, C.byref(p), _ptr(out_v), _ptr(out_q),
-                                            _ptr(a_v), _ptr(a_q), _ptr(ws), B, N, T, d, L, _lib.F32, impl,
-                                            C.c_void_p(stream)), fn)
-        if impl & _lib.FLAG_FAST16:                   # tolerance mode: where _lib.check_range() finds this call's status words
-            _lib.note_status("coattn", saved if saved is not None else ws, (B, N, T, d, L), dev)
         ctx.set_materialize_grads(False)              # (an unused map's gradient stays None: NULL for the C-ABI)
-        if need_grad:
-            ctx.save_for_backward(V, saved, *params, *Qs)
-            ctx.nparams = len(params)
-            ctx.dims = (B, N, T, d, L, impl)
-            ctx.q_len = q_len                         # (the backward must see the forward's lengths)
-        return out_v, out_q, a_v, a_q
+        return _forward(ctx, x_img, x_ques, (W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b), impl, q_len, maps=True)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_v, g_q, g_av, g_aq):
-        lib = _lib.load()
-        B, N, T, d, L, impl = ctx.dims
-        sv = ctx.saved_tensors
-        npar = ctx.nparams
-        V, saved, params, Qs = sv[0], sv[1], sv[2:2 + npar], sv[2 + npar:]
-        dev = V.device
-        g_v = g_v.contiguous() if g_v is not None else torch.zeros((L, B, d), device=dev)
-        g_q = g_q.contiguous() if g_q is not None else torch.zeros((L, B, d), device=dev)
-        g_av = g_av.contiguous() if g_av is not None else None
-        g_aq = g_aq.contiguous() if g_aq is not None else None
-        _, _, bb = _lib.workspace_bytes(B, N, T, d, L, impl)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _lib.scratch(bb, dev, stream)
-        need_dv = ctx.needs_input_grad[0]
-        dV = None
-        if need_dv:                         # gradient of x_img[B,N,d] in the layout of x_img itself
-            dV = (torch.empty((B, N, d), device=dev) if V.stride(2) == 1
-                  else torch.empty((B, d, N), device=dev).permute(0, 2, 1))
-        dQs = [torch.empty_like(q) for q in Qs]
-        grads = [torch.empty_like(t) for t in params]
-        pg = _lib.ParamGrads(*[t.data_ptr() for t in grads])
-        p = _lib.Params(*[t.data_ptr() for t in params])
-        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
-        dqptr = (C.c_void_p * L)(*[q.data_ptr() for q in dQs])
-        args = (C.byref(p), _ptr(saved), _ptr(g_v), _ptr(g_q), _ptr(g_av), _ptr(g_aq), _ptr(dV),
-                *(_strides(dV) if need_dv else (0, 0, 0)), dqptr, C.byref(pg), 0, _ptr(ws), B, N, T, d, L, _lib.F32, impl,
-                C.c_void_p(stream))
-        with _lib.on_device(dev):
-            if ctx.q_len is None:
-                _lib.check(lib.coattn_backward_maps(_ptr(V), *_strides(V), qptr, *args), "coattn_backward_maps")
-            else:
-                _lib.check(lib.coattn_backward_maps_len(_ptr(V), *_strides(V), qptr, _ptr(ctx.q_len), *args),
-                           "coattn_backward_maps_len")
-        if npar == 8:                       # (the reference's affinity: W_b, b_b take no part)
-            grads += [None, None]
-        return (dV, *grads, None, None, *dQs)
+        return _backward(ctx, g_v, g_q, g_av, g_aq)
 
 
 def _param_list(W_v, b_v, W_q, b_q, w_v, c_v, w_q, c_q, W_b, b_b, impl):
@@ -405,6 +345,14 @@ class ParallelCoAttention(nn.Module):
         """(W_b, b_b) when the bilinear affinity is on, else (None, None)."""
         return (self.W_b.weight, self.W_b.bias) if self.affinity == "bilinear" else (None, None)
 
+    def _params(self):
+        """The eight parameters in coattn_params' order, then `_wb()`."""
+        return (self.W_v.weight, self.W_v.bias, self.W_q.weight, self.W_q.bias, self.w_v.weight, self.w_v.bias,
+                self.w_q.weight, self.w_q.bias, *self._wb())
+
+    def _needs_grad(self, x_img, ques) -> bool:
+        return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x_img, *ques, *self._params()))
+
     def _lengths(self, x_img: torch.Tensor, x_ques_lens):
         """int32 [B] lengths on the features' device when the mask is on (required then), else None (ignored)."""
         if not self.question_mask:
@@ -422,20 +370,15 @@ class ParallelCoAttention(nn.Module):
         (coattn_forward_maps / coattn_backward_maps).  v / q and every gradient through them are those of the plain call.
         Where no gradient can be needed (no_grad, or no input that requires one) this is `forward_with_attention`, bit for
         bit."""
-        if return_attention:
-            ques = list(x_ques_hierarchy)
-            params = (self.W_v.weight, self.W_v.bias, self.W_q.weight, self.W_q.bias, self.w_v.weight, self.w_v.bias,
-                      self.w_q.weight, self.w_q.bias, *[t for t in self._wb() if t is not None])
-            if not (torch.is_grad_enabled() and any(t.requires_grad for t in (x_img, *ques, *params))):
-                return self.forward_with_attention(x_img, ques, x_ques_lens)
+        ques = list(x_ques_hierarchy)
+        if return_attention and not self._needs_grad(x_img, ques):
+            return self.forward_with_attention(x_img, ques, x_ques_lens)
         impl = self._impl()
-        W_b, b_b = self._wb()
         q_len = self._lengths(x_img, x_ques_lens)
         if x_img.is_cuda and not (x_img.requires_grad and torch.is_grad_enabled()):
             x_img = native_features(x_img)           # frozen encoder: bf16 / non-native strides in one library pass
-        out = coattention(x_img, list(x_ques_hierarchy), self.W_v.weight, self.W_v.bias, self.W_q.weight,
-                          self.W_q.bias, self.w_v.weight, self.w_v.bias, self.w_q.weight, self.w_q.bias, impl=impl,
-                          q_len=q_len, return_attention=return_attention, W_b=W_b, b_b=b_b)
+        *params, W_b, b_b = self._params()
+        out = coattention(x_img, ques, *params, impl=impl, q_len=q_len, return_attention=return_attention, W_b=W_b, b_b=b_b)
         v, q = out[0], out[1]
         n = v.shape[0]
         if return_attention:
@@ -449,44 +392,12 @@ class ParallelCoAttention(nn.Module):
         (model.py:388), unmasked as the reference's: pad tokens carry weight -- under ``question_mask`` (coattn_infer_len)
         a_q[l, b, t] is 0 for t >= x_ques_lens[b].  Raises if a gradient would be needed."""
         ques = list(x_ques_hierarchy)
-        params = (self.W_v.weight, self.W_v.bias, self.W_q.weight, self.W_q.bias, self.w_v.weight, self.w_v.bias,
-                  self.w_q.weight, self.w_q.bias, *[t for t in self._wb() if t is not None])
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (x_img, *ques, *params)):
+        if self._needs_grad(x_img, ques):
             raise RuntimeError("forward_with_attention is forward only: run it under torch.no_grad() (the maps come from "
                                "the inference path, which keeps no state for a backward)")
         if not x_img.is_cuda:
             raise RuntimeError("ParallelCoAttention (HIP) needs tensors on the GPU; there is no CPU fallback")
         impl = self._impl()
         q_len = self._lengths(x_img, x_ques_lens)
-        V = native_features(x_img)
-        if V.dtype != torch.float32 or any(q.dtype != torch.float32 for q in ques):
-            raise RuntimeError("ParallelCoAttention (HIP) computes in fp32; got %s" % V.dtype)
-        lib = _lib.load()
-        L = len(ques)
-        B, N, d = V.shape
-        T = ques[0].shape[1]
-        for q in ques:
-            if tuple(q.shape) != (B, T, d):
-                raise RuntimeError("question features must all be [B,T,d] = %s, got %s" % ((B, T, d), tuple(q.shape)))
-        Qs = [q.contiguous() for q in ques]
-        ps = [t.detach().contiguous() for t in params]
-        _, fb, _ = _lib.workspace_bytes(B, N, T, d, L, impl)
-        dev = V.device
-        out_v = torch.empty((L, B, d), device=dev, dtype=torch.float32)
-        out_q = torch.empty((L, B, d), device=dev, dtype=torch.float32)
-        a_v = torch.empty((L, B, N), device=dev, dtype=torch.float32)
-        a_q = torch.empty((L, B, T), device=dev, dtype=torch.float32)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ws = _lib.scratch(fb, dev, stream)
-        qptr = (C.c_void_p * L)(*[q.data_ptr() for q in Qs])
-        p = _lib.Params(*[t.data_ptr() for t in ps])
-        args = (C.byref(p), _ptr(out_v), _ptr(out_q), _ptr(a_v), _ptr(a_q), _ptr(ws), B, N, T, d, L, _lib.F32, impl,
-                C.c_void_p(stream))
-        with _lib.on_device(dev):
-            if q_len is None:
-                _lib.check(lib.coattn_infer(_ptr(V), *_strides(V), qptr, *args), "coattn_infer")
-            else:
-                _lib.check(lib.coattn_infer_len(_ptr(V), *_strides(V), qptr, _ptr(q_len), *args), "coattn_infer_len")
-        if impl & _lib.FLAG_FAST16:                   # tolerance mode: the status words are in the workspace
-            _lib.note_status("coattn", ws, (B, N, T, d, L), dev)
-        return [out_v[l] for l in range(L)], [out_q[l] for l in range(L)], a_v, a_q
+        out_v, out_q, a_v, a_q = _forward(None, native_features(x_img), ques, self._params(), impl, q_len, maps=True)
+        return [out_v[l] for l in range(len(ques))], [out_q[l] for l in range(len(ques))], a_v, a_q

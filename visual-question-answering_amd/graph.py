@@ -2,8 +2,9 @@
 entropy, and their backward -- captured into HIP graphs and replayed per step (two host calls instead of ~25 kernel
 launches and two autograd round trips).
 
-What is captured are the C-ABI calls themselves (``coattn_forward`` + ``coattn_head_forward``; ``coattn_head_backward`` +
-``coattn_backward``: asynchronous on the stream they are given, no allocation, no synchronisation -> capture-safe).
+What is captured are the C-ABI calls themselves (``coattn_forward_len`` + ``coattn_head_forward``; ``coattn_head_backward`` +
+``coattn_backward_maps_len`` without map gradients: asynchronous on the stream they are given, no allocation, no
+synchronisation -> capture-safe), bound by name once per address set (``_lib.bind``).
 Outputs, saved state and workspaces are static buffers of this object; the INPUTS (image features, the three question
 levels, labels) are read where they lie: a graph pair is captured per set of input addresses and image-feature strides
 (a training loop's allocator hands the same blocks back step after step; at most ``MAX_KEYS`` pairs, beyond that the
@@ -28,9 +29,9 @@ reference to it across steps (a gradient logger, an EMA of gradients) must clone
 the buffers (C-ABI ``accumulate = 1``); with captured graphs, or when only some of the 16 parameters still hold the static
 buffer, it raises instead of dropping the earlier gradient.
 
-``question_mask=True``: the co-attention calls are the length-masked ones (``coattn_forward_len`` / ``coattn_backward_len``)
-reading a static int32 [B] length buffer, which every call of the node refills from its ``q_len`` argument before the
-forward is issued or replayed -- captured graphs read the lengths of the step they run.
+``question_mask=True``: the co-attention calls read a static int32 [B] length buffer (NULL lengths otherwise: unmasked), which
+every call of the node refills from its ``q_len`` argument before the forward is issued or replayed -- captured graphs read
+the lengths of the step they run.
 
 The co-attention module's ``affinity="bilinear"``: the calls carry ``COATTN_FLAG_BILINEAR`` and ``W_b`` (weight and bias) joins
 the static parameters and gradients (18 instead of 16), eager and captured alike.
@@ -52,14 +53,9 @@ import torch
 
 from . import _lib
 from . import head as _head
-from .coattention import _is_native, _native_layout, _strides, native_features
+from .coattention import _is_native, _native_layout, _shared_args, native_features
 # (the package exports a FUNCTION named `coattention`, which shadows the submodule as an attribute: take the module itself)
 _coattention = sys.modules[_is_native.__module__]
-from .head import _workspace_bytes as _head_ws
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 class HotPathGraph:
@@ -116,7 +112,7 @@ class HotPathGraph:
         self.co_grads = [torch.empty_like(p) for p in self.co_params]
         self.head_grads = [torch.empty_like(p) for p in self.head_params]
         sb, fb, bb = _lib.workspace_bytes(B, N, T, d, 3, flags)
-        hsb, hwb = _head_ws(B, d, mlp, K)
+        hsb, hwb = _lib.head_workspace_bytes(B, d, mlp, K)
         self.saved = torch.empty(sb // 4, **f32); self.ws = torch.empty(max(fb, bb) // 4, **f32)
         self.hsaved = torch.empty(hsb // 4, **f32); self.hws = torch.empty(hwb // 4, **f32)
         self.g_loss = torch.ones(1, **f32)                           # upstream gradient of the loss (device scalar)
@@ -125,11 +121,6 @@ class HotPathGraph:
         self._warm = False
         self._static = ((self.V, self.Q[0], self.Q[1], self.Q[2], self.labels) if loss == "ce"
                         else (self.V, self.Q[0], self.Q[1], self.Q[2], self.ans_idx, self.ans_score))
-        self._lib = _lib.load()
-        self._head_fwd, self._head_fwd_name = ((self._lib.coattn_head_forward, "coattn_head_forward") if loss == "ce" else
-                                               (self._lib.coattn_head_forward_soft, "coattn_head_forward_soft"))
-        self._co_fwd = self._lib.coattn_forward_len if question_mask else self._lib.coattn_forward
-        self._co_bwd = self._lib.coattn_backward_len if question_mask else self._lib.coattn_backward
         self.pair(self._static)
 
     @staticmethod
@@ -152,9 +143,10 @@ class HotPathGraph:
         return (V.data_ptr(), *[t.data_ptr() for t in ins[1:]], V.stride(0), V.stride(1), V.stride(2))
 
     def _plan(self, ins, key=None):
-        """Argument blocks of the four C-ABI calls for the inputs `ins` = (V [B,N,d] in a native layout, Q_w, Q_p, Q_s,
-        labels), built once per address set (everything but the stream).  Parameters are read where they lie (the
-        optimiser updates them in place); the ctypes blocks are kept alive by the plan."""
+        """The four C-ABI calls for the inputs `ins` = (V [B,N,d] in a native layout, Q_w, Q_p, Q_s, labels), bound by name
+        once per address set (everything but the stream): coattn_forward_len and coattn_backward_maps_len with NULL map
+        gradients (NULL lengths when unmasked), the head's forward of this node's loss, coattn_head_backward.  Parameters
+        are read where they lie (the optimiser updates them in place)."""
         key = key or self._key(ins)
         plan = self._plans.get(key)
         if plan is not None:
@@ -162,53 +154,51 @@ class HotPathGraph:
         if len(self._plans) >= 8 * self.MAX_KEYS:                # (eager mode has no graph to keep: drop the oldest)
             self._plans.pop(next(iter(self._plans)))
         B, N, T, d, mlp, K = self.dims
-        V, Qs = ins[0], ins[1:4]
-        # the head's target arguments: int64 labels, or (ans_idx, ans_score, A, kind) of the soft-target call
-        target = ((_ptr(ins[4]),) if self.loss_name == "ce"
-                  else (_ptr(ins[4]), _ptr(ins[5]), self.num_answers, _lib.LOSS_KINDS[self.loss_name]))
-        qptr = (C.c_void_p * 3)(*[t.data_ptr() for t in Qs])
-        dqptr = (C.c_void_p * 3)(*[t.data_ptr() for t in self.dQ])
-        rows = lambda t: (C.c_void_p * 3)(*[t[l].data_ptr() for l in range(3)])   # noqa: E731
-        p = _lib.Params(*[t.data_ptr() for t in self.co_params])
-        pg = _lib.ParamGrads(*[t.data_ptr() for t in self.co_grads])
-        hp = _lib.HeadParams(*[t.data_ptr() for t in self.head_params])
-        hg = _lib.HeadParamGrads(*[t.data_ptr() for t in self.head_grads])
-        rv, rq, rdx = rows(self.v), rows(self.q), rows(self.dx)
-        vs = _strides(V)
-        dvs = (N * d, d, 1) if self.dV is not None else (0, 0, 0)   # the static dV buffer is location-major
-        ql = (_ptr(self.q_len),) if self.q_len is not None else ()  # (the *_len calls: the lengths follow Q)
-        plan = {
-            "keep": (qptr, dqptr, p, pg, hp, hg, rv, rq, rdx),
-            "co_fwd": (_ptr(V), *vs, qptr, *ql, C.byref(p), _ptr(self.v), _ptr(self.q), _ptr(self.saved), _ptr(self.ws),
-                       B, N, T, d, 3, _lib.F32, self.flags),
-            "head_fwd": (rv, rq, C.byref(hp), *target, _ptr(self.logits), _ptr(self.loss), _ptr(self.hsaved),
-                         B, d, mlp, K, _lib.F32, self.head_flags),
-            "head_bwd": (rv, rq, C.byref(hp), _ptr(self.hsaved), _ptr(self.g_loss), None, rdx, None, C.byref(hg), 0,
-                         _ptr(self.hws), B, d, mlp, K, _lib.F32, self.head_flags),
-            "co_bwd": (_ptr(V), *vs, qptr, *ql, C.byref(p), _ptr(self.saved), _ptr(self.dx), _ptr(self.dx), _ptr(self.dV),
-                       *dvs, dqptr, C.byref(pg), 0, _ptr(self.ws), B, N, T, d, 3, _lib.F32, self.flags),
+        co = _shared_args(ins[0], ins[1:4], self.q_len, _lib.Params(*[t.data_ptr() for t in self.co_params]), self.ws,
+                          self.flags)
+        head = dict(v=_lib.rows(self.v), q=_lib.rows(self.q), p=_lib.HeadParams(*[t.data_ptr() for t in self.head_params]),
+                    saved=self.hsaved, B=B, d=d, mlp=mlp, K=K, dtype=_lib.F32, flags=self.head_flags)
+        dv = dict(dV=self.dV, dv_sB=N * d, dv_sN=d, dv_sD=1) if self.dV is not None else {}   # (location-major)
+        if self.loss_name == "ce":
+            head_fwd = _lib.bind("coattn_head_forward", labels=ins[4], logits=self.logits, loss=self.loss, **head)
+        else:
+            head_fwd = _lib.bind("coattn_head_forward_soft", ans_idx=ins[4], ans_score=ins[5], A=self.num_answers,
+                                 kind=_lib.LOSS_KINDS[self.loss_name], logits=self.logits, loss=self.loss, **head)
+        plan = self._plans[key] = {
+            "co_fwd": _lib.bind("coattn_forward_len", v_out=self.v, q_out=self.q, saved=self.saved, **co),
+            "head_fwd": head_fwd,
+            "head_bwd": _lib.bind("coattn_head_backward", g_loss=self.g_loss, dv=_lib.rows(self.dx), accumulate=0, ws=self.hws,
+                                  pg=_lib.HeadParamGrads(*[t.data_ptr() for t in self.head_grads]), **head),
+            "co_bwd": _lib.bind("coattn_backward_maps_len", saved=self.saved, gv=self.dx, gq=self.dx,
+                                dQ=_lib.ptr_array(self.dQ), pg=_lib.ParamGrads(*[t.data_ptr() for t in self.co_grads]),
+                                accumulate=0, **co, **dv),
         }
-        ai = 15 + len(ql)                                        # index of co_bwd's `accumulate`
-        # (variants of the two backward calls: a gradient arriving for the logits; accumulate = 1 for a second backward
-        #  onto the same static gradient buffers; the loss's upstream gradient read where autograd left it)
-        plan["head_bwd_args"] = lambda g_logits, acc, g_loss=None: (plan["head_bwd"][:4] + (_ptr(self.g_loss if g_loss is None else g_loss), _ptr(g_logits))   # noqa: E731
-                                                                    + plan["head_bwd"][6:9] + (acc,) + plan["head_bwd"][10:])
-        plan["co_bwd_args"] = lambda acc: plan["co_bwd"][:ai] + (acc,) + plan["co_bwd"][ai + 1:]   # noqa: E731
-        assert plan["head_bwd"][9] == 0 and plan["head_bwd"][5] is None and plan["co_bwd"][ai] == 0
-        self._plans[key] = plan
         return plan
+
+    @staticmethod
+    def _forward_pair(plan, st):
+        plan["co_fwd"](st)
+        plan["head_fwd"](st)
+
+    def _backward_pair(self, plan, st, g_logits=None, accumulate=0, g_loss=None):
+        """g_logits: a gradient arriving for the logits; accumulate = 1: a second backward onto the same static gradient
+        buffers; g_loss: the loss's upstream gradient read where autograd left it (else the static scalar)."""
+        head, co = plan["head_bwd"], plan["co_bwd"]
+        if g_logits is not None or accumulate or g_loss is not None:
+            head = head.replace(g_loss=self.g_loss if g_loss is None else g_loss, g_logits=g_logits, accumulate=accumulate)
+        if accumulate:
+            co = co.replace(accumulate=accumulate)
+        head(st)
+        co(st)
 
     # the C-ABI calls on `stream`, reading the inputs `ins` = (V [B,N,d] in a native layout, Q_w, Q_p, Q_s, labels)
     def _enqueue(self, ins, stream, fwd=True, bwd=True):
-        lib = self._lib
         plan = self._plan(ins)
         st = C.c_void_p(stream)
         if fwd:
-            _lib.check(self._co_fwd(*plan["co_fwd"], st), "coattn_forward")
-            _lib.check(self._head_fwd(*plan["head_fwd"], st), self._head_fwd_name)
+            self._forward_pair(plan, st)
         if bwd:
-            _lib.check(lib.coattn_head_backward(*plan["head_bwd"], st), "coattn_head_backward")
-            _lib.check(self._co_bwd(*plan["co_bwd"], st), "coattn_backward")
+            self._backward_pair(plan, st)
 
     def usable_in_place(self, ins) -> bool:
         B, N, T, d, _, _ = self.dims
@@ -263,26 +253,16 @@ class HotPathGraph:
         if pair is not _EAGER and (g_logits is not None or accumulate):
             raise RuntimeError("HotPathGraph: a gradient for `logits` / a second backward onto the same gradient buffers "
                                "cannot be replayed from the captured graph (use capture=False, or the module path)")
-        if pair is _EAGER and not fwd and (g_logits is not None or accumulate or g_loss is not None):
-            plan = plan or self._plan(ins)
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            with _lib.on_device(self.device):
-                _lib.check(self._lib.coattn_head_backward(*plan["head_bwd_args"](g_logits, accumulate, g_loss), st), "coattn_head_backward")
-                _lib.check(self._co_bwd(*plan["co_bwd_args"](accumulate), st), "coattn_backward")
-            return
-        if pair is _EAGER:
-            plan = plan or self._plan(ins)
-            lib = self._lib
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            with _lib.on_device(self.device):
-                if fwd:
-                    _lib.check(self._co_fwd(*plan["co_fwd"], st), "coattn_forward")
-                    _lib.check(self._head_fwd(*plan["head_fwd"], st), self._head_fwd_name)
-                else:
-                    _lib.check(lib.coattn_head_backward(*plan["head_bwd"], st), "coattn_head_backward")
-                    _lib.check(self._co_bwd(*plan["co_bwd"], st), "coattn_backward")
-        else:
+        if pair is not _EAGER:
             pair[0 if fwd else 1].replay()
+            return
+        plan = plan or self._plan(ins)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with _lib.on_device(self.device):
+            if fwd:
+                self._forward_pair(plan, st)
+            else:
+                self._backward_pair(plan, st, g_logits, accumulate, g_loss)
 
     def replay(self, ins=None):
         ins = ins or self._static

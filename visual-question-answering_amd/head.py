@@ -15,23 +15,7 @@ import torch
 
 from . import _lib
 
-_ws_cache = {}
 _last = None          # (saved, B, d, mlp, K, device) of the last forward with labels: check_labels() reads its status word
-
-
-def _workspace_bytes(B, d, mlp, K):
-    key = (B, d, mlp, K)
-    hit = _ws_cache.get(key)
-    if hit is None:
-        s, w = C.c_size_t(), C.c_size_t()
-        _lib.check(_lib.load().coattn_head_workspace_bytes(B, d, mlp, K, _lib.F32, C.byref(s), C.byref(w)),
-                   "coattn_head_workspace_bytes")
-        hit = _ws_cache[key] = (s.value, w.value)
-    return hit
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def _flags() -> int:
@@ -39,10 +23,54 @@ def _flags() -> int:
     return 1 if os.environ.get("VQA_HEAD_PERSISTENT", "0") not in ("0", "") else 0
 
 
-def _rows(t):
-    """Host array of the three [B,d] row-block pointers of a contiguous [3,B,d] tensor."""
-    step = t.stride(0) * t.element_size()
-    return (C.c_void_p * 3)(*[t.data_ptr() + l * step for l in range(3)])
+def _forward(ctx, v, q, params, bf16, labels=None, soft=None):
+    """The head's forward, coattn_head_forward with int64 `labels` [B] or None (logits only), coattn_head_forward_soft with
+    soft = (ans_idx int32 [B,A], ans_score fp32 [B,A], kind).  Returns (logits [B,K], loss [] or None)."""
+    W_w, _, W_p, _, W_s, _, W_h, _ = params
+    ctx.flags = _flags() | (_lib.FLAG_BF16_PROJ if bf16 else 0)
+    if not v.is_cuda:
+        raise RuntimeError("answer_head (HIP) needs tensors on the GPU; there is no CPU fallback")
+    if v.dtype != torch.float32 or q.dtype != torch.float32:
+        raise RuntimeError("answer_head (HIP) computes in fp32; got %s" % v.dtype)
+    if v.dim() != 3 or v.shape[0] != 3 or v.shape != q.shape:
+        raise RuntimeError("answer_head: v and q must both be [3,B,d], got %s / %s" % (tuple(v.shape), tuple(q.shape)))
+    _, B, d = v.shape
+    mlp, K = W_s.shape[0], W_h.shape[0]
+    if (tuple(W_w.shape) != (d, d) or tuple(W_p.shape) != (d, 2 * d) or tuple(W_s.shape) != (mlp, 2 * d)
+            or tuple(W_h.shape) != (K, mlp)):
+        raise RuntimeError("answer_head: weight shapes do not match MLPClassifier(hidden_dim=%d, mlp_dim, K)" % d)
+    if soft is None:
+        if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (B,)):
+            raise RuntimeError("answer_head: labels must be int64 [B]")
+        symbol, target = "coattn_head_forward", dict(labels=labels.contiguous() if labels is not None else None)
+    else:
+        ans_idx, ans_score, kind = soft
+        if (ans_idx.dtype != torch.int32 or ans_score.dtype != torch.float32 or ans_idx.dim() != 2 or ans_idx.shape[0] != B
+                or ans_idx.shape != ans_score.shape or not 1 <= ans_idx.shape[1] <= _lib.MAX_ANSWERS):
+            raise RuntimeError("answer_head: targets must be (ans_idx int32 [B,A], ans_score fp32 [B,A]) with 1 <= A <= %d"
+                               % _lib.MAX_ANSWERS)
+        symbol, target = "coattn_head_forward_soft", dict(ans_idx=ans_idx.contiguous(), ans_score=ans_score.contiguous(),
+                                                          A=ans_idx.shape[1], kind=kind)
+    has_loss = soft is not None or labels is not None
+    v, q = v.contiguous(), q.contiguous()
+    ps = [t.contiguous() for t in params]
+    dev = v.device
+    sb, _ = _lib.head_workspace_bytes(B, d, mlp, K)
+    saved = torch.empty(sb // 4, device=dev, dtype=torch.float32)
+    logits = torch.empty((B, K), device=dev, dtype=torch.float32)
+    loss = torch.empty((), device=dev, dtype=torch.float32) if has_loss else None
+    with _lib.on_device(dev):
+        _lib.bind(symbol, v=_lib.rows(v), q=_lib.rows(q), p=_lib.HeadParams(*[t.data_ptr() for t in ps]), logits=logits,
+                  loss=loss, saved=saved, B=B, d=d, mlp=mlp, K=K, dtype=_lib.F32, flags=ctx.flags,
+                  stream=_lib.stream_ptr(dev), **target)()
+    if has_loss:
+        global _last
+        _last = (saved, B, d, mlp, K, dev)
+    if any(ctx.needs_input_grad):
+        ctx.save_for_backward(v, q, saved, *ps)
+        ctx.dims = (B, d, mlp, K)
+        ctx.has_loss = has_loss
+    return logits, loss
 
 
 class _HeadFn(torch.autograd.Function):
@@ -51,49 +79,13 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
     def forward(ctx, v, q, W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h, labels, bf16=False):
-        ctx.flags = _flags() | (_lib.FLAG_BF16_PROJ if bf16 else 0)
-        if not v.is_cuda:
-            raise RuntimeError("answer_head (HIP) needs tensors on the GPU; there is no CPU fallback")
-        if v.dtype != torch.float32 or q.dtype != torch.float32:
-            raise RuntimeError("answer_head (HIP) computes in fp32; got %s" % v.dtype)
-        if v.dim() != 3 or v.shape[0] != 3 or v.shape != q.shape:
-            raise RuntimeError("answer_head: v and q must both be [3,B,d], got %s / %s" % (tuple(v.shape), tuple(q.shape)))
-        _, B, d = v.shape
-        mlp, K = W_s.shape[0], W_h.shape[0]
-        if (tuple(W_w.shape) != (d, d) or tuple(W_p.shape) != (d, 2 * d) or tuple(W_s.shape) != (mlp, 2 * d)
-                or tuple(W_h.shape) != (K, mlp)):
-            raise RuntimeError("answer_head: weight shapes do not match MLPClassifier(hidden_dim=%d, mlp_dim, K)" % d)
-        if labels is not None and (labels.dtype != torch.int64 or tuple(labels.shape) != (B,)):
-            raise RuntimeError("answer_head: labels must be int64 [B]")
-        lib = _lib.load()
-        v, q = v.contiguous(), q.contiguous()
-        ps = [t.contiguous() for t in (W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h)]
-        dev = v.device
-        sb, _ = _workspace_bytes(B, d, mlp, K)
-        saved = torch.empty(sb // 4, device=dev, dtype=torch.float32)
-        logits = torch.empty((B, K), device=dev, dtype=torch.float32)
-        loss = torch.empty((), device=dev, dtype=torch.float32) if labels is not None else None
-        lab = labels.contiguous() if labels is not None else None
-        p = _lib.HeadParams(*[t.data_ptr() for t in ps])
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with _lib.on_device(dev):
-            _lib.check(lib.coattn_head_forward(_rows(v), _rows(q), C.byref(p), _ptr(lab), _ptr(logits), _ptr(loss),
-                                               _ptr(saved), B, d, mlp, K, _lib.F32, ctx.flags, stream), "coattn_head_forward")
-        if labels is not None:
-            global _last
-            _last = (saved, B, d, mlp, K, dev)
-        if any(ctx.needs_input_grad):
-            ctx.save_for_backward(v, q, saved, *ps)
-            ctx.dims = (B, d, mlp, K)
-            ctx.has_loss = labels is not None
-        return logits, loss
+        return _forward(ctx, v, q, (W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h), bf16, labels=labels)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_logits, g_loss):
         v, q, saved, *ps = ctx.saved_tensors
         B, d, mlp, K = ctx.dims
-        lib = _lib.load()
         dev = v.device
         if not ctx.has_loss:
             g_loss = None
@@ -101,18 +93,17 @@ class _HeadFn(torch.autograd.Function):
             return (None,) * 12
         g_logits = g_logits.contiguous().float() if g_logits is not None else None
         g_loss = g_loss.contiguous().float() if g_loss is not None else None
-        _, wb = _workspace_bytes(B, d, mlp, K)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        _, wb = _lib.head_workspace_bytes(B, d, mlp, K)
+        stream = _lib.stream_ptr(dev)
         ws = _lib.scratch(wb, dev, stream)
         need_in = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         dx = torch.empty_like(v) if need_in else None        # d(q_l + v_l): the gradient of BOTH v and q
         grads = [torch.empty_like(t) for t in ps]
-        p = _lib.HeadParams(*[t.data_ptr() for t in ps])
-        pg = _lib.HeadParamGrads(*[t.data_ptr() for t in grads])
         with _lib.on_device(dev):
-            _lib.check(lib.coattn_head_backward(_rows(v), _rows(q), C.byref(p), _ptr(saved), _ptr(g_loss), _ptr(g_logits),
-                                                _rows(dx) if need_in else None, None, C.byref(pg), 0, _ptr(ws),
-                                                B, d, mlp, K, _lib.F32, ctx.flags, C.c_void_p(stream)), "coattn_head_backward")
+            _lib.bind("coattn_head_backward", v=_lib.rows(v), q=_lib.rows(q), p=_lib.HeadParams(*[t.data_ptr() for t in ps]),
+                      saved=saved, g_loss=g_loss, g_logits=g_logits, dv=_lib.rows(dx) if need_in else None,
+                      pg=_lib.HeadParamGrads(*[t.data_ptr() for t in grads]), accumulate=0, ws=ws, B=B, d=d, mlp=mlp, K=K,
+                      dtype=_lib.F32, flags=ctx.flags, stream=stream)()
         return (dx if ctx.needs_input_grad[0] else None, dx if ctx.needs_input_grad[1] else None, *grads, None, None)
 
 
@@ -123,44 +114,7 @@ class _HeadSoftFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)     # fp32 island under autocast
     def forward(ctx, v, q, W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h, ans_idx, ans_score, kind, bf16=False):
-        ctx.flags = _flags() | (_lib.FLAG_BF16_PROJ if bf16 else 0)
-        if not v.is_cuda:
-            raise RuntimeError("answer_head (HIP) needs tensors on the GPU; there is no CPU fallback")
-        if v.dtype != torch.float32 or q.dtype != torch.float32:
-            raise RuntimeError("answer_head (HIP) computes in fp32; got %s" % v.dtype)
-        if v.dim() != 3 or v.shape[0] != 3 or v.shape != q.shape:
-            raise RuntimeError("answer_head: v and q must both be [3,B,d], got %s / %s" % (tuple(v.shape), tuple(q.shape)))
-        _, B, d = v.shape
-        mlp, K = W_s.shape[0], W_h.shape[0]
-        if (tuple(W_w.shape) != (d, d) or tuple(W_p.shape) != (d, 2 * d) or tuple(W_s.shape) != (mlp, 2 * d)
-                or tuple(W_h.shape) != (K, mlp)):
-            raise RuntimeError("answer_head: weight shapes do not match MLPClassifier(hidden_dim=%d, mlp_dim, K)" % d)
-        if (ans_idx.dtype != torch.int32 or ans_score.dtype != torch.float32 or ans_idx.dim() != 2 or ans_idx.shape[0] != B
-                or ans_idx.shape != ans_score.shape or not 1 <= ans_idx.shape[1] <= _lib.MAX_ANSWERS):
-            raise RuntimeError("answer_head: targets must be (ans_idx int32 [B,A], ans_score fp32 [B,A]) with 1 <= A <= %d"
-                               % _lib.MAX_ANSWERS)
-        lib = _lib.load()
-        v, q = v.contiguous(), q.contiguous()
-        ps = [t.contiguous() for t in (W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h)]
-        ai, sc = ans_idx.contiguous(), ans_score.contiguous()
-        dev = v.device
-        sb, _ = _workspace_bytes(B, d, mlp, K)
-        saved = torch.empty(sb // 4, device=dev, dtype=torch.float32)
-        logits = torch.empty((B, K), device=dev, dtype=torch.float32)
-        loss = torch.empty((), device=dev, dtype=torch.float32)
-        p = _lib.HeadParams(*[t.data_ptr() for t in ps])
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        with _lib.on_device(dev):
-            _lib.check(lib.coattn_head_forward_soft(_rows(v), _rows(q), C.byref(p), _ptr(ai), _ptr(sc), ai.shape[1], kind,
-                                                    _ptr(logits), _ptr(loss), _ptr(saved), B, d, mlp, K, _lib.F32, ctx.flags,
-                                                    stream), "coattn_head_forward_soft")
-        global _last
-        _last = (saved, B, d, mlp, K, dev)
-        if any(ctx.needs_input_grad):
-            ctx.save_for_backward(v, q, saved, *ps)
-            ctx.dims = (B, d, mlp, K)
-            ctx.has_loss = True
-        return logits, loss
+        return _forward(ctx, v, q, (W_w, b_w, W_p, b_p, W_s, b_s, W_h, b_h), bf16, soft=(ans_idx, ans_score, kind))
 
     @staticmethod
     def backward(ctx, g_logits, g_loss):
@@ -176,7 +130,7 @@ def check_labels() -> None:
     saved, B, d, mlp, K, dev = _last
     lib = _lib.load()
     with _lib.on_device(dev):
-        rc = lib.coattn_head_status(_ptr(saved), B, d, mlp, K, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        rc = lib.coattn_head_status(_lib.ptr(saved), B, d, mlp, K, C.c_void_p(_lib.stream_ptr(dev)))
     if rc == -2:
         raise IndexError(lib.coattn_last_error().decode())
     _lib.check(rc, "coattn_head_status")

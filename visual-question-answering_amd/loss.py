@@ -10,10 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+from ._lib import ptr as _ptr
 
 
 _last = None          # (ws, B, device) of the last call: check_labels() reads its status word

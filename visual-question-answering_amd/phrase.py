@@ -10,10 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+from ._lib import ptr as _ptr
 
 
 def _workspace_bytes(B, T, E):
