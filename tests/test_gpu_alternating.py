@@ -2,8 +2,6 @@
 float64 oracle of tests/_alternating.py, on the general-shape path (small odd shapes) and the tuned kernels (config 2 at
 N = 49 and 196), both feature layouts, masked and unmasked, with and without map gradients; the identities it keeps
 (inference, repeatability, pad rows); the refusals; and the module / Trainer / predict surface."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -17,102 +15,8 @@ pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 NAMES = AL.NAMES
-TOL = 2e-5
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def case(B, N, T, d, seed=3, L=3):
-    g = torch.Generator().manual_seed(seed)
-    P = AL.make_params(d, seed)
-    V = torch.randn(B, N, d, generator=g, dtype=torch.float64)
-    Qs = [torch.randn(B, T, d, generator=g, dtype=torch.float64) * (2.0 / d) ** 0.5 for _ in range(L)]
-    gv = torch.randn(L, B, d, generator=g, dtype=torch.float64)
-    gq = torch.randn(L, B, d, generator=g, dtype=torch.float64)
-    return V, Qs, P, gv, gq
-
-
-def run(V, Qs, P, gv=None, gq=None, layout="lm", lens=None, g_av=None, g_aq=None, accumulate=0, grads_init=None,
-        need_dv=True, infer=False, flags=0, expect_rc=0):
-    """One C-ABI forward (+ backward when gv is given).  V [B,N,d] values; layout "lm" hands a [B,N,d] buffer, "cm" a
-    [B,d,N] one.  Returns a dict of fp32 results on the host."""
-    lib = _lib.load()
-    B, N, d = V.shape
-    L, T = len(Qs), Qs[0].shape[1]
-    if layout == "lm":
-        Vd = V.float().to(DEV).contiguous()
-    else:
-        Vd = V.float().to(DEV).permute(0, 2, 1).contiguous().permute(0, 2, 1)
-    sB, sN, sD = Vd.stride()
-    Qd = [q.float().to(DEV).contiguous() for q in Qs]
-    ps = [P[n].float().to(DEV).contiguous() for n in NAMES]
-    p = _lib.AltParams(*[t.data_ptr() for t in ps])
-    qlen = torch.tensor(lens, dtype=torch.int32, device=DEV) if lens is not None else None
-    s = C.c_size_t(); f = C.c_size_t(); b = C.c_size_t()
-    rc = lib.coattn_alt_workspace_bytes(B, N, T, d, L, 0, flags, C.byref(s), C.byref(f), C.byref(b))
-    if flags:
-        assert rc < 0 and b"flags" in lib.coattn_last_error()
-        s, f, b = (C.c_size_t(x) for x in _lib.alt_workspace_bytes(B, N, T, d, L))
-    else:
-        assert rc == 0
-    saved = None if infer else torch.empty(s.value // 4 + 1, device=DEV)
-    ws = torch.empty(max(f.value, b.value) // 4 + 1, device=DEV)
-    v = torch.empty(L, B, d, device=DEV); q = torch.empty(L, B, d, device=DEV)
-    av = torch.empty(L, B, N, device=DEV); aq = torch.empty(L, B, T, device=DEV)
-    qptr = (C.c_void_p * L)(*[x.data_ptr() for x in Qd])
-    rc = lib.coattn_alt_forward(_ptr(Vd), sB, sN, sD, qptr, _ptr(qlen), C.byref(p), _ptr(v), _ptr(q), _ptr(av), _ptr(aq),
-                                _ptr(saved), _ptr(ws), B, N, T, d, L, 0, flags, None)
-    if expect_rc:
-        assert rc < 0, rc
-        return None
-    assert rc == 0, lib.coattn_last_error()
-    out = {"v": v, "q": q, "a_v": av, "a_q": aq}
-    if gv is not None:
-        gvd, gqd = gv.float().to(DEV).contiguous(), gq.float().to(DEV).contiguous()
-        gavd = g_av.float().to(DEV).contiguous() if g_av is not None else None
-        gaqd = g_aq.float().to(DEV).contiguous() if g_aq is not None else None
-        dV = (torch.full_like(Vd, float("nan")) if need_dv else None)
-        dQ = [torch.full_like(x, float("nan")) for x in Qd]
-        grads = ([t.float().to(DEV).clone() for t in grads_init] if grads_init is not None
-                 else [torch.full_like(t, float("nan")) for t in ps])
-        pg = _lib.AltParamGrads(*[t.data_ptr() for t in grads])
-        dqptr = (C.c_void_p * L)(*[x.data_ptr() for x in dQ])
-        dvs = dV.stride() if need_dv else (0, 0, 0)
-        rc = lib.coattn_alt_backward(_ptr(Vd), sB, sN, sD, qptr, _ptr(qlen), C.byref(p), _ptr(saved), _ptr(gvd), _ptr(gqd),
-                                     _ptr(gavd), _ptr(gaqd), _ptr(dV), *dvs, dqptr, C.byref(pg), accumulate, _ptr(ws),
-                                     B, N, T, d, L, 0, 0, None)
-        assert rc == 0, lib.coattn_last_error()
-        out["dV"] = dV
-        out["dQ"] = torch.stack(dQ)
-        for n, t in zip(NAMES, grads):
-            out["d" + n] = t
-    torch.cuda.synchronize()
-    return {k: (x.cpu() if x is not None else None) for k, x in out.items()}
-
-
-def rel(a, b, floor=1e-30):
-    a, b = a.detach().double(), b.detach().double()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(floor))
-
-
-# The gradients of the score biases c_h1..3 are zero in exact arithmetic (a softmax does not see a shift): they are compared as
-# absolute errors, as tests/test_gpu_bilinear.py does for c_v, c_q
-ABS = ("dc_h1", "dc_h2", "dc_h3")
-
-
-def check(out, ref, tol=TOL, keys=None, loose=None):
-    loose = loose or {}
-    keys = keys or [k for k in out if out[k] is not None]
-    errs = {}
-    for k in keys:
-        r = torch.stack(ref[k]) if isinstance(ref[k], list) else ref[k]
-        errs[k] = rel(out[k], r.reshape(out[k].shape), 1.0 if k in ABS else 1e-30)
-    bad = {k: e for k, e in errs.items() if not e <= loose.get(k, tol)}
-    assert not bad, (bad, errs)
-    return errs
-
+TOL = AL.TOL
+case, run, rel, check, ABS = AL.case, AL.run, AL.rel, AL.check, AL.ABS
 
 SMALL = [(4, 7, 5, 64), (3, 7, 5, 96), (1, 7, 5, 64)]
 

@@ -206,12 +206,20 @@ __global__ __launch_bounds__(alt_threads<NLV>()) void guided_bwd_kernel(const Gu
 #pragma unroll
   for (int v = 0; v < NLV; ++v) {
     if (v >= nl) break;
+    // ds_r = a_r (da_r - sum a da) in two passes: S = sum a da in fp32 is off by about eps |da|, which the plain formula
+    // leaves in sum_r ds_r (it should be 0) -- as large as ds itself when the da of the live rows are close to each other.
+    // The second pass measures what is left, S2 = sum a (da - S), and takes it out: sum_r ds_r is then 0 to the rounding of
+    // ds, and the rounding of da moves all ds_r of a sample by one common factor (without it: 6.3e-5 on dW_x3 at d = 1,
+    // LAB_NOTES.md section 11)
     float t = 0.f;
     for (int r = tid; r < Re; r += kAltThreads) t += as[v][r] * dss[v][r];
     const float S = block_sum<kAltWaves>(t, red);
+    float t2 = 0.f;
+    for (int r = tid; r < Re; r += kAltThreads) t2 += as[v][r] * (dss[v][r] - S);
+    const float S2 = block_sum<kAltWaves>(t2, red);
     float u = 0.f;
     for (int r = tid; r < Re; r += kAltThreads) {
-      const float ds = as[v][r] * (dss[v][r] - S);
+      const float ds = as[v][r] * ((dss[v][r] - S) - S2);
       dss[v][r] = ds;
       u += ds;
     }
@@ -519,7 +527,10 @@ extern "C" int coattn_alt_forward(const void* V, int64_t v_sB, int64_t v_sN, int
                                   void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
   CA_TRY(alt_check(B, N, T, d, L, dtype, flags));
   CA_TRY(alt_check_v(v_sB, v_sN, v_sD, N, d, "coattn_alt_forward: V"));
-  CA_CHECK_ARG(V && Q && p && v_out && q_out && ws, "coattn_alt_forward: null argument");
+  {
+    const struct { const void* ptr; const char* name; } req[] = {{V, "V"}, {Q, "Q"}, {p, "p"}, {v_out, "v_out"}, {q_out, "q_out"}, {ws, "ws"}};
+    for (const auto& a : req) CA_CHECK_ARG(a.ptr, "coattn_alt_forward: %s is NULL", a.name);
+  }
   for (int l = 0; l < L; ++l) CA_CHECK_ARG(Q[l], "coattn_alt_forward: Q[%d] is NULL", l);
   const void* const* pp = (const void* const*)p;
   for (int i = 0; i < 16; ++i) CA_CHECK_ARG(pp[i], "coattn_alt_forward: parameter %d is NULL", i);
@@ -617,7 +628,11 @@ extern "C" int coattn_alt_backward(const void* V, int64_t v_sB, int64_t v_sN, in
   CA_TRY(alt_check(B, N, T, d, L, dtype, flags));
   CA_TRY(alt_check_v(v_sB, v_sN, v_sD, N, d, "coattn_alt_backward: V"));
   if (dV) CA_TRY(alt_check_v(dv_sB, dv_sN, dv_sD, N, d, "coattn_alt_backward: dV"));
-  CA_CHECK_ARG(V && Q && p && pg && saved && gv && gq && dQ && ws, "coattn_alt_backward: null argument");
+  {
+    const struct { const void* ptr; const char* name; } req[] = {{V, "V"}, {Q, "Q"}, {p, "p"}, {pg, "pg"}, {saved, "saved"}, {gv, "gv"},
+                                                                 {gq, "gq"}, {dQ, "dQ"}, {ws, "ws"}};
+    for (const auto& a : req) CA_CHECK_ARG(a.ptr, "coattn_alt_backward: %s is NULL", a.name);
+  }
   for (int l = 0; l < L; ++l) CA_CHECK_ARG(Q[l] && dQ[l], "coattn_alt_backward: Q[%d] / dQ[%d] is NULL", l, l);
   const void* const* pp = (const void* const*)p;
   void* const* gp = (void* const*)pg;
