@@ -1,7 +1,7 @@
 """float64 oracle of the alternating co-attention (include/coattn.h v0.11.0; Lu et al. 2016 section 3.3): torch autograd of
 the definition, per sample on Q[b, :len_b] when masked (the maps padded with 0), as tests/_bilinear.py does for the bilinear
 form; the C-ABI runner of the family (case, run, check: feature and gradient layouts, guard words behind every buffer the
-calls write); and paths(), the dispatch rules of csrc/coattn_alt.hip restated in plain Python."""
+calls write); and paths(), the dispatch rules of csrc/coattn_alt.hip (alt_linear, alt_wgrad) restated in plain Python."""
 import ctypes as C
 
 import torch
@@ -295,7 +295,8 @@ MAX_PARTS = 32                     # kAltMaxParts
 
 
 def _projection(M, K, strides=(), aligned=True):
-    """alt_linear / alt_linear_t (gemm_w_supported, exact mode): the pre-split-weight kernel or the general GEMM."""
+    """The linear job alt_linear over plain rows (gemm_w_supported, exact mode): the pre-split-weight kernel or the general
+    GEMM."""
     ok = M >= 128 and K >= 32 and K % 32 == 0 and all(s % 4 == 0 for s in strides) and aligned
     return "gemm_w" if ok else "general"
 
@@ -325,10 +326,11 @@ def _wgrad(rows, levels, n_out, d, aligned=True):
 
 
 def paths(B, N, T, d, L, layout="lm", dv_layout="same"):
-    """Which GEMM every product of one forward + backward call takes, from the rules of alt_linear, alt_linear_t, alt_wgrad
-    and the strided-V branches of csrc/coattn_alt.hip (exact mode: gemm_bf never applies; workspace offsets and whole
-    allocations are 16-byte aligned).  Returns a dict: per product one of "gemm_w", "gemm_w_ask", "general", "general_mdiv",
-    "gemm_tn", "splitk", "grouped" (dV: None without a dV), and "parts": the part count of every fixed-order reduction."""
+    """Which GEMM every product of one forward + backward call takes, from the rules of the linear job alt_linear (rows and
+    strided views of V / dV) and the weight-gradient job alt_wgrad of csrc/coattn_alt.hip (exact mode: gemm_bf never
+    applies; workspace offsets and whole allocations are 16-byte aligned).  Returns a dict: per product one of "gemm_w",
+    "gemm_w_ask", "general", "general_mdiv", "gemm_tn", "splitk", "grouped" (dV: None without a dV), and "parts": the part
+    count of every fixed-order reduction."""
     if dv_layout == "same":
         dv_layout = layout
     _, off, (sB, sN, sD) = layout_geometry(B, N, d, layout)

@@ -8,9 +8,10 @@ Bound (that of tests/test_gpu_alternating.py): max|err| / max|ref| <= 2e-5 on ev
 gradients dc_h* (zero in exact arithmetic) as absolute errors.  Every case prints its worst error per output group.
 
 Which kernel a product reaches is stated in the case's id; the id comes from tests/_alternating.py paths(), the dispatch
-rules of alt_linear, alt_linear_t, alt_wgrad and the strided-V branches restated in Python (tests/test_alternating_cpu.py
-pins them at every threshold), and every table row below is held against paths() when the module is collected.  The
-library's launch marks (coattn_profile_begin / _end) are per phase, not per kernel, so the path is not asserted on the GPU.
+rules of the linear job (alt_linear) and the weight-gradient job (alt_wgrad) restated in Python
+(tests/test_alternating_cpu.py pins them at every threshold), and every table row below is held against paths() when the
+module is collected.  The library's launch marks (coattn_profile_begin / _end) are per phase, not per kernel, so the path
+is not asserted on the GPU; the marks themselves are pinned by test_launch_marks.
 
 Every run also checks the guard words of tests/_alternating.py run(): `saved`, both workspaces, every output and gradient
 are allocated at exactly their size, and a padded dV keeps every cell outside its view."""
@@ -363,7 +364,7 @@ def test_nan_stays_in_its_sample(layout):
 
 # ---- g. refusals ---------------------------------------------------------------------------------------------------------
 # Real buffers at (2, 7, 5, 64); one argument wrong per call.  Every check sits before the first launch of its entry point
-# (alt_check, alt_check_v and the NULL / accumulate checks at the head of coattn_alt_forward / coattn_alt_backward), so
+# (alt_check, check_vlayout and the NULL / accumulate checks at the head of coattn_alt_forward / coattn_alt_backward), so
 # no call below reaches a kernel: it returns < 0, names the argument and leaves every pre-filled buffer as it was.
 RB, RN, RT, RD, RL = 2, 7, 5, 64, 3
 FILL = 0x3FC00000 + 0x1234          # the bit pattern the buffers are pre-filled with
@@ -492,3 +493,35 @@ def test_bad_dv_strides_are_ignored_without_dv(refusal):
     assert r.backward(dV=None, dv_sB=EXTENT, dv_sN=0, dv_sD=-1) == 0, _lib.load().coattn_last_error()
     torch.cuda.synchronize()
     assert all(bool(torch.isfinite(g).all()) for g in r.grads)
+
+
+# ---- h. launch marks -----------------------------------------------------------------------------------------------------
+# The marks of one forward and of one backward, recorded with the library of the commit before the host driver was split
+# into AltCall and its named steps: the split must reproduce them.
+FWD_MARKS = ["alt_projections", "alt_guided"]
+BWD_MARKS = ["alt_guided_bwd", "alt_input_grads", "alt_param_grads"]
+
+
+def profiled_marks(stateless):
+    """The launch-group marks of run() between coattn_profile_begin / _end at (2, 3, 2, 64), L = 3, location-major: a
+    forward with `saved` and its backward with dV, or (stateless) a forward without `saved`, then a forward + backward
+    without dV."""
+    lib = _lib.load()
+    V, Qs, P, gv, gq = AL.case(2, 3, 2, 64, seed=5)
+    torch.cuda.synchronize()
+    _lib.check(lib.coattn_profile_begin(None), "coattn_profile_begin")
+    if stateless:
+        AL.run(V, Qs, P, infer=True)
+    AL.run(V, Qs, P, gv, gq, need_dv=not stateless)
+    us = (C.c_float * 48)()
+    names = C.create_string_buffer(2048)
+    n = lib.coattn_profile_end(us, names, 2048, 48)
+    assert n >= 0, lib.coattn_last_error().decode()
+    marks = names.value.decode().split("\n") if n else []
+    assert len(marks) == n
+    return marks
+
+
+@pytest.mark.parametrize("stateless", [False, True], ids=["saved_dV", "stateless_no_dV"])
+def test_launch_marks(stateless):
+    assert profiled_marks(stateless) == (FWD_MARKS if stateless else []) + FWD_MARKS + BWD_MARKS

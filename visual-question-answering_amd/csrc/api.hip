@@ -779,7 +779,7 @@ static int check_bilinear(int flags, const coattn_params* p, const coattn_param_
   return 0;
 }
 
-static int check_vlayout(const VLayout& v, int N, int d, const char* what) {
+int check_vlayout(const VLayout& v, int N, int d, const char* what) {
   CA_CHECK_ARG(v.sN > 0 && v.sD > 0 && v.sB > 0, "%s: strides must be positive (sB=%ld sN=%ld sD=%ld)", what, v.sB, v.sN, v.sD);
   // the extent of one sample must not reach into the next one
   CA_CHECK_ARG((long)(N - 1) * v.sN + (long)(d - 1) * v.sD < v.sB, "%s: sample stride %ld is smaller than a sample's extent", what, v.sB);

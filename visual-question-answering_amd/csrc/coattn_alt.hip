@@ -9,6 +9,7 @@
 // on the level, so they are read once per sample.  No float atomics: every sum runs in a fixed order (bitwise repeatable).
 #include "common.h"
 #include "fused.h"
+#include <initializer_list>
 
 namespace {
 
@@ -18,8 +19,6 @@ constexpr int kAltMaxD = 1024;         // hidden size
 // threads per workgroup: 512 for steps 1 and 3 (one workgroup per sample and level), 1024 for step 2 (one per sample: B of them,
 // fewer than the CUs at B = 160, so each takes all the waves it can)
 template <int NLV> constexpr int alt_threads() { return NLV == 1 ? 512 : 1024; }
-
-inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 // One guided-attention step for a workgroup: sample b = blockIdx.x, levels [l0, l0 + nl) with l0 = blockIdx.y (NLV = 1: one
 // level, steps 1 and 3) or l0 = 0, nl = L (NLV = kAltMaxL: step 2, the levels share X and P).
@@ -330,29 +329,30 @@ struct AltSaved {                      // offsets in floats (forward -> backward
 AltSaved alt_saved(int B, int N, int T, int d, int L) {
   AltSaved s;
   size_t o = 0;
-  s.x13 = o; o += al64((size_t)L * B * T * 2 * d);   // [X1 | X3] = Q_l [W_x1; W_x3]^T + [b_x1; b_x3]
-  s.x2 = o;  o += al64((size_t)B * N * d);           // X2 = V W_x2^T + b_x2
-  s.g2 = o;  o += al64((size_t)L * B * d);           // s^ W_g2^T + b_g2
-  s.g3 = o;  o += al64((size_t)L * B * d);           // v^ W_g3^T + b_g3
-  s.sh = o;  o += al64((size_t)L * B * d);           // s^
-  s.vh = o;  o += al64((size_t)L * B * d);           // v^
-  s.as = o;  o += al64((size_t)L * B * T);
-  s.av = o;  o += al64((size_t)L * B * N);
-  s.aq = o;  o += al64((size_t)L * B * T);
+  s.x13 = o; o += fal64((size_t)L * B * T * 2 * d);   // [X1 | X3] = Q_l [W_x1; W_x3]^T + [b_x1; b_x3]
+  s.x2 = o;  o += fal64((size_t)B * N * d);           // X2 = V W_x2^T + b_x2
+  s.g2 = o;  o += fal64((size_t)L * B * d);           // s^ W_g2^T + b_g2
+  s.g3 = o;  o += fal64((size_t)L * B * d);           // v^ W_g3^T + b_g3
+  s.sh = o;  o += fal64((size_t)L * B * d);           // s^
+  s.vh = o;  o += fal64((size_t)L * B * d);           // v^
+  s.as = o;  o += fal64((size_t)L * B * T);
+  s.av = o;  o += fal64((size_t)L * B * N);
+  s.aq = o;  o += fal64((size_t)L * B * T);
   s.total = o;
   return s;
 }
+// floats of the weight image a linear job writes for W [N][K] (AltLinear::img), the size of every img* slot of both plans
+size_t alt_img_floats(int N, int K) { return fal64(wsplit_bytes(N, K) / sizeof(float) + 1); }
 struct AltFwdWs { size_t wcat, bcat, img13, img2, imgg2, imgg3, total; };    // floats, after the saved-sized block
 AltFwdWs alt_fwd_ws(int d) {
   AltFwdWs w;
   size_t o = 0;
-  const size_t img = al64(wsplit_bytes(d, d) / sizeof(float) + 1), img2d = al64(wsplit_bytes(2 * d, d) / sizeof(float) + 1);
-  w.wcat = o; o += al64((size_t)2 * d * d);
-  w.bcat = o; o += al64((size_t)2 * d);
-  w.img13 = o; o += img2d;
-  w.img2 = o; o += img;
-  w.imgg2 = o; o += img;
-  w.imgg3 = o; o += img;
+  w.wcat = o; o += fal64((size_t)2 * d * d);
+  w.bcat = o; o += fal64((size_t)2 * d);
+  w.img13 = o; o += alt_img_floats(2 * d, d);
+  w.img2 = o; o += alt_img_floats(d, d);
+  w.imgg2 = o; o += alt_img_floats(d, d);
+  w.imgg3 = o; o += alt_img_floats(d, d);
   w.total = o;
   return w;
 }
@@ -361,23 +361,22 @@ constexpr int kAltMaxParts = 32;
 AltBwdWs alt_bwd_ws(int B, int N, int T, int d, int L) {
   AltBwdWs w;
   size_t o = 0;
-  const size_t img = al64(wsplit_bytes(d, d) / sizeof(float) + 1), img2d = al64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1);
-  w.dh13 = o; o += al64((size_t)L * B * T * 2 * d);
-  w.dx2 = o;  o += al64((size_t)B * N * d);
-  w.dg1 = o;  o += al64((size_t)L * B * d);
-  w.dg2 = o;  o += al64((size_t)L * B * d);
-  w.dg3 = o;  o += al64((size_t)L * B * d);
-  w.dvt = o;  o += al64((size_t)L * B * d);
-  w.dsh = o;  o += al64((size_t)L * B * d);
-  w.wp1 = o;  o += al64((size_t)L * B * (d + 1));
-  w.wp2 = o;  o += al64((size_t)B * (d + 1));
-  w.wp3 = o;  o += al64((size_t)L * B * (d + 1));
-  w.part = o; o += al64((size_t)kAltMaxParts * 2 * d * d);   // split-K parts of the weight gradients
-  w.wcat = o; o += al64((size_t)2 * d * d);
-  w.img13 = o; o += img2d;
-  w.img2 = o; o += img;
-  w.imgg2 = o; o += img;
-  w.imgg3 = o; o += img;
+  w.dh13 = o; o += fal64((size_t)L * B * T * 2 * d);
+  w.dx2 = o;  o += fal64((size_t)B * N * d);
+  w.dg1 = o;  o += fal64((size_t)L * B * d);
+  w.dg2 = o;  o += fal64((size_t)L * B * d);
+  w.dg3 = o;  o += fal64((size_t)L * B * d);
+  w.dvt = o;  o += fal64((size_t)L * B * d);
+  w.dsh = o;  o += fal64((size_t)L * B * d);
+  w.wp1 = o;  o += fal64((size_t)L * B * (d + 1));
+  w.wp2 = o;  o += fal64((size_t)B * (d + 1));
+  w.wp3 = o;  o += fal64((size_t)L * B * (d + 1));
+  w.part = o; o += fal64((size_t)kAltMaxParts * 2 * d * d);   // split-K parts of the weight gradients
+  w.wcat = o; o += fal64((size_t)2 * d * d);
+  w.img13 = o; o += alt_img_floats(d, 2 * d);
+  w.img2 = o; o += alt_img_floats(d, d);
+  w.imgg2 = o; o += alt_img_floats(d, d);
+  w.imgg3 = o; o += alt_img_floats(d, d);
   w.total = o;
   return w;
 }
@@ -392,62 +391,124 @@ int alt_check(int B, int N, int T, int d, int L, int dtype, int flags) {
   CA_CHECK_ARG(L > 0 && L <= kAltMaxL, "alternating co-attention: L=%d outside [1, %d]", L, kAltMaxL);
   return 0;
 }
-int alt_check_v(int64_t sB, int64_t sN, int64_t sD, int N, int d, const char* what) {
-  CA_CHECK_ARG(sN > 0 && sD > 0 && sB > 0, "%s: strides must be positive (sB=%ld sN=%ld sD=%ld)", what, (long)sB, (long)sN, (long)sD);
-  CA_CHECK_ARG((long)(N - 1) * sN + (long)(d - 1) * sD < sB, "%s: sample stride %ld is smaller than a sample's extent", what, (long)sB);
+
+// One alternating call as its C-ABI wrapper fills it once alt_check has passed; every step of the forward and the backward
+// reads its operands, offsets and base pointers from here.
+struct AltCall {
+  int B, N, T, d, L;
+  hipStream_t s;
+  const float* V; VLayout vl;            // x_img[B,N,d] by its element strides
+  const float* const* Q;                 // [L] levels [B][T][d]
+  const int* qlen;                       // [B] or NULL
+  const coattn_alt_params* p;
+  AltSaved so;                           // offsets of the state ...
+  const float* sv;                       // ... in the caller's `saved`, or (forward, saved NULL) at the head of the workspace
+  float* ws;                             // the workspace (forward: behind the state when it holds it), offsets fo / wo
+  // forward
+  float* st;                             // sv, to write
+  bool keep;                             // the caller gave `saved`
+  float* v_out; float* q_out; float* av_out; float* aq_out;   // [L][B][d] x 2; [L][B][N], [L][B][T], each may be NULL
+  AltFwdWs fo;
+  // backward
+  const float* gv; const float* gq;      // [L][B][d] upstream gradients of v, q
+  const float* g_av; const float* g_aq;  // upstream gradients of the maps, NULL = 0
+  float* dV; VLayout dvl;                // NULL: the image features need no gradient
+  float* const* dQ;
+  const coattn_alt_param_grads* pg;      // NULL in a forward
+  int accumulate;
+  AltBwdWs wo;
+};
+AltCall alt_call(const void* V, VLayout vl, const void* const* Q, const int32_t* q_len, const coattn_alt_params* p, int B, int N,
+                 int T, int d, int L, void* stream) {
+  AltCall c = {};
+  c.B = B; c.N = N; c.T = T; c.d = d; c.L = L; c.s = (hipStream_t)stream;
+  c.V = (const float*)V; c.vl = vl; c.Q = (const float* const*)Q; c.qlen = q_len; c.p = p;
+  c.so = alt_saved(B, N, T, d, L);
+  return c;
+}
+
+// The pointers a call cannot do without: `req` by name, then every level of Q and the 16 parameters (backward: with dQ's
+// levels and the 16 gradients)
+struct AltReq { const void* ptr; const char* name; };
+int alt_check_ptrs(const AltCall& c, const char* fn, std::initializer_list<AltReq> req) {
+  for (const AltReq& a : req) CA_CHECK_ARG(a.ptr, "%s: %s is NULL", fn, a.name);
+  const void* const* pp = (const void* const*)c.p;
+  void* const* gp = (void* const*)c.pg;
+  for (int l = 0; l < c.L; ++l) {
+    if (gp) { CA_CHECK_ARG(c.Q[l] && c.dQ[l], "%s: Q[%d] / dQ[%d] is NULL", fn, l, l); }
+    else { CA_CHECK_ARG(c.Q[l], "%s: Q[%d] is NULL", fn, l); }
+  }
+  for (int i = 0; i < 16; ++i) {
+    if (gp) { CA_CHECK_ARG(pp[i] && gp[i], "%s: parameter or gradient %d is NULL", fn, i); }
+    else { CA_CHECK_ARG(pp[i], "%s: parameter %d is NULL", fn, i); }
+  }
   return 0;
 }
 
-// y[z][m][:] = x[z][m][:] W^T + bias (M rows, x rows ld_x apart or the a_ptrs table) on the pre-split-weight kernel when it takes
-// the shape (the weight image `img` written here), else on the general GEMM
-struct Lin {
-  const float* x; const float* x_ptrs[kAltMaxL]; long x_sz; int ld_x;
-  const float* W; const float* bias; float* y; long y_sz; int ld_y;
-  int M, N, K, batch;
+// How the general GEMM walks the M rows of an operand: row-major rows `ld` apart (v NULL), or the [B, n, cols] view `v`, whose
+// rows split by sample (mdiv / sdiv) only when the samples do not abut.  rows: the view is plain row-major rows as well
+struct AltRows { long sm, sk; int mdiv; long sdiv; bool rows; };
+AltRows alt_rows_of(const VLayout* v, int ld, int n, int cols) {
+  if (!v) return AltRows{ld, 1, 0, 0, true};
+  const bool abut = v->sB == (long)n * v->sN;
+  return AltRows{v->sN, v->sD, abut ? 0 : n, abut ? 0 : v->sB, v->sD == 1 && v->sN == cols && v->sB == (long)n * cols};
+}
+
+// The linear job: y[z][m][:] = x[z][m][:] W^T + bias (W [N][K], the forward's projections) or x[z][m][:] W (w_kn: W [K][N], the
+// back-projections dx = dy W), M rows per batch entry -- on the pre-split-weight kernel when it takes the shape (the weight
+// image `img` is written here), else on the general GEMM
+struct AltLinear {
+  const float* x; const float* const* x_tab; long x_sz; int ld_x;    // x_z: table entry z, or x + z x_sz; rows ld_x apart ...
+  const VLayout* x_view;                                             // ... or (not NULL) x as a [M / n, n, K] view by its strides
+  const float* W; bool w_kn; const float* bias;                      // bias [N] or NULL
+  float* y; float* const* y_tab; long y_sz; int ld_y;                // the same for y
+  const VLayout* y_view;                                             // [M / n, n, N]
+  int M, N, K, batch, n;                                             // n: rows per sample of a view
+  void* img;                                                         // the job's weight-image slot (alt_img_floats(N, K) floats)
 };
-int alt_linear(const Lin& l, void* img, hipStream_t s) {
+// one batch entry of plain rows, x rows K and y rows N apart
+AltLinear alt_rows_job(const float* x, const float* W, bool w_kn, const float* bias, float* y, int M, int N, int K, void* img) {
+  AltLinear l = {};
+  l.x = x; l.ld_x = K; l.W = W; l.w_kn = w_kn; l.bias = bias; l.y = y; l.ld_y = N; l.M = M; l.N = N; l.K = K; l.batch = 1; l.img = img;
+  return l;
+}
+int alt_linear(const AltLinear& l, hipStream_t s) {
+  const AltRows a = alt_rows_of(l.x_view, l.ld_x, l.n, l.K), c = alt_rows_of(l.y_view, l.ld_y, l.n, l.N);
   WGemm g = {};
-  g.A = l.x; g.a_sz = l.x_sz; g.a_sm = l.ld_x;
-  for (int t = 0; t < kAltMaxL; ++t) g.a_ptrs[t] = l.x_ptrs[t];
-  g.Wf = img; g.C = l.y; g.c_sz = l.y_sz; g.c_sm = l.ld_y; g.bias_n = l.bias; g.out_scale = 1.f;
+  g.A = l.x; g.Wf = l.img; g.C = l.y; g.c_sz = l.y_sz; g.c_sm = (int)c.sm; g.bias_n = l.bias; g.out_scale = 1.f;
   g.M = l.M; g.N = l.N; g.K = l.K; g.batch = l.batch; g.np = 3;
-  if (!l.x_ptrs[0] && l.batch == 1) g.a_sz = 0;
-  if (gemm_w_supported(g) && (l.ld_y & 3) == 0 && !gemm_bf_supported(g)) {
-    const WSplit job{l.W, img, l.N, l.K, 0, l.K, wimg_pieces(g), nullptr};
+  if (a.rows) {
+    g.a_sm = (int)a.sm;
+    g.a_sz = l.x_tab || l.batch > 1 ? l.x_sz : 0;      // (0 for a single unbatched operand)
+  } else {                                             // channel-major x: A contiguous along m (the kernel's a_sk form)
+    g.a_sk = (int)a.sk; g.a_mdiv = l.n; g.a_sdiv = l.x_view->sB;
+  }
+  coattn_gemm_desc e = {};
+  e.A = l.x; e.a_sz = l.x_sz; e.a_sm = a.sm; e.a_sk = a.sk; e.a_mdiv = a.mdiv; e.a_sdiv = a.sdiv;
+  e.B = l.W; e.b_sk = l.w_kn ? l.N : 1; e.b_sn = l.w_kn ? 1 : l.K;
+  e.C = l.y; e.c_sz = l.y_sz; e.c_sm = c.sm; e.c_sn = c.sk; e.c_mdiv = c.mdiv; e.c_sdiv = c.sdiv; e.bias_n = l.bias;
+  e.M = l.M; e.N = l.N; e.K = l.K; e.batch = l.batch;
+  for (int t = 0; t < l.batch; ++t) {
+    if (l.x_tab) { g.a_ptrs[t] = l.x_tab[t]; e.a_ptrs[t] = l.x_tab[t]; }
+    if (l.y_tab) { g.c_ptrs[t] = l.y_tab[t]; e.c_ptrs[t] = l.y_tab[t]; }
+  }
+  // The kernel stores rows only (a strided y: the general GEMM) and takes a view of x only along m, within the offsets its
+  // a_sk form keeps (a_sk is an int).  Its 16-byte stores need no test of their own: ld_y is d or 2d and K, a multiple of
+  // 32 here, is d or 2d, so ld_y % 4 == 0
+  const bool view_ok = a.rows || (l.x_view->sN == 1 && l.x_view->sD < (1L << 30) && l.x_view->sB < (1L << 40));
+  if (c.rows && view_ok && gemm_w_supported(g) && !gemm_bf_supported(g)) {
+    const WSplit job{l.W, l.img, l.N, l.K, l.w_kn ? 1 : 0, l.w_kn ? l.N : l.K, wimg_pieces(g), nullptr};
     CA_TRY(launch_wsplit(&job, 1, s));
     return launch_gemm_wx(&g, 1, s);
   }
-  coattn_gemm_desc d = {};
-  d.A = l.x; d.a_sz = l.x_sz; d.a_sm = l.ld_x; d.a_sk = 1;
-  for (int t = 0; t < kAltMaxL; ++t) d.a_ptrs[t] = l.x_ptrs[t];
-  d.B = l.W; d.b_sk = 1; d.b_sn = l.K;
-  d.C = l.y; d.c_sz = l.y_sz; d.c_sm = l.ld_y; d.c_sn = 1; d.bias_n = l.bias;
-  d.M = l.M; d.N = l.N; d.K = l.K; d.batch = l.batch;
-  return launch_gemm_f32(d, s);
+  return launch_gemm_f32(e, s);
 }
 
-// y[m][:] = x[m][:] W (W [K][N] row-major: dx = dy W) -- the back-projections -- same dispatch
-int alt_linear_t(const float* x, int ld_x, long x_sz, const float* W, float* const* y_ptrs, float* y, long y_sz, int M, int N, int K,
-                 int batch, void* img, hipStream_t s) {
-  WGemm g = {};
-  g.A = x; g.a_sz = batch > 1 ? x_sz : 0; g.a_sm = ld_x;
-  g.Wf = img; g.C = y; g.c_sz = y_sz; g.c_sm = N; g.out_scale = 1.f;
-  if (y_ptrs) for (int t = 0; t < batch; ++t) g.c_ptrs[t] = y_ptrs[t];
-  g.M = M; g.N = N; g.K = K; g.batch = batch; g.np = 3;
-  if (gemm_w_supported(g) && !gemm_bf_supported(g)) {
-    const WSplit job{W, img, N, K, 1, N, wimg_pieces(g), nullptr};
-    CA_TRY(launch_wsplit(&job, 1, s));
-    return launch_gemm_wx(&g, 1, s);
-  }
-  coattn_gemm_desc d = {};
-  d.A = x; d.a_sz = x_sz; d.a_sm = ld_x; d.a_sk = 1;
-  d.B = W; d.b_sk = N; d.b_sn = 1;
-  d.C = y; d.c_sz = y_sz; d.c_sm = N; d.c_sn = 1;
-  if (y_ptrs) for (int t = 0; t < batch; ++t) d.c_ptrs[t] = y_ptrs[t];
-  d.M = M; d.N = N; d.K = K; d.batch = batch;
-  return launch_gemm_f32(d, s);
+// the next job of a reduce launch: dst[j] (+)= sum over p < nparts of src[p ld + j], j < n
+void alt_reduce_job(AltReduce& r, const float* src, void* dst, long n, long ld, int nparts) {
+  const int k = r.njobs++;
+  r.src[k] = src; r.dst[k] = (float*)dst; r.n[k] = n; r.ld[k] = ld; r.nparts[k] = nparts;
 }
-
 int launch_alt_reduce(const AltReduce& r, hipStream_t s) {
   long nmax = 0;
   for (int i = 0; i < r.njobs; ++i) nmax = r.n[i] > nmax ? r.n[i] : nmax;
@@ -456,44 +517,70 @@ int launch_alt_reduce(const AltReduce& r, hipStream_t s) {
   return 0;
 }
 
-// dW (+)= sum over rows of dY^T X, dY rows [rows][n_out] (ld_dy), X rows [rows][n_in] (ld_x) per level (x_ptrs) or once;
-// the [n_out][n_in] result may be split by rows into dW0 (rows < split) and dW1.  Split-K parts + a fixed-order reduce.
-int alt_wgrad(const float* dy, int ld_dy, long dy_sl, const float* const* x_ptrs, const float* x, int ld_x, int rows, int levels,
-              int n_out, int n_in, float* dW0, float* dW1, int split, int accumulate, float* part, hipStream_t s) {
-  TnGemm t = {};
-  t.A = dy; t.a_ld = ld_dy; t.a_sl = dy_sl;
-  t.B = x; t.b_ld = ld_x;
-  if (x_ptrs) for (int l = 0; l < levels; ++l) t.b_ptrs[l] = x_ptrs[l];
-  t.C = part; t.M = n_out; t.N = n_in; t.K = rows; t.levels = levels; t.np = 3;
+// The weight-gradient job: dW (+)= sum over rows of dY^T X, dY rows [rows][n_out] (ld_dy) per level, X rows [rows][n_in] (ld_x)
+// per level (x_tab) or once (x); the [n_out][n_in] result may be split by rows into dW0 (rows < split) and dW1.  Parts in the
+// call's workspace + a fixed-order reduce.  The parts come from gemm_tn when it takes the shape, else from the general GEMM's
+// split-K level by level; X = the image features in another layout than rows (x_view): from the general GEMM over groups of
+// G = ceil(B / kAltMaxParts) samples,  dW[j][k] = sum_b sum_n dY[b][n][j] V[b][n][k]
+struct AltWgrad {
+  const float* dy; int ld_dy; long dy_sl;
+  const float* x; const float* const* x_tab; int ld_x;
+  const VLayout* x_view;                 // (not NULL) x as the [B, N, n_in] view of the call's image features
+  int rows, levels, n_out, n_in;
+  float* dW0; float* dW1; int split;
+};
+int alt_wgrad(const AltWgrad& w, const AltCall& c) {
+  float* part = c.ws + c.wo.part;
+  const long mn = (long)w.n_out * w.n_in;
+  // parts [batch] = dY_z^T X_z on the general GEMM; the caller adds how X and the contraction are walked
+  auto part_job = [&](const float* dy, const float* x, float* out, int K, int batch) {
+    coattn_gemm_desc g = {};
+    g.A = dy; g.a_sm = 1; g.a_sk = w.ld_dy; g.B = x; g.C = out; g.c_sz = mn; g.c_sm = w.n_in; g.c_sn = 1;
+    g.M = w.n_out; g.N = w.n_in; g.K = K; g.batch = batch;
+    return g;
+  };
   int parts;
-  if (gemm_tn_supported(t)) {
-    int ks, S;
-    parts = gemm_tn_plan(t, kAltMaxParts, &ks, &S);
-    CA_TRY(launch_gemm_tn(&t, &ks, &S, 1, s));
+  if (!alt_rows_of(w.x_view, w.ld_x, c.N, w.n_in).rows) {
+    const int G = (c.B + kAltMaxParts - 1) / kAltMaxParts;
+    parts = (c.B + G - 1) / G;
+    coattn_gemm_desc g = part_job(w.dy, w.x, part, c.N, parts);
+    g.a_si = (int64_t)c.N * w.ld_dy; g.a_sz = G * g.a_si;
+    g.b_sk = w.x_view->sN; g.b_sn = w.x_view->sD; g.b_si = w.x_view->sB; g.b_sz = G * g.b_si;
+    g.inner = G; g.inner_total = c.B;
+    CA_TRY(launch_gemm_f32(g, c.s));
   } else {
-    const int per = (kAltMaxParts / levels) > 0 ? kAltMaxParts / levels : 1;
-    int ks = (rows + per - 1) / per;
-    ks = (ks + 15) / 16 * 16;
-    const int S = (rows + ks - 1) / ks;
-    for (int l = 0; l < levels; ++l) {
-      coattn_gemm_desc g = {};
-      g.A = dy + (long)l * dy_sl; g.a_sm = 1; g.a_sk = ld_dy;
-      g.B = x_ptrs ? x_ptrs[l] : x; g.b_sk = ld_x; g.b_sn = 1;
-      g.C = part + (size_t)l * S * n_out * n_in; g.c_sz = (int64_t)n_out * n_in; g.c_sm = n_in; g.c_sn = 1;
-      g.M = n_out; g.N = n_in; g.K = rows; g.batch = S; g.ksplit = ks;
-      CA_TRY(launch_gemm_f32(g, s));
+    TnGemm t = {};
+    t.A = w.dy; t.a_ld = w.ld_dy; t.a_sl = w.dy_sl;
+    t.B = w.x; t.b_ld = w.ld_x;
+    if (w.x_tab) for (int l = 0; l < w.levels; ++l) t.b_ptrs[l] = w.x_tab[l];
+    t.C = part; t.M = w.n_out; t.N = w.n_in; t.K = w.rows; t.levels = w.levels; t.np = 3;
+    if (gemm_tn_supported(t)) {
+      int ks, S;
+      parts = gemm_tn_plan(t, kAltMaxParts, &ks, &S);
+      CA_TRY(launch_gemm_tn(&t, &ks, &S, 1, c.s));
+    } else {
+      const int per = (kAltMaxParts / w.levels) > 0 ? kAltMaxParts / w.levels : 1;
+      int ks = (w.rows + per - 1) / per;
+      ks = (ks + 15) / 16 * 16;
+      const int S = (w.rows + ks - 1) / ks;
+      for (int l = 0; l < w.levels; ++l) {
+        coattn_gemm_desc g = part_job(w.dy + (long)l * w.dy_sl, w.x_tab ? w.x_tab[l] : w.x, part + (size_t)l * S * mn, w.rows, S);
+        g.b_sk = w.ld_x; g.b_sn = 1; g.ksplit = ks;
+        CA_TRY(launch_gemm_f32(g, c.s));
+      }
+      parts = w.levels * S;
     }
-    parts = levels * S;
   }
   AltReduce r = {};
-  r.accumulate = accumulate;
-  r.src[0] = part; r.dst[0] = dW0; r.n[0] = (long)split * n_in; r.ld[0] = (long)n_out * n_in; r.nparts[0] = parts;
-  r.njobs = 1;
-  if (dW1) {
-    r.src[1] = part + (size_t)split * n_in; r.dst[1] = dW1; r.n[1] = (long)(n_out - split) * n_in; r.ld[1] = r.ld[0];
-    r.nparts[1] = parts; r.njobs = 2;
-  }
-  return launch_alt_reduce(r, s);
+  r.accumulate = c.accumulate;
+  alt_reduce_job(r, part, w.dW0, (long)w.split * w.n_in, mn, parts);
+  if (w.dW1) alt_reduce_job(r, part + (size_t)w.split * w.n_in, w.dW1, (long)(w.n_out - w.split) * w.n_in, mn, parts);
+  return launch_alt_reduce(r, c.s);
+}
+// a weight gradient of one level without a split: dW [n][n] (+)= dY^T X, both [rows][n] row-major (x_view NULL) or X the features
+int alt_wgrad_square(const AltCall& c, const float* dy, const float* x, const VLayout* x_view, int rows, void* dW) {
+  const AltWgrad w = {dy, c.d, 0, x, nullptr, c.d, x_view, rows, 1, c.d, c.d, (float*)dW, nullptr, c.d};
+  return alt_wgrad(w, c);
 }
 
 template <int NLV>
@@ -508,6 +595,162 @@ int launch_guided(bool fwd, const GuidedArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL(guided_bwd_kernel<NLV>, grid, dim3(alt_threads<NLV>()), 0, s, a);
   CA_CHECK_LAUNCH(fwd ? "guided_fwd" : "guided_bwd");
   return 0;
+}
+
+// What the guided steps of a call share, forward and backward: steps 1 and 3 attend the question levels, their projections
+// the halves of [X1 | X3] ...
+GuidedArgs alt_q_side(const AltCall& c) {
+  GuidedArgs q = {};
+  for (int i = 0; i < c.L; ++i) q.x[i] = c.Q[i];
+  q.x_sB = (long)c.T * c.d; q.x_sR = c.d; q.x_sD = 1;
+  q.p_sL = (long)c.B * c.T * 2 * c.d; q.p_ld = 2 * c.d; q.len = c.qlen; q.B = c.B; q.R = c.T; q.d = c.d; q.L = c.L;
+  return q;
+}
+// ... and step 2 the image features by their strides under the guide g2, every level of a sample against the same V and X2
+GuidedArgs alt_v_side(const AltCall& c) {
+  GuidedArgs a = {};
+  for (int i = 0; i < kAltMaxL; ++i) a.x[i] = c.V;
+  a.x_sB = c.vl.sB; a.x_sR = c.vl.sN; a.x_sD = c.vl.sD;
+  a.p = c.sv + c.so.x2; a.p_sL = 0; a.p_ld = c.d; a.g = c.sv + c.so.g2; a.w = (const float*)c.p->w_h2;
+  a.B = c.B; a.R = c.N; a.d = c.d; a.L = c.L;
+  return a;
+}
+
+// ---- the forward's steps
+int alt_fwd_projections(const AltCall& c) {
+  const coattn_alt_params* p = c.p;
+  const int d = c.d;
+  float* wf = c.ws;
+  // [X1 | X3] of every level: ONE projection against the stacked [W_x1; W_x3]
+  CA_TRY(launch_concat_cols((const float*)p->W_x1, d * d, (const float*)p->W_x3, d * d, wf + c.fo.wcat, 1, c.s));
+  CA_TRY(launch_concat_cols((const float*)p->b_x1, d, (const float*)p->b_x3, d, wf + c.fo.bcat, 1, c.s));
+  AltLinear x13 = alt_rows_job(nullptr, wf + c.fo.wcat, false, wf + c.fo.bcat, c.st + c.so.x13, c.B * c.T, 2 * d, d, wf + c.fo.img13);
+  x13.x_tab = c.Q; x13.y_sz = (long)c.B * c.T * 2 * d; x13.batch = c.L;
+  CA_TRY(alt_linear(x13, c.s));
+  // X2 = V W_x2^T + b_x2, once per sample (not per level)
+  AltLinear x2 = alt_rows_job(c.V, (const float*)p->W_x2, false, (const float*)p->b_x2, c.st + c.so.x2, c.B * c.N, d, d, wf + c.fo.img2);
+  x2.x_view = &c.vl; x2.n = c.N;
+  return alt_linear(x2, c.s);
+}
+int alt_fwd_guided(const AltCall& c) {
+  const coattn_alt_params* p = c.p;
+  const int d = c.d, LB = c.L * c.B;
+  float* sv = c.st;
+  const AltSaved& so = c.so;
+  // step 1: s^ = guided(Q, 0)
+  GuidedArgs a1 = alt_q_side(c);
+  a1.p = sv + so.x13; a1.w = (const float*)p->w_h1; a1.c = (const float*)p->c_h1; a1.a = sv + so.as; a1.xhat = sv + so.sh;
+  CA_TRY(launch_guided<1>(true, a1, c.s));
+  // step 2: v^ = guided(V, s^ W_g2^T + b_g2), the levels of a sample in one workgroup
+  CA_TRY(alt_linear(alt_rows_job(sv + so.sh, (const float*)p->W_g2, false, (const float*)p->b_g2, sv + so.g2, LB, d, d,
+                                 c.ws + c.fo.imgg2), c.s));
+  GuidedArgs a2 = alt_v_side(c);
+  a2.c = (const float*)p->c_h2;
+  a2.a = c.av_out && !c.keep ? c.av_out : sv + so.av; a2.a2 = c.av_out && c.keep ? c.av_out : nullptr;
+  a2.xhat = c.keep ? sv + so.vh : c.v_out;
+  CA_TRY(launch_guided<kAltMaxL>(true, a2, c.s));
+  const float* vh = a2.xhat;
+  // step 3: q^ = guided(Q, v^ W_g3^T + b_g3)
+  CA_TRY(alt_linear(alt_rows_job(vh, (const float*)p->W_g3, false, (const float*)p->b_g3, sv + so.g3, LB, d, d,
+                                 c.ws + c.fo.imgg3), c.s));
+  GuidedArgs a3 = alt_q_side(c);
+  a3.p = sv + so.x13 + d; a3.g = sv + so.g3; a3.w = (const float*)p->w_h3; a3.c = (const float*)p->c_h3;
+  a3.a = c.aq_out && !c.keep ? c.aq_out : sv + so.aq; a3.a2 = c.aq_out && c.keep ? c.aq_out : nullptr;
+  a3.xhat = c.q_out;
+  CA_TRY(launch_guided<1>(true, a3, c.s));
+  if (c.keep && hipMemcpyAsync(c.v_out, vh, (size_t)LB * d * sizeof(float), hipMemcpyDeviceToDevice, c.s) != hipSuccess) {
+    coattn_set_error("coattn_alt_forward: hipMemcpyAsync failed");
+    return -3;
+  }
+  return 0;
+}
+
+// ---- the backward's steps
+int alt_bwd_guided(const AltCall& c) {
+  const coattn_alt_params* p = c.p;
+  const int d = c.d, LB = c.L * c.B;
+  const float* sv = c.sv;
+  float* w = c.ws;
+  const AltSaved& so = c.so;
+  const AltBwdWs& wo = c.wo;
+  GuidedArgs q = alt_q_side(c);
+  q.dh_sL = q.p_sL; q.dh_ld = 2 * d;                    // [dH1 | dH3], laid out as [X1 | X3]
+  // step 3: dH3 (into the right half of [dH1 | dH3]), dg3 = sum_t dH3
+  GuidedArgs a3 = q;
+  a3.p = sv + so.x13 + d; a3.g = sv + so.g3; a3.w = (const float*)p->w_h3; a3.a_in = sv + so.aq;
+  a3.gx = c.gq; a3.ga = c.g_aq; a3.dh = w + wo.dh13 + d; a3.dg = w + wo.dg3; a3.dw_part = w + wo.wp3;
+  CA_TRY(launch_guided<1>(false, a3, c.s));
+  // gradient into v^: gv + dg3 W_g3 (the sum is formed by step 2's kernel)
+  CA_TRY(alt_linear(alt_rows_job(w + wo.dg3, (const float*)p->W_g3, true, nullptr, w + wo.dvt, LB, d, d, w + wo.imgg3), c.s));
+  // step 2: sum_l dH2_l into dX2, dg2 = sum_n dH2
+  GuidedArgs a2 = alt_v_side(c);
+  a2.a_in = sv + so.av; a2.gx = c.gv; a2.gx2 = w + wo.dvt; a2.gx_tot = w + wo.dvt; a2.ga = c.g_av;
+  a2.dh = w + wo.dx2; a2.dh_ld = d; a2.dg = w + wo.dg2; a2.dw_part = w + wo.wp2;
+  CA_TRY(launch_guided<kAltMaxL>(false, a2, c.s));
+  // gradient into s^: dg2 W_g2
+  CA_TRY(alt_linear(alt_rows_job(w + wo.dg2, (const float*)p->W_g2, true, nullptr, w + wo.dsh, LB, d, d, w + wo.imgg2), c.s));
+  // step 1: dH1 (into the left half)
+  GuidedArgs a1 = q;
+  a1.p = sv + so.x13; a1.w = (const float*)p->w_h1; a1.a_in = sv + so.as;
+  a1.gx = w + wo.dsh; a1.dh = w + wo.dh13; a1.dg = w + wo.dg1; a1.dw_part = w + wo.wp1;
+  return launch_guided<1>(false, a1, c.s);
+}
+int alt_bwd_input_grads(const AltCall& c) {
+  const coattn_alt_params* p = c.p;
+  const int B = c.B, N = c.N, d = c.d, L = c.L;
+  const long BT = (long)B * c.T;
+  const float* sv = c.sv;
+  float* w = c.ws;
+  const AltBwdWs& wo = c.wo;
+  // dQ_l = [dH1 | dH3]_l [W_x1; W_x3] (K = 2d) + the rank-1 terms of steps 1 and 3
+  CA_TRY(launch_concat_cols((const float*)p->W_x1, d * d, (const float*)p->W_x3, d * d, w + wo.wcat, 1, c.s));
+  AltLinear dq = alt_rows_job(w + wo.dh13, w + wo.wcat, true, nullptr, nullptr, (int)BT, d, 2 * d, w + wo.img13);
+  dq.x_sz = BT * 2 * d; dq.y_tab = c.dQ; dq.batch = L;
+  CA_TRY(alt_linear(dq, c.s));
+  DqRank1 k = {};
+  for (int l = 0; l < L; ++l) k.dq[l] = c.dQ[l];
+  k.as = sv + c.so.as; k.gs = w + wo.dsh; k.aq = sv + c.so.aq; k.gq = c.gq; k.B = B; k.T = c.T; k.d = d;
+  hipLaunchKernelGGL(alt_dq_rank1_kernel, dim3((unsigned)((BT * d + 255) / 256), L), dim3(256), 0, c.s, k);
+  CA_CHECK_LAUNCH("alt_dq_rank1");
+  if (!c.dV) return 0;
+  // dV = dX2 W_x2 + sum_l a_v,l (x) gv^_l
+  AltLinear dv = alt_rows_job(w + wo.dx2, (const float*)p->W_x2, true, nullptr, c.dV, B * N, d, d, w + wo.img2);
+  dv.y_view = &c.dvl; dv.n = N;
+  CA_TRY(alt_linear(dv, c.s));
+  const DvRank1 r = {c.dV, c.dvl.sB, c.dvl.sN, c.dvl.sD, sv + c.so.av, w + wo.dvt, B, N, d, L};
+  hipLaunchKernelGGL(alt_dv_rank1_kernel, dim3((unsigned)(((long)B * N * d + 255) / 256)), dim3(256), 0, c.s, r);
+  CA_CHECK_LAUNCH("alt_dv_rank1");
+  return 0;
+}
+int alt_bwd_param_grads(const AltCall& c) {
+  const coattn_alt_param_grads* pg = c.pg;
+  const int B = c.B, d = c.d, LB = c.L * c.B;
+  float* w = c.ws;
+  const AltBwdWs& wo = c.wo;
+  const AltWgrad w13 = {w + wo.dh13, 2 * d, (long)B * c.T * 2 * d, nullptr, c.Q, d, nullptr, B * c.T, c.L, 2 * d, d,
+                        (float*)pg->dW_x1, (float*)pg->dW_x3, d};
+  CA_TRY(alt_wgrad(w13, c));
+  CA_TRY(alt_wgrad_square(c, w + wo.dx2, c.V, &c.vl, B * c.N, pg->dW_x2));
+  CA_TRY(alt_wgrad_square(c, w + wo.dg2, c.sv + c.so.sh, nullptr, LB, pg->dW_g2));
+  CA_TRY(alt_wgrad_square(c, w + wo.dg3, c.sv + c.so.vh, nullptr, LB, pg->dW_g3));
+  // w_h / c_h of the three steps (the per-workgroup partials [d + 1]) and the biases: b_x1 from the rows of dg1 = sum_t dH1;
+  // b_x2, b_g2 both from the rows of dg2 = sum_n dH2, and b_x3, b_g3 from those of dg3 (each pair adds into the same
+  // pre-activation, so their gradients are the same sum: no column-sum pass over dH)
+  AltReduce r = {};
+  r.accumulate = c.accumulate;
+  const float* wp[3] = {w + wo.wp1, w + wo.wp2, w + wo.wp3};
+  void* const dw[3] = {pg->dw_h1, pg->dw_h2, pg->dw_h3}, * const dc[3] = {pg->dc_h1, pg->dc_h2, pg->dc_h3};
+  const int np[3] = {LB, B, LB};
+  for (int i = 0; i < 3; ++i) {
+    alt_reduce_job(r, wp[i], dw[i], d, d + 1, np[i]);
+    alt_reduce_job(r, wp[i] + d, dc[i], 1, d + 1, np[i]);
+  }
+  alt_reduce_job(r, w + wo.dg2, pg->db_g2, d, d, LB);
+  alt_reduce_job(r, w + wo.dg3, pg->db_g3, d, d, LB);
+  alt_reduce_job(r, w + wo.dg1, pg->db_x1, d, d, LB);
+  alt_reduce_job(r, w + wo.dg2, pg->db_x2, d, d, LB);
+  alt_reduce_job(r, w + wo.dg3, pg->db_x3, d, d, LB);
+  return launch_alt_reduce(r, c.s);
 }
 
 }  // namespace
@@ -526,97 +769,18 @@ extern "C" int coattn_alt_forward(const void* V, int64_t v_sB, int64_t v_sN, int
                                   const coattn_alt_params* p, void* v_out, void* q_out, void* av_out, void* aq_out, void* saved,
                                   void* ws, int B, int N, int T, int d, int L, int dtype, int flags, void* stream) {
   CA_TRY(alt_check(B, N, T, d, L, dtype, flags));
-  CA_TRY(alt_check_v(v_sB, v_sN, v_sD, N, d, "coattn_alt_forward: V"));
-  {
-    const struct { const void* ptr; const char* name; } req[] = {{V, "V"}, {Q, "Q"}, {p, "p"}, {v_out, "v_out"}, {q_out, "q_out"}, {ws, "ws"}};
-    for (const auto& a : req) CA_CHECK_ARG(a.ptr, "coattn_alt_forward: %s is NULL", a.name);
-  }
-  for (int l = 0; l < L; ++l) CA_CHECK_ARG(Q[l], "coattn_alt_forward: Q[%d] is NULL", l);
-  const void* const* pp = (const void* const*)p;
-  for (int i = 0; i < 16; ++i) CA_CHECK_ARG(pp[i], "coattn_alt_forward: parameter %d is NULL", i);
-  hipStream_t s = (hipStream_t)stream;
-  const AltSaved so = alt_saved(B, N, T, d, L);
-  float* sv = saved ? (float*)saved : (float*)ws;
-  float* wf = (float*)ws + (saved ? 0 : so.total);
-  const AltFwdWs fo = alt_fwd_ws(d);
-  const float* const* Qf = (const float* const*)Q;
-  const long BT = (long)B * T, Bd = (long)B * d;
-  // [X1 | X3] of every level: ONE projection against the stacked [W_x1; W_x3]
-  CA_TRY(launch_concat_cols((const float*)p->W_x1, d * d, (const float*)p->W_x3, d * d, wf + fo.wcat, 1, s));
-  CA_TRY(launch_concat_cols((const float*)p->b_x1, d, (const float*)p->b_x3, d, wf + fo.bcat, 1, s));
-  {
-    Lin l = {};
-    for (int i = 0; i < L; ++i) l.x_ptrs[i] = Qf[i];
-    l.ld_x = d; l.W = wf + fo.wcat; l.bias = wf + fo.bcat; l.y = sv + so.x13; l.y_sz = BT * 2 * d; l.ld_y = 2 * d;
-    l.M = (int)BT; l.N = 2 * d; l.K = d; l.batch = L;
-    CA_TRY(alt_linear(l, wf + fo.img13, s));
-  }
-  // X2 = V W_x2^T + b_x2, once per sample (not per level)
-  const bool v_rows = v_sD == 1 && v_sN == d && v_sB == (int64_t)N * d;
-  if (v_rows) {
-    Lin l = {};
-    l.x = (const float*)V; l.ld_x = d; l.W = (const float*)p->W_x2; l.bias = (const float*)p->b_x2; l.y = sv + so.x2; l.ld_y = d;
-    l.M = B * N; l.N = d; l.K = d; l.batch = 1;
-    CA_TRY(alt_linear(l, wf + fo.img2, s));
-  } else {
-    WGemm g = {};               // channel-major V: A contiguous along m (the pre-split-weight kernel's a_sk form)
-    g.A = (const float*)V; g.a_sk = (int)v_sD; g.a_mdiv = N; g.a_sdiv = v_sB; g.Wf = wf + fo.img2; g.C = sv + so.x2; g.c_sm = d;
-    g.bias_n = (const float*)p->b_x2; g.out_scale = 1.f; g.M = B * N; g.N = d; g.K = d; g.batch = 1; g.np = 3;
-    if (v_sN == 1 && v_sD < (1L << 30) && v_sB < (1L << 40) && gemm_w_supported(g) && !gemm_bf_supported(g)) {
-      const WSplit job{(const float*)p->W_x2, wf + fo.img2, d, d, 0, d, wimg_pieces(g), nullptr};
-      CA_TRY(launch_wsplit(&job, 1, s));
-      CA_TRY(launch_gemm_wx(&g, 1, s));
-    } else {
-      coattn_gemm_desc c = {};
-      c.A = (const float*)V; c.a_sm = v_sN; c.a_sk = v_sD;
-      if (v_sB != (int64_t)N * v_sN) { c.a_mdiv = N; c.a_sdiv = v_sB; }
-      c.B = (const float*)p->W_x2; c.b_sk = 1; c.b_sn = d; c.C = sv + so.x2; c.c_sm = d; c.c_sn = 1; c.bias_n = (const float*)p->b_x2;
-      c.M = B * N; c.N = d; c.K = d; c.batch = 1;
-      CA_TRY(launch_gemm_f32(c, s));
-    }
-  }
-  prof_mark(s, "alt_projections");
-  GuidedArgs q = {};
-  for (int i = 0; i < L; ++i) q.x[i] = Qf[i];
-  q.x_sB = (long)T * d; q.x_sR = d; q.x_sD = 1;
-  q.p_sL = BT * 2 * d; q.p_ld = 2 * d; q.len = q_len; q.B = B; q.R = T; q.d = d; q.L = L;
-  // step 1: s^ = guided(Q, 0)
-  GuidedArgs a1 = q;
-  a1.p = sv + so.x13; a1.w = (const float*)p->w_h1; a1.c = (const float*)p->c_h1; a1.a = sv + so.as; a1.xhat = sv + so.sh;
-  CA_TRY(launch_guided<1>(true, a1, s));
-  // step 2: v^ = guided(V, s^ W_g2^T + b_g2), the levels of a sample in one workgroup
-  {
-    Lin l = {};
-    l.x = sv + so.sh; l.ld_x = d; l.W = (const float*)p->W_g2; l.bias = (const float*)p->b_g2; l.y = sv + so.g2; l.ld_y = d;
-    l.M = L * B; l.N = d; l.K = d; l.batch = 1;
-    CA_TRY(alt_linear(l, wf + fo.imgg2, s));
-  }
-  GuidedArgs a2 = {};
-  for (int i = 0; i < kAltMaxL; ++i) a2.x[i] = (const float*)V;
-  a2.x_sB = v_sB; a2.x_sR = v_sN; a2.x_sD = v_sD;
-  a2.p = sv + so.x2; a2.p_sL = 0; a2.p_ld = d; a2.g = sv + so.g2; a2.w = (const float*)p->w_h2; a2.c = (const float*)p->c_h2;
-  a2.B = B; a2.R = N; a2.d = d; a2.L = L;
-  a2.a = av_out && !saved ? (float*)av_out : sv + so.av; a2.a2 = av_out && saved ? (float*)av_out : nullptr;
-  a2.xhat = saved ? sv + so.vh : (float*)v_out;
-  CA_TRY(launch_guided<kAltMaxL>(true, a2, s));
-  const float* vh = a2.xhat;
-  // step 3: q^ = guided(Q, v^ W_g3^T + b_g3)
-  {
-    Lin l = {};
-    l.x = vh; l.ld_x = d; l.W = (const float*)p->W_g3; l.bias = (const float*)p->b_g3; l.y = sv + so.g3; l.ld_y = d;
-    l.M = L * B; l.N = d; l.K = d; l.batch = 1;
-    CA_TRY(alt_linear(l, wf + fo.imgg3, s));
-  }
-  GuidedArgs a3 = q;
-  a3.p = sv + so.x13 + d; a3.g = sv + so.g3; a3.w = (const float*)p->w_h3; a3.c = (const float*)p->c_h3;
-  a3.a = aq_out && !saved ? (float*)aq_out : sv + so.aq; a3.a2 = aq_out && saved ? (float*)aq_out : nullptr;
-  a3.xhat = (float*)q_out;
-  CA_TRY(launch_guided<1>(true, a3, s));
-  if (saved && hipMemcpyAsync(v_out, vh, (size_t)L * Bd * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
-    coattn_set_error("coattn_alt_forward: hipMemcpyAsync failed");
-    return -3;
-  }
-  prof_mark(s, "alt_guided");
+  AltCall c = alt_call(V, VLayout{v_sB, v_sN, v_sD}, Q, q_len, p, B, N, T, d, L, stream);
+  CA_TRY(check_vlayout(c.vl, N, d, "coattn_alt_forward: V"));
+  CA_TRY(alt_check_ptrs(c, "coattn_alt_forward", {{V, "V"}, {Q, "Q"}, {p, "p"}, {v_out, "v_out"}, {q_out, "q_out"}, {ws, "ws"}}));
+  c.keep = saved != nullptr;
+  c.st = (float*)(saved ? saved : ws); c.sv = c.st;
+  c.ws = (float*)ws + (saved ? 0 : c.so.total);
+  c.fo = alt_fwd_ws(d);
+  c.v_out = (float*)v_out; c.q_out = (float*)q_out; c.av_out = (float*)av_out; c.aq_out = (float*)aq_out;
+  CA_TRY(alt_fwd_projections(c));
+  prof_mark(c.s, "alt_projections");
+  CA_TRY(alt_fwd_guided(c));
+  prof_mark(c.s, "alt_guided");
   return 0;
 }
 
@@ -626,132 +790,20 @@ extern "C" int coattn_alt_backward(const void* V, int64_t v_sB, int64_t v_sN, in
                                    const coattn_alt_param_grads* pg, int accumulate, void* ws, int B, int N, int T, int d, int L,
                                    int dtype, int flags, void* stream) {
   CA_TRY(alt_check(B, N, T, d, L, dtype, flags));
-  CA_TRY(alt_check_v(v_sB, v_sN, v_sD, N, d, "coattn_alt_backward: V"));
-  if (dV) CA_TRY(alt_check_v(dv_sB, dv_sN, dv_sD, N, d, "coattn_alt_backward: dV"));
-  {
-    const struct { const void* ptr; const char* name; } req[] = {{V, "V"}, {Q, "Q"}, {p, "p"}, {pg, "pg"}, {saved, "saved"}, {gv, "gv"},
-                                                                 {gq, "gq"}, {dQ, "dQ"}, {ws, "ws"}};
-    for (const auto& a : req) CA_CHECK_ARG(a.ptr, "coattn_alt_backward: %s is NULL", a.name);
-  }
-  for (int l = 0; l < L; ++l) CA_CHECK_ARG(Q[l] && dQ[l], "coattn_alt_backward: Q[%d] / dQ[%d] is NULL", l, l);
-  const void* const* pp = (const void* const*)p;
-  void* const* gp = (void* const*)pg;
-  for (int i = 0; i < 16; ++i) CA_CHECK_ARG(pp[i] && gp[i], "coattn_alt_backward: parameter or gradient %d is NULL", i);
+  AltCall c = alt_call(V, VLayout{v_sB, v_sN, v_sD}, Q, q_len, p, B, N, T, d, L, stream);
+  c.dV = (float*)dV; c.dvl = VLayout{dv_sB, dv_sN, dv_sD}; c.dQ = (float* const*)dQ; c.pg = pg; c.accumulate = accumulate;
+  CA_TRY(check_vlayout(c.vl, N, d, "coattn_alt_backward: V"));
+  if (dV) CA_TRY(check_vlayout(c.dvl, N, d, "coattn_alt_backward: dV"));
+  CA_TRY(alt_check_ptrs(c, "coattn_alt_backward", {{V, "V"}, {Q, "Q"}, {p, "p"}, {pg, "pg"}, {saved, "saved"}, {gv, "gv"}, {gq, "gq"},
+                                                   {dQ, "dQ"}, {ws, "ws"}}));
   CA_CHECK_ARG(accumulate == 0 || accumulate == 1, "coattn_alt_backward: accumulate must be 0 or 1");
-  hipStream_t s = (hipStream_t)stream;
-  const AltSaved so = alt_saved(B, N, T, d, L);
-  const AltBwdWs wo = alt_bwd_ws(B, N, T, d, L);
-  const float* sv = (const float*)saved;
-  float* w = (float*)ws;
-  const float* const* Qf = (const float* const*)Q;
-  const long BT = (long)B * T;
-  GuidedArgs q = {};
-  for (int i = 0; i < L; ++i) q.x[i] = Qf[i];
-  q.x_sB = (long)T * d; q.x_sR = d; q.x_sD = 1;
-  q.p_sL = BT * 2 * d; q.p_ld = 2 * d; q.len = q_len; q.B = B; q.R = T; q.d = d; q.L = L;
-  q.dh_sL = BT * 2 * d; q.dh_ld = 2 * d;
-  // step 3: dH3 (into the right half of [dH1 | dH3]), dg3 = sum_t dH3
-  GuidedArgs a3 = q;
-  a3.p = sv + so.x13 + d; a3.g = sv + so.g3; a3.w = (const float*)p->w_h3; a3.a_in = sv + so.aq;
-  a3.gx = (const float*)gq; a3.ga = (const float*)g_aq; a3.dh = w + wo.dh13 + d; a3.dg = w + wo.dg3; a3.dw_part = w + wo.wp3;
-  CA_TRY(launch_guided<1>(false, a3, s));
-  // gradient into v^: gv + dg3 W_g3 (the sum is formed by step 2's kernel)
-  CA_TRY(alt_linear_t(w + wo.dg3, d, 0, (const float*)p->W_g3, nullptr, w + wo.dvt, 0, L * B, d, d, 1, w + wo.imgg3, s));
-  // step 2: sum_l dH2_l into dX2, dg2 = sum_n dH2
-  GuidedArgs a2 = {};
-  for (int i = 0; i < kAltMaxL; ++i) a2.x[i] = (const float*)V;
-  a2.x_sB = v_sB; a2.x_sR = v_sN; a2.x_sD = v_sD;
-  a2.p = sv + so.x2; a2.p_ld = d; a2.g = sv + so.g2; a2.w = (const float*)p->w_h2; a2.a_in = sv + so.av;
-  a2.B = B; a2.R = N; a2.d = d; a2.L = L;
-  a2.gx = (const float*)gv; a2.gx2 = w + wo.dvt; a2.gx_tot = w + wo.dvt; a2.ga = (const float*)g_av;
-  a2.dh = w + wo.dx2; a2.dh_ld = d; a2.dg = w + wo.dg2; a2.dw_part = w + wo.wp2;
-  CA_TRY(launch_guided<kAltMaxL>(false, a2, s));
-  // gradient into s^: dg2 W_g2
-  CA_TRY(alt_linear_t(w + wo.dg2, d, 0, (const float*)p->W_g2, nullptr, w + wo.dsh, 0, L * B, d, d, 1, w + wo.imgg2, s));
-  // step 1: dH1 (into the left half)
-  GuidedArgs a1 = q;
-  a1.p = sv + so.x13; a1.w = (const float*)p->w_h1; a1.a_in = sv + so.as;
-  a1.gx = w + wo.dsh; a1.dh = w + wo.dh13; a1.dg = w + wo.dg1; a1.dw_part = w + wo.wp1;
-  CA_TRY(launch_guided<1>(false, a1, s));
-  prof_mark(s, "alt_guided_bwd");
-  // dQ_l = [dH1 | dH3]_l [W_x1; W_x3] (K = 2d) + the rank-1 terms of steps 1 and 3
-  CA_TRY(launch_concat_cols((const float*)p->W_x1, d * d, (const float*)p->W_x3, d * d, w + wo.wcat, 1, s));
-  {
-    float* yp[kAltMaxL] = {};
-    for (int l = 0; l < L; ++l) yp[l] = (float*)dQ[l];
-    CA_TRY(alt_linear_t(w + wo.dh13, 2 * d, BT * 2 * d, w + wo.wcat, yp, nullptr, 0, (int)BT, d, 2 * d, L, w + wo.img13, s));
-    DqRank1 k = {};
-    for (int l = 0; l < L; ++l) k.dq[l] = (float*)dQ[l];
-    k.as = sv + so.as; k.gs = w + wo.dsh; k.aq = sv + so.aq; k.gq = (const float*)gq; k.B = B; k.T = T; k.d = d;
-    hipLaunchKernelGGL(alt_dq_rank1_kernel, dim3((unsigned)((BT * d + 255) / 256), L), dim3(256), 0, s, k);
-    CA_CHECK_LAUNCH("alt_dq_rank1");
-  }
-  // dV = dX2 W_x2 + sum_l a_v,l (x) gv^_l
-  if (dV) {
-    const bool lm = dv_sD == 1 && dv_sN == d && dv_sB == (int64_t)N * d;
-    if (lm) {
-      CA_TRY(alt_linear_t(w + wo.dx2, d, 0, (const float*)p->W_x2, nullptr, (float*)dV, 0, B * N, d, d, 1, w + wo.img2, s));
-    } else {
-      coattn_gemm_desc g = {};
-      g.A = w + wo.dx2; g.a_sm = d; g.a_sk = 1;
-      g.B = (const float*)p->W_x2; g.b_sk = d; g.b_sn = 1;
-      g.C = (float*)dV; g.c_sm = dv_sN; g.c_sn = dv_sD;
-      if (dv_sB != (int64_t)N * dv_sN) { g.c_mdiv = N; g.c_sdiv = dv_sB; }
-      g.M = B * N; g.N = d; g.K = d; g.batch = 1;
-      CA_TRY(launch_gemm_f32(g, s));
-    }
-    DvRank1 k = {(float*)dV, (long)dv_sB, (long)dv_sN, (long)dv_sD, sv + so.av, w + wo.dvt, B, N, d, L};
-    hipLaunchKernelGGL(alt_dv_rank1_kernel, dim3((unsigned)(((long)B * N * d + 255) / 256)), dim3(256), 0, s, k);
-    CA_CHECK_LAUNCH("alt_dv_rank1");
-  }
-  prof_mark(s, "alt_input_grads");
-  // parameter gradients
-  float* part = w + wo.part;
-  CA_TRY(alt_wgrad(w + wo.dh13, 2 * d, BT * 2 * d, Qf, nullptr, d, (int)BT, L, 2 * d, d, (float*)pg->dW_x1, (float*)pg->dW_x3, d,
-                   accumulate, part, s));
-  const bool v_rows = v_sD == 1 && v_sN == d && v_sB == (int64_t)N * d;
-  if (v_rows) {
-    CA_TRY(alt_wgrad(w + wo.dx2, d, 0, nullptr, (const float*)V, d, B * N, 1, d, d, (float*)pg->dW_x2, nullptr, d, accumulate, part, s));
-  } else {
-    // dW_x2[j][k] = sum_b sum_n dX2[b][n][j] V[b][n][k] over groups of samples (strided V)
-    const int G = (B + kAltMaxParts - 1) / kAltMaxParts, S = (B + G - 1) / G;
-    coattn_gemm_desc g = {};
-    g.A = w + wo.dx2; g.a_sm = 1; g.a_sk = d; g.a_si = (int64_t)N * d; g.a_sz = (int64_t)G * N * d;
-    g.B = (const float*)V; g.b_sk = v_sN; g.b_sn = v_sD; g.b_si = v_sB; g.b_sz = (int64_t)G * v_sB;
-    g.C = part; g.c_sz = (int64_t)d * d; g.c_sm = d; g.c_sn = 1;
-    g.M = d; g.N = d; g.K = N; g.batch = S; g.inner = G; g.inner_total = B;
-    CA_TRY(launch_gemm_f32(g, s));
-    AltReduce r = {};
-    r.src[0] = part; r.dst[0] = (float*)pg->dW_x2; r.n[0] = (long)d * d; r.ld[0] = (long)d * d; r.nparts[0] = S; r.njobs = 1;
-    r.accumulate = accumulate;
-    CA_TRY(launch_alt_reduce(r, s));
-  }
-  CA_TRY(alt_wgrad(w + wo.dg2, d, 0, nullptr, sv + so.sh, d, L * B, 1, d, d, (float*)pg->dW_g2, nullptr, d, accumulate, part, s));
-  CA_TRY(alt_wgrad(w + wo.dg3, d, 0, nullptr, sv + so.vh, d, L * B, 1, d, d, (float*)pg->dW_g3, nullptr, d, accumulate, part, s));
-  {
-    // w_h / c_h of the three steps (the per-workgroup partials [d + 1]) and the biases: b_x1 from the rows of dg1 = sum_t dH1;
-    // b_x2, b_g2 both from the rows of dg2 = sum_n dH2, and b_x3, b_g3 from those of dg3 (each pair adds into the same
-    // pre-activation, so their gradients are the same sum: no column-sum pass over dH)
-    AltReduce r = {};
-    r.accumulate = accumulate;
-    const float* wp[3] = {w + wo.wp1, w + wo.wp2, w + wo.wp3};
-    float* dw[3] = {(float*)pg->dw_h1, (float*)pg->dw_h2, (float*)pg->dw_h3};
-    float* dc[3] = {(float*)pg->dc_h1, (float*)pg->dc_h2, (float*)pg->dc_h3};
-    const int np[3] = {L * B, B, L * B};
-    for (int i = 0; i < 3; ++i) {
-      r.src[2 * i] = wp[i]; r.dst[2 * i] = dw[i]; r.n[2 * i] = d; r.ld[2 * i] = d + 1; r.nparts[2 * i] = np[i];
-      r.src[2 * i + 1] = wp[i] + d; r.dst[2 * i + 1] = dc[i]; r.n[2 * i + 1] = 1; r.ld[2 * i + 1] = d + 1; r.nparts[2 * i + 1] = np[i];
-    }
-    r.src[6] = w + wo.dg2; r.dst[6] = (float*)pg->db_g2; r.n[6] = d; r.ld[6] = d; r.nparts[6] = L * B;
-    r.src[7] = w + wo.dg3; r.dst[7] = (float*)pg->db_g3; r.n[7] = d; r.ld[7] = d; r.nparts[7] = L * B;
-    const float* dgs[3] = {w + wo.dg1, w + wo.dg2, w + wo.dg3};
-    float* dbx[3] = {(float*)pg->db_x1, (float*)pg->db_x2, (float*)pg->db_x3};
-    for (int i = 0; i < 3; ++i) {
-      r.src[8 + i] = dgs[i]; r.dst[8 + i] = dbx[i]; r.n[8 + i] = d; r.ld[8 + i] = d; r.nparts[8 + i] = L * B;
-    }
-    r.njobs = 11;
-    CA_TRY(launch_alt_reduce(r, s));
-  }
-  prof_mark(s, "alt_param_grads");
+  c.sv = (const float*)saved; c.ws = (float*)ws; c.wo = alt_bwd_ws(B, N, T, d, L);
+  c.gv = (const float*)gv; c.gq = (const float*)gq; c.g_av = (const float*)g_av; c.g_aq = (const float*)g_aq;
+  CA_TRY(alt_bwd_guided(c));
+  prof_mark(c.s, "alt_guided_bwd");
+  CA_TRY(alt_bwd_input_grads(c));
+  prof_mark(c.s, "alt_input_grads");
+  CA_TRY(alt_bwd_param_grads(c));
+  prof_mark(c.s, "alt_param_grads");
   return 0;
 }

@@ -11,6 +11,8 @@ struct VLayout {
 };
 inline bool v_is_lm(const VLayout& v, int N, int d) { (void)N; return v.sD == 1 && v.sN == d; }
 inline bool v_is_cm(const VLayout& v, int N, int d) { (void)d; return v.sN == 1 && v.sD == N; }
+// the one stride check of every entry point that takes such a view (api.hip): positive strides, samples that do not overlap
+int check_vlayout(const VLayout& v, int N, int d, const char* what);
 
 int fused_supported(int B, int N, int T, int d, int L);
 inline bool fused_layout_ok(const VLayout& v, int N, int d) { return v_is_lm(v, N, d) || v_is_cm(v, N, d); }
