@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -552,6 +552,41 @@ size_t coattn_adam_workspace_bytes(const coattn_adam_tensor* t, int n_tensors);
 int coattn_adam_step(const coattn_adam_tensor* t, int n_tensors, int step, double lr, double beta1, double beta2,
                      double eps, double weight_decay, double max_grad_norm, void* norm_out, void* ws, size_t ws_bytes,
                      void* stream);
+
+/* ---- the frozen image encoder's glue (v0.14.0): train-mode BatchNorm2d + ReLU + optional 2x2 max-pool, fp32, NHWC ----
+ * The reference never puts its frozen VGG11-bn in eval mode (model.py:239-241): every step normalises each convolution's
+ * output with fresh batch statistics.  The convolutions stay on MIOpen; this call replaces the memory-bound chain between
+ * two of them -- BatchNorm2d (batch statistics, affine, running statistics with a momentum), ReLU and, with `pool`,
+ * MaxPool2d(2, 2) (no padding, floor mode: Ho = H / 2, Wo = W / 2, an odd last row / column is dropped) -- by two passes
+ * over x (csrc/encoder.hip): statistics accumulated in double, then normalise + pool + ReLU in one pass.  Forward only.
+ *   x            : fp32, physically [B][H][W][C] with C contiguous (a channels_last [B,C,H,W] tensor), 16-byte aligned; read only
+ *   gamma, beta  : fp32 [C], BatchNorm2d's weight and bias
+ *   conv_bias    : fp32 [C] or NULL: a frozen bias of the convolution that the caller left out of x.  It cancels in the
+ *                  normalised output and survives only in the running mean, where it is added here.
+ *   running_mean, running_var : fp32 [C], updated in place: rm = (1 - momentum) rm + momentum (mean + conv_bias),
+ *                  rv = (1 - momentum) rv + momentum var n / (n - 1) with n = B H W
+ *   y            : fp32 [B][Ho][Wo][C] (pool) or [B][H][W][C], 16-byte aligned, not x
+ *   stats_out    : fp32 [2][C] or NULL: the batch mean of x (without conv_bias) and the biased batch variance
+ *   ws           : the workspace size call's bytes, 16-byte aligned, contents need no initialisation
+ *   relu         : 0 leaves the ReLU out
+ * y = relu(max over the window of ((x - mean) * gamma / sqrt(var + eps) + beta)); NaN propagates as in PyTorch; a constant
+ * channel (var = 0) gives beta.  Results are bitwise repeatable (fixed-order reductions, no atomics).
+ * The supported-shape query returns 1 only for dtype COATTN_F32, C a power of two in 16 .. 512, B H W >= 2, B H W C < 2^31
+ * and, with pool, H >= 2 and W >= 2; it makes no GPU call.  The workspace size of an unsupported shape is 0.
+ * Argument errors (an unsupported shape, a NULL or misaligned pointer, momentum outside [0, 1], eps <= 0): -1 before any
+ * HIP call. */
+int coattn_bn_supported(int B, int H, int W, int C, int pool, int dtype);
+size_t coattn_bn_workspace_bytes(int B, int H, int W, int C);
+int coattn_bn_relu_pool_forward(const void* x, const void* gamma, const void* beta, const void* conv_bias,
+                                void* running_mean, void* running_var, double momentum, double eps, void* y,
+                                void* stats_out, void* ws, int B, int H, int W, int C, int pool, int relu, int dtype,
+                                void* stream);
+
+/* The 2x2 / stride-2 / floor-mode max-pool and the ReLU alone, in one pass: y [B][H/2][W/2][C] = relu(max over each window of
+ * x [B][H][W][C]) -- fp32, C contiguous, 16-byte aligned, y not x.  Maximum and ReLU are exact operations, so y has the values
+ * of PyTorch's max_pool2d followed by relu bit for bit (NaN propagates the same way).  Shapes: those the supported-shape
+ * query above accepts with pool = 1; anything else, or a NULL / misaligned pointer: -1 before any HIP call. */
+int coattn_relu_pool_forward(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

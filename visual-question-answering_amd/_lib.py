@@ -24,7 +24,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_forward_maps", "coattn_forward_maps_len", "coattn_backward_maps", "coattn_backward_maps_len",
            "coattn_alt_workspace_bytes", "coattn_alt_forward", "coattn_alt_backward",
            "coattn_soft_loss_forward", "coattn_vqa_score", "coattn_head_forward_soft",
-           "coattn_adam_workspace_bytes", "coattn_adam_step")
+           "coattn_adam_workspace_bytes", "coattn_adam_step",
+           "coattn_bn_supported", "coattn_bn_workspace_bytes", "coattn_bn_relu_pool_forward", "coattn_relu_pool_forward")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -304,6 +305,14 @@ def load() -> C.CDLL:
     lib.coattn_adam_workspace_bytes.restype = C.c_size_t
     lib.coattn_adam_step.argtypes = ([C.POINTER(AdamTensor), C.c_int, C.c_int] + [C.c_double] * 6
                                      + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    # the frozen encoder's BatchNorm + ReLU + max-pool (v0.14.0): (x, gamma, beta, conv_bias, running_mean, running_var,
+    # momentum, eps, y, stats_out, ws, B, H, W, C, pool, relu, dtype, stream)
+    lib.coattn_bn_supported.argtypes = [C.c_int] * 6
+    lib.coattn_bn_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.coattn_bn_workspace_bytes.restype = C.c_size_t
+    lib.coattn_bn_relu_pool_forward.argtypes = ([C.c_void_p] * 6 + [C.c_double] * 2 + [C.c_void_p] * 3 + [C.c_int] * 7
+                                                + [C.c_void_p])
+    lib.coattn_relu_pool_forward.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]
     _lib = lib
     return lib
 

@@ -1,0 +1,121 @@
+"""The memory-bound glue of the frozen image encoder on the HIP library (csrc/encoder.hip, include/coattn.h v0.14.0), for
+channels_last fp32 tensors; the convolutions stay on MIOpen.  ``modules.run_conv_bn_stack`` decides which layer takes what:
+
+* ``relu_pool``: ``MaxPool2d(2, 2)`` + ``ReLU`` in one pass.  Both are exact operations: the values are the stock kernels' bit
+  for bit.  The default (``mode() == "pool"``).
+* ``bn_relu_pool``: train-mode ``BatchNorm2d`` + ``ReLU`` + an optional ``MaxPool2d(2, 2)`` in two passes over the convolution
+  output, statistics in double.  More accurate than the stock chain, but not its bits: a training trajectory leaves the stock
+  one at rounding level and drifts from there.  Opt-in: ``VQA_ENCODER_FUSED=1``.
+
+``VQA_ENCODER_FUSED=0`` keeps every stock kernel."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def pool_is_2x2(pool: nn.MaxPool2d) -> bool:
+    """kernel 2, stride 2, no padding, no dilation, floor mode, no indices: the one pool the kernel implements."""
+    stride = pool.kernel_size if pool.stride is None else pool.stride
+    return (_pair(pool.kernel_size) == (2, 2) and _pair(stride) == (2, 2) and _pair(pool.padding) == (0, 0)
+            and _pair(pool.dilation) == (1, 1) and not pool.ceil_mode and not pool.return_indices)
+
+
+def mode() -> str:
+    """VQA_ENCODER_FUSED: "0" -> "stock", "1" -> "bn" (BatchNorm too), anything else or unset -> "pool" (the exact pool + ReLU)."""
+    return {"0": "stock", "1": "bn"}.get(os.environ.get("VQA_ENCODER_FUSED", ""), "pool")
+
+
+def relu_pool_fusable(pool: nn.MaxPool2d, x: torch.Tensor) -> bool:
+    """A 2x2 pool of a CUDA fp32 channels_last tensor that autograd need not record, of a shape the kernel takes."""
+    if mode() == "stock" or not pool_is_2x2(pool) or (torch.is_grad_enabled() and x.requires_grad):
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    B, Ch, H, W = x.shape
+    return bool(_lib.load().coattn_bn_supported(B, H, W, Ch, 1, _lib.F32))
+
+
+def relu_pool(x: torch.Tensor) -> torch.Tensor:
+    """relu(max_pool2d(x, 2, 2)) of a channels_last fp32 [B,C,H,W] tensor as a channels_last tensor, bit for bit.  Forward
+    only; runs on torch's current stream."""
+    B, Ch, H, W = x.shape
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
+        raise ValueError("relu_pool: needs a CUDA fp32 channels_last [B,C,H,W] tensor, got %s %s strides %s"
+                         % (tuple(x.shape), x.dtype, x.stride()))
+    y = torch.empty((B, Ch, H // 2, W // 2), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.load().coattn_relu_pool_forward(_lib.ptr(x), _lib.ptr(y), B, H, W, Ch, _lib.F32,
+                                                        C.c_void_p(_lib.stream_ptr(x.device))), "coattn_relu_pool_forward")
+    return y
+
+
+def modules_fusable(conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, x: torch.Tensor) -> bool:
+    """What can be told before the convolution runs: batch statistics with tracked running statistics and a momentum, an
+    affine map, nothing for autograd to record, a convolution bias that is absent or frozen (it moves into the running
+    mean), a 2x2 pool or none, and VQA_ENCODER_FUSED=1."""
+    if mode() != "bn" or not x.is_cuda:
+        return False
+    if not (bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None and bn.running_mean is not None):
+        return False
+    params = (conv.weight, conv.bias, bn.weight, bn.bias)
+    if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)):
+        return False
+    if conv.padding_mode != "zeros":
+        return False
+    b = conv.bias
+    if b is not None and (b.requires_grad or b.dtype != torch.float32 or b.device != x.device or not b.is_contiguous()):
+        return False
+    return pool is None or pool_is_2x2(pool)
+
+
+def output_fusable(z: torch.Tensor, bn: nn.BatchNorm2d, pool: bool) -> bool:
+    """The convolution output the kernels take: CUDA, fp32, physically [B,H,W,C], a shape coattn_bn_supported accepts; and
+    BatchNorm2d's parameters and buffers in fp32 beside it."""
+    if not (z.is_cuda and z.dtype == torch.float32 and z.dim() == 4 and z.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        if t.dtype != torch.float32 or t.device != z.device or not t.is_contiguous():
+            return False
+    B, Ch, H, W = z.shape
+    return bool(_lib.load().coattn_bn_supported(B, H, W, Ch, int(pool), _lib.F32))
+
+
+def bn_relu_pool(x: torch.Tensor, bn: nn.BatchNorm2d, conv_bias=None, pool: bool = False, stats_out=None) -> torch.Tensor:
+    """relu(max_pool2d(bn(x), 2, 2)) (pool) or relu(bn(x)) of a channels_last fp32 [B,C,H,W] tensor with `bn` in train
+    mode, as a channels_last tensor; `bn`'s running statistics and num_batches_tracked move as nn.BatchNorm2d moves them.
+    `conv_bias`: the frozen bias of the convolution that produced x WITHOUT it -- added to the running mean, the only place
+    it survives batch normalisation.  `stats_out`: an fp32 [2, C] tensor that receives the batch mean of x and its biased
+    variance.  Forward only; runs on torch's current stream."""
+    lib = _lib.load()
+    B, Ch, H, W = x.shape
+    for t, shape in ((conv_bias, (Ch,)), (stats_out, (2, Ch))):
+        if t is not None and not (t.dtype == torch.float32 and t.device == x.device and t.is_contiguous()
+                                  and tuple(t.shape) == shape):
+            raise ValueError("bn_relu_pool: conv_bias / stats_out must be contiguous fp32 [C] / [2, C] tensors on x's device")
+    if not output_fusable(x, bn, pool):
+        raise ValueError("bn_relu_pool: needs a CUDA fp32 channels_last [B,C,H,W] tensor of a shape coattn_bn_supported "
+                         "takes, got %s %s strides %s" % (tuple(x.shape), x.dtype, x.stride()))
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    y = torch.empty((B, Ch, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    # the workspace comes from torch's allocator under the current stream, per call: the encoder may run one step ahead
+    # on its own stream while an inline pass runs on the main one
+    ws = torch.empty((lib.coattn_bn_workspace_bytes(B, H, W, Ch) + 3) // 4, device=x.device, dtype=torch.float32)
+    with torch.no_grad(), _lib.on_device(x.device):
+        rc = lib.coattn_bn_relu_pool_forward(_lib.ptr(x), _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(conv_bias),
+                                             _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.momentum),
+                                             float(bn.eps), _lib.ptr(y), _lib.ptr(stats_out), _lib.ptr(ws), B, H, W, Ch,
+                                             int(pool), 1, _lib.F32, C.c_void_p(_lib.stream_ptr(x.device)))
+        _lib.check(rc, "coattn_bn_relu_pool_forward")
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+    return y

@@ -27,6 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 
+from . import encoder
 from .alternating import AlternatingCoAttention
 from .coattention import ParallelCoAttention
 from .head import answer_head
@@ -80,8 +81,19 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
       only place the bias survives (running_var is shift-invariant).  Outputs differ from the plain
       graph by fp32 rounding only (tests/test_net_cpu.py).
 
-    Anything that does not match these patterns (eval-mode BatchNorm, trainable bias, other modules)
-    is executed as is.  ``VQA_ENCODER_REWRITE=0`` disables both rewrites."""
+    On top of them, where the tensor is CUDA fp32 channels_last and autograd need not record the step (a frozen encoder, or
+    no_grad), the HIP library takes over memory-bound glue (``encoder.py``, csrc/encoder.hip); the convolutions stay on MIOpen:
+
+    * by default ``ReLU(MaxPool2d(2, 2)(x))`` runs as ONE pass (``encoder.relu_pool``) instead of two kernels; both operations are
+      exact, so every value keeps its bits;
+    * with ``VQA_ENCODER_FUSED=1`` a whole ``Conv2d -> BatchNorm2d -> ReLU [-> MaxPool2d(2, 2)]`` group runs everything after the
+      convolution in two passes over its output (``encoder.bn_relu_pool``), the bias fold included.  Its statistics are summed
+      in double, in another order than MIOpen's: values agree with the stock chain to rounding, not bit for bit.
+
+    ``VQA_ENCODER_FUSED=0`` keeps the stock kernels.
+
+    Anything that does not match these patterns (eval-mode BatchNorm, trainable bias, NCHW, autocast, other modules)
+    is executed as is.  ``VQA_ENCODER_REWRITE=0`` disables all of it."""
     mods = list(seq)
     if os.environ.get("VQA_ENCODER_REWRITE", "1") == "0":
         return seq(x)
@@ -89,15 +101,23 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
     while i < n:
         m = mods[i]
         nxt = mods[i + 1] if i + 1 < n else None
-        if (isinstance(m, nn.Conv2d) and m.bias is not None and not m.bias.requires_grad and m.padding_mode == "zeros"
+        pool = mods[i + 3] if i + 3 < n and isinstance(mods[i + 3], nn.MaxPool2d) else None
+        fuse = (isinstance(m, nn.Conv2d) and isinstance(nxt, nn.BatchNorm2d) and i + 2 < n and isinstance(mods[i + 2], nn.ReLU)
+                and encoder.modules_fusable(m, nxt, pool, x))
+        if (isinstance(m, nn.Conv2d) and (fuse or (m.bias is not None and not m.bias.requires_grad)) and m.padding_mode == "zeros"
                 and isinstance(nxt, nn.BatchNorm2d) and nxt.training and nxt.momentum is not None):
-            x = nxt(F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups))
-            if nxt.track_running_stats and nxt.running_mean is not None:
+            x = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
+            if fuse and encoder.output_fusable(x, nxt, pool is not None):
+                x = encoder.bn_relu_pool(x, nxt, conv_bias=m.bias, pool=pool is not None)
+                i += 3 if pool is None else 4
+                continue
+            x = nxt(x)
+            if m.bias is not None and nxt.track_running_stats and nxt.running_mean is not None:
                 with torch.no_grad():
                     nxt.running_mean.add_(m.bias.to(nxt.running_mean.dtype), alpha=nxt.momentum)
             i += 2
         elif isinstance(m, nn.ReLU) and isinstance(nxt, nn.MaxPool2d):
-            x = F.relu(nxt(x), inplace=True)
+            x = encoder.relu_pool(x) if encoder.relu_pool_fusable(nxt, x) else F.relu(nxt(x), inplace=True)
             i += 2
         else:
             x = m(x)
