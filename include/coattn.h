@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -587,6 +587,31 @@ int coattn_bn_relu_pool_forward(const void* x, const void* gamma, const void* be
  * of PyTorch's max_pool2d followed by relu bit for bit (NaN propagates the same way).  Shapes: those the supported-shape
  * query above accepts with pool = 1; anything else, or a NULL / misaligned pointer: -1 before any HIP call. */
 int coattn_relu_pool_forward(const void* x, void* y, int B, int H, int W, int C, int dtype, void* stream);
+
+/* ---- the same chain with the STOCK kernels' bits (v0.15.0) ----
+ * MIOpen's multi-kernel spatial forward-training BatchNorm (NHWC, fp32) is fp32 arithmetic in a fixed order: per thread a
+ * sequential sum of x and fma(x, x, .) over the samples of one pixel position, one LDS halving tree per workgroup, a second
+ * kernel that adds the workgroups' partials in a strided order, the same tree times 1 / (B H W), var = max(fma(-mean, mean,
+ * E[x^2]), 0), invstd = rsq(var + eps); then y = fma(gamma, (x - mean) * invstd, beta).  This call sums in that order with that
+ * formula, so mean, invstd, the running statistics and y are MIOpen's bit for bit -- in two passes over x instead of three,
+ * with the 2x2 max-pool (floor mode) and the ReLU in the second.  Which order MIOpen uses depends on the geometry it compiles
+ * for the shape; the geometry query reproduces it for the shapes it was read off for and answers 0 for every other one.
+ *   coattn_bn_exact_geometry : 0 = not covered (dtype not COATTN_F32, C not 64 / 128 / 256 / 512, B > 1024, H W C in the
+ *                  unobserved band 153601 .. 163839, H W = 1 modulo the workgroup's 8 or 16 pixels, more than 65535 pixel groups (the grid's
+ *                  limit: H W > 1048560 at 16 pixels), B H W C >= 2^31); otherwise 10, the number of ints written to `out`
+ *                  (may be NULL): vector width along C, workgroup shape g0 (channel groups) x g1 (pixels) x g2 (sample groups),
+ *                  samples per thread, pixel groups, sample groups, the final kernel's workgroup shape f0 x f1 x f2.  No GPU call.
+ *   x, y, gamma, beta, running_mean, running_var, B, H, W, C, pool, relu, dtype, stream : as for coattn_bn_relu_pool_forward
+ *                  (the running statistics move as MIOpen moves them: there is no conv_bias here)
+ *   save_mean, save_invstd : fp32 [C], written: the batch mean and 1 / sqrt(var + eps), MIOpen's saved statistics
+ *   ws           : coattn_bn_exact_workspace_bytes, the per-workgroup partials; contents need no initialisation
+ * Every pointer 16-byte aligned.  Argument errors (a shape that is not covered, a NULL or misaligned pointer, y == x, momentum
+ * outside [0, 1], eps <= 0): -1 before any HIP call; the workspace size of a shape that is not covered is 0. */
+int coattn_bn_exact_geometry(int B, int H, int W, int C, int dtype, int* out);
+size_t coattn_bn_exact_workspace_bytes(int B, int H, int W, int C);
+int coattn_bn_exact_forward(const void* x, const void* gamma, const void* beta, void* running_mean, void* running_var,
+                            double momentum, double eps, void* y, void* save_mean, void* save_invstd, void* ws, int B, int H,
+                            int W, int C, int pool, int relu, int dtype, void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

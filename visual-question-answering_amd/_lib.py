@@ -25,7 +25,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_alt_workspace_bytes", "coattn_alt_forward", "coattn_alt_backward",
            "coattn_soft_loss_forward", "coattn_vqa_score", "coattn_head_forward_soft",
            "coattn_adam_workspace_bytes", "coattn_adam_step",
-           "coattn_bn_supported", "coattn_bn_workspace_bytes", "coattn_bn_relu_pool_forward", "coattn_relu_pool_forward")
+           "coattn_bn_supported", "coattn_bn_workspace_bytes", "coattn_bn_relu_pool_forward", "coattn_relu_pool_forward",
+           "coattn_bn_exact_geometry", "coattn_bn_exact_workspace_bytes", "coattn_bn_exact_forward")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -313,6 +314,13 @@ def load() -> C.CDLL:
     lib.coattn_bn_relu_pool_forward.argtypes = ([C.c_void_p] * 6 + [C.c_double] * 2 + [C.c_void_p] * 3 + [C.c_int] * 7
                                                 + [C.c_void_p])
     lib.coattn_relu_pool_forward.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]
+    # the stock BatchNorm kernels' bits (v0.15.0): (x, gamma, beta, running_mean, running_var, momentum, eps, y, save_mean,
+    # save_invstd, ws, B, H, W, C, pool, relu, dtype, stream)
+    lib.coattn_bn_exact_geometry.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)]
+    lib.coattn_bn_exact_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.coattn_bn_exact_workspace_bytes.restype = C.c_size_t
+    lib.coattn_bn_exact_forward.argtypes = ([C.c_void_p] * 5 + [C.c_double] * 2 + [C.c_void_p] * 4 + [C.c_int] * 7
+                                            + [C.c_void_p])
     _lib = lib
     return lib
 

@@ -23,6 +23,17 @@
 //
 // Traffic per layer of S bytes: S (statistics) + S (normalise) + S/4 or S written, plus the partials (32 bytes per channel
 // and statistics workgroup, held below ~2 % of S by the grid size).
+//
+// The same two passes with the STOCK kernels' bits (coattn_bn_exact_forward, C-ABI 0.15.0; the default route of encoder.py once a
+// shape is verified): MIOpen's multi-kernel spatial BatchNorm is plain fp32 arithmetic in a fixed order, so summing in that order
+// gives its mean, invstd, running statistics and y bit for bit (DESIGN 3.12 "The stock kernels' bits"):
+//
+//   bn_stats_miopen_kernel     workgroup g0 x g1 (channel groups of four x pixels): a thread owns one pixel position and four
+//                              channels and adds its B samples in order, sum += x and sq = fma(x, x, sq) in fp32; one halving
+//                              tree over the g1 pixels in LDS; one [C][2] fp32 partial per workgroup.
+//   bn_finalize_miopen_kernel  workgroup 2 x f1: thread (., t) adds the partials t, t + f1, ... in order, the same tree, times
+//                              1 / (B H W); var = max(fma(-mean, mean, E[x^2]), 0), invstd = rsq(var + eps), the running statistics.
+//   bn_relu_pool_kernel<POOL, true, true>   t = fma(gamma, (x - mean) * invstd, beta) per element, then the maximum, then ReLU.
 #include <math.h>
 
 #include "common.h"
@@ -144,14 +155,124 @@ __global__ __launch_bounds__(kThreads) void bn_finalize_kernel(const f64x2* __re
   }
 }
 
+// ---- MIOpen's summation order (the multi-kernel form of its spatial forward-training BatchNorm, NHWC, fp32, vector width 4) ----
+// The geometry MIOpen compiles per shape, as bn_exact_geometry() reproduces it; each field under the name of coattn.h.
+struct BnGeom {
+  int vec, g0, g1, g2, nel, ngrps, ngrps2, f0, f1, f2;
+};
+constexpr int kGeomInts = 10;
+constexpr int kExactLoads = 8;  // 16-byte loads in flight per thread; the adds stay in sample order
+
+__device__ __forceinline__ void acc_miopen(f32x4& sum, f32x4& sq, const f32x4 v) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    sum[e] += v[e];
+    sq[e] = __builtin_fmaf(v[e], v[e], sq[e]);
+  }
+}
+
+// The stock kernels' LDS tree: element (xl, yl) at 2 (xl + yl * xs), pairs (sum, sq); `size` rows are halved down to row 0 --
+// always row r += row r + red -- and every thread reads row 0 of its column back, times `scale`.
+__device__ __forceinline__ void tree_miopen(f32x4& sum, f32x4& sq, float scale, f32x4* lds, int xs, int xl, int yl, int size) {
+  const int o1 = 2 * (xl + yl * xs);
+  lds[o1] = sum;
+  lds[o1 + 1] = sq;
+  __syncthreads();
+  for (int red = size >> 1; red > 0; red >>= 1) {
+    if (yl < red) {
+      const int o2 = o1 + red * xs * 2;
+      sum += lds[o2];
+      sq += lds[o2 + 1];
+      lds[o1] = sum;
+      lds[o1 + 1] = sq;
+    }
+    __syncthreads();
+  }
+  sum = lds[2 * xl] * scale;
+  sq = lds[2 * xl + 1] * scale;
+}
+
+// grid (c4 / g0, ngrps, ngrps2), block (g0, g1, g2), LDS 32 g0 g1 g2 bytes.  Thread (x, y, z) owns pixel y of the samples
+// z nel .. z nel + nel - 1, channels 4 x .. 4 x + 3.  partial[((bz * ngrps + by) * c4 + x) * 2 + {0, 1}] = (sum, sum of squares).
+__global__ __launch_bounds__(1024) void bn_stats_miopen_kernel(const f32x4* __restrict__ x, f32x4* __restrict__ partial, BnGeom g,
+                                                               int B, int HW, int c4) {
+  extern __shared__ f32x4 lds_stats[];
+  const int xl = threadIdx.x, yl = threadIdx.y + threadIdx.z * g.g1;
+  const int xg = blockIdx.x * g.g0 + xl, yg = blockIdx.y * g.g1 + threadIdx.y, zg = blockIdx.z * g.g2 + threadIdx.z;
+  f32x4 sum = {0.f, 0.f, 0.f, 0.f}, sq = {0.f, 0.f, 0.f, 0.f};
+  const int n0 = zg * g.nel;
+  if (yg < HW && n0 < B) {
+    const int64_t sample4 = (int64_t)HW * c4;                      // one sample in 16-byte units
+    const f32x4* p = x + ((int64_t)n0 * sample4 + (int64_t)yg * c4 + xg);
+    const int nel = B - n0 < g.nel ? B - n0 : g.nel;
+    int n = 0;
+    for (; n + kExactLoads <= nel; n += kExactLoads) {
+      f32x4 v[kExactLoads];
+#pragma unroll
+      for (int u = 0; u < kExactLoads; ++u) v[u] = p[(n + u) * sample4];
+#pragma unroll
+      for (int u = 0; u < kExactLoads; ++u) acc_miopen(sum, sq, v[u]);
+    }
+    for (; n < nel; ++n) acc_miopen(sum, sq, p[n * sample4]);
+  }
+  tree_miopen(sum, sq, 1.f, lds_stats, g.g0, xl, yl, g.g1 * g.g2);
+  if (yl == 0) {
+    f32x4* out = partial + (((int64_t)blockIdx.z * g.ngrps + blockIdx.y) * c4 + xg) * 2;
+    out[0] = sum;
+    out[1] = sq;
+  }
+}
+
+// grid c4 / f0, block (f0, f1, f2), LDS 32 f0 f1 f2 bytes.  `inhw` = float(1.0 / (B H W)), `unbias` = n / (n - 1) in fp32 with
+// n = float(B H W) -- the constants the stock kernel is compiled with; `factor` = float(momentum), `eps` = float(eps).
+__global__ __launch_bounds__(1024) void bn_finalize_miopen_kernel(const f32x4* __restrict__ partial, BnGeom g, int c4, float inhw,
+                                                                  float unbias, float factor, float eps, f32x4* running_mean,
+                                                                  f32x4* running_var, f32x4* __restrict__ save_mean,
+                                                                  f32x4* __restrict__ save_invstd) {
+  extern __shared__ f32x4 lds_final[];
+  const int xl = threadIdx.x, yl = threadIdx.y + threadIdx.z * g.f1;
+  const int xg = blockIdx.x * g.f0 + xl;
+  f32x4 mean = {0.f, 0.f, 0.f, 0.f}, var = {0.f, 0.f, 0.f, 0.f};
+  for (int z = threadIdx.z; z < g.ngrps2; z += g.f2)
+    for (int y = threadIdx.y; y < g.ngrps; y += g.f1) {
+      const f32x4* p = partial + (((int64_t)z * g.ngrps + y) * c4 + xg) * 2;
+      mean += p[0];
+      var += p[1];
+    }
+  tree_miopen(mean, var, inhw, lds_final, g.f0, xl, yl, g.f1 * g.f2);
+  f32x4 invstd;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    var[e] = __builtin_fmaxf(__builtin_fmaf(-mean[e], mean[e], var[e]), 0.f);   // (OpenCL's max: a NaN variance becomes 0)
+    invstd[e] = __builtin_amdgcn_rsqf(var[e] + eps);
+  }
+  if (yl != 0) return;
+  const f32x4 rm = running_mean[xg], rv = running_var[xg];
+  f32x4 nm, nv;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    nm[e] = __builtin_fmaf(mean[e], factor, __builtin_fmaf(-factor, rm[e], rm[e]));
+    const float adjust = var[e] * unbias;
+    nv[e] = __builtin_fmaf(1.f - factor, rv[e], factor * adjust);
+  }
+  running_mean[xg] = nm;
+  running_var[xg] = nv;
+  save_mean[xg] = mean;
+  save_invstd[xg] = invstd;
+}
+
 struct Affine {
-  float mean[4], lo[4], scale[4], beta[4];
+  float mean[4], lo[4], scale[4], beta[4], gamma[4];
 };
 
+// STOCK: MIOpen's normalise kernel, t = mad(gamma, (x - mean) * invstd, beta) with `scale` = invstd
+template <bool STOCK>
 __device__ __forceinline__ f32x4 affine(const f32x4 v, const Affine& a) {
   f32x4 t;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) t[e] = fmaf((v[e] - a.mean[e]) - a.lo[e], a.scale[e], a.beta[e]);
+  for (int e = 0; e < 4; ++e)
+    t[e] = STOCK ? __builtin_fmaf(a.gamma[e], (v[e] - a.mean[e]) * a.scale[e], a.beta[e])
+                 : fmaf((v[e] - a.mean[e]) - a.lo[e], a.scale[e], a.beta[e]);
   return t;
 }
 // PyTorch's maximum: a NaN wins
@@ -170,9 +291,11 @@ __device__ __forceinline__ f32x4 relu_nan(const f32x4 a) {
 
 // One thread per 16 bytes of output: o = output pixel * c4 + channel group.  total4 = output pixels * c4; H, W: the INPUT's.
 // AFFINE = false: the 2x2 maximum and the ReLU alone (ws_f, beta not read): max and ReLU are exact, so the result has the bits of
-// max_pool2d followed by relu.
-template <bool POOL, bool AFFINE = true>
+// max_pool2d followed by relu.  STOCK: ws_f = save_mean, ws_f + 2 C = save_invstd (the caller passes `scale` itself) and
+// `gamma` is read: the stock normalise kernel's map.
+template <bool POOL, bool AFFINE = true, bool STOCK = false>
 __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __restrict__ x, const float* __restrict__ ws_f,
+                                                                const float* __restrict__ scale, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, f32x4* __restrict__ y,
                                                                 int H, int W, int C, int c4_shift, int64_t total4, int relu) {
   const int tid = threadIdx.x;
@@ -182,8 +305,9 @@ __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __r
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     a.mean[e] = AFFINE ? ws_f[4 * cg + e] : 0.f;
-    a.lo[e] = AFFINE ? ws_f[C + 4 * cg + e] : 0.f;
-    a.scale[e] = AFFINE ? ws_f[2 * C + 4 * cg + e] : 1.f;
+    a.lo[e] = AFFINE && !STOCK ? ws_f[C + 4 * cg + e] : 0.f;
+    a.scale[e] = AFFINE ? scale[4 * cg + e] : 1.f;
+    a.gamma[e] = STOCK ? gamma[4 * cg + e] : 1.f;
     a.beta[e] = AFFINE ? beta[4 * cg + e] : 0.f;
   }
   const int64_t stride = (int64_t)gridDim.x * kThreads;
@@ -197,7 +321,7 @@ __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __r
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         if (o + u * stride < total4) {
-          const f32x4 t = affine(v[u], a);
+          const f32x4 t = affine<STOCK>(v[u], a);
           y[o + u * stride] = relu ? relu_nan(t) : t;
         }
     }
@@ -225,8 +349,8 @@ __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __r
 #pragma unroll
     for (int u = 0; u < 2; ++u)
       if (live[u]) {
-        const f32x4 t = AFFINE ? max_nan(max_nan(affine(v[u][0], a), affine(v[u][1], a)),
-                                         max_nan(affine(v[u][2], a), affine(v[u][3], a)))
+        const f32x4 t = AFFINE ? max_nan(max_nan(affine<STOCK>(v[u][0], a), affine<STOCK>(v[u][1], a)),
+                                         max_nan(affine<STOCK>(v[u][2], a), affine<STOCK>(v[u][3], a)))
                                : max_nan(max_nan(v[u][0], v[u][1]), max_nan(v[u][2], v[u][3]));
         y[o + u * stride] = relu ? relu_nan(t) : t;
       }
@@ -296,10 +420,10 @@ extern "C" int coattn_bn_relu_pool_forward(const void* x, const void* gamma, con
   if (blocks > kMaxNormBlocks) blocks = kMaxNormBlocks;
   if (pool)
     hipLaunchKernelGGL(bn_relu_pool_kernel<true>, dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x, ws_f,
-                       (const float*)beta, (f32x4*)y, H, W, C, log2_exact(c4), total4, relu);
+                       ws_f + 2 * C, (const float*)nullptr, (const float*)beta, (f32x4*)y, H, W, C, log2_exact(c4), total4, relu);
   else
     hipLaunchKernelGGL(bn_relu_pool_kernel<false>, dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x, ws_f,
-                       (const float*)beta, (f32x4*)y, H, W, C, log2_exact(c4), total4, relu);
+                       ws_f + 2 * C, (const float*)nullptr, (const float*)beta, (f32x4*)y, H, W, C, log2_exact(c4), total4, relu);
   CA_CHECK_LAUNCH("bn_relu_pool");
   prof_mark(s, "bn_relu_pool");
   return 0;
@@ -320,8 +444,115 @@ extern "C" int coattn_relu_pool_forward(const void* x, void* y, int B, int H, in
   int64_t blocks = (total4 + (int64_t)kThreads * 2 - 1) / ((int64_t)kThreads * 2);
   if (blocks > kMaxNormBlocks) blocks = kMaxNormBlocks;
   hipLaunchKernelGGL((bn_relu_pool_kernel<true, false>), dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x,
-                     (const float*)nullptr, (const float*)nullptr, (f32x4*)y, H, W, C, log2_exact(c4), total4, 1);
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (f32x4*)y, H, W,
+                     C, log2_exact(c4), total4, 1);
   CA_CHECK_LAUNCH("relu_pool");
   prof_mark(s, "relu_pool");
+  return 0;
+}
+
+// ---- the stock kernels' bits (v0.15.0) ------------------------------------------------------------------------------------
+namespace {
+
+// The geometry MIOpen gives its multi-kernel NHWC fp32 form, as read off its kernel builds (the table of
+// observed values): vector width 4 along C, workgroups of 16 channel groups x g1 pixels, every thread adds all B samples
+// (one sample group), the final kernel runs 2 channel groups x 8 g1 partial lanes.  g1 is 8 up to H W C = 153600 and 16 from
+// 163840 on (every observed shape, C = 64 .. 512; B, 1 .. 1024, does not enter); between the two nothing was observed and
+// nothing is covered.
+constexpr int64_t kSmallMaxHWC = 153600, kLargeMinHWC = 163840;
+constexpr int kExactMaxB = 1024;
+
+bool bn_exact_geometry(int B, int H, int W, int C, int dtype, BnGeom* g) {
+  if (dtype != COATTN_F32 || !coattn_bn_supported(B, H, W, C, 0, dtype)) return false;
+  if (C < 64 || B > kExactMaxB) return false;                     // C / 4 a multiple of the 16 channel groups of a workgroup
+  const int64_t hw = (int64_t)H * W, hwc = hw * C;
+  if (hwc > kSmallMaxHWC && hwc < kLargeMinHWC) return false;
+  g->vec = 4;
+  g->g0 = 16;
+  g->g1 = hwc <= kSmallMaxHWC ? 8 : 16;
+  g->g2 = 1;
+  g->nel = B;
+  g->ngrps = (int)((hw + g->g1 - 1) / g->g1);
+  g->ngrps2 = 1;
+  g->f0 = 2;
+  g->f1 = g->g0 * g->g1 / 2;
+  g->f2 = 1;
+  // MIOpen keeps its partials in two pixel rows of y per workgroup; where the last workgroup has one pixel only
+  // (H W = 1 mod g1) it stores them another way and, with few samples, sums differently: observed, not reproduced
+  if (hw % g->g1 == 1) return false;
+  return g->ngrps <= 65535;                                         // (grid.y)
+}
+
+inline size_t exact_partial_bytes(const BnGeom& g, int C) { return (size_t)g.ngrps * g.ngrps2 * C * 2 * sizeof(float); }
+
+}  // namespace
+
+extern "C" int coattn_bn_exact_geometry(int B, int H, int W, int C, int dtype, int* out) {
+  BnGeom g;
+  if (!bn_exact_geometry(B, H, W, C, dtype, &g)) return 0;
+  if (out) {
+    const int v[kGeomInts] = {g.vec, g.g0, g.g1, g.g2, g.nel, g.ngrps, g.ngrps2, g.f0, g.f1, g.f2};
+    for (int i = 0; i < kGeomInts; ++i) out[i] = v[i];
+  }
+  return kGeomInts;
+}
+
+extern "C" size_t coattn_bn_exact_workspace_bytes(int B, int H, int W, int C) {
+  BnGeom g;
+  if (!bn_exact_geometry(B, H, W, C, COATTN_F32, &g)) {
+    coattn_set_error("bn_exact_workspace_bytes: B=%d H=%d W=%d C=%d is not a covered shape (coattn_bn_exact_geometry)", B, H, W, C);
+    return 0;
+  }
+  return exact_partial_bytes(g, C);
+}
+
+extern "C" int coattn_bn_exact_forward(const void* x, const void* gamma, const void* beta, void* running_mean, void* running_var,
+                                       double momentum, double eps, void* y, void* save_mean, void* save_invstd, void* ws, int B,
+                                       int H, int W, int C, int pool, int relu, int dtype, void* stream) {
+  CA_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && C >= 1, "bn_exact_forward: B=%d H=%d W=%d C=%d (all must be >= 1)", B, H, W, C);
+  BnGeom g;
+  CA_CHECK_ARG(bn_exact_geometry(B, H, W, C, dtype, &g) && coattn_bn_supported(B, H, W, C, pool, dtype),
+               "bn_exact_forward: B=%d H=%d W=%d C=%d pool=%d dtype=%d is not a covered shape (coattn_bn_exact_geometry)", B, H,
+               W, C, pool, dtype);
+  CA_CHECK_ARG(x && gamma && beta && running_mean && running_var && y && save_mean && save_invstd && ws,
+               "bn_exact_forward: a null x / gamma / beta / running_mean / running_var / y / save_mean / save_invstd / ws");
+  CA_CHECK_ARG(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(ws) |
+                 reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(running_mean) |
+                 reinterpret_cast<uintptr_t>(running_var) | reinterpret_cast<uintptr_t>(save_mean) |
+                 reinterpret_cast<uintptr_t>(save_invstd)) & 15) == 0,
+               "bn_exact_forward: every pointer must be 16-byte aligned");
+  CA_CHECK_ARG(x != y, "bn_exact_forward: y must not be x");
+  CA_CHECK_ARG(momentum >= 0.0 && momentum <= 1.0, "bn_exact_forward: momentum %g outside [0, 1]", momentum);
+  CA_CHECK_ARG(eps > 0.0, "bn_exact_forward: eps %g (must be > 0)", eps);
+  hipStream_t s = (hipStream_t)stream;
+  const int c4 = C / 4, hw = H * W;
+  const int64_t pixels = (int64_t)B * hw;
+  f32x4* partial = (f32x4*)ws;
+  hipLaunchKernelGGL(bn_stats_miopen_kernel, dim3(c4 / g.g0, g.ngrps, g.ngrps2), dim3(g.g0, g.g1, g.g2),
+                     (size_t)2 * g.g0 * g.g1 * g.g2 * sizeof(f32x4), s, (const f32x4*)x, partial, g, B, hw, c4);
+  CA_CHECK_LAUNCH("bn_stats_miopen");
+  // the constants of the stock build: INHW = float(1.0 / n) as a kernel argument, n / (n - 1) folded in fp32
+  const float n_f = (float)pixels;
+  const float inhw = (float)(1.0 / (double)pixels), unbias = pixels == 1 ? 1.f : n_f / (n_f - 1.f);
+  hipLaunchKernelGGL(bn_finalize_miopen_kernel, dim3(c4 / g.f0), dim3(g.f0, g.f1, g.f2),
+                     (size_t)2 * g.f0 * g.f1 * g.f2 * sizeof(f32x4), s, (const f32x4*)partial, g, c4, inhw, unbias,
+                     (float)momentum, (float)eps, (f32x4*)running_mean, (f32x4*)running_var, (f32x4*)save_mean,
+                     (f32x4*)save_invstd);
+  CA_CHECK_LAUNCH("bn_finalize_miopen");
+  const int64_t out_pixels = pool ? (int64_t)B * (H / 2) * (W / 2) : pixels;
+  const int64_t total4 = out_pixels * c4;
+  const int per_thread = pool ? 2 : 4;
+  int64_t blocks = (total4 + (int64_t)kThreads * per_thread - 1) / ((int64_t)kThreads * per_thread);
+  if (blocks > kMaxNormBlocks) blocks = kMaxNormBlocks;
+  if (pool)
+    hipLaunchKernelGGL((bn_relu_pool_kernel<true, true, true>), dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x,
+                       (const float*)save_mean, (const float*)save_invstd, (const float*)gamma, (const float*)beta, (f32x4*)y, H,
+                       W, C, log2_exact(c4), total4, relu);
+  else
+    hipLaunchKernelGGL((bn_relu_pool_kernel<false, true, true>), dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x,
+                       (const float*)save_mean, (const float*)save_invstd, (const float*)gamma, (const float*)beta, (f32x4*)y, H,
+                       W, C, log2_exact(c4), total4, relu);
+  CA_CHECK_LAUNCH("bn_relu_pool_exact");
+  prof_mark(s, "bn_exact");
   return 0;
 }

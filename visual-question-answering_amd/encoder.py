@@ -1,8 +1,12 @@
-"""The memory-bound glue of the frozen image encoder on the HIP library (csrc/encoder.hip, include/coattn.h v0.14.0), for
+"""The memory-bound glue of the frozen image encoder on the HIP library (csrc/encoder.hip, include/coattn.h v0.15.0), for
 channels_last fp32 tensors; the convolutions stay on MIOpen.  ``modules.run_conv_bn_stack`` decides which layer takes what:
 
 * ``relu_pool``: ``MaxPool2d(2, 2)`` + ``ReLU`` in one pass.  Both are exact operations: the values are the stock kernels' bit
   for bit.  The default (``mode() == "pool"``).
+* ``bn_exact``: train-mode ``BatchNorm2d`` + ``ReLU`` + an optional ``MaxPool2d(2, 2)`` in two passes, summed in MIOpen's order
+  with MIOpen's formula: the stock chain's bits.  Also the default, but only for a shape that ``bn_exact_or_stock`` has compared
+  with the stock chain once in this process and found equal in every bit (``exact_report()``); ``VQA_ENCODER_EXACT_BN=0``
+  turns it off.
 * ``bn_relu_pool``: train-mode ``BatchNorm2d`` + ``ReLU`` + an optional ``MaxPool2d(2, 2)`` in two passes over the convolution
   output, statistics in double.  More accurate than the stock chain, but not its bits: a training trajectory leaves the stock
   one at rounding level and drifts from there.  Opt-in: ``VQA_ENCODER_FUSED=1``.
@@ -12,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import warnings
 
 import torch
 import torch.nn as nn
@@ -63,7 +68,22 @@ def modules_fusable(conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, x: torch.Tensor) 
     """What can be told before the convolution runs: batch statistics with tracked running statistics and a momentum, an
     affine map, nothing for autograd to record, a convolution bias that is absent or frozen (it moves into the running
     mean), a 2x2 pool or none, and VQA_ENCODER_FUSED=1."""
-    if mode() != "bn" or not x.is_cuda:
+    return mode() == "bn" and _group_fusable(conv, bn, pool, x)
+
+
+def exact_enabled() -> bool:
+    """The default mode, unless VQA_ENCODER_EXACT_BN=0."""
+    return mode() == "pool" and os.environ.get("VQA_ENCODER_EXACT_BN", "1") != "0"
+
+
+def exact_modules_fusable(conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, x: torch.Tensor) -> bool:
+    """modules_fusable's conditions for the route with the stock kernels' bits: the default mode instead of VQA_ENCODER_FUSED=1,
+    and no autocast (the stock BatchNorm then sees another dtype)."""
+    return exact_enabled() and not torch.is_autocast_enabled() and _group_fusable(conv, bn, pool, x)
+
+
+def _group_fusable(conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, x: torch.Tensor) -> bool:
+    if not x.is_cuda:
         return False
     if not (bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None and bn.running_mean is not None):
         return False
@@ -119,3 +139,108 @@ def bn_relu_pool(x: torch.Tensor, bn: nn.BatchNorm2d, conv_bias=None, pool: bool
         if bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)
     return y
+
+
+# ---- the stock kernels' bits: verified per shape, or not used -------------------------------------------------------------
+GEOMETRY_FIELDS = ("vec", "g0", "g1", "g2", "samples_per_thread", "pixel_groups", "sample_groups", "f0", "f1", "f2")
+_exact = {}                   # (device index, B, C, H, W, pool) -> {"verified": bool, "first_difference": name or None, "geometry": {...}}
+
+
+def exact_geometry(B: int, H: int, W: int, Ch: int):
+    """The geometry MIOpen's multi-kernel BatchNorm runs a channels_last fp32 [B,Ch,H,W] tensor with, as coattn_bn_exact_geometry
+    reproduces it (a dict over GEOMETRY_FIELDS), or None for a shape the rule does not cover."""
+    out = (C.c_int * len(GEOMETRY_FIELDS))()
+    n = _lib.load().coattn_bn_exact_geometry(B, H, W, Ch, _lib.F32, out)
+    return dict(zip(GEOMETRY_FIELDS, out)) if n == len(GEOMETRY_FIELDS) else None
+
+
+def exact_output_fusable(z: torch.Tensor, bn: nn.BatchNorm2d, pool: bool) -> bool:
+    """output_fusable, a shape whose MIOpen geometry is known, and 16-byte aligned tensors throughout (the kernels read the
+    parameters and the running statistics four channels at a time; a view at an odd offset stays on the stock chain)."""
+    if not output_fusable(z, bn, pool) or exact_geometry(z.shape[0], z.shape[2], z.shape[3], z.shape[1]) is None:
+        return False
+    return all(t.data_ptr() % 16 == 0 for t in (z, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+
+def exact_report() -> dict:
+    """{(device index, B, C, H, W, pool): {"verified", "first_difference", "geometry"}} of every shape compared so far."""
+    return {k: dict(v) for k, v in _exact.items()}
+
+
+def _bn_exact_raw(x, weight, bias, running_mean, running_var, momentum, eps, pool: bool):
+    lib = _lib.load()
+    B, Ch, H, W = x.shape
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    y = torch.empty((B, Ch, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    save = torch.empty((2, Ch), device=x.device, dtype=torch.float32)
+    ws = torch.empty((lib.coattn_bn_exact_workspace_bytes(B, H, W, Ch) + 3) // 4, device=x.device, dtype=torch.float32)
+    with torch.no_grad(), _lib.on_device(x.device):
+        rc = lib.coattn_bn_exact_forward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
+                                         _lib.ptr(running_var), float(momentum), float(eps), _lib.ptr(y), _lib.ptr(save[0]),
+                                         _lib.ptr(save[1]), _lib.ptr(ws), B, H, W, Ch, int(pool), 1, _lib.F32,
+                                         C.c_void_p(_lib.stream_ptr(x.device)))
+        _lib.check(rc, "coattn_bn_exact_forward")
+    return y, save[0], save[1]
+
+
+def bn_exact(x: torch.Tensor, bn: nn.BatchNorm2d, pool: bool = False) -> torch.Tensor:
+    """relu(max_pool2d(bn(x), 2, 2)) (pool) or relu(bn(x)) of a channels_last fp32 [B,C,H,W] tensor with `bn` in train mode, summed
+    in MIOpen's order: the stock chain's bits, `bn`'s running statistics and num_batches_tracked included (a convolution bias left
+    out of x is the caller's to add to the running mean).  Forward only; runs on torch's current stream."""
+    if not exact_output_fusable(x, bn, pool):
+        raise ValueError("bn_exact: needs a CUDA fp32 channels_last [B,C,H,W] tensor of a shape coattn_bn_exact_geometry "
+                         "covers, got %s %s strides %s" % (tuple(x.shape), x.dtype, x.stride()))
+    y, _, _ = _bn_exact_raw(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, pool)
+    if bn.num_batches_tracked is not None:
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+    return y
+
+
+def _stock_chain(x: torch.Tensor, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+    """What the default route ran before there was bn_exact: the stock BatchNorm, then relu_pool or the stock ReLU."""
+    z = bn(x)
+    if pool is None:
+        return torch.relu_(z)
+    return relu_pool(z) if relu_pool_fusable(pool, z) else torch.relu_(pool(z))
+
+
+def _differs(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """A 0-d bool tensor: some element of a is not b's (torch.equal with NaNs in the same places), without a host read."""
+    return ~((a == b) | (a.isnan() & b.isnan())).all()
+
+
+def _verify(x: torch.Tensor, bn: nn.BatchNorm2d, pool, key) -> torch.Tensor:
+    """The first call of a shape: the stock chain's result, and beside it bn_exact on clones of the running statistics,
+    compared bit for bit.  One host synchronisation."""
+    with torch.no_grad():
+        rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+        y = _stock_chain(x, bn, pool)
+        _, save_mean, save_invstd = torch.miopen_batch_norm(x, bn.weight, bn.bias, rm0.clone(), rv0.clone(), True,
+                                                            bn.momentum, bn.eps)
+        mine_y, mine_mean, mine_invstd = _bn_exact_raw(x, bn.weight, bn.bias, rm0, rv0, bn.momentum, bn.eps, pool is not None)
+        names = ("y", "running_mean", "running_var", "save_mean", "save_invstd")
+        pairs = ((mine_y, y), (rm0, bn.running_mean), (rv0, bn.running_var), (mine_mean, save_mean), (mine_invstd, save_invstd))
+        flags = torch.stack([_differs(a, b) for a, b in pairs]).tolist()
+    first = next((n for n, f in zip(names, flags) if f), None)
+    B, Ch, H, W = x.shape
+    _exact[key] = {"verified": first is None, "first_difference": first, "geometry": exact_geometry(B, H, W, Ch)}
+    if first is not None:
+        warnings.warn("encoder: bn_exact does not reproduce the stock BatchNorm for B=%d C=%d H=%d W=%d pool=%d (%s differs); "
+                      "this shape stays on the stock kernels" % (B, Ch, H, W, int(pool is not None), first))
+    return y
+
+
+def bn_exact_or_stock(x: torch.Tensor, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+    """relu([max_pool2d](bn(x))) with the stock chain's bits, `pool` a 2x2 MaxPool2d or None: through bn_exact for a shape that
+    was compared with the stock chain once in this process and found equal, through the stock chain otherwise -- the first
+    time a (device, B, C, H, W, pool) is seen (the comparison itself; not while the stream is capturing, where nothing is
+    compared or remembered) and for good after a difference, which is reported once."""
+    B, Ch, H, W = x.shape
+    key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), B, Ch, H, W, pool is not None)
+    state = _exact.get(key)
+    if state is None:
+        if torch.cuda.is_current_stream_capturing():
+            return _stock_chain(x, bn, pool)
+        return _verify(x, bn, pool, key)
+    return bn_exact(x, bn, pool is not None) if state["verified"] else _stock_chain(x, bn, pool)

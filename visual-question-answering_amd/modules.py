@@ -86,6 +86,11 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
 
     * by default ``ReLU(MaxPool2d(2, 2)(x))`` runs as ONE pass (``encoder.relu_pool``) instead of two kernels; both operations are
       exact, so every value keeps its bits;
+    * by default too, a whole ``Conv2d -> BatchNorm2d -> ReLU [-> MaxPool2d(2, 2)]`` group runs everything after the convolution
+      in two passes that sum in MIOpen's order with MIOpen's formula (``encoder.bn_exact``): the stock chain's bits.  Only for a
+      shape whose first call in this process, which runs the stock chain, found the two equal in every bit
+      (``encoder.bn_exact_or_stock``, ``encoder.exact_report()``); ``VQA_ENCODER_EXACT_BN=0`` turns it off.  The frozen
+      convolution bias stays the separate ``running_mean.add_`` it is on the stock route;
     * with ``VQA_ENCODER_FUSED=1`` a whole ``Conv2d -> BatchNorm2d -> ReLU [-> MaxPool2d(2, 2)]`` group runs everything after the
       convolution in two passes over its output (``encoder.bn_relu_pool``), the bias fold included.  Its statistics are summed
       in double, in another order than MIOpen's: values agree with the stock chain to rounding, not bit for bit.
@@ -102,20 +107,22 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
         m = mods[i]
         nxt = mods[i + 1] if i + 1 < n else None
         pool = mods[i + 3] if i + 3 < n and isinstance(mods[i + 3], nn.MaxPool2d) else None
-        fuse = (isinstance(m, nn.Conv2d) and isinstance(nxt, nn.BatchNorm2d) and i + 2 < n and isinstance(mods[i + 2], nn.ReLU)
-                and encoder.modules_fusable(m, nxt, pool, x))
-        if (isinstance(m, nn.Conv2d) and (fuse or (m.bias is not None and not m.bias.requires_grad)) and m.padding_mode == "zeros"
-                and isinstance(nxt, nn.BatchNorm2d) and nxt.training and nxt.momentum is not None):
+        group = isinstance(m, nn.Conv2d) and isinstance(nxt, nn.BatchNorm2d) and i + 2 < n and isinstance(mods[i + 2], nn.ReLU)
+        fuse = group and encoder.modules_fusable(m, nxt, pool, x)
+        exact = group and encoder.exact_modules_fusable(m, nxt, pool, x)
+        if (isinstance(m, nn.Conv2d) and (fuse or exact or (m.bias is not None and not m.bias.requires_grad))
+                and m.padding_mode == "zeros" and isinstance(nxt, nn.BatchNorm2d) and nxt.training and nxt.momentum is not None):
             x = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
             if fuse and encoder.output_fusable(x, nxt, pool is not None):
                 x = encoder.bn_relu_pool(x, nxt, conv_bias=m.bias, pool=pool is not None)
                 i += 3 if pool is None else 4
                 continue
-            x = nxt(x)
+            exact = exact and encoder.exact_output_fusable(x, nxt, pool is not None)
+            x = encoder.bn_exact_or_stock(x, nxt, pool) if exact else nxt(x)
             if m.bias is not None and nxt.track_running_stats and nxt.running_mean is not None:
                 with torch.no_grad():
                     nxt.running_mean.add_(m.bias.to(nxt.running_mean.dtype), alpha=nxt.momentum)
-            i += 2
+            i += 2 if not exact else 3 if pool is None else 4
         elif isinstance(m, nn.ReLU) and isinstance(nxt, nn.MaxPool2d):
             x = encoder.relu_pool(x) if encoder.relu_pool_fusable(nxt, x) else F.relu(nxt(x), inplace=True)
             i += 2
