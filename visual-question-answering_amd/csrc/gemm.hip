@@ -110,6 +110,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmK g) {
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  // BM = 32 (one 32 x 32 tile per wave): the k pairs alternate between two accumulators that the epilogue adds -- two
+  // independent MFMA chains, each sum half as long.  With one accumulator the rounding of a contraction over N = 4096
+  // locations (H_q's argument P_q + C P_v at T <= 64) moved H_q by up to 1e-5, and db_v with it (LAB_NOTES.md section 13)
+  constexpr bool TWO_ACC = (BM == 32);
+  f32x16 acc2;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
 
   float ra[EA], rb[EB];
   // step -> (inner index, k0)
@@ -165,11 +172,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmK g) {
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+          if (TWO_ACC && (kk & 2)) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc2, 0, 0, 0);
+          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
     }
     if (step + 1 < nsteps) store_step(buf ^ 1);
     __syncthreads();
   }
+  if (TWO_ACC) acc[0][0] += acc2;
 
   // epilogue: C/D layout col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
   float* Cb = g.c_ptrs[0] ? g.c_ptrs[z & 7] : g.C + (long)z * g.c_sz;
