@@ -625,7 +625,11 @@ int coattn_bn_exact_forward(const void* x, const void* gamma, const void* beta, 
  * replace A/B/C/Cin with t = z (ptr_by_inner = 0) or t = ig (ptr_by_inner = 1).
  * b_imod > 0: the inner stride of B wraps, B[ig] = B + (ig % b_imod) * b_si.
  * kband_n > 0 (multiple of 128, at most 3 bands): columns [j*kband_n, (j+1)*kband_n) contract only
- * over k in [kband_lo[j], kband_hi[j]) -- block-sparse B operands (n-gram taps of phrase.hip). */
+ * over k in [kband_lo[j], kband_hi[j]) -- block-sparse B operands (n-gram taps of phrase.hip).  The bounds are
+ * multiples of 4 inside [0, K]; lo == hi is an empty band (C = act(out_scale * biases + beta * Cin)); B is never
+ * read outside its bands.
+ * NaN and inf propagate: a non-finite element of A reaches exactly its row of C, one of B its column -- in the
+ * bf16 modes too (the staging keeps every NaN pattern a NaN). */
 typedef struct coattn_gemm_desc {
   const void* A; const void* B; const void* Cin; void* C;
   const void* bias_n; const void* bias_m;
@@ -651,7 +655,7 @@ int coattn_gemm_f32(const coattn_gemm_desc* g, void* stream);
  * kernel pair coattn_forward uses for both projections.  flags bit 0: `wimg` already holds the image of this
  * W (skip the split) -- WRITTEN BY A CALL WITH THE SAME N, K, precision flags (bits 2, 3) AND ON THE SAME KERNEL: the image's
  * format belongs to the kernel that reads it (three-piece fragments for gemm_w.hip, hi-only 1 KB chunks for gemm_bf.hip), and
- * which kernel runs depends on M (>= 256 and a multiple of 256 for gemm_bf.hip), ld_x and the alignment of x as well.  Reuse
+ * which kernel runs depends on M (>= 256 for gemm_bf.hip; a ragged last row tile is masked), ld_x and the alignment of x as well.  Reuse
  * an image only across calls of one shape class -- e.g. the steps of a loop over equal batches; a last partial batch with
  * another M must split again.  The library cannot check this (the image carries no tag).  flags bit 2 (COATTN_FLAG_BF16_PROJ): operands rounded to bf16, one MFMA per product.  K % 32 == 0, M >= 128, x 16-byte aligned with ld_x % 4 == 0; other shapes: error -1
  * (use coattn_gemm_f32).  bias may be NULL; out_scale 0 means 1.
@@ -675,8 +679,11 @@ int coattn_linear_weight_grad(const void* dy, int64_t ld_dy, const void* x, int6
 
 /* Same contract with the operands rounded to bf16 (round to nearest even) while they are staged and
  * contracted on v_mfma_f32_32x32x16_bf16 (fp32 accumulate / output): the arithmetic of
- * COATTN_FLAG_BF16_PROJ.  Shapes the bf16 kernels do not take (unaligned strides, M < 128) are computed
- * in exact fp32 instead. */
+ * COATTN_FLAG_BF16_PROJ.  Every shape the aligned path of coattn_gemm_f32 takes runs in this mode with every
+ * field of the descriptor.  Of the others (unaligned strides, M < 128), a plain product with B contiguous along
+ * k -- A, B, C, bias_n, out_scale, an a_ptrs table by batch and the row splits of A and C, nothing else -- does
+ * too; any further field (Cin or a cin_ptrs table, bias_m, act, inner > 1, an inner_total below batch, ksplit,
+ * b_imod, kband_n, b_ptrs, c_ptrs, ptr_by_inner) or an unaligned A or B makes such a shape an exact fp32 product instead. */
 int coattn_gemm_bf16(const coattn_gemm_desc* g, void* stream);
 
 /* ---- one-shot gradient exchange over peer-mapped buckets (data-parallel training) -----------

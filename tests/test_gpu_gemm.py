@@ -166,7 +166,10 @@ def test_gemm_large_m(a_m):
 
 @pytest.mark.parametrize("a_m,b_n", [(True, True), (False, True), (True, False), (False, False)])
 def test_gemm_small_tile_dispatch(a_m, b_n):
-    """Launches with 769..2303 128-row tiles switch to 64-row tiles (all four staging layouts)."""
+    """1,024 tiles of 128 rows, all four staging layouts.  Between 769 and 2,303 such tiles the f32-MFMA form of
+    gemm_f32_vec_kernel switches to 64-row tiles -- but launch_gemm_f32 takes the three-piece form first (COATTN_GEMM_X3 = 1,
+    the default), which has 128-row tiles at every size: today this shape runs gemm_f32_vec_kernel<.., 128, 2>, and the
+    64-row instantiations are reachable only behind the developer switches.  (The name is kept: it is the test's id.)"""
     torch.manual_seed(8)
     Z, M, N, K = 4, 2048, 2048, 64                  # 16 x 16 x 4 = 1024 tiles of 128 rows
     A = torch.randn(Z, K, M, device="cuda") if a_m else torch.randn(Z, M, K, device="cuda")

@@ -208,12 +208,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmK g) {
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ short f2bf(float x) {            // round to nearest even (inputs are finite)
-  unsigned u = __builtin_bit_cast(unsigned, x);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (short)(u >> 16);
-}
-
 // ---- aligned fast path: BK = 32, float4 global loads, one LDS buffer + register prefetch --------
 // Operand images: an operand whose fast (contiguous) axis is the tile row/column index (AM / BN)
 // is staged as [k][m] with 16-byte LDS writes; an operand that is contiguous along k is staged
@@ -233,6 +227,13 @@ typedef float f32x2g __attribute__((ext_vector_type(2)));
 typedef __bf16 bfv2g __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {      // one v_cvt_pk_bf16_f32 (round to nearest even)
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2g{a, b}), bfv2g));
+}
+// fp32 -> bf16 for the single-piece modes, on the same instruction: round to nearest even, and a NaN stays a NaN whatever its
+// payload (integer rounding -- adding 0x7FFF + the low bit to the pattern -- carried 0x7FFFFFFF into -0 and wrapped 0xFFFFFFFF
+// to +0; a compare and select in front of it cost the bf16 mode of the vec kernel 25 %: LAB_NOTES section 14)
+typedef unsigned u32x2g __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ bf16x4 f2bf4(const f32x4& v) {
+  return __builtin_bit_cast(bf16x4, (u32x2g{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])}));
 }
 __device__ __forceinline__ float sub1(float a, float b) {                 // one v_sub_f32 (never paired into v_pk_add_f32)
   float r;
@@ -413,11 +414,11 @@ __global__ __launch_bounds__(256) void gemm_f32_vec_kernel(const GemmK g) {
     if constexpr (MODE == 1) {
 #pragma unroll
       for (int i = 0; i < FA; ++i) {
-        *reinterpret_cast<bf16x4*>(&Ah[a_lds[i]]) = bf16x4{f2bf(ra[i][0]), f2bf(ra[i][1]), f2bf(ra[i][2]), f2bf(ra[i][3])};
+        *reinterpret_cast<bf16x4*>(&Ah[a_lds[i]]) = f2bf4(ra[i]);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        *reinterpret_cast<bf16x4*>(&Bh[b_lds[i]]) = bf16x4{f2bf(rb[i][0]), f2bf(rb[i][1]), f2bf(rb[i][2]), f2bf(rb[i][3])};
+        *reinterpret_cast<bf16x4*>(&Bh[b_lds[i]]) = f2bf4(rb[i]);
       }
       return;
     }
@@ -690,14 +691,13 @@ __global__ __launch_bounds__(256) void gemm_bf16in_kernel(const GemmK g) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (AM) {                                              // 4 rows m..m+3 of one k: transposing 2-byte writes
+        const bf16x4 v = f2bf4(ra[i]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) As[(a_m[i] + e) * LDR + a_k[i]] = f2bf(ra[i][e]);
+        for (int e = 0; e < 4; ++e) As[(a_m[i] + e) * LDR + a_k[i]] = v[e];
       } else {
-        *reinterpret_cast<bf16x4*>(&As[a_m[i] * LDR + a_k[i]]) =
-            bf16x4{f2bf(ra[i][0]), f2bf(ra[i][1]), f2bf(ra[i][2]), f2bf(ra[i][3])};
+        *reinterpret_cast<bf16x4*>(&As[a_m[i] * LDR + a_k[i]]) = f2bf4(ra[i]);
       }
-      *reinterpret_cast<bf16x4*>(&Bs[b_n[i] * LDR + b_k[i]]) =
-          bf16x4{f2bf(rb[i][0]), f2bf(rb[i][1]), f2bf(rb[i][2]), f2bf(rb[i][3])};
+      *reinterpret_cast<bf16x4*>(&Bs[b_n[i] * LDR + b_k[i]]) = f2bf4(rb[i]);
     }
   };
   if (nsteps > 0) { load_regs(0); store_regs(); }
@@ -886,6 +886,8 @@ int launch_gemm_bf16in(const coattn_gemm_desc& d, hipStream_t s) {
   bool tab_ok = true;
   for (int t = 0; t < 8; ++t) tab_ok = tab_ok && ((((uintptr_t)d.a_ptrs[t]) & 15) == 0);
   const bool ok = (d.A || d.a_ptrs[0]) && tab_ok && (!d.a_ptrs[0] || d.batch <= 8) && d.B && d.C && !d.Cin && !d.bias_m && d.act == 0 && d.inner <= 1 && d.ksplit == 0 &&
+                  d.kband_n == 0 && !d.cin_ptrs[0] && d.b_imod == 0 && (d.inner_total == 0 || d.inner_total >= d.batch) &&   // (the kernel below reads none of them;
+                  // with inner <= 1 an inner_total that covers every batch entry clips nothing: grad_dw_sample_groups at B <= 32)
                   !d.ptr_by_inner && !d.b_ptrs[0] && !d.c_ptrs[0] && d.b_sk == 1 && al4(d.b_sn) && al4(d.K) &&
                   (a_m ? true : (d.a_sk == 1 && al4(d.a_sm))) &&
                   al4(d.a_sz) && al4(d.b_sz) && ((((uintptr_t)d.A) | ((uintptr_t)d.B)) & 15) == 0;
