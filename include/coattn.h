@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -612,6 +612,41 @@ size_t coattn_bn_exact_workspace_bytes(int B, int H, int W, int C);
 int coattn_bn_exact_forward(const void* x, const void* gamma, const void* beta, void* running_mean, void* running_var,
                             double momentum, double eps, void* y, void* save_mean, void* save_invstd, void* ws, int B, int H,
                             int W, int C, int pool, int relu, int dtype, void* stream);
+
+/* ---- layer 1 of the frozen encoder: convolution, BatchNorm, ReLU and pool with the STOCK kernels' bits (v0.16.0) ----
+ * conv2d(image, weight, padding 1) for 3 -> 64 channels and a 3x3 kernel, stride 1, no bias, in the arithmetic of the
+ * Composable Kernel grouped convolution MIOpen runs this layer with: gemm-k = (ky, kx, c), c fastest, 27 terms padded with
+ * zeros to 32; every output one chain from 0 of sixteen v_mfma_f32_32x32x2_f32, MFMA i adding the terms 16 (i / 8) + i % 8 and
+ * that + 8 (lane half g holds the terms 8 g .. 8 g + 7 of each block of 16); a tap outside the image is a zero that is
+ * multiplied all the same
+ * (an infinite weight gives NaN along the border, as the stock kernel does).  One kernel writes x and adds it into the
+ * statistics in the order of coattn_bn_exact_forward's first kernel (the wave that computes a pixel group's outputs owns its
+ * sums); the second and third kernel of that call then run unchanged on x: the results are those of coattn_bn_exact_forward on x.
+ *   coattn_conv1_bn_exact_supported : 1 only for dtype COATTN_F32, Cin = 3, Cout = 64 and a (B, H, W, 64) that
+ *                  coattn_bn_exact_geometry covers (with pool: H, W >= 2); no GPU call
+ *   image        : fp32, physically [B][H][W][3] (a channels_last [B,3,H,W] tensor), 4-byte aligned; read only
+ *   weight       : fp32, physically [64][3][3][3] = [co][ky][kx][c] (a channels_last [64,3,3,3] tensor), 4-byte aligned; read only
+ *   x_out        : fp32 [B][H][W][64], written: the convolution; or NULL: x is kept in ws (size it with with_x = 1)
+ *   y, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, pool, stream : as for
+ *                  coattn_bn_exact_forward (the ReLU is always applied)
+ *   ws           : coattn_conv1_bn_exact_workspace_bytes(B, H, W, with_x): the partials, then x if with_x; 16-byte aligned
+ * Argument errors (a shape that is not covered, a NULL or misaligned pointer, aliased image / x_out / y, momentum outside
+ * [0, 1], eps <= 0): -1 before any HIP call; the workspace size of a shape that is not covered is 0.
+ * coattn_conv1_probe -- DEVELOPER ONLY, not part of the stable interface: the entry tools/probe_conv1_exact.py drives, kept so that
+ * the arithmetic can be probed again when MIOpen changes its solver; nothing in the package calls it -- x alone, by a slow kernel of one thread per output whose chain is switchable
+ * -- order 0 .. 5: (ky,kx,c) (ky,c,kx) (c,ky,kx) (kx,ky,c) (c,kx,ky) (kx,c,ky), last fastest, 28 terms; order 6 + 2 j + f:
+ * (ky,kx,c) padded to 32 and taken in pairs (t, t + D) within blocks of 2 D, D = 8, 4, 2, 16 for j = 0 .. 3, f = 1 the upper
+ * term first; step 0 fmaf, 1 multiply then add; halves 1, or 2: two chains over the halves of the terms, added; skip 1: zero
+ * terms left out -- or, order -1 / -2, by the fast kernel with D = 8 (the one the forward call runs) / D = 4.  ws as above
+ * with with_x = 0. */
+int coattn_conv1_bn_exact_supported(int B, int H, int W, int Cin, int Cout, int pool, int dtype);
+size_t coattn_conv1_bn_exact_workspace_bytes(int B, int H, int W, int with_x);
+int coattn_conv1_bn_exact_forward(const void* image, const void* weight, const void* gamma, const void* beta, void* running_mean,
+                                  void* running_var, double momentum, double eps, void* x_out, void* y, void* save_mean,
+                                  void* save_invstd, void* ws, int B, int H, int W, int Cin, int Cout, int pool, int dtype,
+                                  void* stream);
+int coattn_conv1_probe(const void* image, const void* weight, void* x, void* ws, int B, int H, int W, int order, int step,
+                       int halves, int skip, void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

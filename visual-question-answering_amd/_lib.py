@@ -26,7 +26,9 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_soft_loss_forward", "coattn_vqa_score", "coattn_head_forward_soft",
            "coattn_adam_workspace_bytes", "coattn_adam_step",
            "coattn_bn_supported", "coattn_bn_workspace_bytes", "coattn_bn_relu_pool_forward", "coattn_relu_pool_forward",
-           "coattn_bn_exact_geometry", "coattn_bn_exact_workspace_bytes", "coattn_bn_exact_forward")
+           "coattn_bn_exact_geometry", "coattn_bn_exact_workspace_bytes", "coattn_bn_exact_forward",
+           "coattn_conv1_bn_exact_supported", "coattn_conv1_bn_exact_workspace_bytes", "coattn_conv1_bn_exact_forward",
+           "coattn_conv1_probe")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -321,6 +323,14 @@ def load() -> C.CDLL:
     lib.coattn_bn_exact_workspace_bytes.restype = C.c_size_t
     lib.coattn_bn_exact_forward.argtypes = ([C.c_void_p] * 5 + [C.c_double] * 2 + [C.c_void_p] * 4 + [C.c_int] * 7
                                             + [C.c_void_p])
+    # layer 1 of the frozen encoder, convolution + statistics in one pass (v0.16.0): (image, weight, gamma, beta, running_mean,
+    # running_var, momentum, eps, x_out, y, save_mean, save_invstd, ws, B, H, W, Cin, Cout, pool, dtype, stream)
+    lib.coattn_conv1_bn_exact_supported.argtypes = [C.c_int] * 7
+    lib.coattn_conv1_bn_exact_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.coattn_conv1_bn_exact_workspace_bytes.restype = C.c_size_t
+    lib.coattn_conv1_bn_exact_forward.argtypes = ([C.c_void_p] * 6 + [C.c_double] * 2 + [C.c_void_p] * 5 + [C.c_int] * 7
+                                                  + [C.c_void_p])
+    lib.coattn_conv1_probe.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]
     _lib = lib
     return lib
 

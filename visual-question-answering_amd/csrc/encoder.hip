@@ -34,6 +34,10 @@
 //   bn_finalize_miopen_kernel  workgroup 2 x f1: thread (., t) adds the partials t, t + f1, ... in order, the same tree, times
 //                              1 / (B H W); var = max(fma(-mean, mean, E[x^2]), 0), invstd = rsq(var + eps), the running statistics.
 //   bn_relu_pool_kernel<POOL, true, true>   t = fma(gamma, (x - mean) * invstd, beta) per element, then the maximum, then ReLU.
+//
+// Layer 1 (coattn_conv1_bn_exact_forward, C-ABI 0.16.0): conv1_stats_miopen_kernel computes the 3 -> 64 channel convolution in the
+// stock convolution's arithmetic and, in the same pass, the partials bn_stats_miopen_kernel would have left; the two kernels
+// above follow unchanged.
 #include <math.h>
 
 #include "common.h"
@@ -261,6 +265,198 @@ __global__ __launch_bounds__(1024) void bn_finalize_miopen_kernel(const f32x4* _
   save_invstd[xg] = invstd;
 }
 
+// ---- layer 1 (3 -> 64 channels, 3x3, padding 1): the convolution in the stock kernel's arithmetic, statistics riding along ----
+// MIOpen runs this layer on Composable Kernel's grouped forward convolution (GridwiseGemmMultipleD_xdl_cshuffle, fp32, one wave
+// per 64 x 64 tile, KPerBlock 16, K1 4, 32x32 XDL): gemm-k = (ky, kx, c), c fastest, 27 terms padded with zeros to 32; the wave
+// tile is v_mfma_f32_32x32x2_f32, whose two k come from the two lane halves, and the blockwise GEMM gives lane half g the terms
+// 8 g .. 8 g + 7 of each block of 16.  So every output is ONE chain from 0 of sixteen MFMAs, MFMA i adding the terms
+// (16 (i / 8) + i % 8, the same + 8): 0, 8, 1, 9, .. 7, 15, 16, 24, .. 23, 31.  A tap outside the image is a zero that is still
+// multiplied.  The same instruction on the same pairs gives its bits (DESIGN 3.12 "Layer 1").
+constexpr int kConv1Terms = 32;
+constexpr int kConv1Mfmas = kConv1Terms / 2;
+constexpr int kConv1Pixels = 32;   // the 32 columns of the MFMA: the pixels of one wave
+
+// the term MFMA i takes from lane half g when half g holds D consecutive terms of each block of 2 D
+template <int D>
+__device__ __forceinline__ constexpr int conv1_term(int i, int g) { return (i / D) * 2 * D + g * D + i % D; }
+
+// grid ceil(H W / 32), block 128 (two waves), LDS 16 KB.  The workgroup owns the pixels 32 blockIdx.x .. + 31, wave hh of it
+// the output channels 32 hh .. 32 hh + 31; lane l = (g = l >> 5, p = l & 31).
+//   A operand: lane (g, p) holds the terms of half g of pixel p (sixteen 4-byte loads per sample).
+//   B operand: lane (g, p) holds the weights of output channel 32 hh + p for the terms of half g, loaded once;
+//              weight is [64][3][3][3] = [co][ky][kx][c].
+//   D: register v = 4 b + r of lane (g, p) is pixel 8 b + 4 g + r, channel 32 hh + p: a store of one register writes two
+//      whole 128-byte lines (32 consecutive channels of two pixels).  Whole lines are what the 2 GB write needs: with the
+//      operands the other way round (a lane holding four channels of one pixel, 16-byte stores) every store instruction
+//      wrote 32 bytes into each of 32 lines and the kernel ran at the stock convolution's 2.3 TB/s.
+// The wave walks the B samples in order; each (pixel, channel) is added into its own (sum, sq) exactly as the element of
+// thread (channel group, pixel) of bn_stats_miopen_kernel is: sum += x, sq = fma(x, x, sq).  The tree then halves the g1 pixels of each pixel group (g1 = 16: two groups per workgroup; g1 = 8:
+// four) in the stock order and writes the same [C][2] partials.
+template <int D>
+__global__ __launch_bounds__(128) void conv1_stats_miopen_kernel(
+    const float* __restrict__ image, const float* __restrict__ weight, float* __restrict__ x, float* __restrict__ partial, int B,
+    int H, int W, int g1, int ngrps) {
+  __shared__ float lds[kConv1Pixels * 64 * 2];                      // [pixel][channel]{sum, sq}
+  const int hh = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 5, p = lane & 31;
+  const int HW = H * W;
+  const int pbase = blockIdx.x * kConv1Pixels, pix = pbase + p;
+  const bool live = pix < HW;                                       // (of the pixel whose terms this lane loads)
+  const bool full = pbase + kConv1Pixels <= HW;                     // (of the workgroup: no masked pixel)
+  const int h = pix / W, w = pix - h * W;
+  const int ch = 32 * hh + p;
+  float wt[kConv1Mfmas];
+  int off[kConv1Mfmas];                                             // (0 where the term is a zero: the load is made and dropped)
+  unsigned real = 0;                                                // bit i: term i is a tap inside the image
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) {
+    const int k = conv1_term<D>(i, g);
+    const int tap = k / 3, c = k - 3 * tap, ky = tap / 3, kx = tap - 3 * ky;
+    const int ih = h + ky - 1, iw = w + kx - 1;
+    const bool in = live && k < 27 && ih >= 0 && ih < H && iw >= 0 && iw < W;
+    off[i] = in ? (ih * W + iw) * 3 + c : 0;
+    real |= in ? 1u << i : 0u;
+    const float wk = weight[ch * 27 + (k < 27 ? k : 26)];
+    wt[i] = k < 27 ? wk : 0.f;
+  }
+  const int64_t sample = (int64_t)HW * 3;
+  // two buffers of terms, for the samples n and n + 1; a term's register is reloaded for sample n + 2 as soon as its MFMA has
+  // read it.  Two samples ahead, not one: a wait for a load also waits for every store issued before it, and these loads
+  // are issued before the stores of the samples n and n + 1, so the chain of sample n + 2 waits for stores two samples old.
+  float even[kConv1Mfmas], odd[kConv1Mfmas];
+  const float* image1 = image + (B > 1 ? sample : 0);
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) even[i] = image[off[i]];
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) odd[i] = image1[off[i]];
+  float sum[16], sq[16];                                            // [v]: pixel 8 (v >> 2) + 4 g + (v & 3), channel ch
+#pragma unroll
+  for (int v = 0; v < 16; ++v) sum[v] = sq[v] = 0.f;
+  float* xo = x + ((int64_t)(pbase + 4 * g) * 64 + ch);             // register v goes (8 (v >> 2) + (v & 3)) pixels further
+  const int64_t xstep = (int64_t)HW * 64;
+  auto one_sample = [&](float (&terms)[kConv1Mfmas], int n) {
+    const float* ahead = image + (int64_t)(n + 2 < B ? n + 2 : B - 1) * sample;      // (the last two reload the last sample)
+    f32x16 acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < kConv1Mfmas; ++i) {
+      const float t = (real >> i) & 1u ? terms[i] : 0.f;
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(t, wt[i], acc, 0, 0, 0);
+      terms[i] = ahead[off[i]];
+    }
+    if (full) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        xo[(8 * (v >> 2) + (v & 3)) * 64] = acc[v];
+        sum[v] += acc[v];
+        sq[v] = __builtin_fmaf(acc[v], acc[v], sq[v]);
+      }
+    } else {
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (pbase + 8 * (v >> 2) + 4 * g + (v & 3) < HW) {
+          xo[(8 * (v >> 2) + (v & 3)) * 64] = acc[v];
+          sum[v] += acc[v];
+          sq[v] = __builtin_fmaf(acc[v], acc[v], sq[v]);
+        }
+    }
+    xo += xstep;
+  };
+  for (int n = 0; n < B; n += 2) {
+    one_sample(even, n);
+    if (n + 1 < B) one_sample(odd, n + 1);
+  }
+  // the stock tree over the g1 pixel rows of a pixel group: row r += row r + red, red = g1 / 2 .. 1
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int o = ((8 * (v >> 2) + 4 * g + (v & 3)) * 64 + ch) * 2;
+    lds[o] = sum[v];
+    lds[o + 1] = sq[v];
+  }
+  __syncthreads();
+  for (int red = g1 >> 1; red > 0; red >>= 1) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const int q = 8 * (v >> 2) + 4 * g + (v & 3);
+      if ((q & (g1 - 1)) < red) {
+        const int o = (q * 64 + ch) * 2, o2 = o + red * 128;
+        sum[v] += lds[o2];
+        sq[v] += lds[o2 + 1];
+        lds[o] = sum[v];
+        lds[o + 1] = sq[v];
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int q = 8 * (v >> 2) + 4 * g + (v & 3), grp = (pbase + q) / g1;
+    if ((q & (g1 - 1)) == 0 && grp < ngrps) {
+      float* out = partial + (((int64_t)grp * 16 + (ch >> 2)) * 2) * 4 + (ch & 3);
+      out[0] = sum[v];
+      out[4] = sq[v];
+    }
+  }
+}
+
+// The slow probe of tools/probe_conv1_exact.py: one thread per output, the chain's order and step switchable.
+//   order : 0 (ky, kx, c)  1 (ky, c, kx)  2 (c, ky, kx)  3 (kx, ky, c)  4 (c, kx, ky)  5 (kx, c, ky), last fastest, 28 terms;
+//           6 + 2 j + f: (ky, kx, c) padded to 32 terms and taken in pairs (t, t + D) within blocks of 2 D, D = 8, 4, 2, 16 for
+//           j = 0 .. 3 -- the order a k-reducing MFMA gives when each lane half holds D consecutive terms --, f = 1: the upper
+//           term of a pair first
+//   step  : 0 fmaf   1 multiply, then add (two roundings)
+//   halves: 1 one chain   2 two chains over the first and the second half of the terms, added
+//   skip  : 1 leaves the taps outside the image and the padding terms out instead of multiplying zeros
+__global__ __launch_bounds__(256) void conv1_probe_kernel(const float* __restrict__ image, const float* __restrict__ weight,
+                                                          float* __restrict__ x, int64_t total, int H, int W, int order, int step,
+                                                          int halves, int skip) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int co = (int)(i & 63);
+  const int64_t pixel = i >> 6;
+  const int w = (int)(pixel % W), h = (int)((pixel / W) % H);
+  const int64_t n = pixel / ((int64_t)W * H);
+  const int terms = order < 6 ? 28 : 32;
+  const int pair = order - 6, dist = pair < 0 ? 1 : (pair >> 1) == 0 ? 8 : (pair >> 1) == 1 ? 4 : (pair >> 1) == 2 ? 2 : 16;
+  float acc[2] = {0.f, 0.f};
+  for (int s = 0; s < terms; ++s) {
+    int t = s;
+    if (pair >= 0) {
+      const int r = s % (2 * dist), gsel = (r & 1) ^ (pair & 1);
+      t = (s / (2 * dist)) * 2 * dist + gsel * dist + (r >> 1);
+    }
+    float a = 0.f, v = 0.f;
+    bool real = false;
+    if (t < 27) {
+      const int i0 = t / 9, i1 = (t / 3) % 3, i2 = t % 3;         // slowest .. fastest
+      int ky, kx, c;
+      switch (order) {
+        case 1: ky = i0, c = i1, kx = i2; break;
+        case 2: c = i0, ky = i1, kx = i2; break;
+        case 3: kx = i0, ky = i1, c = i2; break;
+        case 4: c = i0, kx = i1, ky = i2; break;
+        case 5: kx = i0, c = i1, ky = i2; break;
+        default: ky = i0, kx = i1, c = i2; break;
+      }
+      a = weight[co * 27 + (ky * 3 + kx) * 3 + c];
+      const int hh = h + ky - 1, ww = w + kx - 1;
+      if (hh >= 0 && hh < H && ww >= 0 && ww < W) {
+        v = image[((n * H + hh) * W + ww) * 3 + c];
+        real = true;
+      }
+    }
+    if (skip && !real) continue;
+    float& sacc = acc[halves == 2 && s >= terms / 2 ? 1 : 0];
+    if (step == 0) {
+      sacc = __builtin_fmaf(a, v, sacc);
+    } else {
+      const float prod = __fmul_rn(a, v);
+      sacc = __fadd_rn(prod, sacc);
+    }
+  }
+  x[i] = halves == 2 ? __fadd_rn(acc[0], acc[1]) : acc[0];
+}
+
 struct Affine {
   float mean[4], lo[4], scale[4], beta[4], gamma[4];
 };
@@ -485,6 +681,37 @@ bool bn_exact_geometry(int B, int H, int W, int C, int dtype, BnGeom* g) {
 
 inline size_t exact_partial_bytes(const BnGeom& g, int C) { return (size_t)g.ngrps * g.ngrps2 * C * 2 * sizeof(float); }
 
+// bn_finalize_miopen_kernel and the normalise (+ pool) + ReLU pass over x, behind a statistics kernel that left `partial`
+int exact_tail(const void* x, const void* gamma, const void* beta, void* running_mean, void* running_var, double momentum,
+               double eps, void* y, void* save_mean, void* save_invstd, const f32x4* partial, const BnGeom& g, int B, int H, int W,
+               int C, int pool, int relu, hipStream_t s) {
+  const int c4 = C / 4;
+  const int64_t pixels = (int64_t)B * H * W;
+  // the constants of the stock build: INHW = float(1.0 / n) as a kernel argument, n / (n - 1) folded in fp32
+  const float n_f = (float)pixels;
+  const float inhw = (float)(1.0 / (double)pixels), unbias = pixels == 1 ? 1.f : n_f / (n_f - 1.f);
+  hipLaunchKernelGGL(bn_finalize_miopen_kernel, dim3(c4 / g.f0), dim3(g.f0, g.f1, g.f2),
+                     (size_t)2 * g.f0 * g.f1 * g.f2 * sizeof(f32x4), s, (const f32x4*)partial, g, c4, inhw, unbias,
+                     (float)momentum, (float)eps, (f32x4*)running_mean, (f32x4*)running_var, (f32x4*)save_mean,
+                     (f32x4*)save_invstd);
+  CA_CHECK_LAUNCH("bn_finalize_miopen");
+  const int64_t out_pixels = pool ? (int64_t)B * (H / 2) * (W / 2) : pixels;
+  const int64_t total4 = out_pixels * c4;
+  const int per_thread = pool ? 2 : 4;
+  int64_t blocks = (total4 + (int64_t)kThreads * per_thread - 1) / ((int64_t)kThreads * per_thread);
+  if (blocks > kMaxNormBlocks) blocks = kMaxNormBlocks;
+  if (pool)
+    hipLaunchKernelGGL((bn_relu_pool_kernel<true, true, true>), dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x,
+                       (const float*)save_mean, (const float*)save_invstd, (const float*)gamma, (const float*)beta, (f32x4*)y, H,
+                       W, C, log2_exact(c4), total4, relu);
+  else
+    hipLaunchKernelGGL((bn_relu_pool_kernel<false, true, true>), dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x,
+                       (const float*)save_mean, (const float*)save_invstd, (const float*)gamma, (const float*)beta, (f32x4*)y, H,
+                       W, C, log2_exact(c4), total4, relu);
+  CA_CHECK_LAUNCH("bn_relu_pool_exact");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int coattn_bn_exact_geometry(int B, int H, int W, int C, int dtype, int* out) {
@@ -526,33 +753,102 @@ extern "C" int coattn_bn_exact_forward(const void* x, const void* gamma, const v
   CA_CHECK_ARG(eps > 0.0, "bn_exact_forward: eps %g (must be > 0)", eps);
   hipStream_t s = (hipStream_t)stream;
   const int c4 = C / 4, hw = H * W;
-  const int64_t pixels = (int64_t)B * hw;
   f32x4* partial = (f32x4*)ws;
   hipLaunchKernelGGL(bn_stats_miopen_kernel, dim3(c4 / g.g0, g.ngrps, g.ngrps2), dim3(g.g0, g.g1, g.g2),
                      (size_t)2 * g.g0 * g.g1 * g.g2 * sizeof(f32x4), s, (const f32x4*)x, partial, g, B, hw, c4);
   CA_CHECK_LAUNCH("bn_stats_miopen");
-  // the constants of the stock build: INHW = float(1.0 / n) as a kernel argument, n / (n - 1) folded in fp32
-  const float n_f = (float)pixels;
-  const float inhw = (float)(1.0 / (double)pixels), unbias = pixels == 1 ? 1.f : n_f / (n_f - 1.f);
-  hipLaunchKernelGGL(bn_finalize_miopen_kernel, dim3(c4 / g.f0), dim3(g.f0, g.f1, g.f2),
-                     (size_t)2 * g.f0 * g.f1 * g.f2 * sizeof(f32x4), s, (const f32x4*)partial, g, c4, inhw, unbias,
-                     (float)momentum, (float)eps, (f32x4*)running_mean, (f32x4*)running_var, (f32x4*)save_mean,
-                     (f32x4*)save_invstd);
-  CA_CHECK_LAUNCH("bn_finalize_miopen");
-  const int64_t out_pixels = pool ? (int64_t)B * (H / 2) * (W / 2) : pixels;
-  const int64_t total4 = out_pixels * c4;
-  const int per_thread = pool ? 2 : 4;
-  int64_t blocks = (total4 + (int64_t)kThreads * per_thread - 1) / ((int64_t)kThreads * per_thread);
-  if (blocks > kMaxNormBlocks) blocks = kMaxNormBlocks;
-  if (pool)
-    hipLaunchKernelGGL((bn_relu_pool_kernel<true, true, true>), dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x,
-                       (const float*)save_mean, (const float*)save_invstd, (const float*)gamma, (const float*)beta, (f32x4*)y, H,
-                       W, C, log2_exact(c4), total4, relu);
-  else
-    hipLaunchKernelGGL((bn_relu_pool_kernel<false, true, true>), dim3((unsigned)blocks), dim3(kThreads), 0, s, (const f32x4*)x,
-                       (const float*)save_mean, (const float*)save_invstd, (const float*)gamma, (const float*)beta, (f32x4*)y, H,
-                       W, C, log2_exact(c4), total4, relu);
-  CA_CHECK_LAUNCH("bn_relu_pool_exact");
+  if (exact_tail(x, gamma, beta, running_mean, running_var, momentum, eps, y, save_mean, save_invstd, partial, g, B, H, W, C, pool,
+                 relu, s))
+    return -1;
   prof_mark(s, "bn_exact");
+  return 0;
+}
+
+// ---- layer 1: convolution + statistics in one pass, the stock kernels' bits (v0.16.0) -----------------------------------------
+namespace {
+
+constexpr int kConv1PairDistance = 8;   // terms per lane half and block: KPerBlock / 2 of the stock kernel
+
+inline size_t conv1_partial_bytes(const BnGeom& g) { return (exact_partial_bytes(g, 64) + 255) & ~(size_t)255; }
+
+void launch_conv1(int dist, const void* image, const void* weight, void* x, void* partial, const BnGeom& g, int B, int H, int W,
+                  hipStream_t s) {
+  const int blocks = (H * W + kConv1Pixels - 1) / kConv1Pixels;
+  if (dist == 8)
+    hipLaunchKernelGGL(conv1_stats_miopen_kernel<8>, dim3(blocks), dim3(128), 0, s, (const float*)image, (const float*)weight,
+                       (float*)x, (float*)partial, B, H, W, g.g1, g.ngrps);
+  else
+    hipLaunchKernelGGL(conv1_stats_miopen_kernel<4>, dim3(blocks), dim3(128), 0, s, (const float*)image, (const float*)weight,
+                       (float*)x, (float*)partial, B, H, W, g.g1, g.ngrps);
+}
+
+}  // namespace
+
+extern "C" int coattn_conv1_bn_exact_supported(int B, int H, int W, int Cin, int Cout, int pool, int dtype) {
+  BnGeom g;
+  if (Cin != 3 || Cout != 64) return 0;
+  return bn_exact_geometry(B, H, W, Cout, dtype, &g) && coattn_bn_supported(B, H, W, Cout, pool, dtype) ? 1 : 0;
+}
+
+extern "C" size_t coattn_conv1_bn_exact_workspace_bytes(int B, int H, int W, int with_x) {
+  BnGeom g;
+  if (!bn_exact_geometry(B, H, W, 64, COATTN_F32, &g)) {
+    coattn_set_error("conv1_bn_exact_workspace_bytes: B=%d H=%d W=%d is not a covered shape (coattn_conv1_bn_exact_supported)", B, H, W);
+    return 0;
+  }
+  return conv1_partial_bytes(g) + (with_x ? (size_t)B * H * W * 64 * sizeof(float) : 0);
+}
+
+extern "C" int coattn_conv1_bn_exact_forward(const void* image, const void* weight, const void* gamma, const void* beta,
+                                             void* running_mean, void* running_var, double momentum, double eps, void* x_out,
+                                             void* y, void* save_mean, void* save_invstd, void* ws, int B, int H, int W, int Cin,
+                                             int Cout, int pool, int dtype, void* stream) {
+  CA_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1, "conv1_bn_exact_forward: B=%d H=%d W=%d Cin=%d Cout=%d (all must be >= 1)",
+               B, H, W, Cin, Cout);
+  BnGeom g;
+  CA_CHECK_ARG(coattn_conv1_bn_exact_supported(B, H, W, Cin, Cout, pool, dtype) && bn_exact_geometry(B, H, W, Cout, dtype, &g),
+               "conv1_bn_exact_forward: B=%d H=%d W=%d Cin=%d Cout=%d pool=%d dtype=%d is not a covered shape "
+               "(coattn_conv1_bn_exact_supported)", B, H, W, Cin, Cout, pool, dtype);
+  CA_CHECK_ARG(image && weight && gamma && beta && running_mean && running_var && y && save_mean && save_invstd && ws,
+               "conv1_bn_exact_forward: a null image / weight / gamma / beta / running_mean / running_var / y / save_mean / "
+               "save_invstd / ws");
+  CA_CHECK_ARG(((reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(ws) |
+                 reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(running_mean) |
+                 reinterpret_cast<uintptr_t>(running_var) | reinterpret_cast<uintptr_t>(save_mean) |
+                 reinterpret_cast<uintptr_t>(save_invstd)) & 15) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(weight)) & 3) == 0,
+               "conv1_bn_exact_forward: x_out, y, ws, the BatchNorm vectors must be 16-byte aligned, image and weight 4-byte aligned");
+  CA_CHECK_ARG(momentum >= 0.0 && momentum <= 1.0, "conv1_bn_exact_forward: momentum %g outside [0, 1]", momentum);
+  CA_CHECK_ARG(eps > 0.0, "conv1_bn_exact_forward: eps %g (must be > 0)", eps);
+  void* x = x_out ? x_out : (void*)((char*)ws + conv1_partial_bytes(g));
+  CA_CHECK_ARG(x != y && x != image && y != image, "conv1_bn_exact_forward: image, x_out and y must be three buffers");
+  hipStream_t s = (hipStream_t)stream;
+  launch_conv1(kConv1PairDistance, image, weight, x, ws, g, B, H, W, s);
+  CA_CHECK_LAUNCH("conv1_stats_miopen");
+  if (exact_tail(x, gamma, beta, running_mean, running_var, momentum, eps, y, save_mean, save_invstd, (const f32x4*)ws, g, B, H, W,
+                 Cout, pool, 1, s))
+    return -1;
+  prof_mark(s, "conv1_bn_exact");
+  return 0;
+}
+
+extern "C" int coattn_conv1_probe(const void* image, const void* weight, void* x, void* ws, int B, int H, int W, int order, int step,
+                                  int halves, int skip, void* stream) {
+  BnGeom g;
+  CA_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && bn_exact_geometry(B, H, W, 64, COATTN_F32, &g),
+               "conv1_probe: B=%d H=%d W=%d is not a covered shape (coattn_conv1_bn_exact_supported)", B, H, W);
+  CA_CHECK_ARG(image && weight && x && ws && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
+               "conv1_probe: a null or misaligned image / weight / x / ws");
+  CA_CHECK_ARG(order >= -2 && order <= 13 && (step == 0 || step == 1) && (halves == 1 || halves == 2) && (skip == 0 || skip == 1),
+               "conv1_probe: order=%d step=%d halves=%d skip=%d", order, step, halves, skip);
+  hipStream_t s = (hipStream_t)stream;
+  if (order < 0) {
+    launch_conv1(order == -1 ? 8 : 4, image, weight, x, ws, g, B, H, W, s);
+  } else {
+    const int64_t total = (int64_t)B * H * W * 64;
+    hipLaunchKernelGGL(conv1_probe_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)image,
+                       (const float*)weight, (float*)x, total, H, W, order, step, halves, skip);
+  }
+  CA_CHECK_LAUNCH("conv1_probe");
   return 0;
 }

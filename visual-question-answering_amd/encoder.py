@@ -1,5 +1,6 @@
-"""The memory-bound glue of the frozen image encoder on the HIP library (csrc/encoder.hip, include/coattn.h v0.15.0), for
-channels_last fp32 tensors; the convolutions stay on MIOpen.  ``modules.run_conv_bn_stack`` decides which layer takes what:
+"""The memory-bound glue of the frozen image encoder on the HIP library (csrc/encoder.hip, include/coattn.h v0.16.0), for
+channels_last fp32 tensors; the convolutions stay on MIOpen, but for the first.  ``modules.run_conv_bn_stack`` decides which
+layer takes what:
 
 * ``relu_pool``: ``MaxPool2d(2, 2)`` + ``ReLU`` in one pass.  Both are exact operations: the values are the stock kernels' bit
   for bit.  The default (``mode() == "pool"``).
@@ -7,6 +8,10 @@ channels_last fp32 tensors; the convolutions stay on MIOpen.  ``modules.run_conv
   with MIOpen's formula: the stock chain's bits.  Also the default, but only for a shape that ``bn_exact_or_stock`` has compared
   with the stock chain once in this process and found equal in every bit (``exact_report()``); ``VQA_ENCODER_EXACT_BN=0``
   turns it off.
+* ``bn_exact(..., conv=conv)``: the same with the first convolution (3 -> 64 channels, 3x3, padding 1) in front, computed in
+  the stock kernel's arithmetic by the kernel that also sums its statistics.  The default for the first group, again only for a
+  shape that ``conv1_bn_exact_or_stock`` has compared with the stock convolution and chain once and found equal in every bit;
+  ``VQA_ENCODER_EXACT_CONV1=0`` turns it off (and so does whatever turns ``bn_exact`` off).
 * ``bn_relu_pool``: train-mode ``BatchNorm2d`` + ``ReLU`` + an optional ``MaxPool2d(2, 2)`` in two passes over the convolution
   output, statistics in double.  More accurate than the stock chain, but not its bits: a training trajectory leaves the stock
   one at rounding level and drifts from there.  Opt-in: ``VQA_ENCODER_FUSED=1``.
@@ -143,7 +148,9 @@ def bn_relu_pool(x: torch.Tensor, bn: nn.BatchNorm2d, conv_bias=None, pool: bool
 
 # ---- the stock kernels' bits: verified per shape, or not used -------------------------------------------------------------
 GEOMETRY_FIELDS = ("vec", "g0", "g1", "g2", "samples_per_thread", "pixel_groups", "sample_groups", "f0", "f1", "f2")
-_exact = {}                   # (device index, B, C, H, W, pool) -> {"verified": bool, "first_difference": name or None, "geometry": {...}}
+# (device index, B, C, H, W, pool) -> {"verified": bool, "first_difference": name or None, "geometry": {...}}, and where the
+# tensor was the first convolution's output and that route was compared too, "conv1": {"verified", "first_difference"}
+_exact = {}
 
 
 def exact_geometry(B: int, H: int, W: int, Ch: int):
@@ -163,8 +170,10 @@ def exact_output_fusable(z: torch.Tensor, bn: nn.BatchNorm2d, pool: bool) -> boo
 
 
 def exact_report() -> dict:
-    """{(device index, B, C, H, W, pool): {"verified", "first_difference", "geometry"}} of every shape compared so far."""
-    return {k: dict(v) for k, v in _exact.items()}
+    """{(device index, B, C, H, W, pool): {"verified", "first_difference", "geometry"}} of every shape compared so far; the
+    entry of a first-convolution output also holds "conv1": {"verified", "first_difference"} once conv1_bn_exact_or_stock has
+    compared that route (a key of the entry: it cannot collide with a BatchNorm shape)."""
+    return {k: {n: dict(t) if n == "conv1" else t for n, t in v.items()} for k, v in _exact.items()}
 
 
 def _bn_exact_raw(x, weight, bias, running_mean, running_var, momentum, eps, pool: bool):
@@ -183,14 +192,23 @@ def _bn_exact_raw(x, weight, bias, running_mean, running_var, momentum, eps, poo
     return y, save[0], save[1]
 
 
-def bn_exact(x: torch.Tensor, bn: nn.BatchNorm2d, pool: bool = False) -> torch.Tensor:
+def bn_exact(x: torch.Tensor, bn: nn.BatchNorm2d, pool: bool = False, conv=None) -> torch.Tensor:
     """relu(max_pool2d(bn(x), 2, 2)) (pool) or relu(bn(x)) of a channels_last fp32 [B,C,H,W] tensor with `bn` in train mode, summed
     in MIOpen's order: the stock chain's bits, `bn`'s running statistics and num_batches_tracked included (a convolution bias left
-    out of x is the caller's to add to the running mean).  Forward only; runs on torch's current stream."""
-    if not exact_output_fusable(x, bn, pool):
-        raise ValueError("bn_exact: needs a CUDA fp32 channels_last [B,C,H,W] tensor of a shape coattn_bn_exact_geometry "
-                         "covers, got %s %s strides %s" % (tuple(x.shape), x.dtype, x.stride()))
-    y, _, _ = _bn_exact_raw(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, pool)
+    out of x is the caller's to add to the running mean).  With `conv`, the encoder's first convolution, x is ITS input, a
+    channels_last [B,3,H,W] image: conv2d(x, conv.weight, padding=1) without the bias is computed in the stock kernel's arithmetic
+    by the kernel that sums the statistics (coattn_conv1_bn_exact_forward).  Forward only; runs on torch's current stream."""
+    if conv is not None:
+        if not conv1_inputs_fusable(x, conv, bn, pool):
+            raise ValueError("bn_exact: with conv it needs a CUDA fp32 channels_last [B,3,H,W] image, a 3 -> 64 channel 3x3 / stride 1 "
+                             "/ padding 1 convolution with channels_last weights and a shape coattn_conv1_bn_exact_supported "
+                             "covers, got %s %s strides %s" % (tuple(x.shape), x.dtype, x.stride()))
+        _, y, _, _ = _conv1_raw(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, pool, False)
+    else:
+        if not exact_output_fusable(x, bn, pool):
+            raise ValueError("bn_exact: needs a CUDA fp32 channels_last [B,C,H,W] tensor of a shape coattn_bn_exact_geometry "
+                             "covers, got %s %s strides %s" % (tuple(x.shape), x.dtype, x.stride()))
+        y, _, _ = _bn_exact_raw(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, pool)
     if bn.num_batches_tracked is not None:
         with torch.no_grad():
             bn.num_batches_tracked.add_(1)
@@ -231,11 +249,18 @@ def _verify(x: torch.Tensor, bn: nn.BatchNorm2d, pool, key) -> torch.Tensor:
     return y
 
 
-def bn_exact_or_stock(x: torch.Tensor, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+def bn_exact_or_stock(x: torch.Tensor, bn: nn.BatchNorm2d, pool, conv=None) -> torch.Tensor:
     """relu([max_pool2d](bn(x))) with the stock chain's bits, `pool` a 2x2 MaxPool2d or None: through bn_exact for a shape that
     was compared with the stock chain once in this process and found equal, through the stock chain otherwise -- the first
     time a (device, B, C, H, W, pool) is seen (the comparison itself; not while the stream is capturing, where nothing is
-    compared or remembered) and for good after a difference, which is reported once."""
+    compared or remembered) and for good after a difference, which is reported once.  With `conv`, x is the input of the
+    encoder's first convolution and the convolution is part of the contract: conv1_bn_exact_or_stock."""
+    if conv is not None:
+        return _conv1_or_stock(x, conv, bn, pool)
+    return _bn_or_stock(x, bn, pool)
+
+
+def _bn_or_stock(x: torch.Tensor, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
     B, Ch, H, W = x.shape
     key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), B, Ch, H, W, pool is not None)
     state = _exact.get(key)
@@ -244,3 +269,111 @@ def bn_exact_or_stock(x: torch.Tensor, bn: nn.BatchNorm2d, pool) -> torch.Tensor
             return _stock_chain(x, bn, pool)
         return _verify(x, bn, pool, key)
     return bn_exact(x, bn, pool is not None) if state["verified"] else _stock_chain(x, bn, pool)
+
+
+# ---- the first convolution with its statistics riding along: verified per shape, or not used ------------------------------
+def conv1_enabled() -> bool:
+    """Where bn_exact is the default, unless VQA_ENCODER_EXACT_CONV1=0."""
+    return exact_enabled() and os.environ.get("VQA_ENCODER_EXACT_CONV1", "1") != "0"
+
+
+def conv1_inputs_fusable(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool: bool) -> bool:
+    """A CUDA fp32 channels_last [B,3,H,W] image, a 3 -> 64 channel 3x3 convolution of stride 1, zero padding 1, no dilation and
+    no groups whose fp32 weights are channels_last too (the stock call then answers channels_last, and gemm-k runs (ky, kx, c)
+    through memory), BatchNorm2d's parameters and buffers in fp32 and 16-byte aligned, a shape the library covers."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    if not (conv.in_channels == 3 and conv.out_channels == 64 and _pair(conv.kernel_size) == (3, 3) and _pair(conv.stride) == (1, 1)
+            and not isinstance(conv.padding, str) and _pair(conv.padding) == (1, 1) and _pair(conv.dilation) == (1, 1)
+            and conv.groups == 1 and conv.padding_mode == "zeros" and x.shape[1] == 3):
+        return False
+    w = conv.weight
+    if not (w.dtype == torch.float32 and w.device == x.device and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        if t is None or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or t.data_ptr() % 16 != 0:
+            return False
+    if bn.num_features != 64 or x.data_ptr() % 4 != 0 or w.data_ptr() % 4 != 0:
+        return False
+    B, _, H, W = x.shape
+    return bool(_lib.load().coattn_conv1_bn_exact_supported(B, H, W, 3, 64, int(pool), _lib.F32))
+
+
+def conv1_modules_fusable(conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, x: torch.Tensor) -> bool:
+    """exact_modules_fusable's conditions, VQA_ENCODER_EXACT_CONV1, and conv1_inputs_fusable."""
+    return (conv1_enabled() and not torch.is_autocast_enabled() and _group_fusable(conv, bn, pool, x)
+            and conv1_inputs_fusable(x, conv, bn, pool is not None))
+
+
+def _conv1_raw(image, weight, gamma, beta, running_mean, running_var, momentum, eps, pool: bool, want_x: bool):
+    lib = _lib.load()
+    B, _, H, W = image.shape
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    dev = image.device
+    y = torch.empty((B, 64, Ho, Wo), device=dev, dtype=torch.float32, memory_format=torch.channels_last)
+    x = torch.empty((B, 64, H, W), device=dev, dtype=torch.float32, memory_format=torch.channels_last) if want_x else None
+    save = torch.empty((2, 64), device=dev, dtype=torch.float32)
+    # (from torch's allocator under the current stream, per call, as bn_relu_pool's: x lives in it when the caller wants none)
+    ws = torch.empty((lib.coattn_conv1_bn_exact_workspace_bytes(B, H, W, int(not want_x)) + 3) // 4, device=dev, dtype=torch.float32)
+    with torch.no_grad(), _lib.on_device(dev):
+        rc = lib.coattn_conv1_bn_exact_forward(_lib.ptr(image), _lib.ptr(weight), _lib.ptr(gamma), _lib.ptr(beta),
+                                               _lib.ptr(running_mean), _lib.ptr(running_var), float(momentum), float(eps),
+                                               _lib.ptr(x), _lib.ptr(y), _lib.ptr(save[0]), _lib.ptr(save[1]), _lib.ptr(ws), B, H, W,
+                                               3, 64, int(pool), _lib.F32, C.c_void_p(_lib.stream_ptr(dev)))
+        _lib.check(rc, "coattn_conv1_bn_exact_forward")
+    return x, y, save[0], save[1]
+
+
+def _conv1_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+    """What the group ran before there was this route: the stock convolution without its bias, then bn_exact_or_stock's contract
+    (or the stock chain, should the convolution answer in another layout)."""
+    z = torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+    return _bn_or_stock(z, bn, pool) if exact_output_fusable(z, bn, pool is not None) else _stock_chain(z, bn, pool)
+
+
+def _verify_conv1(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, key) -> torch.Tensor:
+    """The first call of a shape: the stock group's result, and beside it the one-pass route on clones of the running
+    statistics, compared bit for bit.  One host synchronisation (and the BatchNorm comparison's, if this is its first call too)."""
+    with torch.no_grad():
+        rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+        z = torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+        if not exact_output_fusable(z, bn, pool is not None):
+            return _stock_chain(z, bn, pool)                        # (another layout: nothing compared, nothing remembered)
+        y = _bn_or_stock(z, bn, pool)
+        _, save_mean, save_invstd = torch.miopen_batch_norm(z, bn.weight, bn.bias, rm0.clone(), rv0.clone(), True,
+                                                            bn.momentum, bn.eps)
+        mine_x, mine_y, mine_mean, mine_invstd = _conv1_raw(x, conv.weight, bn.weight, bn.bias, rm0, rv0, bn.momentum, bn.eps,
+                                                            pool is not None, True)
+        names = ("x", "y", "running_mean", "running_var", "save_mean", "save_invstd")
+        pairs = ((mine_x, z), (mine_y, y), (rm0, bn.running_mean), (rv0, bn.running_var), (mine_mean, save_mean),
+                 (mine_invstd, save_invstd))
+        flags = torch.stack([_differs(a, b) for a, b in pairs]).tolist()
+    first = next((n for n, f in zip(names, flags) if f), None)
+    B, _, H, W = x.shape
+    _exact.setdefault(key, {"verified": False, "first_difference": None, "geometry": exact_geometry(B, H, W, 64)})["conv1"] = {
+        "verified": first is None, "first_difference": first}
+    if first is not None:
+        warnings.warn("encoder: the one-pass first convolution does not reproduce the stock kernels for B=%d H=%d W=%d pool=%d "
+                      "(%s differs); this shape stays on the stock kernels" % (B, H, W, int(pool is not None), first))
+    return y
+
+
+def _conv1_or_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+    B, _, H, W = x.shape
+    key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), B, 64, H, W, pool is not None)
+    state = (_exact.get(key) or {}).get("conv1")
+    if state is None:
+        if torch.cuda.is_current_stream_capturing():
+            return _conv1_stock(x, conv, bn, pool)
+        return _verify_conv1(x, conv, bn, pool, key)
+    return bn_exact(x, bn, pool is not None, conv=conv) if state["verified"] else _conv1_stock(x, conv, bn, pool)
+
+
+def conv1_bn_exact_or_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+    """relu([max_pool2d](bn(conv2d(x)))) of the encoder's first group, the convolution without its bias, with the stock kernels'
+    bits; bn_exact_or_stock's contract with the convolution inside it: through the one-pass route (bn_exact with conv) for a
+    (device, B, H, W, pool) that was compared with the stock convolution and chain once in this process and found equal -- the
+    convolution output, y, both running statistics and both saved statistics, element for element, NaNs in place --, through
+    the stock kernels the first time (the comparison itself; not while the stream is capturing) and for good after a
+    difference, which is reported once.  The caller has checked conv1_modules_fusable."""
+    return bn_exact_or_stock(x, bn, pool, conv=conv)

@@ -91,6 +91,10 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
       shape whose first call in this process, which runs the stock chain, found the two equal in every bit
       (``encoder.bn_exact_or_stock``, ``encoder.exact_report()``); ``VQA_ENCODER_EXACT_BN=0`` turns it off.  The frozen
       convolution bias stays the separate ``running_mean.add_`` it is on the stock route;
+    * by default too, the FIRST group, where it is the VGG's 3 -> 64 channel 3x3 convolution on a channels_last image with
+      channels_last weights, runs the convolution itself in the kernel that sums the statistics, in the stock convolution's
+      arithmetic (``encoder.conv1_bn_exact_or_stock``): no zero fill, no separate statistics pass.  Verified per shape against the
+      stock convolution and chain like the route above, or not used; ``VQA_ENCODER_EXACT_CONV1=0`` turns it off;
     * with ``VQA_ENCODER_FUSED=1`` a whole ``Conv2d -> BatchNorm2d -> ReLU [-> MaxPool2d(2, 2)]`` group runs everything after the
       convolution in two passes over its output (``encoder.bn_relu_pool``), the bias fold included.  Its statistics are summed
       in double, in another order than MIOpen's: values agree with the stock chain to rounding, not bit for bit.
@@ -112,6 +116,13 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
         exact = group and encoder.exact_modules_fusable(m, nxt, pool, x)
         if (isinstance(m, nn.Conv2d) and (fuse or exact or (m.bias is not None and not m.bias.requires_grad))
                 and m.padding_mode == "zeros" and isinstance(nxt, nn.BatchNorm2d) and nxt.training and nxt.momentum is not None):
+            if exact and i == 0 and encoder.conv1_modules_fusable(m, nxt, pool, x):
+                x = encoder.conv1_bn_exact_or_stock(x, m, nxt, pool)
+                if m.bias is not None:
+                    with torch.no_grad():
+                        nxt.running_mean.add_(m.bias.to(nxt.running_mean.dtype), alpha=nxt.momentum)
+                i += 3 if pool is None else 4
+                continue
             x = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
             if fuse and encoder.output_fusable(x, nxt, pool is not None):
                 x = encoder.bn_relu_pool(x, nxt, conv_bias=m.bias, pool=pool is not None)
