@@ -29,6 +29,12 @@
  *              location-major [B][N][d]: (v_sB >= N*d, v_sN = d, v_sD = 1) -- what a channels_last encoder
  *                             emits (x_img is then contiguous);
  *            any other strides take the general-shape kernels.  dV is described the same way.
+ *            Alignment: the fused kernels read V in 16-byte units, so they also want every sample to start
+ *            on a 16-byte boundary -- V itself, and v_sB a multiple of 4 floats.  A V that is not (a view
+ *            that starts at an odd element, a sample pitch of N*d + 1) is a general-shape call under
+ *            COATTN_IMPL_AUTO and is refused (-1, nothing launched) under COATTN_IMPL_FUSED, by the forward
+ *            and the backward alike.  The general-shape kernels take any 4-byte aligned V.  Q[l] may sit at
+ *            any 4-byte aligned address on either path.
  *   Q[l]   : [B, T, d]  contiguous, l = 0..L-1 (word, phrase, sentence; model.py:298).
  *   W_v,W_q: [d, d] (nn.Linear.weight, out x in); b_v,b_q: [d]; w_v,w_q: [d]; c_v,c_q: [1]
  *            (model.py:350-354).  W_b (model.py:347) is dead in the reference; it is read only under

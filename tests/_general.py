@@ -28,7 +28,13 @@ def _dev():
 def layout_geometry(B, N, d, layout):
     """(floats of the buffer, (sB, sN, sD)) of the [B,N,d] view a layout hands to the C-ABI.  cm: [B,d,N]; lm: [B,N,d];
     strided: location-major rows padded to sN = d + 4, every sample padded by 8 floats (neither dense layout);
-    sd2: every second float of a [B,N,2d] buffer (sD = 2: neither axis contiguous)."""
+    sd2: every second float of a [B,N,2d] buffer (sD = 2: neither axis contiguous).  Not in LAYOUTS (tests/_fused.py): the
+    dense layouts with a gap behind every sample -- lm_gap (sB = N d + 64), lm_gap4 (+ 4), lm_gap1 (+ 1: samples off the
+    16-byte boundary), cm_gap (sB = d N + 64), cm_gap1 (+ 1)."""
+    gaps = {"lm_gap": 64, "lm_gap4": 4, "lm_gap1": 1, "cm_gap": 64, "cm_gap1": 1}
+    if layout in gaps:
+        sB = N * d + gaps[layout]
+        return B * sB, ((sB, d, 1) if layout.startswith("lm") else (sB, 1, N))
     if layout == "lm":
         return B * N * d, (N * d, d, 1)
     if layout == "cm":
@@ -56,12 +62,13 @@ class Arena:
             self.body.fill_(fill)
         self.view = None
 
-    def placed(self, B, N, d, layout, values=None):
-        """The [B,N,d] view of `layout` in the body: `values`, or NaN; the body's other cells keep the marker."""
+    def placed(self, B, N, d, layout, values=None, offset=0):
+        """The [B,N,d] view of `layout` in the body, `offset` floats behind its start: `values`, or NaN; the body's other
+        cells keep the marker."""
         n, strides = layout_geometry(B, N, d, layout)
-        assert n == self.n
+        assert n + offset == self.n
         self.body.view(torch.int32).fill_(GUARD_BITS)
-        self.view = torch.as_strided(self.body, (B, N, d), strides, self.body.storage_offset())
+        self.view = torch.as_strided(self.body, (B, N, d), strides, self.body.storage_offset() + offset)
         if values is not None:
             self.view.copy_(values)
         else:
@@ -95,8 +102,20 @@ def state_views(saved, B, N, T, d, L):
     return out
 
 
+def profile_marks(lib):
+    """coattn_profile_end: the launch marks recorded since coattn_profile_begin on this thread."""
+    us = (C.c_float * 48)()
+    names = C.create_string_buffer(2048)
+    n = lib.coattn_profile_end(us, names, 2048, 48)
+    assert n >= 0, lib.coattn_last_error().decode()
+    torch.cuda.synchronize()
+    marks = names.value.decode().split("\n") if n else []
+    assert len(marks) == n
+    return marks
+
+
 def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=None, layout="cm", dv_layout="same",
-        flags=_lib.IMPL_GENERAL, accumulate=0, grads_init=None):
+        flags=_lib.IMPL_GENERAL, accumulate=0, grads_init=None, v_off=0, q_off=0, attn=False, profile=False, allow_nan=False):
     """One forward (+ backward when gv is given) through the C-ABI.  V [B,d,N] values (as oracle.coattn_oracle makes them),
     handed over in the physical `layout` (LAYOUTS); family (FAMILIES): coattn_forward / _backward ("plain"), their _len
     forms ("len", with `lens`), coattn_forward_maps / _backward_maps ("maps", "maps_len": g_av / g_aq may be given) or
@@ -107,7 +126,11 @@ def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=N
     coattn_workspace_bytes or the shape gives, NaN-filled, inside an Arena; after the calls every margin holds the marker, a
     padded dV keeps every cell outside its view, and no output cell is NaN.  Returns fp32 results on the host: v, q, a_v,
     a_q, C (from the state, not for "infer"), and with a backward dV_phys [B,d,N] (None without dV), dQ [L,B,T,d] and
-    d<name>."""
+    d<name>.
+    v_off / q_off: floats (0 or 1) by which the V view / every Q_l is moved off its 16-byte aligned start.  attn (families
+    "plain" and "len"): coattn_attention_forward(_len) follows on the same `saved` with fresh NaN-filled v, q and workspace
+    arenas; v, q are then that call's and "v_fwd", "q_fwd" the forward's.  profile: the forward call(s) run between
+    coattn_profile_begin / _end and "marks" is the list of launch marks.  allow_nan: outputs may hold NaN (poisoned inputs)."""
     lib = _lib.load()
     DEV = _dev()
     assert family in FAMILIES
@@ -120,8 +143,12 @@ def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=N
     if dv_layout == "same":
         dv_layout = layout
     n_v, vstr = layout_geometry(B, N, d, layout)
-    Vd = Arena(n_v, fill=None).placed(B, N, d, layout, V.float().permute(0, 2, 1).to(DEV))
+    Vd = Arena(n_v + v_off, fill=None).placed(B, N, d, layout, V.float().permute(0, 2, 1).to(DEV), offset=v_off)
+    assert Vd.data_ptr() % 16 == 4 * v_off
     Qd = [q.float().to(DEV).contiguous() for q in Qs]
+    if q_off:
+        Qd = [torch.cat([q.new_zeros(q_off), q.reshape(-1)])[q_off:].view(q.shape) for q in Qd]
+        assert all(q.data_ptr() % 16 == 4 * q_off for q in Qd)
     ps = [P[k].float().to(DEV).contiguous() for k in names]
     p = _lib.Params(*[t.data_ptr() for t in ps])
     sb, fb, bb = (C.c_size_t() for _ in range(3))
@@ -155,11 +182,24 @@ def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=N
         else:
             symbol = "coattn_forward" + sfx
     call = _lib.bind(symbol, **fwd)
+    if profile:
+        torch.cuda.synchronize()
+        _lib.check(lib.coattn_profile_begin(st), "coattn_profile_begin")
     rc = call.fn(*call)
     assert rc == 0, (symbol, lib.coattn_last_error())
-    torch.cuda.synchronize()
     out = {"v": v, "q": q}
     written = ["v", "q"]
+    if attn:
+        assert family in ("plain", "len")
+        for k, n in (("ws_attn", fb.value // 4), ("v_attn", L * B * d), ("q_attn", L * B * d)):
+            g[k] = Arena(n)
+        out.update(v_fwd=v, q_fwd=q, v=g["v_attn"].body.view(L, B, d), q=g["q_attn"].body.view(L, B, d))
+        written += ["v_fwd", "q_fwd"]
+        call = _lib.bind("coattn_attention_forward" + sfx, **dict(fwd, v_out=out["v"], q_out=out["q"], ws=g["ws_attn"].body))
+        rc = call.fn(*call)
+        assert rc == 0, (call.name, lib.coattn_last_error())
+    marks = profile_marks(lib) if profile else None
+    torch.cuda.synchronize()
     if family == "infer" or family.startswith("maps"):
         out.update(a_v=a_v, a_q=a_q)
         written += ["a_v", "a_q"]
@@ -219,8 +259,11 @@ def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=N
     for k, a in g.items():
         a.check(k)
     for k in written:
-        assert not bool(torch.isnan(out[k]).any()), "%s: a cell is NaN (left unwritten, or computed from one that was)" % k
-    return {k: (x.detach().cpu().contiguous() if x is not None else None) for k, x in out.items()}
+        assert allow_nan or not bool(torch.isnan(out[k]).any()), "%s: a cell is NaN (left unwritten, or computed from one that was)" % k
+    res = {k: (x.detach().cpu().contiguous() if x is not None else None) for k, x in out.items()}
+    if profile:
+        res["marks"] = marks
+    return res
 
 
 # ---- the dispatch rules, restated ------------------------------------------------------------------------------------------
@@ -300,24 +343,26 @@ def mask_rows_grid(R, W):
     return gx, n > gx * 256
 
 
-def _gemm_w(M, K, batch, a_sm=0, a_sz=0, a_sk=0, a_mdiv=0, a_sdiv=0):
-    """gemm_w_supported (exact mode, aligned pointers, weight image below 1 GiB)."""
-    ok = M >= 128 and K >= 32 and K % 32 == 0 and a_sz % 4 == 0 and 1 <= batch <= 8
+def _gemm_w(M, K, batch, a_sm=0, a_sz=0, a_sk=0, a_mdiv=0, a_sdiv=0, f16=False):
+    """gemm_w_supported (aligned pointers, weight image below 1 GiB).  f16: the tolerance mode's two FP16 pieces, whose range
+    report lives in this kernel -- any M runs on it then; otherwise M >= 128."""
+    ok = M >= (1 if f16 else 128) and K >= 32 and K % 32 == 0 and a_sz % 4 == 0 and 1 <= batch <= 8
     if a_sk:
         return (ok and a_mdiv > 0 and _al4(a_mdiv, a_sk, a_sdiv, M)
                 and (((M - 1) // a_mdiv + 1) * a_sdiv + K * a_sk) * 4 < 0x40000000)
     return ok and a_sm % 4 == 0 and (M * a_sm + K) * 4 < 0x40000000
 
 
-def projection_jobs(B, N, T, d, L, strides):
-    """api.hip projection_jobs: (v_w, q_w), which projections run on the pre-split-weight kernel."""
+def projection_jobs(B, N, T, d, L, strides, f16=False, v_aligned=True, q_aligned=True):
+    """api.hip projection_jobs: (v_w, q_w), which projections run on the pre-split-weight kernel.  f16: asked for two FP16
+    pieces (want_f16); v_aligned / q_aligned: V / every Q_l on a 16-byte boundary (gemm_w_supported's `pal`)."""
     sB, sN, sD = strides
     v_w = False
     if sD == 1 and sB == N * sN and sN < (1 << 24):
-        v_w = _gemm_w(B * N, d, 1, a_sm=sN)
+        v_w = _gemm_w(B * N, d, 1, a_sm=sN, f16=f16)
     elif sN == 1 and sD < (1 << 24):
-        v_w = _gemm_w(B * N, d, 1, a_sk=sD, a_mdiv=N, a_sdiv=sB)
-    return v_w, _gemm_w(B * T, d, L, a_sm=d)
+        v_w = _gemm_w(B * N, d, 1, a_sk=sD, a_mdiv=N, a_sdiv=sB, f16=f16)
+    return v_w and v_aligned, _gemm_w(B * T, d, L, a_sm=d, f16=f16) and q_aligned
 
 
 def paths(B, N, T, d, L, layout="cm", dv_layout="same", flags=_lib.IMPL_GENERAL, keep=True):

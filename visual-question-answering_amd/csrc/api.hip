@@ -731,12 +731,17 @@ int backward_general(const Ctx& c) {
   return 0;
 }
 
-int pick_impl(int flags, int B, int N, int T, int d, int L, const VLayout& vl, int* fused) {
+// The fused forward reads V in 16-byte units (LDS-DMA in phase 1, the attended-feature passes of location-major features): every
+// sample must start on a 16-byte boundary -- the base pointer, and v_sB a multiple of 4 floats (include/coattn.h "Layouts").
+// Anything else is a general-shape call, in the forward and the backward alike: both ask here with the same V, so a state is
+// always read by the path that wrote it.
+int pick_impl(int flags, const void* V, int B, int N, int T, int d, int L, const VLayout& vl, int* fused) {
   const int sel = flags & 3;
-  const int ok = fused_supported(B, N, T, d, L) && fused_layout_ok(vl, N, d);
+  const bool aligned = (((uintptr_t)V) & 15) == 0 && (vl.sB & 3) == 0;
+  const int ok = fused_supported(B, N, T, d, L) && fused_layout_ok(vl, N, d) && aligned;
   if (sel == COATTN_IMPL_FUSED) {
-    CA_CHECK_ARG(ok, "fused kernels do not support B=%d N=%d T=%d d=%d L=%d with V strides (%ld, %ld, %ld)", B, N, T, d, L,
-                 vl.sB, vl.sN, vl.sD);
+    CA_CHECK_ARG(ok, "fused kernels do not support B=%d N=%d T=%d d=%d L=%d with V strides (%ld, %ld, %ld)%s", B, N, T, d, L,
+                 vl.sB, vl.sN, vl.sD, aligned ? "" : ": V and v_sB must be 16-byte aligned");
     *fused = 1;
   } else if (sel == COATTN_IMPL_GENERAL) {
     *fused = 0;
@@ -800,7 +805,7 @@ static int forward_impl(Ctx c, void* ws, int dtype, int flags, bool do_proj) {
   const bool bil = bilinear(flags);
   CA_TRY(check_bilinear(flags, p, nullptr));
   int fused = 0;
-  CA_TRY(pick_impl(flags, B, N, T, d, L, c.vl, &fused));
+  CA_TRY(pick_impl(flags, c.V, B, N, T, d, L, c.vl, &fused));
   c.keep = c.state != nullptr;
   if (!c.keep) c.state = (float*)ws;                  // inference: state lives in the workspace
   c.tail = (float*)ws + saved_floats(B, N, T, d, L, bil);
@@ -894,7 +899,7 @@ static int backward_impl(Ctx c, int dtype, int flags) {
                "backward: null parameter-gradient pointer");
   CA_TRY(check_bilinear(flags, p, pg));
   int fused = 0;
-  CA_TRY(pick_impl(flags, B, N, T, d, L, c.vl, &fused));
+  CA_TRY(pick_impl(flags, c.V, B, N, T, d, L, c.vl, &fused));
   call_modes(c, flags, fused);
   BilBwd bb = {};
   if (bilinear(flags)) {                              // K from the forward's `saved`, dK into the workspace
