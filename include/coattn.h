@@ -654,6 +654,52 @@ int coattn_conv1_bn_exact_forward(const void* image, const void* weight, const v
 int coattn_conv1_probe(const void* image, const void* weight, void* x, void* ws, int B, int H, int W, int order, int step,
                        int halves, int skip, void* stream);
 
+/* ---- the sentence LSTM of the question hierarchy (v0.17.0; csrc/lstm.hip) ----
+ * Reference model.py:286-296 -- pack_padded_sequence -> nn.LSTM (one layer, one direction, zero initial state) ->
+ * pad_packed_sequence -- restated without packing, lengths read on the device:
+ *   gates_t = X[:,t] W_ih^T + b_ih + h_{t-1} W_hh^T + b_hh          (gate order i, f, g, o: nn.LSTM's storage)
+ *   c_t = sigmoid(f) c_{t-1} + sigmoid(i) tanh(g)      h_t = sigmoid(o) tanh(c_t)
+ *   out[b,t,:]      = t < len_b ? h_t[b]   : 0         (selected, not multiplied: exact zeros)
+ *   x_masked[b,t,:] = t < len_b ? X[b,t,:] : 0         (the phrase level as pad_packed_sequence returns it)
+ * Exact fp32 only (the f32 MFMA and the three-piece projections): `flags` must be 0, any precision flag (COATTN_FLAG_FAST16,
+ * COATTN_FLAG_BF16_PROJ, ...) is refused with -1.
+ *   X            : fp32 [B][T][E], read only.  No output or gradient depends on the rows t >= len_b, for any values there of
+ *                  magnitude up to 3.38e38 (bf16's largest finite value), the range of the projections' bf16 pieces that
+ *                  live rows have too: dW_ih = dgates^T X multiplies those rows by the exact zeros of dgates, and a larger
+ *                  value rounds to infinity in its leading piece (0 * inf = NaN in dW_ih).
+ *   len          : int32 [B] on the device.  Values outside [1, T] are clamped on the device (0 acts as 1, T + 5 as T), as
+ *                  in the *_len entry points; no order is required and nothing reads them on the host.  THE BACKWARD MUST BE
+ *                  GIVEN THE SAME VALUES AS THE FORWARD that wrote `saved` (the saved state holds zeros past them).
+ *   p            : W_ih [4H][E], W_hh [4H][H], b_ih [4H], b_hh [4H] as nn.LSTM stores weight_ih_l0 ... bias_hh_l0
+ *   out          : fp32 [B][T][H], written
+ *   x_masked     : fp32 [B][T][E], written; may be NULL
+ *   saved        : `saved` bytes of the workspace size call, written for the backward: the activated gates [B][T][4H], the
+ *                  cell state [B][T][H] and h_prev [B][T][H] (h_prev[b][t] = out[b][t-1], zeros at t = 0), zeros on the rows
+ *                  past a length.  NULL: forward only (`out` has the same bits).
+ *   ws           : ws_fwd / ws_bwd bytes, contents need no initialisation.  The backward reads nothing of the forward's.
+ * Backward: g_out [B][T][H] and g_xmasked [B][T][E] (may be NULL) are the gradients at out and x_masked; their rows
+ * t >= len_b are not read for their values.  dX [B][T][E] (may be NULL: the product is skipped, the parameter gradients keep
+ * their bits) = the LSTM's gradient + g_xmasked on live rows, exact zeros on the others.  pg: dW_ih, dW_hh, db_ih, db_hh
+ * (db_ih = db_hh = the column sums of the gate gradients); accumulate bit 0 adds onto the four.  The backward reads X, len, p,
+ * saved and the two incoming gradients, nothing else.  `out` is NOT read -- h_{t-1} of every row is h_prev in `saved` -- and
+ * is reserved: it may be NULL (it is only checked for alignment), and a caller need not keep the forward's out for this call.
+ * One launch per time step in each direction, chained on the stream; every launch is deterministic (fixed-order sums, no
+ * float atomics): same inputs, same bits.  A non-finite value in a live row of one sample reaches that sample's rows of out
+ * and dX only (and the parameter gradients).
+ * Supported (the query returns 1): dtype COATTN_F32, B >= 1, 1 <= T <= 64, E and H multiples of 32 in 32 .. 2048, and
+ * B T 4 max(E, H) < 2^31 (32-bit element offsets of the GEMM layer).  Every buffer 16-byte aligned.
+ * Argument errors (a NULL required pointer, a non-positive size, flags != 0, another dtype, an unsupported shape, a
+ * misaligned buffer): -1 with a coattn_last_error message before any device work.  No allocation, no synchronisation. */
+typedef struct coattn_lstm_params      { const void *w_ih, *w_hh, *b_ih, *b_hh; } coattn_lstm_params;
+typedef struct coattn_lstm_param_grads { void *w_ih, *w_hh, *b_ih, *b_hh; } coattn_lstm_param_grads;
+int coattn_lstm_supported(int B, int T, int E, int H, int dtype);
+int coattn_lstm_workspace_bytes(int B, int T, int E, int H, int dtype, size_t* saved, size_t* ws_fwd, size_t* ws_bwd);
+int coattn_lstm_forward(const void* X, const int32_t* len, const coattn_lstm_params* p, void* out, void* x_masked,
+                        void* saved, void* ws, int B, int T, int E, int H, int dtype, int flags, void* stream);
+int coattn_lstm_backward(const void* X, const int32_t* len, const coattn_lstm_params* p, const void* out, const void* saved,
+                         const void* g_out, const void* g_xmasked, void* dX, const coattn_lstm_param_grads* pg,
+                         int accumulate, void* ws, int B, int T, int E, int H, int dtype, int flags, void* stream);
+
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 
 /* Strided, batched fp32 GEMM on the f32 MFMA:

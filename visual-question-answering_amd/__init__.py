@@ -13,7 +13,8 @@ from .alternating import AlternatingCoAttention  # noqa: F401
 from .loss import CrossEntropyLoss, SoftTargetLoss, cross_entropy, soft_target_loss, vqa_score  # noqa: F401
 from .head import answer_head  # noqa: F401
 from .optim import HipAdam  # noqa: F401
+from .lstm import sentence_lstm  # noqa: F401
 
 __all__ = ["ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
-           "SoftTargetLoss", "vqa_score", "HipAdam", "_lib",
+           "SoftTargetLoss", "vqa_score", "HipAdam", "sentence_lstm", "_lib",
            "check_range", "RangeError"]

@@ -28,7 +28,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_bn_supported", "coattn_bn_workspace_bytes", "coattn_bn_relu_pool_forward", "coattn_relu_pool_forward",
            "coattn_bn_exact_geometry", "coattn_bn_exact_workspace_bytes", "coattn_bn_exact_forward",
            "coattn_conv1_bn_exact_supported", "coattn_conv1_bn_exact_workspace_bytes", "coattn_conv1_bn_exact_forward",
-           "coattn_conv1_probe")
+           "coattn_conv1_probe",
+           "coattn_lstm_supported", "coattn_lstm_workspace_bytes", "coattn_lstm_forward", "coattn_lstm_backward")
 
 F32 = 0
 BF16 = 1                  # storage type of coattn_features_native's input
@@ -98,6 +99,15 @@ class HeadParamGrads(C.Structure):
 class AdamTensor(C.Structure):
     # one entry of the optimiser step's list (v0.13.0): parameter, gradient, exp_avg, exp_avg_sq, elements
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+
+
+class LstmParams(C.Structure):
+    # the sentence LSTM (v0.17.0): nn.LSTM's weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+class LstmParamGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
 
 
 class GemmDesc(C.Structure):
@@ -331,6 +341,15 @@ def load() -> C.CDLL:
     lib.coattn_conv1_bn_exact_forward.argtypes = ([C.c_void_p] * 6 + [C.c_double] * 2 + [C.c_void_p] * 5 + [C.c_int] * 7
                                                   + [C.c_void_p])
     lib.coattn_conv1_probe.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]
+    # the sentence LSTM (v0.17.0): (X, len, p, out, x_masked, saved, ws, B, T, E, H, dtype, flags, stream) and
+    # (X, len, p, out, saved, g_out, g_xmasked, dX, pg, accumulate, ws, B, T, E, H, dtype, flags, stream)
+    lib.coattn_lstm_supported.argtypes = [C.c_int] * 5
+    lib.coattn_lstm_workspace_bytes.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_size_t)] * 3
+    lib.coattn_lstm_forward.argtypes = ([C.c_void_p] * 2 + [C.POINTER(LstmParams)] + [C.c_void_p] * 4 + [C.c_int] * 6
+                                        + [C.c_void_p])
+    lib.coattn_lstm_backward.argtypes = ([C.c_void_p] * 2 + [C.POINTER(LstmParams)] + [C.c_void_p] * 5
+                                         + [C.POINTER(LstmParamGrads)] + [C.c_int] + [C.c_void_p] + [C.c_int] * 6
+                                         + [C.c_void_p])
     _lib = lib
     return lib
 
@@ -463,6 +482,11 @@ def workspace_bytes(B, N, T, d, L, flags=0):
 def alt_workspace_bytes(B, N, T, d, L):
     """(saved, ws_fwd, ws_bwd) in bytes of the alternating co-attention (exact mode)."""
     return _bytes("coattn_alt_workspace_bytes", 3, B, N, T, d, L, F32, 0)
+
+
+def lstm_workspace_bytes(B, T, E, H):
+    """(saved, ws_fwd, ws_bwd) in bytes of the sentence LSTM."""
+    return _bytes("coattn_lstm_workspace_bytes", 3, B, T, E, H, F32)
 
 
 def head_workspace_bytes(B, d, mlp, K):

@@ -241,9 +241,36 @@ class PhraseConvPool(nn.Module):
         return self.max_pool(grams).squeeze(dim=3)                               # [B, T, E]
 
 
+SENTENCE_IMPLS = ("stock", "hip")
+
+
+def _hip_sentence(enc, phrases) -> bool:
+    """Does this forward of a question encoder take the HIP sentence LSTM on `phrases`, the LSTM's input?
+    ``enc.sentence_impl``: "stock" (the default: pack_padded_sequence -> nn.LSTM -> pad_packed_sequence) or "hip"
+    (lstm.sentence_lstm on the nn.LSTM's own parameters: a CUDA input of a supported shape that is fp32, or any floating
+    type under CUDA autocast, where sentence_lstm is an fp32 island that casts it -- the BERT encoder's bf16 word level;
+    CPU tensors, other shapes and other dtypes outside autocast take the stock lines)."""
+    impl = enc.sentence_impl
+    if impl not in SENTENCE_IMPLS:
+        raise ValueError("sentence_impl must be one of %s, got %r" % (SENTENCE_IMPLS, impl))
+    if impl != "hip" or not phrases.is_cuda:
+        return False
+    if phrases.dtype != torch.float32 and not (phrases.is_floating_point() and torch.is_autocast_enabled("cuda")):
+        return False
+    from . import lstm
+    B, T, E = phrases.shape
+    return lstm.supported(B, T, E, enc.sentence_lstm.hidden_size)
+
+
+def _hip_sentence_lstm(rnn, phrases, x_lens):
+    from .lstm import sentence_lstm
+    return sentence_lstm(phrases, x_lens, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
+
+
 class QuestionCoAttentionEncoder(nn.Module):
     """word (embedding) / phrase (n-gram conv + pool) / sentence (LSTM) features, each [B,T,hidden];
-    rows past a question's length are exact zeros at all three levels (padding_idx=0, packed LSTM)."""
+    rows past a question's length are exact zeros at all three levels (padding_idx=0, packed LSTM).
+    ``sentence_impl``: "stock" (default) or "hip" (`_hip_sentence`); parameters and state_dict are the same either way."""
 
     def __init__(self, vocab_size, word_emb_dim, hidden_dim):
         super().__init__()
@@ -251,12 +278,17 @@ class QuestionCoAttentionEncoder(nn.Module):
         self.word_embedding = nn.Embedding(vocab_size, word_emb_dim, padding_idx=0)
         self.phrase_conv_pool = PhraseConvPool(word_emb_dim)
         self.sentence_lstm = nn.LSTM(word_emb_dim, hidden_dim)
+        self.sentence_impl = "stock"
 
     def forward(self, x, x_lens):
         T = x.shape[1]
-        lens = x_lens.cpu() if torch.is_tensor(x_lens) else x_lens    # pack_padded_sequence wants CPU lengths
         words = self.word_embedding(x)
-        phrases = pack_padded_sequence(self.phrase_conv_pool(words), lens, batch_first=True)
+        phrases = self.phrase_conv_pool(words)
+        if _hip_sentence(self, phrases):                              # opt-in: csrc/lstm.hip, lengths stay on the device
+            sentence, phrases = _hip_sentence_lstm(self.sentence_lstm, phrases, x_lens)
+            return words, phrases, sentence
+        lens = x_lens.cpu() if torch.is_tensor(x_lens) else x_lens    # pack_padded_sequence wants CPU lengths
+        phrases = pack_padded_sequence(phrases, lens, batch_first=True)
         sentence, _ = self.sentence_lstm(phrases)
         phrases = pad_packed_sequence(phrases, batch_first=True, total_length=T)[0]
         sentence = pad_packed_sequence(sentence, batch_first=True, total_length=T)[0]
@@ -279,6 +311,7 @@ class QuestionBertCoAttentionEncoder(nn.Module):
         self.word_proj = nn.Linear(bert_dim, hidden_dim)
         self.phrase_conv_pool = PhraseConvPool(hidden_dim)
         self.sentence_lstm = nn.LSTM(hidden_dim, hidden_dim)
+        self.sentence_impl = "stock"                    # as QuestionCoAttentionEncoder.sentence_impl
         self.hidden_dim = hidden_dim
         self.bert.eval()
 
@@ -291,12 +324,16 @@ class QuestionBertCoAttentionEncoder(nn.Module):
 
     def forward(self, x, x_lens):
         T = x.shape[1]
-        lens = x_lens.cpu() if torch.is_tensor(x_lens) else x_lens
         with torch.no_grad():
             tok = self.bert(x)
             tok = tok[0] if isinstance(tok, (tuple, list)) else getattr(tok, "last_hidden_state", tok)
         words = self.word_proj(tok) * (x != 0).unsqueeze(-1).to(tok.dtype)     # zero the pad rows
-        phrases = pack_padded_sequence(self.phrase_conv_pool(words), lens, batch_first=True)
+        phrases = self.phrase_conv_pool(words)
+        if _hip_sentence(self, phrases):                              # (decided on the LSTM's input, fp32 under autocast too)
+            sentence, phrases = _hip_sentence_lstm(self.sentence_lstm, phrases, x_lens)
+            return words, phrases, sentence
+        lens = x_lens.cpu() if torch.is_tensor(x_lens) else x_lens
+        phrases = pack_padded_sequence(phrases, lens, batch_first=True)
         sentence, _ = self.sentence_lstm(phrases)
         phrases = pad_packed_sequence(phrases, batch_first=True, total_length=T)[0]
         sentence = pad_packed_sequence(sentence, batch_first=True, total_length=T)[0]

@@ -163,6 +163,25 @@ def set_affinity(model: nn.Module, affinity: str) -> None:
     co.affinity = affinity
 
 
+SENTENCE_LSTMS = ("stock", "hip")
+
+
+def set_sentence_lstm(model: nn.Module, sentence_lstm: str) -> None:
+    """--sentence_lstm: "stock" (the default: pack_padded_sequence -> nn.LSTM -> pad_packed_sequence) or "hip" (the question
+    encoder's sentence level on lstm.sentence_lstm: same parameters, lengths read on the device).  A module attribute
+    (QuestionCoAttentionEncoder.sentence_impl), not part of the state_dict: a checkpoint does not depend on it.  The models
+    without such an encoder have nothing to switch: asking for "hip" there is an error."""
+    if sentence_lstm not in SENTENCE_LSTMS:
+        raise ValueError("--sentence_lstm must be one of %s, got %r" % (SENTENCE_LSTMS, sentence_lstm))
+    enc = getattr(model, "question_encoder", None)
+    if enc is None or not hasattr(enc, "sentence_impl"):
+        if sentence_lstm != "stock":
+            raise ValueError("--sentence_lstm hip applies to the co-attention models (--model attention*), not to %s"
+                             % type(model).__name__)
+        return
+    enc.sentence_impl = sentence_lstm
+
+
 def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, affinity: str = "reference",
                 co_attention: str = "parallel", **kw) -> nn.Module:
     """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`; affinity: see
@@ -189,6 +208,7 @@ def model_from_args(args):
     model = cfg["model"](cfg["question_params"], cfg["image_params"], K=args.num_cls + 1, **_net_kwargs(co_attention))
     set_question_mask(model, getattr(args, "question_mask", False))
     set_affinity(model, affinity)
+    set_sentence_lstm(model, getattr(args, "sentence_lstm", "stock"))
     return model, cfg
 
 
@@ -426,8 +446,10 @@ class Trainer:
     def __init__(self, model: nn.Module, lr: float = 1e-4, device=None, opt_lvl: int = 0,
                  bucket_mb: float = 16.0, encoder_runahead: bool = True, graph: bool = False, static_hot_path: bool = True,
                  precision: str = "exact", loss: str = "ce", optimizer: str = "torch", weight_decay: float = 0.0,
-                 clip_grad_norm=None):
+                 clip_grad_norm=None, sentence_lstm=None):
         check_loss(loss)
+        if sentence_lstm is not None:                            # "stock" | "hip" (set_sentence_lstm); None: leave the model's
+            set_sentence_lstm(model, sentence_lstm)
         check_optimizer(optimizer, weight_decay, clip_grad_norm)
         self.loss = loss                                         # "ce": int64 labels; "soft_ce" | "bce": step(..., targets=...)
         self.device = device or next(model.parameters()).device
@@ -718,6 +740,11 @@ def build_parser():
                          "'alternating' = three chained guided-attention steps (AlternatingCoAttention; its own state_dict "
                          "keys).  Co-attention models only, exact mode only: not with --affinity bilinear, --opt_lvl >= 1 or "
                          "--precision fast")
+    ap.add_argument("--sentence_lstm", default="stock", choices=list(SENTENCE_LSTMS),
+                    help="the question encoder's sentence LSTM: 'stock' = pack_padded_sequence -> nn.LSTM -> "
+                         "pad_packed_sequence as the reference (model.py:286-296); 'hip' = the length-aware HIP forward / "
+                         "backward on the same parameters (exact fp32, no packing, no host read of the lengths).  "
+                         "Co-attention models only; a checkpoint does not depend on it")
     ap.add_argument("--loss", default="ce", choices=list(LOSSES),
                     help="'ce' = the reference's cross entropy on the majority answer; 'soft_ce' / 'bce' = soft cross entropy / "
                          "binary cross entropy with logits on the soft answer targets (up to --num_answers (answer, score) pairs "
@@ -765,7 +792,8 @@ def main(argv=None):
     if cl:
         model.image_encoder.to(memory_format=torch.channels_last)
     trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss,
-                      optimizer=args.optimizer, weight_decay=args.weight_decay, clip_grad_norm=args.clip_grad_norm)
+                      optimizer=args.optimizer, weight_decay=args.weight_decay, clip_grad_norm=args.clip_grad_norm,
+                      sentence_lstm=args.sentence_lstm)
     n_ans = args.num_answers if args.loss != "ce" else 0
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
