@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -699,6 +699,47 @@ int coattn_lstm_forward(const void* X, const int32_t* len, const coattn_lstm_par
 int coattn_lstm_backward(const void* X, const int32_t* len, const coattn_lstm_params* p, const void* out, const void* saved,
                          const void* g_out, const void* g_xmasked, void* dX, const coattn_lstm_param_grads* pg,
                          int accumulate, void* ws, int B, int T, int E, int H, int dtype, int flags, void* stream);
+
+/* ---- the word level of the question hierarchy: embedding gather and its dense gradient (v0.18.0; csrc/embedding.hip) ----
+ * Reference model.py: nn.Embedding(V, E, padding_idx) over the question's token ids, in front of the phrase and sentence levels.
+ *   ids          : n = B T token ids, contiguous, int32 (ids_dtype = COATTN_IDS_I32) or int64 (COATTN_IDS_I64, a LongTensor as
+ *                  it is: all 64 bits are compared, no conversion launch); aligned to their element size; read on the device only
+ *   W, dW        : fp32 [V][E];  out, g_out : fp32 [n][E];  all contiguous and 16-byte aligned
+ *   padding_idx  : -1 = none, else in [0, V)
+ *   bad_ids      : one int32 on the device, may be NULL; the forward ADDS to it (an integer atomic: the count is exact), the
+ *                  caller zeroes it
+ *   ws           : reserved, may be NULL: coattn_embedding_workspace_bytes reports ws_bwd = 0 (the row owners index the ids in
+ *                  LDS; nothing the library keeps grows with V E, and nothing it would keep holds anything but integers)
+ * Exact fp32 only: dtype must be COATTN_F32 and `flags` 0; any precision flag is refused with -1.
+ * Forward (one launch, 16-byte accesses): out[i] = W[ids[i]] bit for bit -- row padding_idx too, as it is stored (what the stock
+ * module does).  An id outside [0, V) -- negative, >= V, or an int64 whose low 32 bits alone would be a valid row -- gives a row
+ * of exact +0 and adds 1 to *bad_ids; it is never used as an index, and no address outside W is formed.
+ * Backward (ONE launch: no sort, no fill or memset of dW, no float atomics, no host read): dW[v] = sum of g_out[i] over the
+ * positions i with ids[i] == v, for every v other than padding_idx.  Positions whose id is padding_idx or outside [0, V) are
+ * left out by selection: their g_out rows are never loaded, so NaN or 1e30 there changes no bit.  Every element of dW is
+ * written exactly once (the caller need not zero it); row padding_idx and every row without an occurrence are exact +0.
+ * accumulate bit 0: dW[v] = dW[v] + sum (one rounding per element) on the rows with an occurrence, the other rows keep their
+ * bits (they are not written).
+ * SUMMATION ORDER, a pure function of ids (never of scheduling): let p_0 < p_1 < ... < p_{m-1} be the flat positions of token
+ * v (padding and out-of-range positions excluded) and c = COATTN_EMBEDDING_CHUNK.  Chunk k holds the occurrences k c ..
+ * min(m, (k+1) c) - 1 and is summed serially from its first element: s_k = ((g[p_kc] + g[p_kc+1]) + g[p_kc+2]) + ... .  The chunk
+ * sums are combined left to right from the first: dW[v] = ((s_0 + s_1) + s_2) + ... .  One occurrence is therefore a copy (the
+ * sign of a zero included); a token that fills a batch costs m / c + c dependent additions, not m.
+ * A non-finite value in a live g_out row reaches exactly its token's row of dW.  Same inputs, same bits.
+ * Supported (the query returns 1): dtype COATTN_F32, 1 <= n <= 65,536 (the positions are held as 16 bits in LDS), 1 <= V <=
+ * 16,777,216 (2^24), E a multiple of 4 in 4 .. 2048.  Offsets into W, out, g_out and dW are 64-bit.
+ * Argument errors (a NULL required pointer, a non-positive size, flags != 0, another dtype or ids_dtype, an unsupported shape,
+ * padding_idx outside [-1, V), a misaligned buffer): -1 with a coattn_last_error message before any device work.  No
+ * allocation, no synchronisation. */
+#define COATTN_IDS_I32 0
+#define COATTN_IDS_I64 1
+#define COATTN_EMBEDDING_CHUNK 32
+int coattn_embedding_supported(long long n, long long V, int E, int dtype);
+int coattn_embedding_workspace_bytes(long long n, long long V, int E, int dtype, size_t* ws_bwd);
+int coattn_embedding_forward(const void* ids, int ids_dtype, const void* W, void* out, int32_t* bad_ids, long long n, long long V,
+                             int E, long long padding_idx, int dtype, int flags, void* stream);
+int coattn_embedding_backward(const void* ids, int ids_dtype, const void* g_out, void* dW, void* ws, long long n, long long V,
+                              int E, long long padding_idx, int accumulate, int dtype, int flags, void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

@@ -14,7 +14,9 @@ from .loss import CrossEntropyLoss, SoftTargetLoss, cross_entropy, soft_target_l
 from .head import answer_head  # noqa: F401
 from .optim import HipAdam  # noqa: F401
 from .lstm import sentence_lstm  # noqa: F401
+from . import embedding  # noqa: F401
+from .embedding import word_embedding  # noqa: F401
 
-__all__ = ["ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
+__all__ = ["word_embedding", "embedding","ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
            "SoftTargetLoss", "vqa_score", "HipAdam", "sentence_lstm", "_lib",
            "check_range", "RangeError"]

@@ -29,9 +29,12 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_bn_exact_geometry", "coattn_bn_exact_workspace_bytes", "coattn_bn_exact_forward",
            "coattn_conv1_bn_exact_supported", "coattn_conv1_bn_exact_workspace_bytes", "coattn_conv1_bn_exact_forward",
            "coattn_conv1_probe",
-           "coattn_lstm_supported", "coattn_lstm_workspace_bytes", "coattn_lstm_forward", "coattn_lstm_backward")
+           "coattn_lstm_supported", "coattn_lstm_workspace_bytes", "coattn_lstm_forward", "coattn_lstm_backward",
+           "coattn_embedding_supported", "coattn_embedding_workspace_bytes", "coattn_embedding_forward",
+           "coattn_embedding_backward")
 
 F32 = 0
+IDS_I32, IDS_I64 = 0, 1   # ids_dtype of the word embedding calls (v0.18.0: COATTN_IDS_*)
 BF16 = 1                  # storage type of coattn_features_native's input
 IMPL_AUTO, IMPL_GENERAL, IMPL_FUSED = 0, 1, 2
 FLAG_BF16_PROJ = 4
@@ -163,9 +166,18 @@ SIGNATURES = {
     "coattn_head_backward": (_HEAD + _void("saved g_loss g_logits") + _ptrs("dv dq") + (("pg", C.POINTER(HeadParamGrads)),)
                              + _int("accumulate") + _void("ws") + _HEAD_DIMS),
 }
-_INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in SIGNATURES.items()}
+# the word embedding (v0.18.0), in the same form; a table of its own: SIGNATURES is the co-attention and head calls
+_EMB_DIMS = _i64("n V") + _int("E") + _i64("padding_idx")
+EMBEDDING_SIGNATURES = {
+    "coattn_embedding_forward": (_void("ids") + _int("ids_dtype") + _void("W out bad_ids") + _EMB_DIMS + _int("dtype flags")
+                                 + _void("stream")),
+    "coattn_embedding_backward": (_void("ids") + _int("ids_dtype") + _void("g_out dW ws") + _EMB_DIMS
+                                  + _int("accumulate dtype flags") + _void("stream")),
+}
+_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES}
+_INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _TABLE.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
-_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq".split())
+_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids".split())
 _DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
 
 
@@ -210,7 +222,7 @@ class Call(tuple):
 
     def replace(self, **kw):
         """The same call with the given arguments replaced (one list copy: cheap enough for every step)."""
-        sig, index, vals = SIGNATURES[self.name], _INDEX[self.name], list(self)
+        sig, index, vals = _TABLE[self.name], _INDEX[self.name], list(self)
         for n, v in kw.items():
             if n not in index:
                 raise TypeError("%s has no argument %r" % (self.name, n))
@@ -233,7 +245,7 @@ def bind(name: str, **kw) -> Call:
     if unknown:
         raise TypeError("%s has no argument %s" % (name, ", ".join(sorted(unknown))))
     vals = []
-    for n, ctype in SIGNATURES[name]:
+    for n, ctype in _TABLE[name]:
         if n in kw:
             vals.append(_as_arg(kw[n], ctype))
         elif n in _DEFAULTS:
@@ -272,7 +284,7 @@ def load() -> C.CDLL:
             raise RuntimeError("libcoattn_hip.so lacks symbol %s" % name)
     lib.coattn_version.restype = C.c_int
     lib.coattn_last_error.restype = C.c_char_p
-    for name, sig in SIGNATURES.items():                 # the co-attention, alternating and head calls: SIGNATURES
+    for name, sig in _TABLE.items():                     # the co-attention, alternating, head and embedding calls: the tables
         getattr(lib, name).argtypes = [ctype for _, ctype in sig]
     lib.coattn_fused_supported.argtypes = [C.c_int] * 6
     lib.coattn_workspace_bytes.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_size_t)] * 3
@@ -350,6 +362,9 @@ def load() -> C.CDLL:
     lib.coattn_lstm_backward.argtypes = ([C.c_void_p] * 2 + [C.POINTER(LstmParams)] + [C.c_void_p] * 5
                                          + [C.POINTER(LstmParamGrads)] + [C.c_int] + [C.c_void_p] + [C.c_int] * 6
                                          + [C.c_void_p])
+    # the word embedding (v0.18.0): forward and backward are tabled (EMBEDDING_SIGNATURES)
+    lib.coattn_embedding_supported.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int]
+    lib.coattn_embedding_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     _lib = lib
     return lib
 
@@ -487,6 +502,11 @@ def alt_workspace_bytes(B, N, T, d, L):
 def lstm_workspace_bytes(B, T, E, H):
     """(saved, ws_fwd, ws_bwd) in bytes of the sentence LSTM."""
     return _bytes("coattn_lstm_workspace_bytes", 3, B, T, E, H, F32)
+
+
+def embedding_workspace_bytes(n, V, E):
+    """ws_bwd in bytes of the word embedding's backward (no term in V E)."""
+    return _bytes("coattn_embedding_workspace_bytes", 1, n, V, E, F32)[0]
 
 
 def head_workspace_bytes(B, d, mlp, K):

@@ -267,10 +267,30 @@ def _hip_sentence_lstm(rnn, phrases, x_lens):
     return sentence_lstm(phrases, x_lens, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
 
 
+WORD_IMPLS = ("stock", "hip")
+
+
+def _hip_words(enc, x) -> bool:
+    """Does this forward of the question encoder take the HIP word embedding on the ids `x`?  ``enc.word_impl``: "stock"
+    (the default: nn.Embedding's forward) or "hip" (embedding.word_embedding on the nn.Embedding's own weight and
+    padding_idx: ids on CUDA, an fp32 weight, a supported shape; CPU tensors, other dtypes and shapes take the stock line)."""
+    impl = enc.word_impl
+    if impl not in WORD_IMPLS:
+        raise ValueError("word_impl must be one of %s, got %r" % (WORD_IMPLS, impl))
+    emb = enc.word_embedding
+    if impl != "hip" or not x.is_cuda or not emb.weight.is_cuda or emb.weight.dtype != torch.float32:
+        return False
+    if x.is_floating_point() or emb.max_norm is not None or emb.scale_grad_by_freq or emb.sparse:
+        return False
+    from . import embedding
+    return embedding.supported(x.numel(), emb.num_embeddings, emb.embedding_dim)
+
+
 class QuestionCoAttentionEncoder(nn.Module):
     """word (embedding) / phrase (n-gram conv + pool) / sentence (LSTM) features, each [B,T,hidden];
     rows past a question's length are exact zeros at all three levels (padding_idx=0, packed LSTM).
-    ``sentence_impl``: "stock" (default) or "hip" (`_hip_sentence`); parameters and state_dict are the same either way."""
+    ``sentence_impl``: "stock" (default) or "hip" (`_hip_sentence`); ``word_impl``: "stock" (default) or "hip"
+    (`_hip_words`); parameters and state_dict are the same either way."""
 
     def __init__(self, vocab_size, word_emb_dim, hidden_dim):
         super().__init__()
@@ -279,10 +299,15 @@ class QuestionCoAttentionEncoder(nn.Module):
         self.phrase_conv_pool = PhraseConvPool(word_emb_dim)
         self.sentence_lstm = nn.LSTM(word_emb_dim, hidden_dim)
         self.sentence_impl = "stock"
+        self.word_impl = "stock"
 
     def forward(self, x, x_lens):
         T = x.shape[1]
-        words = self.word_embedding(x)
+        if _hip_words(self, x):                                       # opt-in: csrc/embedding.hip, ids stay on the device
+            from .embedding import word_embedding
+            words = word_embedding(x, self.word_embedding.weight, self.word_embedding.padding_idx)
+        else:
+            words = self.word_embedding(x)
         phrases = self.phrase_conv_pool(words)
         if _hip_sentence(self, phrases):                              # opt-in: csrc/lstm.hip, lengths stay on the device
             sentence, phrases = _hip_sentence_lstm(self.sentence_lstm, phrases, x_lens)

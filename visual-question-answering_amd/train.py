@@ -182,6 +182,27 @@ def set_sentence_lstm(model: nn.Module, sentence_lstm: str) -> None:
     enc.sentence_impl = sentence_lstm
 
 
+WORD_EMBEDDINGS = ("stock", "hip")
+
+
+def set_word_embedding(model: nn.Module, word_embedding: str) -> None:
+    """--word_embedding: "stock" (the default: nn.Embedding's forward and PyTorch's embedding backward) or "hip" (the question
+    encoder's word level on embedding.word_embedding: same parameter, same dense gradient, ids read on the device).  A module
+    attribute (QuestionCoAttentionEncoder.word_impl), not part of the state_dict.  Only the LSTM question encoder of
+    --model attention has that word level (attention_bert's is the frozen BERT, the baseline has no such encoder): asking
+    for "hip" elsewhere is an error."""
+    if word_embedding not in WORD_EMBEDDINGS:
+        raise ValueError("--word_embedding must be one of %s, got %r" % (WORD_EMBEDDINGS, word_embedding))
+    enc = getattr(model, "question_encoder", None)
+    if enc is None or not hasattr(enc, "word_impl"):
+        if word_embedding != "stock":
+            raise ValueError("--word_embedding hip applies to the co-attention model with the embedding word level "
+                             "(--model attention), not to %s%s" % (type(model).__name__, "" if enc is None else
+                                                                  " with " + type(enc).__name__))
+        return
+    enc.word_impl = word_embedding
+
+
 def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, affinity: str = "reference",
                 co_attention: str = "parallel", **kw) -> nn.Module:
     """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`; affinity: see
@@ -209,6 +230,7 @@ def model_from_args(args):
     set_question_mask(model, getattr(args, "question_mask", False))
     set_affinity(model, affinity)
     set_sentence_lstm(model, getattr(args, "sentence_lstm", "stock"))
+    set_word_embedding(model, getattr(args, "word_embedding", "stock"))
     return model, cfg
 
 
@@ -446,8 +468,10 @@ class Trainer:
     def __init__(self, model: nn.Module, lr: float = 1e-4, device=None, opt_lvl: int = 0,
                  bucket_mb: float = 16.0, encoder_runahead: bool = True, graph: bool = False, static_hot_path: bool = True,
                  precision: str = "exact", loss: str = "ce", optimizer: str = "torch", weight_decay: float = 0.0,
-                 clip_grad_norm=None, sentence_lstm=None):
+                 clip_grad_norm=None, sentence_lstm=None, word_embedding=None):
         check_loss(loss)
+        if word_embedding is not None:                           # "stock" | "hip" (set_word_embedding); None: leave the model's
+            set_word_embedding(model, word_embedding)
         if sentence_lstm is not None:                            # "stock" | "hip" (set_sentence_lstm); None: leave the model's
             set_sentence_lstm(model, sentence_lstm)
         check_optimizer(optimizer, weight_decay, clip_grad_norm)
@@ -745,6 +769,10 @@ def build_parser():
                          "pad_packed_sequence as the reference (model.py:286-296); 'hip' = the length-aware HIP forward / "
                          "backward on the same parameters (exact fp32, no packing, no host read of the lengths).  "
                          "Co-attention models only; a checkpoint does not depend on it")
+    ap.add_argument("--word_embedding", default="stock", choices=list(WORD_EMBEDDINGS),
+                    help="the question encoder's word level: 'stock' = nn.Embedding and PyTorch's embedding backward; 'hip' = "
+                         "the HIP gather and its dense gradient in one launch each on the same parameter (fixed summation "
+                         "order, no host read of the ids).  --model attention only; a checkpoint does not depend on it")
     ap.add_argument("--loss", default="ce", choices=list(LOSSES),
                     help="'ce' = the reference's cross entropy on the majority answer; 'soft_ce' / 'bce' = soft cross entropy / "
                          "binary cross entropy with logits on the soft answer targets (up to --num_answers (answer, score) pairs "
@@ -793,7 +821,7 @@ def main(argv=None):
         model.image_encoder.to(memory_format=torch.channels_last)
     trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss,
                       optimizer=args.optimizer, weight_decay=args.weight_decay, clip_grad_norm=args.clip_grad_norm,
-                      sentence_lstm=args.sentence_lstm)
+                      sentence_lstm=args.sentence_lstm, word_embedding=args.word_embedding)
     n_ans = args.num_answers if args.loss != "ce" else 0
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
