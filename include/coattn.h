@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -740,6 +740,44 @@ int coattn_embedding_forward(const void* ids, int ids_dtype, const void* W, void
                              int E, long long padding_idx, int dtype, int flags, void* stream);
 int coattn_embedding_backward(const void* ids, int ids_dtype, const void* g_out, void* dW, void* ws, long long n, long long V,
                               int E, long long padding_idx, int accumulate, int dtype, int flags, void* stream);
+
+/* ---- feature dropout: a counter RNG, the mask regenerated in the backward (v0.19.0; csrc/dropout.hip) ----
+ * Lu et al. 2016 apply dropout 0.5 to every q_l + v_l in front of the recursive answer encoding.  Here it is one launch on the
+ * attended features between the co-attention and the answer head (fp32, contiguous, n elements), and one launch on their
+ * gradient.  No mask is stored, no float atomics are used, nothing is read on the host.
+ * MASK DEFINITION (the contract; tests/_dropout.py restates it in numpy):
+ *   - Element i of n has block j = i >> 2 and word w = i & 3.
+ *   - r = Philox4x32-10(counter = (lo32(j), hi32(j), lo32(step), hi32(step)), key = (lo32(seed), hi32(seed)))[w].
+ *   - The constants are the standard ones: multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85,
+ *     ten rounds.
+ *   - thr = (uint32) floor((double)p * 2^32).  An element is kept iff r >= thr.
+ *   - scale = (float)(1.0 / (1.0 - (double)p)).
+ *   - y[i] = x[i] * (keep ? scale : 0.0f).  This is a float multiply: NaN and inf propagate as in
+ *     torch.nn.functional.dropout (a dropped inf or NaN is NaN), a dropped negative value gives -0.
+ *   - With n <= 2^31 - 4, counter word 1 is always 0.  It is in the contract so that a later, larger limit does not change any
+ *     mask.
+ * p = 0 keeps every element and multiplies it by 1.0f.  The 16-byte and the per-element form of the kernel (chosen by the
+ * alignment of the launch's pointers) give the same bits.
+ * STATE: a 32-byte device buffer the caller owns, 4-byte aligned: u64 seed, u64 step (both little-endian word pairs), then 16
+ * bytes for the library's own use (a ticket: 0 between calls; the caller zeroes them once).  `step` is the index of the mask
+ * most recently drawn.  The caller may rewrite seed and step between calls, in stream order.
+ *   coattn_dropout_forward   y0 = x0 * mask and, when x1 / y1 are given, y1 = x1 * mask with the SAME mask (x1 = y1 = NULL: one
+ *                            pair).  advance = 1: draws mask step + 1 and leaves `step` incremented when the call has completed
+ *                            on the stream (the workgroup that finishes last stores it; no second launch).  advance = 0: redraws
+ *                            mask `step` and writes nothing to the state.  y may equal x (in place); any other overlap is the
+ *                            caller's error.
+ *   coattn_dropout_backward  dx = g * mask(step); in place allowed.  It never advances: any number of backwards after one
+ *                            forward see that forward's mask.
+ *   coattn_dropout_supported 1 for 1 <= n <= 2^31 - 4, else 0.
+ * Refused with -1 and a coattn_last_error message, nothing launched: p < 0, p >= 1 or p NaN; n outside the supported range; a
+ * NULL x0, y0, g, dx or state; exactly one of x1 / y1 given; a pointer not 4-byte aligned.
+ * The calls are stream-ordered; no allocation, no synchronisation, no host read, no host-side state: they can be captured into
+ * a HIP graph, and each replay of an advancing forward draws a fresh mask.  Two advancing forwards on one state must be ordered
+ * (one stream, or an event between them). */
+int coattn_dropout_supported(long long n);
+int coattn_dropout_forward(const void* x0, void* y0, const void* x1, void* y1, long long n, float p, void* state, int advance,
+                           void* stream);
+int coattn_dropout_backward(const void* g, void* dx, long long n, float p, void* state, void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

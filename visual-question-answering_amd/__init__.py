@@ -16,7 +16,9 @@ from .optim import HipAdam  # noqa: F401
 from .lstm import sentence_lstm  # noqa: F401
 from . import embedding  # noqa: F401
 from .embedding import word_embedding  # noqa: F401
+from . import dropout  # noqa: F401
+from .dropout import DropoutState, feature_dropout, rank_seed  # noqa: F401
 
 __all__ = ["word_embedding", "embedding","ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
            "SoftTargetLoss", "vqa_score", "HipAdam", "sentence_lstm", "_lib",
-           "check_range", "RangeError"]
+           "check_range", "RangeError", "dropout", "DropoutState", "feature_dropout", "rank_seed"]

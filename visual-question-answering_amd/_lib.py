@@ -31,7 +31,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_conv1_probe",
            "coattn_lstm_supported", "coattn_lstm_workspace_bytes", "coattn_lstm_forward", "coattn_lstm_backward",
            "coattn_embedding_supported", "coattn_embedding_workspace_bytes", "coattn_embedding_forward",
-           "coattn_embedding_backward")
+           "coattn_embedding_backward",
+           "coattn_dropout_supported", "coattn_dropout_forward", "coattn_dropout_backward")
 
 F32 = 0
 IDS_I32, IDS_I64 = 0, 1   # ids_dtype of the word embedding calls (v0.18.0: COATTN_IDS_*)
@@ -174,10 +175,16 @@ EMBEDDING_SIGNATURES = {
     "coattn_embedding_backward": (_void("ids") + _int("ids_dtype") + _void("g_out dW ws") + _EMB_DIMS
                                   + _int("accumulate dtype flags") + _void("stream")),
 }
-_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES}
+# feature dropout (v0.19.0), a table of its own as well; p is the one float argument of the tabled calls
+DROPOUT_SIGNATURES = {
+    "coattn_dropout_forward": (_void("x0 y0 x1 y1") + _i64("n") + _of(C.c_float)("p") + _void("state") + _int("advance")
+                               + _void("stream")),
+    "coattn_dropout_backward": _void("g dx") + _i64("n") + _of(C.c_float)("p") + _void("state stream"),
+}
+_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES, **DROPOUT_SIGNATURES}
 _INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _TABLE.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
-_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids".split())
+_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids x1 y1".split())
 _DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
 
 
@@ -365,6 +372,8 @@ def load() -> C.CDLL:
     # the word embedding (v0.18.0): forward and backward are tabled (EMBEDDING_SIGNATURES)
     lib.coattn_embedding_supported.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int]
     lib.coattn_embedding_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    # feature dropout (v0.19.0): forward and backward are tabled (DROPOUT_SIGNATURES)
+    lib.coattn_dropout_supported.argtypes = [C.c_int64]
     _lib = lib
     return lib
 

@@ -40,6 +40,12 @@ the static parameters and gradients (18 instead of 16), eager and captured alike
 the third argument of a call is the pair ``(ans_idx int32 [B,A], ans_score fp32 [B,A])`` -- read where it lies like ``labels``,
 or copied into the node's static ``ans_idx`` / ``ans_score`` buffers.  The default ``loss="ce"`` builds the node described above.
 
+``dropout=p, dropout_state=DropoutState`` (p > 0): feature dropout (dropout.py, include/coattn.h v0.19.0) between the co-attention
+and the head -- the forward is ``co_fwd``, ``coattn_dropout_forward`` in place on the static ``v`` and ``q`` (one mask for both,
+advance = 1), ``head_fwd``; the backward ``head_bwd``, ``coattn_dropout_backward`` in place on ``dx``, ``co_bwd`` -- issued eagerly
+or captured alike: the step counter is on the device, so every replay draws a fresh mask, and a second backward
+(``accumulate = 1``) meets the mask of its forward again.  The default ``dropout=0.0`` issues exactly the four calls above.
+
 ``logits`` is returned as a fresh tensor (``alias_outputs=True``: the static buffer itself, overwritten by the next
 step).  A gradient arriving for ``logits`` is added by the head's backward in eager mode; under graph capture it raises.
 """
@@ -52,6 +58,7 @@ from typing import Sequence
 import torch
 
 from . import _lib
+from . import dropout as _dropout
 from . import head as _head
 from .coattention import _is_native, _native_layout, _shared_args, native_features
 # (the package exports a FUNCTION named `coattention`, which shadows the submodule as an attribute: take the module itself)
@@ -63,8 +70,13 @@ class HotPathGraph:
 
     def __init__(self, co_attention, mlp_classify, B: int, N: int, T: int, need_dv: bool = False, flags: int = 0,
                  capture: bool = True, direct_grads: bool = False, alias_outputs: bool = False,
-                 question_mask: bool = False, loss: str = "ce", num_answers: int = 10):
+                 question_mask: bool = False, loss: str = "ce", num_answers: int = 10, dropout: float = 0.0,
+                 dropout_state=None):
         self.co, self.mlp = co_attention, mlp_classify
+        self.dropout = _dropout.check_p(dropout)
+        if self.dropout > 0 and not isinstance(dropout_state, _dropout.DropoutState):
+            raise ValueError("HotPathGraph(dropout=%g) needs dropout_state=DropoutState(...)" % self.dropout)
+        self.dropout_state = dropout_state if self.dropout > 0 else None
         if loss != "ce" and loss not in _lib.LOSS_KINDS:
             raise ValueError("HotPathGraph: loss must be 'ce', 'soft_ce' or 'bce', got %r" % (loss,))
         if loss != "ce" and not 1 <= int(num_answers) <= _lib.MAX_ANSWERS:
@@ -82,6 +94,8 @@ class HotPathGraph:
                 raise RuntimeError("HotPathGraph: the bilinear affinity is not available in the reduced-precision mode")
             flags |= _lib.FLAG_BILINEAR
         self.flags = flags
+        if self.dropout_state is not None and self.dropout_state.device != dev:
+            raise RuntimeError("HotPathGraph: the DropoutState lives on %s, the parameters on %s" % (self.dropout_state.device, dev))
         self.head_flags = _lib.FLAG_BF16_PROJ if getattr(mlp_classify, "bf16_products", False) else 0
         f32 = dict(device=dev, dtype=torch.float32)
         # static inputs, used when the caller's tensors are not taken in place (layout, alignment, too many address sets)
@@ -173,11 +187,19 @@ class HotPathGraph:
                                 dQ=_lib.ptr_array(self.dQ), pg=_lib.ParamGrads(*[t.data_ptr() for t in self.co_grads]),
                                 accumulate=0, **co, **dv),
         }
+        if self.dropout > 0:                                     # in place on the static buffers, between the calls above
+            n, state = 3 * B * d, self.dropout_state.buf
+            plan["drop_fwd"] = _lib.bind("coattn_dropout_forward", x0=self.v, y0=self.v, x1=self.q, y1=self.q, n=n,
+                                         p=self.dropout, state=state, advance=1)
+            plan["drop_bwd"] = _lib.bind("coattn_dropout_backward", g=self.dx, dx=self.dx, n=n, p=self.dropout, state=state)
         return plan
 
     @staticmethod
-    def _forward_pair(plan, st):
+    def _forward_pair(plan, st, advance=1):
+        """advance = 0 (the warm-up ahead of a capture): the dropout redraws the current mask and leaves the state alone."""
         plan["co_fwd"](st)
+        if "drop_fwd" in plan:
+            (plan["drop_fwd"] if advance else plan["drop_fwd"].replace(advance=0))(st)
         plan["head_fwd"](st)
 
     def _backward_pair(self, plan, st, g_logits=None, accumulate=0, g_loss=None):
@@ -189,14 +211,16 @@ class HotPathGraph:
         if accumulate:
             co = co.replace(accumulate=accumulate)
         head(st)
+        if "drop_bwd" in plan:
+            plan["drop_bwd"](st)
         co(st)
 
     # the C-ABI calls on `stream`, reading the inputs `ins` = (V [B,N,d] in a native layout, Q_w, Q_p, Q_s, labels)
-    def _enqueue(self, ins, stream, fwd=True, bwd=True):
+    def _enqueue(self, ins, stream, fwd=True, bwd=True, advance=1):
         plan = self._plan(ins)
         st = C.c_void_p(stream)
         if fwd:
-            self._forward_pair(plan, st)
+            self._forward_pair(plan, st, advance)
         if bwd:
             self._backward_pair(plan, st)
 
@@ -228,7 +252,7 @@ class HotPathGraph:
                 side = torch.cuda.Stream(self.device)
                 side.wait_stream(cur)
                 with torch.cuda.stream(side):
-                    self._enqueue(ins, side.cuda_stream)
+                    self._enqueue(ins, side.cuda_stream, advance=0)      # (no mask is drawn by a warm-up)
                 cur.wait_stream(side)
                 self._warm = True
             torch.cuda.synchronize(self.device)
@@ -334,6 +358,9 @@ class _HotPathFn(torch.autograd.Function):
         plan = hp._plan(ins, key) if pair is _EAGER else None   # (built once per address set; the backward reuses it)
         hp.run(pair, ins, True, plan)
         ctx.plan = plan
+        if hp.dropout_state is not None:                         # (host-side tag only: dropout._backward's "still my mask?")
+            hp.dropout_state.draws += 1
+            ctx.draw = hp.dropout_state.draws
         # (as head.answer_head after a forward with labels: Trainer.check_labels() reads this step's status word)
         _head._last = (hp.hsaved, B, d, mlp, K, hp.device)
         if hp.flags & _lib.FLAG_FAST16:                          # tolerance mode: this step's status words (_lib.check_range())
@@ -353,6 +380,9 @@ class _HotPathFn(torch.autograd.Function):
         hp = ctx.hp
         if g_loss is None and g_logits is None:
             return (None,) * len(ctx.needs_input_grad)
+        if hp.dropout_state is not None and ctx.draw != hp.dropout_state.draws:
+            raise RuntimeError("HotPathGraph: the DropoutState has drawn another mask (or was re-seeded) since this forward; "
+                               "its backward must run before the next forward on the same state")
         direct = None
         if g_loss is None:
             hp.g_loss.zero_()

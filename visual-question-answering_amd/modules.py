@@ -30,6 +30,7 @@ from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 from . import encoder
 from .alternating import AlternatingCoAttention
 from .coattention import ParallelCoAttention
+from .dropout import DropoutState, check_p, feature_dropout
 from .head import answer_head
 
 _VGG11_CFG = (64, "M", 128, "M", 256, 256, "M", 512, 512, "M", 512, 512, "M")
@@ -445,6 +446,10 @@ class HierarchicalCoAttentionNet(nn.Module):
         self.hot_path_static = False
         self.hot_path_direct_grads = False
         self._graphs = {}
+        # feature dropout (dropout.py; set_feature_dropout): probability applied in training to the six attended features in
+        # front of the answer head, and the device-side state its masks are drawn from.  Neither is part of the state_dict.
+        self.feature_dropout = 0.0
+        self.dropout_state = None
 
     def forward(self, x_img, x_ques, x_ques_lens, return_attention=False, targets=None, loss_kind="soft_ce"):
         return self.forward_features(self.image_encoder(x_img), x_ques, x_ques_lens, return_attention=return_attention,
@@ -461,7 +466,10 @@ class HierarchicalCoAttentionNet(nn.Module):
         (logits, loss, a_v, a_q) with `labels` -- differentiable, for a loss on them (ParallelCoAttention.forward).  This
         takes the per-module path, never the hot-path node (`hot_path_static` / `hot_path_graph`).
         targets = (ans_idx int32 [B,A], ans_score fp32 [B,A]) in place of `labels`: the loss is the soft-target loss
-        `loss_kind` ("soft_ce" | "bce", loss.soft_target_loss); everything above holds with "labels" read as "targets"."""
+        `loss_kind` ("soft_ce" | "bce", loss.soft_target_loss); everything above holds with "labels" read as "targets".
+        In training mode with ``feature_dropout`` > 0 (set_feature_dropout) every route -- per-module, with the attention
+        maps, the alternating form, the hot-path node -- drops the six attended features in front of the answer head under one
+        mask drawn from ``dropout_state`` (dropout.py); in eval mode, or with 0, none does and the state is not touched."""
         if labels is not None and targets is not None:
             raise ValueError("forward_features: give labels or targets, not both")
         if targets is not None and loss_kind not in ("soft_ce", "bce"):
@@ -472,20 +480,25 @@ class HierarchicalCoAttentionNet(nn.Module):
         if callable(x_img_features):            # resolved only now: the question side is queued first
             x_img_features = x_img_features()
         masked = self._question_mask()
+        drop = self._dropout_p()
         if return_attention:
             lens = (x_ques_lens,) if masked else ()
             v, q, a_v, a_q = self.co_attention(x_img_features, x_ques_features, *lens, return_attention=True)
+            if drop:
+                v, q = feature_dropout(v, q, drop, self.dropout_state)
             if has_loss:
                 return (*self.mlp_classify.forward_loss(v, q, **tk), a_v, a_q)
             return self.mlp_classify(v, q), a_v, a_q
         if (has_loss and (self.hot_path_graph or self.hot_path_static) and x_img_features.is_cuda
                 and torch.is_grad_enabled() and self.co_attention_form == "parallel"):     # (the node is parallel-only)
             return self._graphed(x_img_features, x_ques_features, labels, x_ques_lens if masked else None, targets=targets,
-                                 loss_kind=loss_kind)
+                                 loss_kind=loss_kind, dropout=drop)
         if masked:
             x_img_attn, x_ques_attn = self.co_attention(x_img_features, x_ques_features, x_ques_lens)
         else:
             x_img_attn, x_ques_attn = self.co_attention(x_img_features, x_ques_features)
+        if drop:
+            x_img_attn, x_ques_attn = feature_dropout(x_img_attn, x_ques_attn, drop, self.dropout_state)
         if has_loss:
             return self.mlp_classify.forward_loss(x_img_attn, x_ques_attn, **tk)
         return self.mlp_classify(x_img_attn, x_ques_attn)
@@ -494,7 +507,8 @@ class HierarchicalCoAttentionNet(nn.Module):
         """Inference with the co-attention maps: (logits [B,K], a_v [3,B,N], a_q [3,B,T]) for the word, phrase and sentence
         levels.  Index n of a_v is location n of the encoder's flattened grid (model.py:215-217: row-major over 7 x 7 at
         224 px, 14 x 14 at 448 px); a_q is unmasked over the T token positions (model.py:388) -- or, with the co-attention's
-        ``question_mask`` on, 0 past each question's length.  The logits equal `forward`'s under no_grad bit for bit.
+        ``question_mask`` on, 0 past each question's length.  The logits equal `forward`'s under no_grad bit for bit -- in eval
+        mode or with ``feature_dropout = 0``: this is the inference call and never applies dropout, `forward` does in training.
         Forward only: raises where a gradient would be needed."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("forward_with_attention is forward only: run it under torch.no_grad()")
@@ -510,7 +524,15 @@ class HierarchicalCoAttentionNet(nn.Module):
     def _question_mask(self) -> bool:
         return bool(getattr(self.co_attention, "question_mask", False))
 
-    def _graphed(self, x_img_features, x_ques_features, labels, x_ques_lens=None, targets=None, loss_kind="soft_ce"):
+    def _dropout_p(self) -> float:
+        """The feature-dropout probability of this forward: 0 in eval mode (the state is then never touched)."""
+        p = float(self.feature_dropout) if self.training else 0.0
+        if p and self.dropout_state is None:
+            raise RuntimeError("feature_dropout = %g without a dropout_state: use set_feature_dropout(model, p, seed)" % p)
+        return p
+
+    def _graphed(self, x_img_features, x_ques_features, labels, x_ques_lens=None, targets=None, loss_kind="soft_ce",
+                 dropout=0.0):
         """co-attention + answer head + loss, forward AND backward, as one autograd node over static buffers (graph.py),
         built per (B, N, T) on first use: replayed from captured HIP graphs (``net.hot_path_graph = True``,
         ``Trainer(graph=True)``) or with its four C-ABI calls issued eagerly (``net.hot_path_static``, the Trainer's
@@ -525,6 +547,7 @@ class HierarchicalCoAttentionNet(nn.Module):
                bool(self.mlp_classify.bf16_products), bool(self.hot_path_graph), bool(self.hot_path_direct_grads),
                bool(self.co_attention.fast_products), self._question_mask(),
                ("ce", 0) if targets is None else (loss_kind, int(targets[0].shape[1])),
+               (dropout, self.dropout_state.data_ptr()) if dropout else (0.0, 0),   # p and the state's address
                getattr(self.co_attention, "affinity", "reference"))
         hp = self._graphs.get(key)
         # (the node reads the parameters where they lie: one built before the module was moved -- .to(), .cuda(), new
@@ -535,7 +558,8 @@ class HierarchicalCoAttentionNet(nn.Module):
             hp = self._graphs[key] = HotPathGraph(self.co_attention, self.mlp_classify, B, N, T, need_dv=key[3],
                                                   flags=(_lib.FLAG_BF16_PROJ if key[4] else 0) | _lib.precision_flag(key[8] and not key[4]),
                                                   capture=key[6], direct_grads=key[7], question_mask=key[9],
-                                                  **({} if targets is None else dict(loss=key[10][0], num_answers=key[10][1])))
+                                                  **({} if targets is None else dict(loss=key[10][0], num_answers=key[10][1])),
+                                                  **(dict(dropout=dropout, dropout_state=self.dropout_state) if dropout else {}))
         return hp(x_img_features, x_ques_features, labels if targets is None else targets, q_len=x_ques_lens)
 
 
@@ -591,3 +615,17 @@ class VQABaselineNet(nn.Module):
     def forward(self, x_img, x_ques, x_ques_len):
         joint = self.image_encoder(x_img) * self.question_encoder(x_ques, x_ques_len)
         return self.fc_final(self.mlp(joint))
+
+
+def set_feature_dropout(model: nn.Module, p: float, seed: int = 0) -> None:
+    """Feature dropout of probability `p` on a HierarchicalCoAttentionNet (``model.feature_dropout``), its masks drawn from a
+    fresh ``DropoutState(seed)`` on the device the model's parameters are on -- call it after moving the model.  p = 0 switches
+    it off and drops the state.  Other models have no such site: p > 0 is an error for them."""
+    p = check_p(p)
+    if not isinstance(model, HierarchicalCoAttentionNet):
+        if p > 0:
+            raise ValueError("feature dropout applies to the co-attention models (HierarchicalCoAttentionNet), not to %s"
+                             % type(model).__name__)
+        return
+    model.feature_dropout = p
+    model.dropout_state = DropoutState(seed, next(model.parameters()).device) if p > 0 else None

@@ -23,7 +23,8 @@ import torch.utils.data
 
 from . import dist as vdist
 from .loss import CrossEntropyLoss, SoftTargetLoss
-from .modules import HierarchicalCoAttentionNet, VQABaselineNet
+from .dropout import rank_seed
+from .modules import HierarchicalCoAttentionNet, VQABaselineNet, set_feature_dropout  # noqa: F401  (set_feature_dropout: re-exported)
 
 PATH_VGG_WEIGHTS = None      # the reference hard-codes a local .pth (utils.py:15); none ships here
 
@@ -203,6 +204,20 @@ def set_word_embedding(model: nn.Module, word_embedding: str) -> None:
     enc.word_impl = word_embedding
 
 
+def check_dropout(model_name: str, dropout: float, opt_lvl: int = 0) -> None:
+    """--dropout P: feature dropout on the six attended features in front of the answer head (dropout.py), 0 = off (the
+    default).  P must lie in [0, 1); P > 0 exists for the co-attention models only and not in the reduced-precision mode
+    (--opt_lvl >= 1): both are errors."""
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError("--dropout must be in [0, 1), got %r" % (dropout,))
+    if dropout == 0:
+        return
+    if not str(model_name).startswith("attention"):
+        raise ValueError("--dropout applies to the co-attention models (--model attention*), not to %s" % model_name)
+    if opt_lvl > 0:
+        raise ValueError("--dropout is not available with --opt_lvl >= 1 (the reduced-precision mode)")
+
+
 def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, affinity: str = "reference",
                 co_attention: str = "parallel", **kw) -> nn.Module:
     """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`; affinity: see
@@ -222,6 +237,7 @@ def model_from_args(args):
     steps and `validate` then pass the lengths through), --affinity likewise.  (train.main, predict.main)"""
     affinity = getattr(args, "affinity", "reference")
     check_affinity(args.model, affinity, getattr(args, "opt_lvl", 0))
+    check_dropout(args.model, getattr(args, "dropout", 0.0), getattr(args, "opt_lvl", 0))
     co_attention = getattr(args, "co_attention", "parallel")
     check_co_attention(args.model, co_attention, affinity, getattr(args, "opt_lvl", 0), getattr(args, "precision", "exact"))
     cfg = setup_model_configs(args, args.vocab_size)             # (as main.py:388)
@@ -456,6 +472,9 @@ class Trainer:
     `clip_grad_norm` (by the global norm of the averaged gradients: it runs behind the reducer; the norm of the last step stays
     on the device as ``trainer.optimizer.grad_norm``) need.
 
+    feature_dropout=P > 0 (with dropout_seed): dropout on the attended features in front of the answer head, CUDA and
+    opt_lvl 0 only (modules.set_feature_dropout; masks from dropout_seed + rank, nothing taken from torch's generators).
+
     Encoder run-ahead: when the image encoder is frozen (the reference default, main.py:67 /
     model.py:239-241) its output does not depend on the optimiser state, so ``step(...,
     next_image=...)`` launches the stock encoder for the NEXT batch on a second, high-priority HIP
@@ -468,7 +487,8 @@ class Trainer:
     def __init__(self, model: nn.Module, lr: float = 1e-4, device=None, opt_lvl: int = 0,
                  bucket_mb: float = 16.0, encoder_runahead: bool = True, graph: bool = False, static_hot_path: bool = True,
                  precision: str = "exact", loss: str = "ce", optimizer: str = "torch", weight_decay: float = 0.0,
-                 clip_grad_norm=None, sentence_lstm=None, word_embedding=None):
+                 clip_grad_norm=None, sentence_lstm=None, word_embedding=None, feature_dropout: float = 0.0,
+                 dropout_seed: int = 0):
         check_loss(loss)
         if word_embedding is not None:                           # "stock" | "hip" (set_word_embedding); None: leave the model's
             set_word_embedding(model, word_embedding)
@@ -477,6 +497,11 @@ class Trainer:
         check_optimizer(optimizer, weight_decay, clip_grad_norm)
         self.loss = loss                                         # "ce": int64 labels; "soft_ce" | "bce": step(..., targets=...)
         self.device = device or next(model.parameters()).device
+        if feature_dropout:                                      # (refused before anything of the model is switched)
+            if self.device.type != "cuda":
+                raise ValueError("Trainer(feature_dropout > 0) needs a model on the GPU (the dropout has no CPU fallback)")
+            if opt_lvl > 0:
+                raise ValueError("Trainer(feature_dropout > 0) is not available with opt_lvl >= 1 (the reduced-precision mode)")
         self.model = model
         # Precision of the HIP path's fp32 products (include/coattn.h "Widths of the fp32 mode"): "exact" -- the default, the
         # reference's arithmetic (main.py --opt_lvl 0) -- is fp32-accurate products over fp32's range, the modules' and the
@@ -498,6 +523,11 @@ class Trainer:
             self.optimizer = torch.optim.Adam(model.parameters(), lr)
         self.opt_lvl = opt_lvl
         set_reduced_precision(model, opt_lvl)                    # AMP: projections on the bf16 MFMA as well
+        # feature_dropout > 0: dropout on the attended features in front of the answer head (dropout.py), its masks drawn on the
+        # device from (dropout_seed + rank, step): data-parallel ranks draw different masks, torch's generators are not touched.
+        # 0 (the default) leaves the model as it is.  The step counter is not part of a checkpoint.
+        if feature_dropout:
+            set_feature_dropout(model, feature_dropout, rank_seed(dropout_seed, vdist.rank()))
         # graph=True: co-attention + answer head + loss, forward and backward, replayed from one captured HIP graph
         # (graph.py): one host call instead of ~25 launches; same values bit for bit
         if graph and hasattr(model, "hot_path_graph") and self.device.type == "cuda":
@@ -773,6 +803,15 @@ def build_parser():
                     help="the question encoder's word level: 'stock' = nn.Embedding and PyTorch's embedding backward; 'hip' = "
                          "the HIP gather and its dense gradient in one launch each on the same parameter (fixed summation "
                          "order, no host read of the ids).  --model attention only; a checkpoint does not depend on it")
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="feature dropout probability P in [0, 1) on the attended features q_l + v_l in front of the answer head "
+                         "(Lu et al. 2016 use 0.5): one HIP launch per direction, the mask regenerated in the backward.  "
+                         "Co-attention models only, not with --opt_lvl >= 1.  Prediction runs in eval mode and needs no flag.  "
+                         "The checkpoint does not record the mask counter: a resumed run draws other masks than the "
+                         "uninterrupted one would")
+    ap.add_argument("--dropout_seed", type=int, default=0,
+                    help="seed of the dropout masks (rank r of a data-parallel run uses seed + r); torch's generators are not "
+                         "consumed, so images, questions, labels and weights keep their bits for every value")
     ap.add_argument("--loss", default="ce", choices=list(LOSSES),
                     help="'ce' = the reference's cross entropy on the majority answer; 'soft_ce' / 'bce' = soft cross entropy / "
                          "binary cross entropy with logits on the soft answer targets (up to --num_answers (answer, score) pairs "
@@ -821,7 +860,8 @@ def main(argv=None):
         model.image_encoder.to(memory_format=torch.channels_last)
     trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss,
                       optimizer=args.optimizer, weight_decay=args.weight_decay, clip_grad_norm=args.clip_grad_norm,
-                      sentence_lstm=args.sentence_lstm, word_embedding=args.word_embedding)
+                      sentence_lstm=args.sentence_lstm, word_embedding=args.word_embedding, feature_dropout=args.dropout,
+                      dropout_seed=args.dropout_seed)
     n_ans = args.num_answers if args.loss != "ce" else 0
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
