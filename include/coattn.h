@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward; v0.20.0: the gather of cached image features from a table).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -778,6 +778,35 @@ int coattn_dropout_supported(long long n);
 int coattn_dropout_forward(const void* x0, void* y0, const void* x1, void* y1, long long n, float p, void* state, int advance,
                            void* stream);
 int coattn_dropout_backward(const void* g, void* dx, long long n, float p, void* state, void* stream);
+
+/* ---- cached image features: the rows of a batch gathered from a feature table (v0.20.0; csrc/features.hip) ----
+ * The frozen image encoder is a fixed function of the image, so its features can be encoded once into a table and a training or
+ * prediction step reads the rows of its batch instead of running the encoder (Lu et al. 2016 train from such features).
+ *   table     : [S][N][d], contiguous and location-major (what coattn_features_native writes per image), fp32 (table_dtype =
+ *               COATTN_F32) or bf16 (COATTN_BF16: the 16 stored bits); 16-byte aligned; read only
+ *   idx       : B row indices, contiguous, int32 (idx_dtype = COATTN_IDS_I32) or int64 (COATTN_IDS_I64: all 64 bits are
+ *               compared); aligned to their element size; read on the device only, never on the host
+ *   out       : fp32 [B][N][d], contiguous, 16-byte aligned
+ *   bad_idx   : one int32 on the device, may be NULL; the call ADDS to it (an integer atomic: the count is exact), the caller
+ *               zeroes it
+ * out[b] = table[idx[b]]: bit for bit from an fp32 table; from a bf16 table the exact up-cast -- the sixteen bits become the
+ * high half of the fp32 word, so infinities, NaN payloads, denormals and the sign of a zero are kept.  An index outside [0, S)
+ * -- negative, >= S, or an int64 whose low 32 bits alone would be a valid row -- gives a row of exact +0 and adds 1 to
+ * *bad_idx; it is never used as an index, and no address outside `table` is formed.  Repeated indices are fine.
+ * One launch of 16-byte loads and stores with 64-bit element offsets (S N d may pass 2^31 elements and 2^32 bytes).  No float
+ * arithmetic, no atomics on floats: same inputs, same bits.  A row is cut into passes of COATTN_FEATURES_THREADS *
+ * COATTN_FEATURES_LOADS 16-byte loads (4 fp32 or 8 bf16 elements each), one workgroup per (row, pass).
+ * Supported (the query returns 1): table_dtype COATTN_F32 or COATTN_BF16, flags 0, S >= 1, B >= 1, 1 <= N <= 4096, 1 <= d <=
+ * 2048, N d a multiple of 4 (fp32) or 8 (bf16), and B times the passes of a row at most 2^24 - 1 (B <= 8,191 for the largest
+ * row there is; 16,777,215 for a row of one pass).
+ * Argument errors (a NULL table, idx or out, a non-positive size, flags != 0, another table_dtype or idx_dtype, an unsupported
+ * shape, a misaligned buffer): -1 with a coattn_last_error message before any device work.  No allocation, no synchronisation;
+ * the call can be captured into a HIP graph. */
+#define COATTN_FEATURES_THREADS 256
+#define COATTN_FEATURES_LOADS 4
+int coattn_features_gather_supported(long long S, long long B, int N, int d, int table_dtype, int flags);
+int coattn_features_gather(const void* table, int table_dtype, const void* idx, int idx_dtype, void* out, int32_t* bad_idx,
+                           long long S, long long B, int N, int d, int flags, void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

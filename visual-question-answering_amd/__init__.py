@@ -18,7 +18,10 @@ from . import embedding  # noqa: F401
 from .embedding import word_embedding  # noqa: F401
 from . import dropout  # noqa: F401
 from .dropout import DropoutState, feature_dropout, rank_seed  # noqa: F401
+from . import features  # noqa: F401
+from .features import FeatureTable, gather_features  # noqa: F401
 
 __all__ = ["word_embedding", "embedding","ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
            "SoftTargetLoss", "vqa_score", "HipAdam", "sentence_lstm", "_lib",
-           "check_range", "RangeError", "dropout", "DropoutState", "feature_dropout", "rank_seed"]
+           "check_range", "RangeError", "dropout", "DropoutState", "feature_dropout", "rank_seed",
+           "features", "FeatureTable", "gather_features"]

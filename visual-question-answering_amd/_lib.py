@@ -32,11 +32,12 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_lstm_supported", "coattn_lstm_workspace_bytes", "coattn_lstm_forward", "coattn_lstm_backward",
            "coattn_embedding_supported", "coattn_embedding_workspace_bytes", "coattn_embedding_forward",
            "coattn_embedding_backward",
-           "coattn_dropout_supported", "coattn_dropout_forward", "coattn_dropout_backward")
+           "coattn_dropout_supported", "coattn_dropout_forward", "coattn_dropout_backward",
+           "coattn_features_gather_supported", "coattn_features_gather")
 
 F32 = 0
 IDS_I32, IDS_I64 = 0, 1   # ids_dtype of the word embedding calls (v0.18.0: COATTN_IDS_*)
-BF16 = 1                  # storage type of coattn_features_native's input
+BF16 = 1                  # storage type of coattn_features_native's input and of a bf16 feature table (coattn_features_gather)
 IMPL_AUTO, IMPL_GENERAL, IMPL_FUSED = 0, 1, 2
 FLAG_BF16_PROJ = 4
 FLAG_BF16_IN = 8          # linear entry points: x (dy) stored as bf16
@@ -181,10 +182,15 @@ DROPOUT_SIGNATURES = {
                                + _void("stream")),
     "coattn_dropout_backward": _void("g dx") + _i64("n") + _of(C.c_float)("p") + _void("state stream"),
 }
-_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES, **DROPOUT_SIGNATURES}
+# the gather of cached image features (v0.20.0), a table of its own as well
+FEATURES_SIGNATURES = {
+    "coattn_features_gather": (_void("table") + _int("table_dtype") + _void("idx") + _int("idx_dtype") + _void("out bad_idx")
+                               + _i64("S B") + _int("N d flags") + _void("stream")),
+}
+_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES, **DROPOUT_SIGNATURES, **FEATURES_SIGNATURES}
 _INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _TABLE.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
-_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids x1 y1".split())
+_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1".split())
 _DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
 
 
@@ -374,6 +380,8 @@ def load() -> C.CDLL:
     lib.coattn_embedding_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
     # feature dropout (v0.19.0): forward and backward are tabled (DROPOUT_SIGNATURES)
     lib.coattn_dropout_supported.argtypes = [C.c_int64]
+    # cached image features (v0.20.0): the gather is tabled (FEATURES_SIGNATURES); (S, B, N, d, table_dtype, flags)
+    lib.coattn_features_gather_supported.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
     _lib = lib
     return lib
 

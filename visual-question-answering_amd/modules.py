@@ -512,7 +512,13 @@ class HierarchicalCoAttentionNet(nn.Module):
         Forward only: raises where a gradient would be needed."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("forward_with_attention is forward only: run it under torch.no_grad()")
-        x_img_features = self.image_encoder(x_img)
+        return self.forward_features_with_attention(self.image_encoder(x_img), x_ques, x_ques_lens)
+
+    def forward_features_with_attention(self, x_img_features, x_ques, x_ques_lens):
+        """`forward_with_attention` from already-encoded image features [B,N,d] (the rows of a feature table,
+        features.gather_features): the image encoder is not called.  Same results, same restrictions."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("forward_features_with_attention is forward only: run it under torch.no_grad()")
         x_ques_features = [q if q.dtype == torch.float32 else q.float()       # (the fp32 island, as _CoAttentionFn's cast)
                            for q in self.question_encoder(x_ques, x_ques_lens)]
         if self._question_mask():

@@ -69,8 +69,12 @@ def main(argv=None):
         raise SystemExit("only --synthetic true is available: the VQA dataset is not present in this environment")
     try:
         T.check_loss(args.loss, args.num_answers)
+        if args.val_image_features:
+            raise ValueError("--val_image_features is train.py's; prediction takes the test split's table as --image_features")
+        T.check_image_features(args)
     except ValueError as e:
         ap.error(str(e))
+    cached = bool(args.image_features)     # the test split's feature table (extract --split test) in place of the encoder
 
     if torch.cuda.is_available():
         device = torch.device("cuda", args.gpu_id)
@@ -93,7 +97,15 @@ def main(argv=None):
     n_cls = args.num_cls + 1
     k = min(args.topk, n_cls)
     ds = T.SyntheticVQADataset(args.test_size, size, args.max_seq_length, args.vocab_size, n_cls, TEST_SEED,
-                               num_answers=args.num_answers if soft else 0)
+                               num_answers=args.num_answers if soft else 0, images=not cached)
+    feats = None
+    if cached:
+        from .features import FeatureTable, bad_indices
+        feats = FeatureTable.load(args.image_features, device)
+        try:
+            feats.check(args.model, size[0], "test", TEST_SEED, args.test_size)
+        except ValueError as e:
+            ap.error(str(e))
     loader = torch.utils.data.DataLoader(ds, args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
     maps = bool(args.attention_maps)
 
@@ -120,11 +132,18 @@ def main(argv=None):
             targets = [e.to(device) for e in extras]
             idx, label = il[:, 0], il[:, 1]
             image = image.to(device)
-            if cl:
+            if cached:
+                image = feats.gather(image)                     # `image` held the batch's row indices
+            elif cl:
                 image = image.contiguous(memory_format=torch.channels_last)
             question, label_d = question.to(device), label.to(device)
             with T.autocast_for(args.opt_lvl, device):
-                if maps:
+                if cached:
+                    if maps:
+                        logits, av, aq = model.forward_features_with_attention(image, question, ques_len)
+                    else:
+                        logits = model.forward_features(image, question, ques_len)
+                elif maps:
                     logits, av, aq = model.forward_with_attention(image, question, ques_len)
                 else:
                     logits = model(image, question, ques_len)
@@ -144,6 +163,8 @@ def main(argv=None):
                 a_q[idx] = aq.permute(1, 0, 2).float().cpu()
     if device.type == "cuda":
         torch.cuda.synchronize()
+        if cached and bad_indices():
+            raise IndexError("image indices lay outside the feature table (their rows were zeros)")
         if args.precision == "fast" and args.opt_lvl == 0:
             from . import _lib
             _lib.check_range()                   # raises if an operand of the tolerance mode left the FP16-piece range

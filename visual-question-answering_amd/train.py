@@ -218,6 +218,35 @@ def check_dropout(model_name: str, dropout: float, opt_lvl: int = 0) -> None:
         raise ValueError("--dropout is not available with --opt_lvl >= 1 (the reduced-precision mode)")
 
 
+FEATURE_MODELS = ("attention", "attention_resnet", "attention_bert")
+
+
+def check_image_features(args, world: int = 1, validates: bool = False) -> None:
+    """--image_features PATH [--val_image_features PATH]: train (validate) from feature tables of the frozen encoder in eval
+    mode (features.FeatureTable, written by ``python -m vqa_amd.extract``) instead of running the encoder in the step.
+    Refused: a trainable encoder (--vgg_train true: its features change every step), models without a feature grid, a
+    validation run (`validates`) without its own table, a validation table without a training table, and a data-parallel run
+    (`world` > 1) whose path does not hold ``{rank}`` -- every rank's split has its own seed, so every rank needs its own table."""
+    path, val_path = getattr(args, "image_features", None), getattr(args, "val_image_features", None)
+    if not path:
+        if val_path:
+            raise ValueError("--val_image_features needs --image_features (the training table)")
+        return
+    if getattr(args, "vgg_train", False):
+        raise ValueError("--image_features is not available with --vgg_train true: cached features are those of a frozen encoder")
+    if args.model not in FEATURE_MODELS:
+        raise ValueError("--image_features applies to the co-attention models (--model %s), not to %s: it has no feature grid"
+                         % (" | ".join(FEATURE_MODELS), args.model))
+    if validates and not val_path:
+        raise ValueError("--image_features with a validation run (--val_size / --val_batches) needs --val_image_features: the "
+                         "validation split has its own images")
+    if world > 1:
+        for flag, p in (("--image_features", path), ("--val_image_features", val_path)):
+            if p and "{rank}" not in p:
+                raise ValueError("%s with WORLD_SIZE = %d needs {rank} in the path: every rank's split has its own seed, so "
+                                 "every rank reads its own table" % (flag, world))
+
+
 def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, affinity: str = "reference",
                 co_attention: str = "parallel", **kw) -> nn.Module:
     """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`; affinity: see
@@ -622,6 +651,29 @@ class Trainer:
         self.optimizer.step()
         return loss
 
+    def step_features(self, features, question, ques_len, label, targets=None) -> torch.Tensor:
+        """One optimisation step from already-encoded image features [B, N, d] (fp32, device-resident: the rows
+        ``features.gather_features`` takes from a feature table) -- the body of `step` from ``forward_features`` on.  The
+        image encoder is never called, so nothing runs ahead and its BatchNorm statistics stay as they are; the loss, the
+        backward, the gradient reducer and the optimiser are `step`'s."""
+        if (targets is not None) != (self.loss != "ce"):
+            raise ValueError("Trainer(loss=%r).step_features: %s" % (self.loss, "targets=(ans_idx, ans_score) needed"
+                                                                    if targets is None else "takes labels, not targets"))
+        if not hasattr(self.model, "forward_features"):
+            raise ValueError("step_features needs a co-attention model (forward_features); %s has no feature grid"
+                             % type(self.model).__name__)
+        tk = dict(labels=label) if targets is None else dict(targets=tuple(targets), loss_kind=self.loss)
+        with self._autocast():
+            logits, loss = self.model.forward_features(features, question, ques_len, **tk)
+        self.optimizer.zero_grad()
+        if self.reducer is not None:
+            self.reducer.prepare()
+        loss.backward()
+        if self.reducer is not None:
+            self.reducer.finish()
+        self.optimizer.step()
+        return loss
+
     def set_precision(self, precision: str) -> None:
         self.precision = precision
         set_products(self.model, precision)
@@ -664,14 +716,19 @@ class Trainer:
             loss.check_labels()
 
     @torch.no_grad()
-    def validate(self, batches) -> Dict[str, float]:
+    def validate(self, batches, features: bool = False) -> Dict[str, float]:
         """Accuracy / mean CE under eval() (main.py:290-351, without its n_iters+1 / n_iters slip).
         With encoder run-ahead, an encoder pass queued for the next training batch is waited for first
         (its BatchNorm running-statistics update is then already included, i.e. one batch earlier than
         in the serial schedule); pass next_image=None on the step before validating to avoid that.
         Batches are (image, question, ques_len, label) or, with soft answer targets, (..., label, ans_idx, ans_score): the
         dict then gains `vqa_score` (the mean of min(1, t[pred]) over all samples, in [0, 1]: with one-hot targets it is
-        `accuracy` / 100; on the GPU through coattn_vqa_score, summed on the device and read once), and `loss` is this trainer's own loss kind."""
+        `accuracy` / 100; on the GPU through coattn_vqa_score, summed on the device and read once), and `loss` is this trainer's own loss kind.
+        features=True: the first element of a batch is the encoded image features [B, N, d] (the rows of a feature table),
+        handed to ``model.forward_features``; the image encoder is not called."""
+        if features and not hasattr(self.model, "forward_features"):
+            raise ValueError("validate(features=True) needs a co-attention model (forward_features); %s has no feature grid"
+                             % type(self.model).__name__)
         if self.enc_stream is not None:
             torch.cuda.current_stream(self.device).wait_stream(self.enc_stream)
         self.model.eval()
@@ -679,7 +736,8 @@ class Trainer:
         loss = 0.0
         score = None
         for image, question, ques_len, label, *targets in batches:
-            logits = self.model(image, question, ques_len)
+            logits = (self.model.forward_features(image, question, ques_len) if features
+                      else self.model(image, question, ques_len))
             if self.loss != "ce":
                 if not targets:
                     raise ValueError("Trainer(loss=%r).validate: the batches carry no answer targets" % self.loss)
@@ -708,14 +766,29 @@ class SyntheticVQADataset(torch.utils.data.Dataset):
     in for the dataset files this environment does not have; feeds the same DataLoader(batch_size, shuffle, drop_last,
     num_workers) as main.py:129-130."""
 
-    def __init__(self, n_samples, image_size, max_seq_len, vocab_size, num_classes, seed, num_answers: int = 0):
+    def __init__(self, n_samples, image_size, max_seq_len, vocab_size, num_classes, seed, num_answers: int = 0,
+                 images: bool = True):
         self.n, self.size, self.T, self.vocab, self.K, self.seed = n_samples, image_size, max_seq_len, vocab_size, num_classes, seed
         self.A = num_answers          # > 0: samples also carry `answers` int32 [A], `answer_scores` fp32 [A] (synthetic_answers)
+        # images=False (a run on cached image features): the `image` slot carries the sample's index i -- the row of the feature
+        # table -- and no image.  The label is drawn after the image from the same generator, so the image is still drawn, once
+        # per index: the rest of the sample is kept and later epochs do not pay again.  Every other key keeps its bits.
+        self.images = images
+        self._memo = {}
 
     def __len__(self):
         return self.n
 
     def __getitem__(self, i):
+        if not self.images:
+            out = self._memo.get(i)
+            if out is None:
+                out = self._memo[i] = self._draw(i)
+                out["image"] = torch.tensor(i, dtype=torch.int64)
+            return dict(out)
+        return self._draw(i)
+
+    def _draw(self, i):
         g = torch.Generator().manual_seed(self.seed * 1000003 + i)
         n = int(torch.randint(min(3, self.T), self.T + 1, (1,), generator=g))
         q = torch.randint(2, self.vocab, (self.T,), generator=g) * (torch.arange(self.T) < n)
@@ -824,6 +897,14 @@ def build_parser():
     ap.add_argument("--weight_decay", type=float, default=0.0, help="decoupled weight decay (AdamW); --optimizer hip only")
     ap.add_argument("--clip_grad_norm", type=float, default=None,
                     help="clip the gradients to this global norm ahead of the update; --optimizer hip only")
+    ap.add_argument("--image_features", type=str, default=None,
+                    help="train from this feature table (python -m vqa_amd.extract --split train) instead of running the "
+                         "frozen image encoder in the step: each batch's rows are gathered on the device.  The features are the "
+                         "encoder's in eval mode (running statistics), as validation and prediction see them; the table's "
+                         "sidecar must match the run (model, image size, split, seed, samples = --num_steps x --batch_size).  "
+                         "Co-attention models only, not with --vgg_train true; {rank} in the path for data-parallel runs")
+    ap.add_argument("--val_image_features", type=str, default=None,
+                    help="the validation split's table (--split val); required when a run on --image_features validates")
     return ap
 
 
@@ -835,6 +916,11 @@ def main(argv=None):
         raise NotImplementedError("TODO: test mode")          # as the reference, main.py:286-287
     if not args.synthetic:
         raise SystemExit("only --synthetic true is available: the VQA dataset is not present in this environment")
+    n_val = args.val_batches or args.val_size // args.batch_size
+    try:
+        check_image_features(args, int(os.environ.get("WORLD_SIZE", "1")), validates=n_val > 0)
+    except ValueError as e:
+        raise SystemExit(str(e))
 
     rank, world, local = vdist.init_from_env()
     if torch.cuda.is_available():
@@ -866,8 +952,17 @@ def main(argv=None):
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
 
+    cached = bool(args.image_features)                           # the `image` slot of a batch then holds table rows' indices
+
+    def table(path, split, seed, n_samples):
+        from .features import FeatureTable
+        tab = FeatureTable.load(path.replace("{rank}", str(rank)), device)
+        tab.check(args.model, size[0], split, seed, n_samples)   # (before the first step: a table of another run is refused)
+        return tab
+
     def loader(n_samples, seed):
-        ds = SyntheticVQADataset(n_samples, size, args.max_seq_length, args.vocab_size, n_cls, seed, num_answers=n_ans)
+        ds = SyntheticVQADataset(n_samples, size, args.max_seq_length, args.vocab_size, n_cls, seed, num_answers=n_ans,
+                                 images=not cached)
         return torch.utils.data.DataLoader(ds, args.batch_size, shuffle=True, drop_last=True, num_workers=args.num_workers,
                                            generator=torch.Generator().manual_seed(seed))
 
@@ -879,13 +974,16 @@ def main(argv=None):
 
     train_loader = loader(args.num_steps * args.batch_size, 1234 + rank)
     steps_per_epoch = len(train_loader)
+    feats = table(args.image_features, "train", 1234 + rank, args.num_steps * args.batch_size) if cached else None
     val = []
-    n_val = args.val_batches or args.val_size // args.batch_size
     if n_val > 0:
+        val_feats = table(args.val_image_features, "val", 987654 + rank, n_val * args.batch_size) if cached else None
         for b in loader(n_val * args.batch_size, 987654 + rank):
             image, question, ques_len, label, *extras = sorted_host(b)
             image = image.to(device)
-            if cl:
+            if cached:
+                image = val_feats.gather(image)                  # this batch's rows, gathered once
+            elif cl:
                 image = image.contiguous(memory_format=torch.channels_last)
             val.append((image, question.to(device), ques_len, label.to(device), *[e.to(device) for e in extras]))
     val_every = args.val_interval or (args.log_interval if val else 0)
@@ -893,22 +991,31 @@ def main(argv=None):
     t0 = time.time()
     step = 0
     for epoch in range(args.num_epochs):
-        batches = DevicePrefetcher((sorted_host(b) for b in train_loader), device, cl)
+        batches = DevicePrefetcher((sorted_host(b) for b in train_loader), device, cl and not cached)
         for image, question, ques_len, label, *extras in batches:
             validate_now = bool(val) and val_every > 0 and (step + 1) % val_every == 0
-            # no encoder run-ahead across a validation: its BatchNorm statistics must be those of this step
-            nxt, ready = (None, None) if validate_now else batches.peek_image()
-            loss = trainer.step(image, question, ques_len, label, next_image=nxt, next_ready=ready,
-                                targets=tuple(extras) if extras else None)
+            if cached:                                           # `image`: the batch's row indices, on the device
+                loss = trainer.step_features(feats.gather(image), question, ques_len, label,
+                                             targets=tuple(extras) if extras else None)
+            else:
+                # no encoder run-ahead across a validation: its BatchNorm statistics must be those of this step
+                nxt, ready = (None, None) if validate_now else batches.peek_image()
+                loss = trainer.step(image, question, ques_len, label, next_image=nxt, next_ready=ready,
+                                    targets=tuple(extras) if extras else None)
             if (step + 1) % args.log_interval == 0:
                 trainer.check_labels()                           # (the host synchronises here anyway to read the loss)
                 trainer.check_range()
+                if cached and device.type == "cuda":
+                    from .features import bad_indices
+                    n_bad = bad_indices()
+                    if n_bad:
+                        raise IndexError("%d image indices lay outside the feature table (their rows were zeros)" % n_bad)
                 if rank == 0:
                     print(json.dumps({"epoch": epoch + 1, "step": step + 1, "steps_per_epoch": steps_per_epoch,
                                       "loss": round(float(loss), 5), "precision": trainer.precision,
                                       "pairs_per_s": round(world * args.batch_size * (step + 1) / (time.time() - t0), 2)}))
             if validate_now:
-                m = trainer.validate(val)
+                m = trainer.validate(val, features=cached)
                 if rank == 0:
                     print(json.dumps({"step": step + 1, "val_accuracy": round(m["accuracy"], 3), "val_loss": round(m["loss"], 5),
                                       **({"val_vqa_score": round(m["vqa_score"], 5)} if "vqa_score" in m else {})}))
