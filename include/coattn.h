@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward; v0.20.0: the gather of cached image features from a table).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward; v0.20.0: the gather of cached image features from a table; v0.21.0: attention overlays, the maps upsampled over the image and blended into it as uint8 pictures).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -807,6 +807,62 @@ int coattn_dropout_backward(const void* g, void* dx, long long n, float p, void*
 int coattn_features_gather_supported(long long S, long long B, int N, int d, int table_dtype, int flags);
 int coattn_features_gather(const void* table, int table_dtype, const void* idx, int idx_dtype, void* out, int32_t* bad_idx,
                            long long S, long long B, int N, int d, int flags, void* stream);
+
+/* ---- attention overlays: the maps drawn over the image they were computed from (v0.21.0; csrc/overlay.hip) ----
+ * What coattn_infer returns, as pictures: each level's image attention upsampled to the image's size and blended into the
+ * de-normalised image, and under it a strip of that level's question attention.  One launch, 64-bit output offsets, no
+ * allocation, no synchronisation, nothing read on the host but `p`: the call can be captured into a HIP graph.
+ *   image     : fp32 [B][3][H][W] at the element strides sB, sC, sH, sW (any: NCHW, channels-last, padded rows); normalised as
+ *               (x - mean) / std per channel.  A contiguous image -- sW = 1 and sB, sC, sH multiples of 4 -- is read with 16-byte
+ *               loads and must be 16-byte aligned; any other is read element by element (4-byte aligned)
+ *   a_v       : fp32 [L][B][Gh*Gw], the row-major grid coattn_infer writes (av_out)
+ *   a_q       : fp32 [L][B][T] (aq_out), or NULL (then strip_h must be 0); read only when strip_h > 0
+ *   q_len     : B int32 question lengths on the device, or NULL (every row has T entries); a length is clamped to [1, T]
+ *   p         : host structure, below; p->lut a device pointer to fp32 [256][3] in [0, 1], read by the heat mode only
+ *   out       : uint8 [B][L+1][H+strip_h][W][3], interleaved RGB, 16-byte aligned.  Panel 0 is the de-normalised image (its
+ *               strip rows are 0), panel 1+l is level l; every byte is written
+ *   bad_maps  : one int32 on the device, may be NULL; the call ADDS to it (one integer atomic per bad map), the caller zeroes it
+ * One workgroup of COATTN_OVERLAY_THREADS threads owns a band of COATTN_OVERLAY_ROWS output rows of one sample for all
+ * panels: it reads the image band once and writes L+1 bands; the sample's L maps and their reciprocal maxima are found by the
+ * workgroup itself in LDS.  A thread takes 4 pixels at a time and stores them as 12 bytes = 3 whole dwords (hence W % 4 == 0).
+ *
+ * THE ARITHMETIC IS THE CONTRACT.  Every line is one correctly rounded fp32 operation, in this order, none contracted into an
+ * FMA; the same inputs give the same bytes on every run and in every layout of the image.
+ *   Map normalisation, per (l, b):   mx = max a_v;   r = 1.0f / mx;   m[n] = a[n] * r.
+ *     A map is BAD if an entry is NaN, +-inf or < 0, if mx == 0, or if r is not finite (a denormal maximum).  A bad map renders as
+ *     m = 0 everywhere and adds exactly 1 to *bad_maps (by the workgroup of the sample's band 0 only).  a_q follows the same rule
+ *     over its first len_b entries (all T where q_len is NULL), with its own r_q; a bad a_q row counts as well.
+ *   Bilinear upsampling, half-pixel centres, edges clamped (F.interpolate(mode="bilinear", align_corners=False)):
+ *     sy = (float)Gh / (float)H;   src = ((float)y + 0.5f) * sy - 0.5f;   src = max(src, 0);
+ *     i0 = min((int)floor(src), Gh-1);   i1 = min(i0+1, Gh-1);   w1 = src - (float)i0;   w0 = 1 - w1;   the same in x (Gw, W);
+ *     top = m[i0,j0]*wx0 + m[i0,j1]*wx1;   bot likewise on row i1;   u = top*wy0 + bot*wy1.     (H < Gh, downsampling, included)
+ *   Pixel:   xh_c = clamp01(img * std_c + mean_c), clamp01(x) = x >= 0 ? (x <= 1 ? x : 1) : 0 -- a NaN pixel gives 0 and
+ *     touches that pixel only;
+ *     COATTN_OVERLAY_MASK (brightness follows attention):   g = floor + (1-floor)*u, 1-floor computed once;   o_c = xh_c * g;
+ *     COATTN_OVERLAY_HEAT:   k = (int)(u*255 + 0.5f);   o_c = (1-alpha)*xh_c + alpha*lut[k][c], 1-alpha computed once;
+ *     byte = (int)(clamp01(o_c)*255 + 0.5f);   panel 0: o_c = xh_c.
+ *   Question strip, the rows y >= H of panels 1..L:   T cells, cell t = (x*T) / W in integers;   m_q = a_q[l][b][t] * r_q;
+ *     heat: the colour lut[(int)(m_q*255 + 0.5f)], mask: the grey m_q, each through `byte`;   cells t >= len_b are 0.
+ * Supported (the query returns 1): B >= 1, 1 <= L <= 8, 1 <= H, W <= 4096, W % 4 == 0, 1 <= Gh, Gw <= 64, 0 <= strip_h <= 4096,
+ * strip_h == 0 or 1 <= T <= min(W, 4096), mode one of the two, and B times the bands of a sample below 2^31.
+ * Argument errors -- an unsupported shape or mode, strip_h > 0 without a_q, a NULL image, a_v, p or out, the heat mode without
+ * p->lut, alpha or floor outside [0, 1], a std that is not finite or is 0, a mean that is not finite, a misaligned buffer --: -1
+ * with a coattn_last_error message before any device work. */
+#define COATTN_OVERLAY_HEAT 0
+#define COATTN_OVERLAY_MASK 1
+#define COATTN_OVERLAY_ROWS 8
+#define COATTN_OVERLAY_THREADS 256
+typedef struct coattn_overlay_params {
+  float mean[3];        /* the image's normalisation: pixel = img * std + mean */
+  float std[3];
+  float alpha;          /* heat mode: the weight of the colour */
+  float floor;          /* mask mode: the brightness where the attention is 0 */
+  const void* lut;      /* device fp32 [256][3] in [0, 1]; heat mode only (else may be NULL) */
+} coattn_overlay_params;
+int coattn_overlay_supported(int B, int L, int H, int W, int Gh, int Gw, int T, int strip_h, int mode);
+int coattn_overlay_render(const void* image, int64_t sB, int64_t sC, int64_t sH, int64_t sW, const void* a_v, const void* a_q,
+                          const int32_t* q_len, const coattn_overlay_params* p, void* out, int32_t* bad_maps, int B, int L, int H,
+                          int W, int Gh, int Gw, int T, int strip_h, int mode, void* stream);
 
 /* ---- building blocks (exported for the per-kernel parity tests) ------------------------ */
 

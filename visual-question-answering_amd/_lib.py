@@ -33,7 +33,8 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_embedding_supported", "coattn_embedding_workspace_bytes", "coattn_embedding_forward",
            "coattn_embedding_backward",
            "coattn_dropout_supported", "coattn_dropout_forward", "coattn_dropout_backward",
-           "coattn_features_gather_supported", "coattn_features_gather")
+           "coattn_features_gather_supported", "coattn_features_gather",
+           "coattn_overlay_supported", "coattn_overlay_render")
 
 F32 = 0
 IDS_I32, IDS_I64 = 0, 1   # ids_dtype of the word embedding calls (v0.18.0: COATTN_IDS_*)
@@ -46,6 +47,7 @@ FLAG_SPLIT2 = 32          # linear entry points: the two-piece width (hi + mid, 
 FLAG_F16PAIR = 64        # coattn_linear_forward: two FP16 pieces (the form the tolerance mode runs its projections in)
 FLAG_FAST16 = 128        # coattn_forward / coattn_backward / coattn_phrase_*: the tolerance mode (forward products on two FP16
                          # pieces = 22 bits, backward on two bf16 pieces = 16 bits; range report: coattn_status)
+OVERLAY_HEAT, OVERLAY_MASK = 0, 1   # mode of coattn_overlay_render (v0.21.0: COATTN_OVERLAY_*)
 LOSS_SOFT_CE, LOSS_BCE = 1, 2   # loss kinds of the soft-answer-target calls (v0.12.0: COATTN_LOSS_*)
 MAX_ANSWERS = 16         # answer slots per sample the soft-target kernels take
 LOSS_KINDS = {"soft_ce": LOSS_SOFT_CE, "bce": LOSS_BCE}
@@ -113,6 +115,11 @@ class LstmParams(C.Structure):
 
 class LstmParamGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+class OverlayParams(C.Structure):
+    # the attention overlays (v0.21.0): the image's normalisation, the two blend weights, the device pointer of the colour table
+    _fields_ = [("mean", C.c_float * 3), ("std", C.c_float * 3), ("alpha", C.c_float), ("floor", C.c_float), ("lut", C.c_void_p)]
 
 
 class GemmDesc(C.Structure):
@@ -187,10 +194,15 @@ FEATURES_SIGNATURES = {
     "coattn_features_gather": (_void("table") + _int("table_dtype") + _void("idx") + _int("idx_dtype") + _void("out bad_idx")
                                + _i64("S B") + _int("N d flags") + _void("stream")),
 }
-_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES, **DROPOUT_SIGNATURES, **FEATURES_SIGNATURES}
+# the attention overlays (v0.21.0), a table of its own as well
+OVERLAY_SIGNATURES = {
+    "coattn_overlay_render": (_void("image") + _i64("sB sC sH sW") + _void("a_v a_q q_len") + (("p", C.POINTER(OverlayParams)),)
+                              + _void("out bad_maps") + _int("B L H W Gh Gw T strip_h mode") + _void("stream")),
+}
+_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES, **DROPOUT_SIGNATURES, **FEATURES_SIGNATURES, **OVERLAY_SIGNATURES}
 _INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _TABLE.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
-_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1".split())
+_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1 bad_maps".split())
 _DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
 
 
@@ -382,6 +394,8 @@ def load() -> C.CDLL:
     lib.coattn_dropout_supported.argtypes = [C.c_int64]
     # cached image features (v0.20.0): the gather is tabled (FEATURES_SIGNATURES); (S, B, N, d, table_dtype, flags)
     lib.coattn_features_gather_supported.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
+    # attention overlays (v0.21.0): the render is tabled (OVERLAY_SIGNATURES); (B, L, H, W, Gh, Gw, T, strip_h, mode)
+    lib.coattn_overlay_supported.argtypes = [C.c_int] * 9
     _lib = lib
     return lib
 

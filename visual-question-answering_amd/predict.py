@@ -21,6 +21,17 @@ README roadmap.  Same command line as ``train.py`` (the reference's flags) plus 
   VQA accuracy of the prediction -- and the summary ``vqa_score``, their mean; ``loss`` is then that loss kind's mean.  With
   ``bce`` the reported probabilities are per-class sigmoids (they do not sum to 1), else softmax probabilities.
 
+* ``--attention_overlays DIR`` (``attention*`` models on images): the maps as pictures.  For each of the first
+  ``--overlay_samples`` samples in dataset order (default 16; 0 = all) ``DIR/sample_{index:06d}.png``: the image and, beside
+  it, the word, phrase and sentence levels' image attention upsampled over it (with ``--co_attention alternating`` its step-2
+  and step-3 image maps) -- ``--overlay_mode heat`` (default): a colour ramp blended in at ``--overlay_alpha``; ``mask``: the
+  image darkened to ``--overlay_floor`` where the attention is 0, as in the paper's figures --, and under each level
+  ``--overlay_strip`` rows (default 32) of its question attention, one cell per token position, black past ``ques_len`` under
+  ``--question_mask true``.  ``DIR/index.json`` lists per sample ``{file, index, label, top, prob, ques_len, question}``
+  (the token ids: the data is synthetic, so no words are drawn).  ``--image_mean`` / ``--image_std``: the normalisation the
+  images carry (default ImageNet's, main.py:126).  Rendered per batch on the device in one HIP launch
+  (``vqa_amd.overlay.render_attention``); only the chosen samples' bytes come to the host.
+
 The maps come from the forward-only co-attention (``coattn_infer``): no state for a backward is written.  One process:
 multi-GPU prediction is not offered.  Data: the synthetic test split (its own seed), every sample (no drop_last).
 """
@@ -50,6 +61,20 @@ def build_parser():
     ap.add_argument("--attention_maps", type=str, default=None,
                     help="write the co-attention maps here (.npz; attention* models only)")
     ap.add_argument("--test_size", type=int, default=1000, help="test samples (synthetic)")
+    ap.add_argument("--attention_overlays", type=str, default=None, metavar="DIR",
+                    help="write the attention maps drawn over the images here (PNG sheets and index.json; attention* models on "
+                         "images only)")
+    ap.add_argument("--overlay_mode", default="heat", choices=["heat", "mask"],
+                    help="'heat' = a colour ramp blended into the image; 'mask' = brightness follows attention")
+    ap.add_argument("--overlay_samples", type=int, default=16, help="overlays of the first M samples in dataset order (0 = all)")
+    ap.add_argument("--overlay_alpha", type=float, default=0.6, help="heat mode: the weight of the colour, in [0, 1]")
+    ap.add_argument("--overlay_floor", type=float, default=0.3, help="mask mode: the brightness at zero attention, in [0, 1]")
+    ap.add_argument("--image_mean", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="the mean the images were normalised with (default: ImageNet's)")
+    ap.add_argument("--image_std", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="the std the images were normalised with (default: ImageNet's)")
+    ap.add_argument("--overlay_strip", type=int, default=32, metavar="PX",
+                    help="rows of the question-attention strip under every level (0 = none)")
     return ap
 
 
@@ -60,6 +85,17 @@ def main(argv=None):
         ap.error("--model_ckpt is required: prediction runs a trained checkpoint (train.py --save_path / model_{step}.pth)")
     if args.attention_maps and not args.model.startswith("attention"):
         ap.error("--attention_maps needs a co-attention model (--model attention*); %r has no attention maps" % args.model)
+    if args.attention_overlays:
+        if not args.model.startswith("attention"):
+            ap.error("--attention_overlays needs a co-attention model (--model attention*); %r has no attention maps" % args.model)
+        if args.image_features:
+            ap.error("--attention_overlays draws over the images; a run from --image_features (cached features) has no pixels")
+        if args.overlay_samples < 0:
+            ap.error("--overlay_samples must be >= 0 (0 = every sample), got %d" % args.overlay_samples)
+        if args.overlay_strip < 0:
+            ap.error("--overlay_strip must be >= 0, got %d" % args.overlay_strip)
+        if not (0.0 <= args.overlay_alpha <= 1.0 and 0.0 <= args.overlay_floor <= 1.0):
+            ap.error("--overlay_alpha and --overlay_floor must lie in [0, 1]")
     if args.topk < 1 or args.test_size < 1:
         ap.error("--topk and --test_size must be >= 1")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -108,6 +144,16 @@ def main(argv=None):
             ap.error(str(e))
     loader = torch.utils.data.DataLoader(ds, args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
     maps = bool(args.attention_maps)
+    overlays = bool(args.attention_overlays)
+    if overlays:
+        if device.type != "cuda":
+            ap.error("--attention_overlays renders on the GPU (there is no CPU fallback)")
+        from . import overlay as OV
+        os.makedirs(args.attention_overlays, exist_ok=True)
+        n_over = len(ds) if args.overlay_samples == 0 else min(args.overlay_samples, len(ds))
+        over_kw = dict(mode=args.overlay_mode, alpha=args.overlay_alpha, floor=args.overlay_floor, strip=args.overlay_strip,
+                       mean=tuple(args.image_mean or OV.IMAGENET_MEAN), std=tuple(args.image_std or OV.IMAGENET_STD))
+        sheets = {}                                            # sample index -> (file name, token ids)
 
     S = len(ds)
     top = torch.zeros((S, k), dtype=torch.int64)
@@ -137,13 +183,14 @@ def main(argv=None):
             elif cl:
                 image = image.contiguous(memory_format=torch.channels_last)
             question, label_d = question.to(device), label.to(device)
+            draw = overlays and int(idx.min()) < n_over         # a chosen sample is in this batch
             with T.autocast_for(args.opt_lvl, device):
                 if cached:
                     if maps:
                         logits, av, aq = model.forward_features_with_attention(image, question, ques_len)
                     else:
                         logits = model.forward_features(image, question, ques_len)
-                elif maps:
+                elif maps or draw:
                     logits, av, aq = model.forward_with_attention(image, question, ques_len)
                 else:
                     logits = model(image, question, ques_len)
@@ -155,6 +202,15 @@ def main(argv=None):
             probs = torch.sigmoid(logits.float()) if args.loss == "bce" else F.softmax(logits.float(), dim=1)
             pv, pi = probs.topk(k, dim=1)
             top[idx], prob[idx], labels[idx], lens[idx] = pi.cpu(), pv.cpu(), label, ques_len
+            if draw:
+                # drawn on the device from the maps as they are; only the chosen samples' panels come to the host
+                chosen = (idx < n_over).nonzero().flatten()
+                panels = OV.render_attention(image, av.float(), aq.float(), ques_len if args.question_mask else None, **over_kw)
+                panels = panels[chosen.to(device)].cpu()
+                for j, i in enumerate(idx[chosen].tolist()):
+                    name = "sample_%06d.png" % i
+                    OV.write_png(os.path.join(args.attention_overlays, name), OV.sheet(panels[j]))
+                    sheets[i] = (name, question[int(chosen[j])].tolist())
             if maps:
                 if a_v is None:
                     a_v = torch.zeros((S,) + tuple(av.shape[:1]) + tuple(av.shape[2:]), dtype=torch.float32)
@@ -165,6 +221,9 @@ def main(argv=None):
         torch.cuda.synchronize()
         if cached and bad_indices():
             raise IndexError("image indices lay outside the feature table (their rows were zeros)")
+        if overlays and OV.bad_maps():
+            raise FloatingPointError("attention maps could not be normalised for their overlays (NaN, infinite, negative or all "
+                                     "zero); those panels were drawn without attention")
         if args.precision == "fast" and args.opt_lvl == 0:
             from . import _lib
             _lib.check_range()                   # raises if an operand of the tolerance mode left the FP16-piece range
@@ -179,6 +238,11 @@ def main(argv=None):
                 if soft:
                     rec["score"] = float(scores[i])
                 fh.write(json.dumps(rec) + "\n")
+    if overlays:
+        with open(os.path.join(args.attention_overlays, "index.json"), "w") as fh:
+            json.dump([{"file": sheets[i][0], "index": i, "label": int(labels[i]), "top": top[i].tolist(),
+                        "prob": [float(x) for x in prob[i]], "ques_len": int(lens[i]), "question": sheets[i][1]}
+                       for i in sorted(sheets)], fh, indent=1)
     if maps:
         N = a_v.shape[-1]
         H = int(round(math.sqrt(N)))
