@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward; v0.20.0: the gather of cached image features from a table; v0.21.0: attention overlays, the maps upsampled over the image and blended into it as uint8 pictures).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward; v0.20.0: the gather of cached image features from a table; v0.21.0: attention overlays, the maps upsampled over the image and blended into it as uint8 pictures; v0.22.0: the first convolution computed twice and never stored).
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface
@@ -653,6 +653,26 @@ int coattn_conv1_bn_exact_forward(const void* image, const void* weight, const v
                                   void* stream);
 int coattn_conv1_probe(const void* image, const void* weight, void* x, void* ws, int B, int H, int W, int order, int step,
                        int halves, int skip, void* stream);
+
+/* ---- layer 1 with the convolution computed twice and never stored (v0.22.0) ----
+ * The results of coattn_conv1_bn_exact_forward bit for bit -- y, save_mean, save_invstd and the running statistics -- without
+ * x: the first kernel is that call's with its stores left out (the statistics in the same order), the second is unchanged, the
+ * third computes the same chain of MFMAs again and applies the normalise map, the 2x2 maximum and the ReLU of
+ * coattn_bn_exact_forward's third kernel (the same device functions, the window's members in the same order) in registers.  y
+ * is the only large tensor written; the image is read twice.
+ *   coattn_conv1_bn_recompute_workspace_bytes : the partials alone (coattn_conv1_bn_exact_workspace_bytes with with_x = 0)
+ *   every argument : as for coattn_conv1_bn_exact_forward, which has x_out in addition; the same shapes
+ *                  (coattn_conv1_bn_exact_supported), pool 0 or 1, the ReLU always applied
+ * The third kernel's workgroup takes COATTN_CONV1_RECOMPUTE_CHUNK consecutive samples of one tile (pooled: 2 image rows x 16
+ * columns; not pooled: 32 consecutive pixels).
+ * Argument errors (a shape that is not covered, a NULL or misaligned pointer, y == image, momentum outside [0, 1], eps <= 0):
+ * -1 before any HIP call; the workspace size of a shape that is not covered is 0. */
+#define COATTN_CONV1_RECOMPUTE_CHUNK 8
+size_t coattn_conv1_bn_recompute_workspace_bytes(int B, int H, int W);
+int coattn_conv1_bn_recompute_forward(const void* image, const void* weight, const void* gamma, const void* beta,
+                                      void* running_mean, void* running_var, double momentum, double eps, void* y,
+                                      void* save_mean, void* save_invstd, void* ws, int B, int H, int W, int Cin, int Cout, int pool,
+                                      int dtype, void* stream);
 
 /* ---- the sentence LSTM of the question hierarchy (v0.17.0; csrc/lstm.hip) ----
  * Reference model.py:286-296 -- pack_padded_sequence -> nn.LSTM (one layer, one direction, zero initial state) ->

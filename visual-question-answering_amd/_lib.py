@@ -28,7 +28,7 @@ EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coa
            "coattn_bn_supported", "coattn_bn_workspace_bytes", "coattn_bn_relu_pool_forward", "coattn_relu_pool_forward",
            "coattn_bn_exact_geometry", "coattn_bn_exact_workspace_bytes", "coattn_bn_exact_forward",
            "coattn_conv1_bn_exact_supported", "coattn_conv1_bn_exact_workspace_bytes", "coattn_conv1_bn_exact_forward",
-           "coattn_conv1_probe",
+           "coattn_conv1_probe", "coattn_conv1_bn_recompute_workspace_bytes", "coattn_conv1_bn_recompute_forward",
            "coattn_lstm_supported", "coattn_lstm_workspace_bytes", "coattn_lstm_forward", "coattn_lstm_backward",
            "coattn_embedding_supported", "coattn_embedding_workspace_bytes", "coattn_embedding_forward",
            "coattn_embedding_backward",
@@ -199,7 +199,16 @@ OVERLAY_SIGNATURES = {
     "coattn_overlay_render": (_void("image") + _i64("sB sC sH sW") + _void("a_v a_q q_len") + (("p", C.POINTER(OverlayParams)),)
                               + _void("out bad_maps") + _int("B L H W Gh Gw T strip_h mode") + _void("stream")),
 }
-_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES, **DROPOUT_SIGNATURES, **FEATURES_SIGNATURES, **OVERLAY_SIGNATURES}
+# layer 1 of the frozen encoder with the convolution computed twice and never stored (v0.22.0), a table of its own as well;
+# momentum and eps are the double arguments
+CONV1_RECOMPUTE_CHUNK = 8   # COATTN_CONV1_RECOMPUTE_CHUNK: samples per workgroup of the third kernel
+CONV1_SIGNATURES = {
+    "coattn_conv1_bn_recompute_forward": (_void("image weight gamma beta running_mean running_var") + _of(C.c_double)("momentum eps")
+                                          + _void("y save_mean save_invstd ws") + _int("B H W Cin Cout pool dtype")
+                                          + _void("stream")),
+}
+_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES, **DROPOUT_SIGNATURES, **FEATURES_SIGNATURES, **OVERLAY_SIGNATURES,
+          **CONV1_SIGNATURES}
 _INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _TABLE.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
 _DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1 bad_maps".split())
@@ -378,6 +387,9 @@ def load() -> C.CDLL:
     lib.coattn_conv1_bn_exact_forward.argtypes = ([C.c_void_p] * 6 + [C.c_double] * 2 + [C.c_void_p] * 5 + [C.c_int] * 7
                                                   + [C.c_void_p])
     lib.coattn_conv1_probe.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]
+    # the same without x (v0.22.0): the forward is tabled (CONV1_SIGNATURES); (B, H, W)
+    lib.coattn_conv1_bn_recompute_workspace_bytes.argtypes = [C.c_int] * 3
+    lib.coattn_conv1_bn_recompute_workspace_bytes.restype = C.c_size_t
     # the sentence LSTM (v0.17.0): (X, len, p, out, x_masked, saved, ws, B, T, E, H, dtype, flags, stream) and
     # (X, len, p, out, saved, g_out, g_xmasked, dX, pg, accumulate, ws, B, T, E, H, dtype, flags, stream)
     lib.coattn_lstm_supported.argtypes = [C.c_int] * 5

@@ -37,8 +37,12 @@
 //
 // Layer 1 (coattn_conv1_bn_exact_forward, C-ABI 0.16.0): conv1_stats_miopen_kernel computes the 3 -> 64 channel convolution in the
 // stock convolution's arithmetic and, in the same pass, the partials bn_stats_miopen_kernel would have left; the two kernels
-// above follow unchanged.
+// above follow unchanged.  coattn_conv1_bn_recompute_forward (C-ABI 0.22.0) gives the same results without ever storing the
+// convolution output: conv1_stats_miopen_kernel<D, false> sums the statistics alone, conv1_norm_pool_kernel computes the
+// convolution again and normalises, pools and writes y.
 #include <math.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -292,21 +296,13 @@ __device__ __forceinline__ constexpr int conv1_term(int i, int g) { return (i / 
 // The wave walks the B samples in order; each (pixel, channel) is added into its own (sum, sq) exactly as the element of
 // thread (channel group, pixel) of bn_stats_miopen_kernel is: sum += x, sq = fma(x, x, sq).  The tree then halves the g1 pixels of each pixel group (g1 = 16: two groups per workgroup; g1 = 8:
 // four) in the stock order and writes the same [C][2] partials.
+// The operands of lane half g for the pixel (h, w) and the output channel ch: wt[i] the weight and off[i] the image offset of the
+// term MFMA i takes (0 where the term is a zero: the load is made and dropped); bit i of the result: term i is a tap inside the
+// image.  `live` = false: a masked pixel, every term a zero.
 template <int D>
-__global__ __launch_bounds__(128) void conv1_stats_miopen_kernel(
-    const float* __restrict__ image, const float* __restrict__ weight, float* __restrict__ x, float* __restrict__ partial, int B,
-    int H, int W, int g1, int ngrps) {
-  __shared__ float lds[kConv1Pixels * 64 * 2];                      // [pixel][channel]{sum, sq}
-  const int hh = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 5, p = lane & 31;
-  const int HW = H * W;
-  const int pbase = blockIdx.x * kConv1Pixels, pix = pbase + p;
-  const bool live = pix < HW;                                       // (of the pixel whose terms this lane loads)
-  const bool full = pbase + kConv1Pixels <= HW;                     // (of the workgroup: no masked pixel)
-  const int h = pix / W, w = pix - h * W;
-  const int ch = 32 * hh + p;
-  float wt[kConv1Mfmas];
-  int off[kConv1Mfmas];                                             // (0 where the term is a zero: the load is made and dropped)
-  unsigned real = 0;                                                // bit i: term i is a tap inside the image
+__device__ __forceinline__ unsigned conv1_operands(const float* __restrict__ weight, int ch, int g, int h, int w, bool live, int H,
+                                                   int W, float (&wt)[kConv1Mfmas], int (&off)[kConv1Mfmas]) {
+  unsigned real = 0;
 #pragma unroll
   for (int i = 0; i < kConv1Mfmas; ++i) {
     const int k = conv1_term<D>(i, g);
@@ -318,6 +314,71 @@ __global__ __launch_bounds__(128) void conv1_stats_miopen_kernel(
     const float wk = weight[ch * 27 + (k < 27 ? k : 26)];
     wt[i] = k < 27 ? wk : 0.f;
   }
+  return real;
+}
+
+// a term of the sample at `base` (uniform over the wave).  An unsigned BYTE offset keeps the load in its scalar-base form, one
+// VGPR of address per term instead of a 64-bit pair computed per load; the kernel that stores x keeps the element offsets it
+// was tuned with.
+__device__ __forceinline__ float conv1_load(const float* __restrict__ base, int off) { return base[off]; }
+__device__ __forceinline__ float conv1_load(const float* __restrict__ base, unsigned boff) {
+  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + boff);
+}
+
+// One output chain: sixteen MFMAs from 0 over `terms`; a term's register is reloaded from `ahead` as soon as its MFMA has read it.
+template <typename Off>
+__device__ __forceinline__ f32x16 conv1_chain(float (&terms)[kConv1Mfmas], const float (&wt)[kConv1Mfmas],
+                                              const Off (&off)[kConv1Mfmas], unsigned real, const float* __restrict__ ahead) {
+  f32x16 acc;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) {
+    const float t = (real >> i) & 1u ? terms[i] : 0.f;
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(t, wt[i], acc, 0, 0, 0);
+    terms[i] = conv1_load(ahead, off[i]);
+  }
+  return acc;
+}
+
+// The same for both channel halves at once: two chains over one set of terms, the MFMAs of the two interleaved (each chain's order
+// is its own: the bits are conv1_chain's).  One wave then loads a pixel's terms once for all 64 channels.
+template <typename Off>
+__device__ __forceinline__ void conv1_chain2(float (&terms)[kConv1Mfmas], const float (&wt0)[kConv1Mfmas],
+                                             const float (&wt1)[kConv1Mfmas], const Off (&off)[kConv1Mfmas], unsigned real,
+                                             const float* __restrict__ ahead, f32x16& acc0, f32x16& acc1) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc0[e] = acc1[e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) {
+    const float t = (real >> i) & 1u ? terms[i] : 0.f;
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(t, wt0[i], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(t, wt1[i], acc1, 0, 0, 0);
+    terms[i] = conv1_load(ahead, off[i]);
+  }
+}
+
+// STORE = false (pass A of coattn_conv1_bn_recompute_forward): the statistics alone, x is never written and `x` is not read;
+// without the store addresses three waves per SIMD fit without scratch (four do not), which the occupancy hint asks for --
+// a minimum of 1 is the default: the storing kernel is compiled as before.
+template <int D, bool STORE = true>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(STORE ? 1 : 3))) void conv1_stats_miopen_kernel(
+    const float* __restrict__ image, const float* __restrict__ weight, float* __restrict__ x, float* __restrict__ partial, int B,
+    int H, int W, int g1, int ngrps) {
+  __shared__ float lds[kConv1Pixels * 64 * 2];                      // [pixel][channel]{sum, sq}
+  const int hh = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 5, p = lane & 31;
+  const int HW = H * W;
+  const int pbase = blockIdx.x * kConv1Pixels, pix = pbase + p;
+  const bool live = pix < HW;                                       // (of the pixel whose terms this lane loads)
+  const bool full = pbase + kConv1Pixels <= HW;                     // (of the workgroup: no masked pixel)
+  const int h = pix / W, w = pix - h * W;
+  const int ch = 32 * hh + p;
+  float wt[kConv1Mfmas];
+  int off[kConv1Mfmas];
+  const unsigned real = conv1_operands<D>(weight, ch, g, h, w, live, H, W, wt, off);
+  typename std::conditional<STORE, int, unsigned>::type toff[kConv1Mfmas];
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) toff[i] = STORE ? off[i] : (unsigned)off[i] * 4u;   // (H W 12 < 2^29 for a covered shape)
   const int64_t sample = (int64_t)HW * 3;
   // two buffers of terms, for the samples n and n + 1; a term's register is reloaded for sample n + 2 as soon as its MFMA has
   // read it.  Two samples ahead, not one: a wait for a load also waits for every store issued before it, and these loads
@@ -325,29 +386,21 @@ __global__ __launch_bounds__(128) void conv1_stats_miopen_kernel(
   float even[kConv1Mfmas], odd[kConv1Mfmas];
   const float* image1 = image + (B > 1 ? sample : 0);
 #pragma unroll
-  for (int i = 0; i < kConv1Mfmas; ++i) even[i] = image[off[i]];
+  for (int i = 0; i < kConv1Mfmas; ++i) even[i] = conv1_load(image, toff[i]);
 #pragma unroll
-  for (int i = 0; i < kConv1Mfmas; ++i) odd[i] = image1[off[i]];
+  for (int i = 0; i < kConv1Mfmas; ++i) odd[i] = conv1_load(image1, toff[i]);
   float sum[16], sq[16];                                            // [v]: pixel 8 (v >> 2) + 4 g + (v & 3), channel ch
 #pragma unroll
   for (int v = 0; v < 16; ++v) sum[v] = sq[v] = 0.f;
-  float* xo = x + ((int64_t)(pbase + 4 * g) * 64 + ch);             // register v goes (8 (v >> 2) + (v & 3)) pixels further
+  float* xo = STORE ? x + ((int64_t)(pbase + 4 * g) * 64 + ch) : nullptr;   // register v goes (8 (v >> 2) + (v & 3)) pixels further
   const int64_t xstep = (int64_t)HW * 64;
   auto one_sample = [&](float (&terms)[kConv1Mfmas], int n) {
     const float* ahead = image + (int64_t)(n + 2 < B ? n + 2 : B - 1) * sample;      // (the last two reload the last sample)
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int i = 0; i < kConv1Mfmas; ++i) {
-      const float t = (real >> i) & 1u ? terms[i] : 0.f;
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(t, wt[i], acc, 0, 0, 0);
-      terms[i] = ahead[off[i]];
-    }
+    const f32x16 acc = conv1_chain(terms, wt, toff, real, ahead);
     if (full) {
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        xo[(8 * (v >> 2) + (v & 3)) * 64] = acc[v];
+        if constexpr (STORE) xo[(8 * (v >> 2) + (v & 3)) * 64] = acc[v];
         sum[v] += acc[v];
         sq[v] = __builtin_fmaf(acc[v], acc[v], sq[v]);
       }
@@ -355,12 +408,12 @@ __global__ __launch_bounds__(128) void conv1_stats_miopen_kernel(
 #pragma unroll
       for (int v = 0; v < 16; ++v)
         if (pbase + 8 * (v >> 2) + 4 * g + (v & 3) < HW) {
-          xo[(8 * (v >> 2) + (v & 3)) * 64] = acc[v];
+          if constexpr (STORE) xo[(8 * (v >> 2) + (v & 3)) * 64] = acc[v];
           sum[v] += acc[v];
           sq[v] = __builtin_fmaf(acc[v], acc[v], sq[v]);
         }
     }
-    xo += xstep;
+    if constexpr (STORE) xo += xstep;
   };
   for (int n = 0; n < B; n += 2) {
     one_sample(even, n);
@@ -462,26 +515,37 @@ struct Affine {
 };
 
 // STOCK: MIOpen's normalise kernel, t = mad(gamma, (x - mean) * invstd, beta) with `scale` = invstd
+// The per-element and per-window functions of the normalise pass, shared by bn_relu_pool_kernel and conv1_norm_pool_kernel: the
+// two must give the same bits, -0 / +0 and NaN included.
+template <bool STOCK>
+__device__ __forceinline__ float affine1(float v, float mean, float lo, float scale, float gamma, float beta) {
+  return STOCK ? __builtin_fmaf(gamma, (v - mean) * scale, beta) : fmaf((v - mean) - lo, scale, beta);
+}
+// PyTorch's maximum: a NaN wins
+__device__ __forceinline__ float max_nan1(float a, float b) { return (a > b || a != a) ? a : b; }
+__device__ __forceinline__ float relu_nan1(float a) { return a < 0.f ? 0.f : a; }   // (a NaN is not < 0: it stays)
+// the members of a 2x2 window in the order (0, 0), (0, 1), (1, 0), (1, 1) = (dy, dx)
+__device__ __forceinline__ float window_max1(float t00, float t01, float t10, float t11) {
+  return max_nan1(max_nan1(t00, t01), max_nan1(t10, t11));
+}
+
 template <bool STOCK>
 __device__ __forceinline__ f32x4 affine(const f32x4 v, const Affine& a) {
   f32x4 t;
 #pragma unroll
-  for (int e = 0; e < 4; ++e)
-    t[e] = STOCK ? __builtin_fmaf(a.gamma[e], (v[e] - a.mean[e]) * a.scale[e], a.beta[e])
-                 : fmaf((v[e] - a.mean[e]) - a.lo[e], a.scale[e], a.beta[e]);
+  for (int e = 0; e < 4; ++e) t[e] = affine1<STOCK>(v[e], a.mean[e], a.lo[e], a.scale[e], a.gamma[e], a.beta[e]);
   return t;
 }
-// PyTorch's maximum: a NaN wins
-__device__ __forceinline__ f32x4 max_nan(const f32x4 a, const f32x4 b) {
+__device__ __forceinline__ f32x4 window_max(const f32x4 t00, const f32x4 t01, const f32x4 t10, const f32x4 t11) {
   f32x4 m;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) m[e] = (a[e] > b[e] || a[e] != a[e]) ? a[e] : b[e];
+  for (int e = 0; e < 4; ++e) m[e] = window_max1(t00[e], t01[e], t10[e], t11[e]);
   return m;
 }
 __device__ __forceinline__ f32x4 relu_nan(const f32x4 a) {
   f32x4 r;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) r[e] = a[e] < 0.f ? 0.f : a[e];       // (a NaN is not < 0: it stays)
+  for (int e = 0; e < 4; ++e) r[e] = relu_nan1(a[e]);
   return r;
 }
 
@@ -545,11 +609,98 @@ __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __r
 #pragma unroll
     for (int u = 0; u < 2; ++u)
       if (live[u]) {
-        const f32x4 t = AFFINE ? max_nan(max_nan(affine<STOCK>(v[u][0], a), affine<STOCK>(v[u][1], a)),
-                                         max_nan(affine<STOCK>(v[u][2], a), affine<STOCK>(v[u][3], a)))
-                               : max_nan(max_nan(v[u][0], v[u][1]), max_nan(v[u][2], v[u][3]));
+        const f32x4 t = AFFINE ? window_max(affine<STOCK>(v[u][0], a), affine<STOCK>(v[u][1], a), affine<STOCK>(v[u][2], a),
+                                            affine<STOCK>(v[u][3], a))
+                               : window_max(v[u][0], v[u][1], v[u][2], v[u][3]);
         y[o + u * stride] = relu ? relu_nan(t) : t;
       }
+  }
+}
+
+// ---- layer 1 without x (pass B of coattn_conv1_bn_recompute_forward): the convolution again, normalised, pooled, ReLU, y alone ----
+// The chain is conv1_stats_miopen_kernel's (conv1_operands, conv1_chain): an output's bits depend on the term order only, not on
+// the MFMA row its pixel sits in, so the rows are free to be the pixels of whole pooling windows.  No state crosses samples: the
+// grid is (tile, chunk of kConv1NormChunk samples).  A workgroup is ONE wave that runs both channel halves (chain hh: channels
+// 32 hh .. 32 hh + 31) over one set of terms (conv1_chain2): with a wave per half, as above, the two waves issue the same
+// sixteen scattered 4-byte loads per sample, and the pass took 428 us against 388 us this way at the benchmark's shape.  The
+// weights are loaded once per workgroup, the terms of the samples n + 1 and n + 2 are in flight as above (y's stores are older
+// than the loads behind them).
+//   POOL : the tile is 2 image rows x 16 columns, tile t = (pooled row ho = t / cbs, column block cb = t % cbs), cbs = ceil(Wo / 8).
+//          MFMA row slot q = 8 b + 4 g + r is member r (dy = r >> 1, dx = r & 1: bn_relu_pool_kernel's order) of the window
+//          q >> 2 = 2 b + g, the pooled column 8 cb + 2 b + g.  Register v = 4 b + r of chain hh in lane (g, p) holds member r of
+//          that window for channel 32 hh + p: the four registers of a b are one window, normalised, reduced and stored in-lane -- one store per
+//          b, two whole 128-byte lines.  Windows past Wo are masked (their lanes load offset 0 and multiply zeros); floor mode:
+//          the tile never reaches an odd last row or column.
+//   !POOL: the tile is 32 consecutive pixels, stored as conv1_stats_miopen_kernel stores x.
+// 163 VGPRs (both accumulators included), no LDS, no scratch: three waves per SIMD, which the occupancy hint asks for.
+constexpr int kConv1NormChunk = COATTN_CONV1_RECOMPUTE_CHUNK;
+
+template <int D, bool POOL>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void conv1_norm_pool_kernel(
+    const float* __restrict__ image, const float* __restrict__ weight, const float* __restrict__ save_mean,
+    const float* __restrict__ save_invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y,
+    int B, int H, int W, int cbs) {
+  const int lane = threadIdx.x, g = lane >> 5, p = lane & 31;
+  const int HW = H * W, Ho = H >> 1, Wo = W >> 1;
+  const int n0 = blockIdx.y * kConv1NormChunk, n1 = n0 + kConv1NormChunk < B ? n0 + kConv1NormChunk : B;
+  // the pixel whose terms this lane loads: slot p of the tile
+  const int ho = POOL ? blockIdx.x / cbs : 0, cb = POOL ? blockIdx.x - ho * cbs : 0;
+  const int pbase = blockIdx.x * kConv1Pixels;
+  const int pix = pbase + p;
+  const bool live = POOL ? 8 * cb + (p >> 2) < Wo : pix < HW;
+  const int h = POOL ? 2 * ho + ((p >> 1) & 1) : pix / W;
+  const int w = POOL ? 2 * (8 * cb + (p >> 2)) + (p & 1) : pix - h * W;
+  float wt0[kConv1Mfmas], wt1[kConv1Mfmas];                         // channel p and channel 32 + p
+  int off[kConv1Mfmas];
+  const unsigned real = conv1_operands<D>(weight, p, g, h, w, live, H, W, wt0, off);
+  conv1_operands<D>(weight, 32 + p, g, h, w, live, H, W, wt1, off);
+  unsigned boff[kConv1Mfmas];
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) boff[i] = (unsigned)off[i] * 4u;
+  const float mean[2] = {save_mean[p], save_mean[32 + p]}, invstd[2] = {save_invstd[p], save_invstd[32 + p]};
+  const float gm[2] = {gamma[p], gamma[32 + p]}, bt[2] = {beta[p], beta[32 + p]};
+  const int64_t sample = (int64_t)HW * 3;
+  float even[kConv1Mfmas], odd[kConv1Mfmas];
+  const float* image0 = image + (int64_t)n0 * sample;
+  const float* image1 = image + (int64_t)(n0 + 1 < n1 ? n0 + 1 : n0) * sample;
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) even[i] = conv1_load(image0, boff[i]);
+#pragma unroll
+  for (int i = 0; i < kConv1Mfmas; ++i) odd[i] = conv1_load(image1, boff[i]);
+  // POOL: register group b goes 2 b pooled pixels further; !POOL: register v goes (8 (v >> 2) + (v & 3)) pixels further;
+  // the second chain's channel is 32 floats further
+  const int wo = 8 * cb + g;
+  float* yo = POOL ? y + ((((int64_t)n0 * Ho + ho) * Wo + wo) * 64 + p) : y + (((int64_t)n0 * HW + pbase + 4 * g) * 64 + p);
+  const int64_t ystep = POOL ? (int64_t)Ho * Wo * 64 : (int64_t)HW * 64;
+  const bool full = POOL ? 8 * cb + 8 <= Wo : pbase + kConv1Pixels <= HW;   // (of the workgroup: nothing masked)
+  auto one_sample = [&](float (&terms)[kConv1Mfmas], int n) {
+    const float* ahead = image + (int64_t)(n + 2 < n1 ? n + 2 : n1 - 1) * sample;    // (the last two reload the last sample)
+    f32x16 acc[2];
+    conv1_chain2(terms, wt0, wt1, boff, real, ahead, acc[0], acc[1]);
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      if (POOL) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const float m = window_max1(affine1<true>(acc[hh][4 * b], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]),
+                                      affine1<true>(acc[hh][4 * b + 1], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]),
+                                      affine1<true>(acc[hh][4 * b + 2], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]),
+                                      affine1<true>(acc[hh][4 * b + 3], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]));
+          if (full || wo + 2 * b < Wo) yo[2 * b * 64 + 32 * hh] = relu_nan1(m);
+        }
+      } else {
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if (full || pbase + 8 * (v >> 2) + 4 * g + (v & 3) < HW)
+            yo[(8 * (v >> 2) + (v & 3)) * 64 + 32 * hh] =
+                relu_nan1(affine1<true>(acc[hh][v], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]));
+      }
+    }
+    yo += ystep;
+  };
+  for (int n = n0; n < n1; n += 2) {
+    one_sample(even, n);
+    if (n + 1 < n1) one_sample(odd, n + 1);
   }
 }
 
@@ -771,10 +922,14 @@ constexpr int kConv1PairDistance = 8;   // terms per lane half and block: KPerBl
 
 inline size_t conv1_partial_bytes(const BnGeom& g) { return (exact_partial_bytes(g, 64) + 255) & ~(size_t)255; }
 
+// x = NULL: the statistics alone (STORE = false)
 void launch_conv1(int dist, const void* image, const void* weight, void* x, void* partial, const BnGeom& g, int B, int H, int W,
                   hipStream_t s) {
   const int blocks = (H * W + kConv1Pixels - 1) / kConv1Pixels;
-  if (dist == 8)
+  if (!x)
+    hipLaunchKernelGGL((conv1_stats_miopen_kernel<kConv1PairDistance, false>), dim3(blocks), dim3(128), 0, s, (const float*)image,
+                       (const float*)weight, (float*)nullptr, (float*)partial, B, H, W, g.g1, g.ngrps);
+  else if (dist == 8)
     hipLaunchKernelGGL(conv1_stats_miopen_kernel<8>, dim3(blocks), dim3(128), 0, s, (const float*)image, (const float*)weight,
                        (float*)x, (float*)partial, B, H, W, g.g1, g.ngrps);
   else
@@ -829,6 +984,69 @@ extern "C" int coattn_conv1_bn_exact_forward(const void* image, const void* weig
                  Cout, pool, 1, s))
     return -1;
   prof_mark(s, "conv1_bn_exact");
+  return 0;
+}
+
+// ---- layer 1, the convolution computed twice and never stored (v0.22.0) ---------------------------------------------------------
+extern "C" size_t coattn_conv1_bn_recompute_workspace_bytes(int B, int H, int W) {
+  BnGeom g;
+  if (!bn_exact_geometry(B, H, W, 64, COATTN_F32, &g)) {
+    coattn_set_error("conv1_bn_recompute_workspace_bytes: B=%d H=%d W=%d is not a covered shape (coattn_conv1_bn_exact_supported)", B, H, W);
+    return 0;
+  }
+  return conv1_partial_bytes(g);
+}
+
+extern "C" int coattn_conv1_bn_recompute_forward(const void* image, const void* weight, const void* gamma, const void* beta,
+                                                 void* running_mean, void* running_var, double momentum, double eps, void* y,
+                                                 void* save_mean, void* save_invstd, void* ws, int B, int H, int W, int Cin,
+                                                 int Cout, int pool, int dtype, void* stream) {
+  CA_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1, "conv1_bn_recompute_forward: B=%d H=%d W=%d Cin=%d Cout=%d (all must be >= 1)",
+               B, H, W, Cin, Cout);
+  BnGeom g;
+  CA_CHECK_ARG(coattn_conv1_bn_exact_supported(B, H, W, Cin, Cout, pool, dtype) && bn_exact_geometry(B, H, W, Cout, dtype, &g),
+               "conv1_bn_recompute_forward: B=%d H=%d W=%d Cin=%d Cout=%d pool=%d dtype=%d is not a covered shape "
+               "(coattn_conv1_bn_exact_supported)", B, H, W, Cin, Cout, pool, dtype);
+  CA_CHECK_ARG(image && weight && gamma && beta && running_mean && running_var && y && save_mean && save_invstd && ws,
+               "conv1_bn_recompute_forward: a null image / weight / gamma / beta / running_mean / running_var / y / save_mean / "
+               "save_invstd / ws");
+  CA_CHECK_ARG(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(gamma) |
+                 reinterpret_cast<uintptr_t>(beta) | reinterpret_cast<uintptr_t>(running_mean) |
+                 reinterpret_cast<uintptr_t>(running_var) | reinterpret_cast<uintptr_t>(save_mean) |
+                 reinterpret_cast<uintptr_t>(save_invstd)) & 15) == 0 &&
+                   ((reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(weight)) & 3) == 0,
+               "conv1_bn_recompute_forward: y, ws, the BatchNorm vectors must be 16-byte aligned, image and weight 4-byte aligned");
+  CA_CHECK_ARG(momentum >= 0.0 && momentum <= 1.0, "conv1_bn_recompute_forward: momentum %g outside [0, 1]", momentum);
+  CA_CHECK_ARG(eps > 0.0, "conv1_bn_recompute_forward: eps %g (must be > 0)", eps);
+  CA_CHECK_ARG(y != image, "conv1_bn_recompute_forward: image and y must be two buffers");
+  hipStream_t s = (hipStream_t)stream;
+  // pass A: the statistics of the convolution, which is not stored
+  launch_conv1(kConv1PairDistance, image, weight, nullptr, ws, g, B, H, W, s);
+  CA_CHECK_LAUNCH("conv1_stats_miopen");
+  prof_mark(s, "conv1_stats");
+  const int64_t pixels = (int64_t)B * H * W;
+  const float n_f = (float)pixels;
+  const float inhw = (float)(1.0 / (double)pixels), unbias = pixels == 1 ? 1.f : n_f / (n_f - 1.f);   // (as exact_tail)
+  const int c4 = Cout / 4;
+  hipLaunchKernelGGL(bn_finalize_miopen_kernel, dim3(c4 / g.f0), dim3(g.f0, g.f1, g.f2),
+                     (size_t)2 * g.f0 * g.f1 * g.f2 * sizeof(f32x4), s, (const f32x4*)ws, g, c4, inhw, unbias, (float)momentum,
+                     (float)eps, (f32x4*)running_mean, (f32x4*)running_var, (f32x4*)save_mean, (f32x4*)save_invstd);
+  CA_CHECK_LAUNCH("bn_finalize_miopen");
+  prof_mark(s, "conv1_finalize");
+  // pass B: the convolution again, normalised (+ pooled) + ReLU
+  const int chunks = (B + kConv1NormChunk - 1) / kConv1NormChunk;
+  if (pool) {
+    const int cbs = (W / 2 + 7) / 8;
+    hipLaunchKernelGGL((conv1_norm_pool_kernel<kConv1PairDistance, true>), dim3((unsigned)((H / 2) * cbs), chunks), dim3(64), 0, s,
+                       (const float*)image, (const float*)weight, (const float*)save_mean, (const float*)save_invstd,
+                       (const float*)gamma, (const float*)beta, (float*)y, B, H, W, cbs);
+  } else {
+    hipLaunchKernelGGL((conv1_norm_pool_kernel<kConv1PairDistance, false>), dim3((H * W + kConv1Pixels - 1) / kConv1Pixels, chunks),
+                       dim3(64), 0, s, (const float*)image, (const float*)weight, (const float*)save_mean,
+                       (const float*)save_invstd, (const float*)gamma, (const float*)beta, (float*)y, B, H, W, 0);
+  }
+  CA_CHECK_LAUNCH("conv1_norm_pool");
+  prof_mark(s, "conv1_norm_pool");
   return 0;
 }
 

@@ -1,4 +1,4 @@
-"""The memory-bound glue of the frozen image encoder on the HIP library (csrc/encoder.hip, include/coattn.h v0.16.0), for
+"""The memory-bound glue of the frozen image encoder on the HIP library (csrc/encoder.hip, include/coattn.h v0.22.0), for
 channels_last fp32 tensors; the convolutions stay on MIOpen, but for the first.  ``modules.run_conv_bn_stack`` decides which
 layer takes what:
 
@@ -11,7 +11,11 @@ layer takes what:
 * ``bn_exact(..., conv=conv)``: the same with the first convolution (3 -> 64 channels, 3x3, padding 1) in front, computed in
   the stock kernel's arithmetic by the kernel that also sums its statistics.  The default for the first group, again only for a
   shape that ``conv1_bn_exact_or_stock`` has compared with the stock convolution and chain once and found equal in every bit;
-  ``VQA_ENCODER_EXACT_CONV1=0`` turns it off (and so does whatever turns ``bn_exact`` off).
+  ``VQA_ENCODER_EXACT_CONV1=0`` turns it off (and so does whatever turns ``bn_exact`` off).  The convolution output is never
+  stored: one kernel computes it for the statistics, another computes it again and normalises, pools and writes the result
+  (``coattn_conv1_bn_recompute_forward``), compared with the stock kernels in the same first call.
+  ``VQA_ENCODER_CONV1_RECOMPUTE=0`` keeps the form that stores the convolution output and reads it back
+  (``coattn_conv1_bn_exact_forward``), for A/B runs and as an escape.
 * ``bn_relu_pool``: train-mode ``BatchNorm2d`` + ``ReLU`` + an optional ``MaxPool2d(2, 2)`` in two passes over the convolution
   output, statistics in double.  More accurate than the stock chain, but not its bits: a training trajectory leaves the stock
   one at rounding level and drifts from there.  Opt-in: ``VQA_ENCODER_FUSED=1``.
@@ -172,8 +176,9 @@ def exact_output_fusable(z: torch.Tensor, bn: nn.BatchNorm2d, pool: bool) -> boo
 def exact_report() -> dict:
     """{(device index, B, C, H, W, pool): {"verified", "first_difference", "geometry"}} of every shape compared so far; the
     entry of a first-convolution output also holds "conv1": {"verified", "first_difference"} once conv1_bn_exact_or_stock has
-    compared that route (a key of the entry: it cannot collide with a BatchNorm shape)."""
-    return {k: {n: dict(t) if n == "conv1" else t for n, t in v.items()} for k, v in _exact.items()}
+    compared that route (a key of the entry: it cannot collide with a BatchNorm shape), and "conv1_recompute", the same of the
+    form that never stores the convolution output, once that was compared too."""
+    return {k: {n: dict(t) if n in ("conv1", "conv1_recompute") else t for n, t in v.items()} for k, v in _exact.items()}
 
 
 def _bn_exact_raw(x, weight, bias, running_mean, running_var, momentum, eps, pool: bool):
@@ -192,18 +197,20 @@ def _bn_exact_raw(x, weight, bias, running_mean, running_var, momentum, eps, poo
     return y, save[0], save[1]
 
 
-def bn_exact(x: torch.Tensor, bn: nn.BatchNorm2d, pool: bool = False, conv=None) -> torch.Tensor:
+def bn_exact(x: torch.Tensor, bn: nn.BatchNorm2d, pool: bool = False, conv=None, recompute=None) -> torch.Tensor:
     """relu(max_pool2d(bn(x), 2, 2)) (pool) or relu(bn(x)) of a channels_last fp32 [B,C,H,W] tensor with `bn` in train mode, summed
     in MIOpen's order: the stock chain's bits, `bn`'s running statistics and num_batches_tracked included (a convolution bias left
     out of x is the caller's to add to the running mean).  With `conv`, the encoder's first convolution, x is ITS input, a
     channels_last [B,3,H,W] image: conv2d(x, conv.weight, padding=1) without the bias is computed in the stock kernel's arithmetic
-    by the kernel that sums the statistics (coattn_conv1_bn_exact_forward).  Forward only; runs on torch's current stream."""
+    by the kernel that sums the statistics (coattn_conv1_bn_recompute_forward, or coattn_conv1_bn_exact_forward with
+    `recompute` False; None: conv1_recompute_enabled()).  Forward only; runs on torch's current stream."""
     if conv is not None:
         if not conv1_inputs_fusable(x, conv, bn, pool):
             raise ValueError("bn_exact: with conv it needs a CUDA fp32 channels_last [B,3,H,W] image, a 3 -> 64 channel 3x3 / stride 1 "
                              "/ padding 1 convolution with channels_last weights and a shape coattn_conv1_bn_exact_supported "
                              "covers, got %s %s strides %s" % (tuple(x.shape), x.dtype, x.stride()))
-        _, y, _, _ = _conv1_raw(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, pool, False)
+        _, y, _, _ = _conv1_raw(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, pool, False,
+                                recompute)
     else:
         if not exact_output_fusable(x, bn, pool):
             raise ValueError("bn_exact: needs a CUDA fp32 channels_last [B,C,H,W] tensor of a shape coattn_bn_exact_geometry "
@@ -305,7 +312,34 @@ def conv1_modules_fusable(conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, x: torch.Te
             and conv1_inputs_fusable(x, conv, bn, pool is not None))
 
 
-def _conv1_raw(image, weight, gamma, beta, running_mean, running_var, momentum, eps, pool: bool, want_x: bool):
+def conv1_recompute_enabled() -> bool:
+    """The first group computes its convolution twice and never stores it, unless VQA_ENCODER_CONV1_RECOMPUTE=0."""
+    return os.environ.get("VQA_ENCODER_CONV1_RECOMPUTE", "1") != "0"
+
+
+def _conv1_recompute_raw(image, weight, gamma, beta, running_mean, running_var, momentum, eps, pool: bool):
+    """(y, save_mean, save_invstd) of coattn_conv1_bn_recompute_forward: the convolution output is never stored."""
+    lib = _lib.load()
+    B, _, H, W = image.shape
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    dev = image.device
+    y = torch.empty((B, 64, Ho, Wo), device=dev, dtype=torch.float32, memory_format=torch.channels_last)
+    save = torch.empty((2, 64), device=dev, dtype=torch.float32)
+    ws = torch.empty((lib.coattn_conv1_bn_recompute_workspace_bytes(B, H, W) + 3) // 4, device=dev, dtype=torch.float32)
+    with torch.no_grad(), _lib.on_device(dev):
+        _lib.bind("coattn_conv1_bn_recompute_forward", image=image, weight=weight, gamma=gamma, beta=beta,
+                  running_mean=running_mean, running_var=running_var, momentum=float(momentum), eps=float(eps), y=y,
+                  save_mean=save[0], save_invstd=save[1], ws=ws, B=B, H=H, W=W, Cin=3, Cout=64, pool=int(pool), dtype=_lib.F32,
+                  stream=_lib.stream_ptr(dev))()
+    return y, save[0], save[1]
+
+
+def _conv1_raw(image, weight, gamma, beta, running_mean, running_var, momentum, eps, pool: bool, want_x: bool, recompute=None):
+    """(x, y, save_mean, save_invstd) of the first group.  `want_x`: the form that stores the convolution output, which is
+    returned; otherwise x is None and the recompute form runs (`recompute` False, or None and VQA_ENCODER_CONV1_RECOMPUTE=0:
+    the stored form with x in its workspace)."""
+    if not want_x and (conv1_recompute_enabled() if recompute is None else recompute):
+        return (None,) + _conv1_recompute_raw(image, weight, gamma, beta, running_mean, running_var, momentum, eps, pool)
     lib = _lib.load()
     B, _, H, W = image.shape
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
@@ -333,9 +367,12 @@ def _conv1_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) -> 
 
 def _verify_conv1(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, key) -> torch.Tensor:
     """The first call of a shape: the stock group's result, and beside it the one-pass route on clones of the running
-    statistics, compared bit for bit.  One host synchronisation (and the BatchNorm comparison's, if this is its first call too)."""
+    statistics, compared bit for bit.  One host synchronisation (and the BatchNorm comparison's, if this is its first call too).
+    Where the stored form matched and the recompute form is enabled, that form runs once too, on further clones, and its y and
+    statistics are compared (a second synchronisation): what the route runs afterwards is what was compared."""
     with torch.no_grad():
         rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+        rm1, rv1 = rm0.clone(), rv0.clone()                             # (for the recompute form, below)
         z = torch.nn.functional.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
         if not exact_output_fusable(z, bn, pool is not None):
             return _stock_chain(z, bn, pool)                        # (another layout: nothing compared, nothing remembered)
@@ -348,13 +385,29 @@ def _verify_conv1(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, ke
         pairs = ((mine_x, z), (mine_y, y), (rm0, bn.running_mean), (rv0, bn.running_var), (mine_mean, save_mean),
                  (mine_invstd, save_invstd))
         flags = torch.stack([_differs(a, b) for a, b in pairs]).tolist()
-    first = next((n for n, f in zip(names, flags) if f), None)
+        first = next((n for n, f in zip(names, flags) if f), None)
+        del mine_x
+        again = None
+        if first is None and conv1_recompute_enabled():
+            re_y, re_mean, re_invstd = _conv1_recompute_raw(x, conv.weight, bn.weight, bn.bias, rm1, rv1, bn.momentum, bn.eps,
+                                                            pool is not None)
+            pairs = ((re_y, y), (rm1, bn.running_mean), (rv1, bn.running_var), (re_mean, save_mean), (re_invstd, save_invstd))
+            flags = torch.stack([_differs(a, b) for a, b in pairs]).tolist()
+            again = next((n for n, f in zip(names[1:], flags) if f), None)
     B, _, H, W = x.shape
-    _exact.setdefault(key, {"verified": False, "first_difference": None, "geometry": exact_geometry(B, H, W, 64)})["conv1"] = {
-        "verified": first is None, "first_difference": first}
+    entry = _exact.setdefault(key, {"verified": False, "first_difference": None, "geometry": exact_geometry(B, H, W, 64)})
+    entry["conv1"] = {"verified": first is None, "first_difference": first}
+    if first is None and conv1_recompute_enabled():
+        entry["conv1_recompute"] = {"verified": again is None, "first_difference": again}
+    else:
+        entry.pop("conv1_recompute", None)
     if first is not None:
         warnings.warn("encoder: the one-pass first convolution does not reproduce the stock kernels for B=%d H=%d W=%d pool=%d "
                       "(%s differs); this shape stays on the stock kernels" % (B, H, W, int(pool is not None), first))
+    elif again is not None:
+        warnings.warn("encoder: the recomputed first convolution does not reproduce the stock kernels for B=%d H=%d W=%d pool=%d "
+                      "(%s differs); this shape keeps the form that stores the convolution output"
+                      % (B, H, W, int(pool is not None), again))
     return y
 
 
@@ -366,7 +419,18 @@ def _conv1_or_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) 
         if torch.cuda.is_current_stream_capturing():
             return _conv1_stock(x, conv, bn, pool)
         return _verify_conv1(x, conv, bn, pool, key)
-    return bn_exact(x, bn, pool is not None, conv=conv) if state["verified"] else _conv1_stock(x, conv, bn, pool)
+    if not state["verified"]:
+        return _conv1_stock(x, conv, bn, pool)
+    recompute = conv1_recompute_enabled()
+    if recompute:
+        again = _exact[key].get("conv1_recompute")
+        if again is None:                                               # (verified while VQA_ENCODER_CONV1_RECOMPUTE was 0)
+            if not torch.cuda.is_current_stream_capturing():
+                return _verify_conv1(x, conv, bn, pool, key)
+            recompute = False
+        else:
+            recompute = again["verified"]
+    return bn_exact(x, bn, pool is not None, conv=conv, recompute=recompute)
 
 
 def conv1_bn_exact_or_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) -> torch.Tensor:

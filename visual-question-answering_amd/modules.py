@@ -95,7 +95,9 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
     * by default too, the FIRST group, where it is the VGG's 3 -> 64 channel 3x3 convolution on a channels_last image with
       channels_last weights, runs the convolution itself in the kernel that sums the statistics, in the stock convolution's
       arithmetic (``encoder.conv1_bn_exact_or_stock``): no zero fill, no separate statistics pass.  Verified per shape against the
-      stock convolution and chain like the route above, or not used; ``VQA_ENCODER_EXACT_CONV1=0`` turns it off;
+      stock convolution and chain like the route above, or not used; ``VQA_ENCODER_EXACT_CONV1=0`` turns it off.  The
+      convolution is computed twice, once for the statistics and once to be normalised, and its output never stored;
+      ``VQA_ENCODER_CONV1_RECOMPUTE=0`` keeps the form that stores it and reads it back;
     * with ``VQA_ENCODER_FUSED=1`` a whole ``Conv2d -> BatchNorm2d -> ReLU [-> MaxPool2d(2, 2)]`` group runs everything after the
       convolution in two passes over its output (``encoder.bn_relu_pool``), the bias fold included.  Its statistics are summed
       in double, in another order than MIOpen's: values agree with the stock chain to rounding, not bit for bit.
