@@ -13,7 +13,7 @@ import vqa_amd
 from vqa_amd import _lib, modules as M, predict as P, train as T
 
 from tests import _dropout as D
-from tests._header import args as header_args, header
+from tests._header import header
 
 FUNCS = ("coattn_dropout_supported", "coattn_dropout_forward", "coattn_dropout_backward")
 
@@ -85,20 +85,6 @@ def test_header_declares_exports_and_version():
         assert word in hdr, word
     assert vqa_amd.DropoutState is vqa_amd.dropout.DropoutState and vqa_amd.feature_dropout is vqa_amd.dropout.feature_dropout
     assert {"dropout", "DropoutState", "feature_dropout", "rank_seed"} <= set(vqa_amd.__all__)
-
-
-@pytest.mark.parametrize("fn", FUNCS[1:])
-def test_tabled_signature_matches_the_header(fn):
-    declared = [a.rsplit(" ", 1) for a in header_args(header(), fn)]
-    sig = _lib.DROPOUT_SIGNATURES[fn]
-    assert [n for n, _ in sig] == [n for _, n in declared]
-    for (n, ctype), (ctext, _) in zip(sig, declared):
-        if "*" in ctext:
-            assert ctype is C.c_void_p, (fn, n, ctext)
-        else:
-            assert ctype is {"long long": C.c_int64, "int": C.c_int, "float": C.c_float}[ctext], (fn, n, ctext)
-    assert list(getattr(_lib.load(), fn).argtypes) == [t for _, t in sig]
-    assert sig[-1][0] == "stream" and fn not in _lib.SIGNATURES
 
 
 def test_supported_range():

@@ -33,21 +33,6 @@ def test_header_declares_exports_constants_and_version():
     assert vqa_amd.word_embedding is vqa_amd.embedding.word_embedding and "word_embedding" in vqa_amd.__all__
 
 
-@pytest.mark.parametrize("fn", FUNCS[2:])
-def test_tabled_signature_matches_the_header(fn):
-    declared = [a.rsplit(" ", 1) for a in header_args(header(), fn)]            # [C type, argument name]
-    sig = _lib.EMBEDDING_SIGNATURES[fn]
-    assert [n for n, _ in sig] == [n for _, n in declared]
-    for (n, ctype), (ctext, _) in zip(sig, declared):
-        if "*" in ctext:
-            assert ctype is C.c_void_p, (fn, n, ctext)
-        else:
-            assert ctype is {"long long": C.c_int64, "int": C.c_int}[ctext], (fn, n, ctext)
-    assert list(getattr(_lib.load(), fn).argtypes) == [t for _, t in sig]
-    assert sig[-1][0] == "stream"
-    assert fn not in _lib.SIGNATURES                                            # (a table of its own)
-
-
 def test_query_signatures_match_the_header():
     lib, hdr = _lib.load(), header()
     names = [a.split()[-1].lstrip("*") for a in header_args(hdr, "coattn_embedding_supported")]

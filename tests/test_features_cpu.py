@@ -35,15 +35,7 @@ def test_header_declares_exports_constants_and_version():
 
 def test_tabled_signature_matches_the_header():
     fn = "coattn_features_gather"
-    declared = [a.rsplit(" ", 1) for a in header_args(header(), fn)]            # [C type, argument name]
-    sig = _lib.FEATURES_SIGNATURES[fn]
-    assert [n for n, _ in sig] == [n for _, n in declared]
-    for (n, ctype), (ctext, _) in zip(sig, declared):
-        if "*" in ctext:
-            assert ctype is C.c_void_p, (n, ctext)
-        else:
-            assert ctype is {"long long": C.c_int64, "int": C.c_int}[ctext], (n, ctext)
-    assert list(getattr(_lib.load(), fn).argtypes) == [t for _, t in sig] and sig[-1][0] == "stream"
+    assert _lib.SIGNATURES[fn][-1][0] == "stream"                                # (names and types: tests/test_call_layer_cpu.py)
     names = [a.split()[-1] for a in header_args(header(), "coattn_features_gather_supported")]
     assert names == "S B N d table_dtype flags".split()
     assert len(_lib.load().coattn_features_gather_supported.argtypes) == 6

@@ -409,3 +409,341 @@ def test_captured_replay_is_its_own_eager_run_bit_for_bit():
     torch.cuda.synchronize()
     for i, (a, b) in enumerate(zip(outs, ref)):
         _same(a, b, "static output %d" % i)
+
+
+# ---- the calls that were positional inside the package until every entry point got a row -------------------------------------
+# One row per family, on the smallest shape of that feature's own GPU test: the public Python function, then the raw ctypes
+# call by position on the same inputs.  Outputs bit-identical, launch marks the same.
+def _f32(*shape, seed=0, scale=1.0):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return torch.randn(*shape, device="cuda", generator=g) * scale
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _sizes(symbol, n, *dims):
+    M = _lib()
+    out = [C.c_size_t() for _ in range(n)]
+    M.check(getattr(M.load(), symbol)(*dims, *[C.byref(o) for o in out]), symbol)
+    return [o.value for o in out]
+
+
+def _bytes(n):
+    return torch.empty(n, dtype=torch.uint8, device="cuda")
+
+
+@pytest.mark.parametrize("fast", (False, True), ids=("exact", "tolerance"))
+def test_phrase_level_is_the_raw_phrase_calls_bit_for_bit(fast):
+    from vqa_amd.phrase import phrase_conv_pool
+    M = _lib()
+    lib = M.load()
+    B, T, E = 2, 5, 20                                       # (tests/test_gpu_phrase.py)
+    x = _f32(B, T, E, seed=1).requires_grad_(True)
+    ps = [_f32(E, E, k, seed=10 + k, scale=0.2).requires_grad_(True) for k in (1, 2, 3)]
+    bs = [_f32(E, seed=20 + k, scale=0.2).requires_grad_(True) for k in (1, 2, 3)]
+    params = [t for pair in zip(ps, bs) for t in pair]
+    g = _f32(B, T, E, seed=2)
+    res = {}
+    marks = _marked(lambda: res.update(out=phrase_conv_pool(x, *params, bf16=False, fast=fast)))
+    out = res["out"]
+    marks += _marked_backward(out.grad_fn, lambda: out.backward(g))
+    flags = M.FLAG_FAST16 if fast else 0
+    sb, fb, bb = _sizes("coattn_phrase_workspace_bytes", 3, B, T, E, M.F32)
+    raw = [t.detach() for t in params]
+    X, r_out, saved, dX = x.detach(), torch.full_like(g, float("nan")), _bytes(sb), torch.full_like(g, float("nan"))
+    grads = [torch.full_like(t, float("nan")) for t in raw]
+    p, pg = M.PhraseParams(*[t.data_ptr() for t in raw]), M.PhraseParamGrads(*[t.data_ptr() for t in grads])
+    ws_f, ws_b = _bytes(fb), _bytes(bb)
+    raw_marks = _marked(lambda: M.check(lib.coattn_phrase_forward(_vp(X), C.byref(p), _vp(r_out), _vp(saved), _vp(ws_f), B, T, E,
+                                                                  M.F32, flags, _stream()), "coattn_phrase_forward"))
+    raw_marks += _marked(lambda: M.check(lib.coattn_phrase_backward(_vp(X), C.byref(p), _vp(r_out), _vp(saved), _vp(g), _vp(dX),
+                                                                    C.byref(pg), 0, _vp(ws_b), B, T, E, M.F32, flags, _stream()),
+                                         "coattn_phrase_backward"))
+    torch.cuda.synchronize()
+    _same(out.detach(), r_out, "out")
+    _same(x.grad, dX, "dX")
+    for i, (t, b) in enumerate(zip(params, grads)):
+        _same(t.grad, b, "parameter gradient %d" % i)
+    assert marks == raw_marks, (marks, raw_marks)
+    M.check_range()                                          # (the tolerance row's status words were folded: in range)
+
+
+def test_sentence_lstm_is_the_raw_lstm_calls_bit_for_bit():
+    import vqa_amd
+    M = _lib()
+    lib = M.load()
+    B, T, E, H = 3, 5, 64, 32                                # (tests/test_gpu_lstm.py)
+    assert lib.coattn_lstm_supported(B, T, E, H, M.F32) == 1
+    x = _f32(B, T, E, seed=1).requires_grad_(True)
+    params = [(_f32(*s, seed=30 + i, scale=0.2)).requires_grad_(True) for i, s in enumerate(((4 * H, E), (4 * H, H), (4 * H,), (4 * H,)))]
+    lens = torch.tensor([T, 1, 3], dtype=torch.int32, device="cuda")
+    g_out, g_xm = _f32(B, T, H, seed=2), _f32(B, T, E, seed=3)
+    res = {}
+    marks = _marked(lambda: res.update(out=vqa_amd.sentence_lstm(x, lens, *params)))
+    out, x_masked = res["out"]
+    marks += _marked_backward(out.grad_fn, lambda: torch.autograd.backward([out, x_masked], [g_out, g_xm]))
+    sb, fb, bb = _sizes("coattn_lstm_workspace_bytes", 3, B, T, E, H, M.F32)
+    raw = [t.detach() for t in params]
+    X, saved, ws_f, ws_b = x.detach(), _bytes(sb), _bytes(fb), _bytes(bb)
+    r_out, r_xm, dX = torch.full_like(g_out, float("nan")), torch.full_like(g_xm, float("nan")), torch.full_like(g_xm, float("nan"))
+    grads = [torch.full_like(t, float("nan")) for t in raw]
+    p, pg = M.LstmParams(*[t.data_ptr() for t in raw]), M.LstmParamGrads(*[t.data_ptr() for t in grads])
+    raw_marks = _marked(lambda: M.check(lib.coattn_lstm_forward(_vp(X), _vp(lens), C.byref(p), _vp(r_out), _vp(r_xm), _vp(saved),
+                                                                _vp(ws_f), B, T, E, H, M.F32, 0, _stream()), "coattn_lstm_forward"))
+    raw_marks += _marked(lambda: M.check(lib.coattn_lstm_backward(_vp(X), _vp(lens), C.byref(p), None, _vp(saved), _vp(g_out),
+                                                                  _vp(g_xm), _vp(dX), C.byref(pg), 0, _vp(ws_b), B, T, E, H, M.F32,
+                                                                  0, _stream()), "coattn_lstm_backward"))
+    torch.cuda.synchronize()
+    _same(out.detach(), r_out, "out")
+    _same(x_masked.detach(), r_xm, "x_masked")
+    _same(x.grad, dX, "dX")
+    for i, (t, b) in enumerate(zip(params, grads)):
+        _same(t.grad, b, "parameter gradient %d" % i)
+    assert marks == raw_marks and {"lstm_fwd_steps", "lstm_bwd_steps", "lstm_dx"} <= set(marks), (marks, raw_marks)
+
+
+def _targets(B, K, A, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return (torch.randint(-1, K, (B, A), device="cuda", generator=g, dtype=torch.int32), torch.rand(B, A, device="cuda", generator=g))
+
+
+def test_cross_entropy_is_the_raw_ce_call_bit_for_bit_and_reports_a_bad_label():
+    import vqa_amd.loss as LS
+    M = _lib()
+    lib = M.load()
+    B, K = 3, 5                                              # (tests/test_gpu_loss.py)
+    z = _f32(B, K, seed=1).requires_grad_(True)
+    lab = torch.tensor([4, 0, 2], device="cuda")
+    res = {}
+    marks = _marked(lambda: res.update(out=LS.cross_entropy(z, lab)))
+    loss = res["out"]
+    loss.backward()
+    LS.check_labels()                                        # in range: nothing raised
+    (n,) = _sizes("coattn_ce_workspace_bytes", 1, B, K, M.F32)
+    ws = torch.empty(n // 4, device="cuda")
+    r_loss, dz = torch.full((), float("nan"), device="cuda"), torch.full((B, K), float("nan"), device="cuda")
+    raw_marks = _marked(lambda: M.check(lib.coattn_ce_forward(_vp(z.detach()), _vp(lab), _vp(r_loss), _vp(dz), _vp(ws), B, K, M.F32,
+                                                              _stream()), "coattn_ce_forward"))
+    assert lib.coattn_ce_status(_vp(ws), B, _stream()) == 0
+    _same(loss.detach(), r_loss, "loss")
+    _same(z.grad, dz, "dlogits")
+    assert marks == raw_marks
+    # a label out of range: the raw status call's -2 and message are check_labels()'s IndexError
+    bad = torch.tensor([4, K, 2], device="cuda")
+    LS.cross_entropy(z.detach(), bad)
+    M.check(lib.coattn_ce_forward(_vp(z.detach()), _vp(bad), _vp(r_loss), None, _vp(ws), B, K, M.F32, _stream()), "coattn_ce_forward")
+    assert lib.coattn_ce_status(_vp(ws), B, _stream()) == -2
+    message = lib.coattn_last_error().decode()
+    assert message
+    with pytest.raises(IndexError) as e:
+        LS.check_labels()
+    assert str(e.value) == message
+
+
+@pytest.mark.parametrize("kind", ("soft_ce", "bce"))
+def test_soft_loss_and_score_are_the_raw_calls_bit_for_bit(kind):
+    import vqa_amd.loss as LS
+    M = _lib()
+    lib = M.load()
+    B, K, A = 5, 7, 1                                        # (tests/test_gpu_soft_loss.py)
+    z = _f32(B, K, seed=1).requires_grad_(True)
+    ai, sc = _targets(B, K, A, 2)
+    res = {}
+    marks = _marked(lambda: res.update(loss=LS.soft_target_loss(z, ai, sc, kind), score=LS.vqa_score_sum(z, ai, sc)))
+    res["loss"].backward()
+    LS.check_labels()
+    (n,) = _sizes("coattn_ce_workspace_bytes", 1, B, K, M.F32)
+    ws = torch.empty(n // 4, device="cuda")
+    r_loss, dz = torch.full((), float("nan"), device="cuda"), torch.full((B, K), float("nan"), device="cuda")
+    pred, rows, total = torch.full((B,), -7, device="cuda", dtype=torch.int32), torch.full((B,), float("nan"), device="cuda"), torch.full((), float("nan"), device="cuda")
+    Z = z.detach()
+    raw_marks = _marked(lambda: (
+        M.check(lib.coattn_soft_loss_forward(_vp(Z), _vp(ai), _vp(sc), A, M.LOSS_KINDS[kind], _vp(r_loss), _vp(dz), _vp(ws),
+                                             B, K, M.F32, _stream()), "coattn_soft_loss_forward"),
+        M.check(lib.coattn_vqa_score(_vp(Z), _vp(ai), _vp(sc), A, _vp(pred), _vp(rows), _vp(total), _vp(ws),
+                                     B, K, M.F32, _stream()), "coattn_vqa_score")))
+    torch.cuda.synchronize()
+    _same(res["loss"].detach(), r_loss, "loss")
+    _same(z.grad, dz, "dlogits")
+    for a, b, what in zip(res["score"], (pred, rows, total), ("pred", "row_score", "score_sum")):
+        _same(a, b, what)
+    assert marks == raw_marks
+
+
+def test_head_status_reports_a_bad_label_with_the_library_message():
+    from vqa_amd import answer_head
+    import vqa_amd.head as HM
+    from vqa_amd.modules import MLPClassifier
+    M = _lib()
+    lib = M.load()
+    torch.manual_seed(3)
+    head = MLPClassifier(HD, HMLP, HK).cuda()
+    v, q = _f32(3, HB, HD, seed=4, scale=0.3), _f32(3, HB, HD, seed=5, scale=0.3)
+    with torch.no_grad():
+        answer_head(v, q, *head._params(), labels=torch.arange(HB, device="cuda") % HK)
+        HM.check_labels()                                    # in range
+        saved, B, d, mlp, K, _ = HM._last
+        assert lib.coattn_head_status(_vp(saved), B, d, mlp, K, _stream()) == 0
+        bad = torch.arange(HB, device="cuda") % HK
+        bad[2] = HK
+        answer_head(v, q, *head._params(), labels=bad)
+    saved, B, d, mlp, K, _ = HM._last
+    assert lib.coattn_head_status(_vp(saved), B, d, mlp, K, _stream()) == -2
+    message = lib.coattn_last_error().decode()
+    assert message
+    with pytest.raises(IndexError) as e:
+        HM.check_labels()
+    assert str(e.value) == message
+
+
+@pytest.mark.parametrize("clip", (None, 0.5), ids=("unclipped", "clipped"))
+def test_hip_adam_is_the_raw_adam_step_bit_for_bit(clip):
+    import vqa_amd
+    M = _lib()
+    lib = M.load()
+    shapes = ((37,), (16, 64))
+    params = [torch.nn.Parameter(_f32(*s, seed=40 + i)) for i, s in enumerate(shapes)]
+    for i, t in enumerate(params):
+        t.grad = _f32(*t.shape, seed=50 + i)
+    raw_p, raw_g = [t.detach().clone() for t in params], [t.grad.clone() for t in params]
+    raw_m, raw_v = [torch.zeros_like(t) for t in raw_p], [torch.zeros_like(t) for t in raw_p]
+    lr, betas, eps, wd = 1e-2, (0.9, 0.99), 1e-8, 0.1
+    opt = vqa_amd.HipAdam(params, lr=lr, betas=betas, eps=eps, weight_decay=wd, max_grad_norm=clip)
+    marks = _marked(opt.step)
+    arr = (M.AdamTensor * len(raw_p))()
+    for e, p, g, m, v in zip(arr, raw_p, raw_g, raw_m, raw_v):
+        e.p, e.g, e.m, e.v, e.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    ws, norm, nbytes = None, None, 0
+    if clip:
+        nbytes = lib.coattn_adam_workspace_bytes(arr, len(raw_p))
+        assert nbytes > 0
+        ws, norm = torch.empty((nbytes + 7) // 8, device="cuda", dtype=torch.float64), torch.full((), float("nan"), device="cuda")
+    raw_marks = _marked(lambda: M.check(lib.coattn_adam_step(arr, len(raw_p), 1, lr, betas[0], betas[1], eps, wd, float(clip or 0.0),
+                                                             _vp(norm), _vp(ws), nbytes, _stream()), "coattn_adam_step"))
+    torch.cuda.synchronize()
+    for i, t in enumerate(params):
+        _same(t.detach(), raw_p[i], "parameter %d" % i)
+        _same(opt.state[t]["exp_avg"], raw_m[i], "exp_avg %d" % i)
+        _same(opt.state[t]["exp_avg_sq"], raw_v[i], "exp_avg_sq %d" % i)
+    _same(opt.grad_norm, norm, "grad_norm")
+    assert marks == raw_marks and "adam_step" in marks and ("grad_norm" in marks) == bool(clip), (marks, raw_marks)
+
+
+MOMENTUM, EPS = 0.1, 1e-5
+
+
+def _bn(Ch, seed):
+    bn = torch.nn.BatchNorm2d(Ch, momentum=MOMENTUM, eps=EPS).cuda().requires_grad_(False)
+    with torch.no_grad():
+        bn.weight.copy_(_f32(Ch, seed=seed) * 0.5 + 1)
+        bn.bias.copy_(_f32(Ch, seed=seed + 1))
+        bn.running_mean.copy_(_f32(Ch, seed=seed + 2))
+        bn.running_var.copy_(_f32(Ch, seed=seed + 3).abs() + 0.5)
+    return bn
+
+
+def _cl(*shape, seed):
+    return _f32(*shape, seed=seed).contiguous(memory_format=torch.channels_last)
+
+
+def test_encoder_pool_passes_are_the_raw_calls_bit_for_bit():
+    from vqa_amd import encoder
+    M = _lib()
+    lib = M.load()
+    B, Ch, H, W = 2, 16, 4, 4
+    assert lib.coattn_bn_supported(B, H, W, Ch, 1, M.F32) == 1
+    x, bn, conv_bias = _cl(B, Ch, H, W, seed=1), _bn(Ch, 10), _f32(Ch, seed=2)
+    rm, rv = bn.running_mean.clone(), bn.running_var.clone()
+    stats = torch.full((2, Ch), float("nan"), device="cuda")
+    res = {}
+    marks = _marked(lambda: res.update(pool=encoder.relu_pool(x), bn=encoder.bn_relu_pool(x, bn, conv_bias, pool=True, stats_out=stats)))
+    y0, y1, r_stats = (torch.full_like(t, float("nan")) for t in (res["pool"], res["bn"], stats))
+    ws = torch.empty((lib.coattn_bn_workspace_bytes(B, H, W, Ch) + 3) // 4, device="cuda")
+    raw_marks = _marked(lambda: (
+        M.check(lib.coattn_relu_pool_forward(_vp(x), _vp(y0), B, H, W, Ch, M.F32, _stream()), "coattn_relu_pool_forward"),
+        M.check(lib.coattn_bn_relu_pool_forward(_vp(x), _vp(bn.weight), _vp(bn.bias), _vp(conv_bias), _vp(rm), _vp(rv), MOMENTUM, EPS,
+                                                _vp(y1), _vp(r_stats), _vp(ws), B, H, W, Ch, 1, 1, M.F32, _stream()),
+                "coattn_bn_relu_pool_forward")))
+    torch.cuda.synchronize()
+    _same(res["pool"], y0, "relu_pool")
+    _same(res["bn"], y1, "bn_relu_pool")
+    assert res["bn"].is_contiguous(memory_format=torch.channels_last) and res["bn"].shape == (B, Ch, H // 2, W // 2)
+    for a, b, what in ((stats, r_stats, "stats_out"), (bn.running_mean, rm, "running_mean"), (bn.running_var, rv, "running_var")):
+        _same(a, b, what)
+    assert marks == raw_marks and {"relu_pool", "bn_relu_pool"} <= set(marks) and int(bn.num_batches_tracked) == 1, (marks, raw_marks)
+
+
+@pytest.mark.parametrize("pool", (True, False), ids=("pool", "no-pool"))
+def test_bn_exact_is_the_raw_call_bit_for_bit(pool):
+    from vqa_amd import encoder
+    M = _lib()
+    lib = M.load()
+    B, Ch, H, W = 2, 64, 4, 4
+    assert encoder.exact_geometry(B, H, W, Ch) is not None and lib.coattn_bn_supported(B, H, W, Ch, int(pool), M.F32) == 1
+    x, bn = _cl(B, Ch, H, W, seed=1), _bn(Ch, 10)
+    rm, rv = bn.running_mean.clone(), bn.running_var.clone()
+    res = {}
+    marks = _marked(lambda: res.update(y=encoder.bn_exact(x, bn, pool)))
+    y, save = torch.full_like(res["y"], float("nan")), torch.full((2, Ch), float("nan"), device="cuda")
+    ws = torch.empty((lib.coattn_bn_exact_workspace_bytes(B, H, W, Ch) + 3) // 4, device="cuda")
+    raw_marks = _marked(lambda: M.check(lib.coattn_bn_exact_forward(_vp(x), _vp(bn.weight), _vp(bn.bias), _vp(rm), _vp(rv), MOMENTUM, EPS,
+                                                                    _vp(y), _vp(save[0]), _vp(save[1]), _vp(ws), B, H, W, Ch, int(pool),
+                                                                    1, M.F32, _stream()), "coattn_bn_exact_forward"))
+    torch.cuda.synchronize()
+    for a, b, what in ((res["y"], y, "y"), (bn.running_mean, rm, "running_mean"), (bn.running_var, rv, "running_var")):
+        _same(a, b, what)
+    mine = encoder._bn_exact_raw(x, bn.weight, bn.bias, rm.clone(), rv.clone(), MOMENTUM, EPS, pool)[1:]
+    rm2, rv2 = rm.clone(), rv.clone()
+    M.check(lib.coattn_bn_exact_forward(_vp(x), _vp(bn.weight), _vp(bn.bias), _vp(rm2), _vp(rv2), MOMENTUM, EPS, _vp(y), _vp(save[0]),
+                                        _vp(save[1]), _vp(ws), B, H, W, Ch, int(pool), 1, M.F32, _stream()), "coattn_bn_exact_forward")
+    _same(mine[0], save[0], "save_mean")
+    _same(mine[1], save[1], "save_invstd")
+    assert marks == raw_marks and "bn_exact" in marks and bool(torch.isfinite(save).all()), (marks, raw_marks)
+
+
+@pytest.mark.parametrize("want_x", (True, False), ids=("x_out", "x-in-ws"))
+def test_stored_first_convolution_is_the_raw_call_bit_for_bit(want_x):
+    from vqa_amd import encoder
+    M = _lib()
+    lib = M.load()
+    B, H, W, pool = 2, 8, 8, True
+    assert lib.coattn_conv1_bn_exact_supported(B, H, W, 3, 64, int(pool), M.F32) == 1
+    img, w, bn = _cl(B, 3, H, W, seed=1), _cl(64, 3, 3, 3, seed=2) * 0.2, _bn(64, 10)
+    rm, rv = bn.running_mean.clone(), bn.running_var.clone()
+    res = {}
+    marks = _marked(lambda: res.update(out=encoder._conv1_raw(img, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, MOMENTUM,
+                                                              EPS, pool, want_x, recompute=False)))
+    x, y, mean, invstd = res["out"]
+    assert (x is not None) == want_x
+    r_x = torch.full_like(x, float("nan")) if want_x else None
+    r_y, save = torch.full_like(y, float("nan")), torch.full((2, 64), float("nan"), device="cuda")
+    ws = torch.empty((lib.coattn_conv1_bn_exact_workspace_bytes(B, H, W, int(not want_x)) + 3) // 4, device="cuda")
+    raw_marks = _marked(lambda: M.check(lib.coattn_conv1_bn_exact_forward(_vp(img), _vp(w), _vp(bn.weight), _vp(bn.bias), _vp(rm), _vp(rv),
+                                                                          MOMENTUM, EPS, _vp(r_x), _vp(r_y), _vp(save[0]), _vp(save[1]),
+                                                                          _vp(ws), B, H, W, 3, 64, int(pool), M.F32, _stream()),
+                                        "coattn_conv1_bn_exact_forward"))
+    torch.cuda.synchronize()
+    for a, b, what in ((x, r_x, "x"), (y, r_y, "y"), (mean, save[0], "save_mean"), (invstd, save[1], "save_invstd"),
+                       (bn.running_mean, rm, "running_mean"), (bn.running_var, rv, "running_var")):
+        _same(a, b, what)
+    assert marks == raw_marks and "conv1_bn_exact" in marks and bool(torch.isfinite(r_y).all()), (marks, raw_marks)
+
+
+@pytest.mark.parametrize("dtype", (torch.float32, torch.bfloat16), ids=("fp32", "bf16"))
+def test_native_features_is_the_raw_call_bit_for_bit(dtype):
+    from vqa_amd.coattention import native_features
+    M = _lib()
+    lib = M.load()
+    B, N, d = 3, 7, 130                                      # (tests/test_gpu_features.py)
+    x = _f32(B, d, N, seed=1).to(dtype).permute(0, 2, 1)     # channel-major rows of 7 elements: not a native layout
+    res = {}
+    marks = _marked(lambda: res.update(out=native_features(x)))
+    out = torch.full((B, N, d), float("nan"), device="cuda")
+    raw_marks = _marked(lambda: M.check(lib.coattn_features_native(_vp(x), M.BF16 if dtype == torch.bfloat16 else M.F32, *x.stride(),
+                                                                   _vp(out), B, N, d, _stream()), "coattn_features_native"))
+    torch.cuda.synchronize()
+    assert res["out"] is not x and res["out"].dtype == torch.float32
+    _same(res["out"], out, "features")
+    assert torch.equal(out, x.float()) and marks == raw_marks

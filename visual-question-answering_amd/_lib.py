@@ -10,32 +10,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COATTN_LIB_PATH") or os.path.join(_HERE, "libcoattn_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-# every symbol include/coattn.h declares
-EXPORTS = ("coattn_version", "coattn_last_error", "coattn_fused_supported", "coattn_workspace_bytes",
-           "coattn_forward", "coattn_attention_forward", "coattn_backward", "coattn_gemm_f32", "coattn_gemm_bf16",
-           "coattn_phrase_workspace_bytes", "coattn_phrase_forward", "coattn_phrase_backward",
-           "coattn_ce_workspace_bytes", "coattn_ce_forward", "coattn_linear_workspace_bytes", "coattn_linear_forward",
-           "coattn_linear_wgrad_workspace_bytes", "coattn_linear_weight_grad",
-           "coattn_head_workspace_bytes", "coattn_head_forward", "coattn_head_backward", "coattn_head_status",
-           "coattn_ce_status", "coattn_p2p_enable_peer", "coattn_p2p_reduce_scatter", "coattn_p2p_all_gather",
-           "coattn_profile_begin", "coattn_profile_end", "coattn_features_native", "coattn_status",
-           "coattn_phrase_status", "coattn_status_accumulate", "coattn_phrase_status_accumulate", "coattn_infer",
-           "coattn_forward_len", "coattn_infer_len", "coattn_attention_forward_len", "coattn_backward_len",
-           "coattn_forward_maps", "coattn_forward_maps_len", "coattn_backward_maps", "coattn_backward_maps_len",
-           "coattn_alt_workspace_bytes", "coattn_alt_forward", "coattn_alt_backward",
-           "coattn_soft_loss_forward", "coattn_vqa_score", "coattn_head_forward_soft",
-           "coattn_adam_workspace_bytes", "coattn_adam_step",
-           "coattn_bn_supported", "coattn_bn_workspace_bytes", "coattn_bn_relu_pool_forward", "coattn_relu_pool_forward",
-           "coattn_bn_exact_geometry", "coattn_bn_exact_workspace_bytes", "coattn_bn_exact_forward",
-           "coattn_conv1_bn_exact_supported", "coattn_conv1_bn_exact_workspace_bytes", "coattn_conv1_bn_exact_forward",
-           "coattn_conv1_probe", "coattn_conv1_bn_recompute_workspace_bytes", "coattn_conv1_bn_recompute_forward",
-           "coattn_lstm_supported", "coattn_lstm_workspace_bytes", "coattn_lstm_forward", "coattn_lstm_backward",
-           "coattn_embedding_supported", "coattn_embedding_workspace_bytes", "coattn_embedding_forward",
-           "coattn_embedding_backward",
-           "coattn_dropout_supported", "coattn_dropout_forward", "coattn_dropout_backward",
-           "coattn_features_gather_supported", "coattn_features_gather",
-           "coattn_overlay_supported", "coattn_overlay_render")
-
 F32 = 0
 IDS_I32, IDS_I64 = 0, 1   # ids_dtype of the word embedding calls (v0.18.0: COATTN_IDS_*)
 BF16 = 1                  # storage type of coattn_features_native's input and of a bf16 feature table (coattn_features_gather)
@@ -135,32 +109,58 @@ class GemmDesc(C.Structure):
                    ("kband_n", C.c_int), ("kband_lo", C.c_int * 3), ("kband_hi", C.c_int * 3),
                    ("out_scale", C.c_float)])
 
-# ---- the co-attention, alternating and head entry points, argument by argument ------------------------------------------
-# SIGNATURES[symbol] = ((argument name, ctype), ...) with the names and the order of include/coattn.h
-# (tests/test_call_layer_cpu.py holds every row against the header).  load() takes their argtypes from here, bind()
-# turns keyword arguments into the positional tuple.
+# ---- the C-ABI, argument by argument --------------------------------------------------------------------------------------
+# SIGNATURES[symbol] = ((argument name, ctype), ...) for every function include/coattn.h declares, with its names and order
+# (tests/test_call_layer_cpu.py holds every row against the header); RESTYPES the return types that are not int.  load() takes
+# argtypes and restype from here, bind() turns keyword arguments into the positional tuple.  A new entry point is one row.
 def _of(ctype):
     return lambda names: tuple((n, ctype) for n in names.split())
 
 
 _void, _i64, _int, _ptrs = _of(C.c_void_p), _of(C.c_int64), _of(C.c_int), _of(C.POINTER(C.c_void_p))
+_f64, _f32, _sizes, _floats = _of(C.c_double), _of(C.c_float), _of(C.POINTER(C.c_size_t)), _of(C.POINTER(C.c_float))
+
+
+def _to(struct, name="p"):
+    return ((name, C.POINTER(struct)),)
+
+
 _V_Q = _void("V") + _i64("v_sB v_sN v_sD") + _ptrs("Q")
 _LEN, _MAPS, _MAP_GRADS = _void("q_len"), _void("av_out aq_out"), _void("g_av g_aq")
 _DIMS = _int("B N T d L dtype flags") + _void("stream")
-_HEAD = _ptrs("v q") + (("p", C.POINTER(HeadParams)),)
+_HEAD = _ptrs("v q") + _to(HeadParams)
 _HEAD_DIMS = _int("B d mlp K dtype flags") + _void("stream")
+_PHRASE_DIMS = _int("B T E dtype flags") + _void("stream")
+_LSTM_DIMS = _int("B T E H dtype flags") + _void("stream")
+_EMB_DIMS = _i64("n V") + _int("E") + _i64("padding_idx")
+_BN_DIMS = _int("B H W C pool relu dtype") + _void("stream")
+_THREE_SIZES = _sizes("saved ws_fwd ws_bwd")
+CONV1_RECOMPUTE_CHUNK = 8   # COATTN_CONV1_RECOMPUTE_CHUNK: samples per workgroup of the recompute form's third kernel
 
 
 def _forward(lens=(), maps=(), saved=_void("saved"), params=Params):
-    return _V_Q + lens + (("p", C.POINTER(params)),) + _void("v_out q_out") + maps + saved + _void("ws") + _DIMS
+    return _V_Q + lens + _to(params) + _void("v_out q_out") + maps + saved + _void("ws") + _DIMS
 
 
 def _backward(lens=(), maps=(), params=Params, grads=ParamGrads):
-    return (_V_Q + lens + (("p", C.POINTER(params)),) + _void("saved gv gq") + maps + _void("dV") + _i64("dv_sB dv_sN dv_sD")
-            + _ptrs("dQ") + (("pg", C.POINTER(grads)),) + _int("accumulate") + _void("ws") + _DIMS)
+    return (_V_Q + lens + _to(params) + _void("saved gv gq") + maps + _void("dV") + _i64("dv_sB dv_sN dv_sD")
+            + _ptrs("dQ") + _to(grads, "pg") + _int("accumulate") + _void("ws") + _DIMS)
+
+
+def _conv1(outputs):
+    return (_void("image weight gamma beta running_mean running_var") + _f64("momentum eps") + _void(outputs)
+            + _void("save_mean save_invstd ws") + _int("B H W Cin Cout pool dtype") + _void("stream"))
 
 
 SIGNATURES = {
+    "coattn_version": (), "coattn_last_error": (),
+    "coattn_profile_begin": _void("stream"),
+    "coattn_profile_end": _floats("us") + _of(C.c_char_p)("names") + _int("names_bytes max_marks"),
+    "coattn_features_native": _void("x") + _int("x_dtype") + _i64("sB sN sD") + _void("out") + _int("B N d") + _void("stream"),
+    # the parallel and the alternating co-attention
+    "coattn_fused_supported": _int("B N T d L dtype"),
+    "coattn_workspace_bytes": _int("B N T d L dtype flags") + _THREE_SIZES,
+    "coattn_alt_workspace_bytes": _int("B N T d L dtype flags") + _THREE_SIZES,
     "coattn_forward": _forward(), "coattn_forward_len": _forward(_LEN),
     "coattn_attention_forward": _forward(), "coattn_attention_forward_len": _forward(_LEN),
     "coattn_forward_maps": _forward(maps=_MAPS), "coattn_forward_maps_len": _forward(_LEN, _MAPS),
@@ -169,49 +169,92 @@ SIGNATURES = {
     "coattn_backward_maps": _backward(maps=_MAP_GRADS), "coattn_backward_maps_len": _backward(_LEN, _MAP_GRADS),
     "coattn_alt_forward": _forward(_LEN, _MAPS, params=AltParams),
     "coattn_alt_backward": _backward(_LEN, _MAP_GRADS, AltParams, AltParamGrads),
+    "coattn_status": _void("saved") + _int("B N T d L dtype") + _void("stream") + _floats("amax"),
+    "coattn_status_accumulate": _void("saved") + _int("B N T d L dtype") + _void("acc stream"),
+    # the phrase level
+    "coattn_phrase_workspace_bytes": _int("B T E dtype") + _THREE_SIZES,
+    "coattn_phrase_forward": _void("X") + _to(PhraseParams) + _void("out saved ws") + _PHRASE_DIMS,
+    "coattn_phrase_backward": (_void("X") + _to(PhraseParams) + _void("out saved g_out dX") + _to(PhraseParamGrads, "pg")
+                               + _int("accumulate") + _void("ws") + _PHRASE_DIMS),
+    "coattn_phrase_status": _void("saved") + _int("B T E") + _void("stream") + _floats("amax"),
+    "coattn_phrase_status_accumulate": _void("saved") + _int("B T E") + _void("acc stream"),
+    # the losses and the answer head
+    "coattn_ce_workspace_bytes": _int("B K dtype") + _sizes("ws"),
+    "coattn_ce_forward": _void("logits labels loss dlogits ws") + _int("B K dtype") + _void("stream"),
+    "coattn_ce_status": _void("ws") + _int("B") + _void("stream"),
+    "coattn_soft_loss_forward": (_void("logits ans_idx ans_score") + _int("A kind") + _void("loss dlogits ws") + _int("B K dtype")
+                                 + _void("stream")),
+    "coattn_vqa_score": (_void("logits ans_idx ans_score") + _int("A") + _void("pred row_score score_sum ws") + _int("B K dtype")
+                         + _void("stream")),
+    "coattn_head_workspace_bytes": _int("B d mlp K dtype") + _sizes("saved ws_bwd"),
     "coattn_head_forward": _HEAD + _void("labels logits loss saved") + _HEAD_DIMS,
     "coattn_head_forward_soft": (_HEAD + _void("ans_idx ans_score") + _int("A kind") + _void("logits loss saved")
                                  + _HEAD_DIMS),
-    "coattn_head_backward": (_HEAD + _void("saved g_loss g_logits") + _ptrs("dv dq") + (("pg", C.POINTER(HeadParamGrads)),)
+    "coattn_head_backward": (_HEAD + _void("saved g_loss g_logits") + _ptrs("dv dq") + _to(HeadParamGrads, "pg")
                              + _int("accumulate") + _void("ws") + _HEAD_DIMS),
-}
-# the word embedding (v0.18.0), in the same form; a table of its own: SIGNATURES is the co-attention and head calls
-_EMB_DIMS = _i64("n V") + _int("E") + _i64("padding_idx")
-EMBEDDING_SIGNATURES = {
+    "coattn_head_status": _void("saved") + _int("B d mlp K") + _void("stream"),
+    # the optimiser step
+    "coattn_adam_workspace_bytes": _to(AdamTensor, "t") + _int("n_tensors"),
+    "coattn_adam_step": (_to(AdamTensor, "t") + _int("n_tensors step") + _f64("lr beta1 beta2 eps weight_decay max_grad_norm")
+                         + _void("norm_out ws") + _of(C.c_size_t)("ws_bytes") + _void("stream")),
+    # the frozen encoder
+    "coattn_bn_supported": _int("B H W C pool dtype"),
+    "coattn_bn_workspace_bytes": _int("B H W C"),
+    "coattn_bn_relu_pool_forward": (_void("x gamma beta conv_bias running_mean running_var") + _f64("momentum eps")
+                                    + _void("y stats_out ws") + _BN_DIMS),
+    "coattn_relu_pool_forward": _void("x y") + _int("B H W C dtype") + _void("stream"),
+    "coattn_bn_exact_geometry": _int("B H W C dtype") + _of(C.POINTER(C.c_int))("out"),
+    "coattn_bn_exact_workspace_bytes": _int("B H W C"),
+    "coattn_bn_exact_forward": (_void("x gamma beta running_mean running_var") + _f64("momentum eps")
+                                + _void("y save_mean save_invstd ws") + _BN_DIMS),
+    "coattn_conv1_bn_exact_supported": _int("B H W Cin Cout pool dtype"),
+    "coattn_conv1_bn_exact_workspace_bytes": _int("B H W with_x"),
+    "coattn_conv1_bn_exact_forward": _conv1("x_out y"),
+    "coattn_conv1_probe": _void("image weight x ws") + _int("B H W order step halves skip") + _void("stream"),
+    "coattn_conv1_bn_recompute_workspace_bytes": _int("B H W"),
+    "coattn_conv1_bn_recompute_forward": _conv1("y"),
+    # the sentence LSTM, the word embedding, feature dropout, cached features, overlays
+    "coattn_lstm_supported": _int("B T E H dtype"),
+    "coattn_lstm_workspace_bytes": _int("B T E H dtype") + _THREE_SIZES,
+    "coattn_lstm_forward": _void("X len") + _to(LstmParams) + _void("out x_masked saved ws") + _LSTM_DIMS,
+    "coattn_lstm_backward": (_void("X len") + _to(LstmParams) + _void("out saved g_out g_xmasked dX") + _to(LstmParamGrads, "pg")
+                             + _int("accumulate") + _void("ws") + _LSTM_DIMS),
+    "coattn_embedding_supported": _i64("n V") + _int("E dtype"),
+    "coattn_embedding_workspace_bytes": _i64("n V") + _int("E dtype") + _sizes("ws_bwd"),
     "coattn_embedding_forward": (_void("ids") + _int("ids_dtype") + _void("W out bad_ids") + _EMB_DIMS + _int("dtype flags")
                                  + _void("stream")),
     "coattn_embedding_backward": (_void("ids") + _int("ids_dtype") + _void("g_out dW ws") + _EMB_DIMS
                                   + _int("accumulate dtype flags") + _void("stream")),
-}
-# feature dropout (v0.19.0), a table of its own as well; p is the one float argument of the tabled calls
-DROPOUT_SIGNATURES = {
-    "coattn_dropout_forward": (_void("x0 y0 x1 y1") + _i64("n") + _of(C.c_float)("p") + _void("state") + _int("advance")
-                               + _void("stream")),
-    "coattn_dropout_backward": _void("g dx") + _i64("n") + _of(C.c_float)("p") + _void("state stream"),
-}
-# the gather of cached image features (v0.20.0), a table of its own as well
-FEATURES_SIGNATURES = {
+    "coattn_dropout_supported": _i64("n"),
+    "coattn_dropout_forward": _void("x0 y0 x1 y1") + _i64("n") + _f32("p") + _void("state") + _int("advance") + _void("stream"),
+    "coattn_dropout_backward": _void("g dx") + _i64("n") + _f32("p") + _void("state stream"),
+    "coattn_features_gather_supported": _i64("S B") + _int("N d table_dtype flags"),
     "coattn_features_gather": (_void("table") + _int("table_dtype") + _void("idx") + _int("idx_dtype") + _void("out bad_idx")
                                + _i64("S B") + _int("N d flags") + _void("stream")),
-}
-# the attention overlays (v0.21.0), a table of its own as well
-OVERLAY_SIGNATURES = {
-    "coattn_overlay_render": (_void("image") + _i64("sB sC sH sW") + _void("a_v a_q q_len") + (("p", C.POINTER(OverlayParams)),)
+    "coattn_overlay_supported": _int("B L H W Gh Gw T strip_h mode"),
+    "coattn_overlay_render": (_void("image") + _i64("sB sC sH sW") + _void("a_v a_q q_len") + _to(OverlayParams)
                               + _void("out bad_maps") + _int("B L H W Gh Gw T strip_h mode") + _void("stream")),
+    # the GEMM and linear building blocks, the peer-to-peer exchange
+    "coattn_gemm_f32": _to(GemmDesc, "g") + _void("stream"), "coattn_gemm_bf16": _to(GemmDesc, "g") + _void("stream"),
+    "coattn_linear_workspace_bytes": _int("N K"),
+    "coattn_linear_forward": (_void("x") + _i64("ld_x") + _void("W bias y wimg") + _int("M N K") + _f32("out_scale") + _int("flags")
+                              + _void("stream")),
+    "coattn_linear_wgrad_workspace_bytes": _int("n_out n_in"),
+    "coattn_linear_weight_grad": (_void("dy") + _i64("ld_dy") + _void("x") + _i64("ld_x") + _void("dW ws")
+                                  + _int("M n_out n_in accumulate") + _void("stream")),
+    "coattn_p2p_enable_peer": _int("peer_device"),
+    "coattn_p2p_reduce_scatter": _ptrs("peer_bufs") + _int("world rank") + _i64("shard_elems") + _f32("scale") + _void("stream"),
+    "coattn_p2p_all_gather": _ptrs("peer_bufs") + _int("world rank") + _i64("shard_elems") + _void("stream"),
 }
-# layer 1 of the frozen encoder with the convolution computed twice and never stored (v0.22.0), a table of its own as well;
-# momentum and eps are the double arguments
-CONV1_RECOMPUTE_CHUNK = 8   # COATTN_CONV1_RECOMPUTE_CHUNK: samples per workgroup of the third kernel
-CONV1_SIGNATURES = {
-    "coattn_conv1_bn_recompute_forward": (_void("image weight gamma beta running_mean running_var") + _of(C.c_double)("momentum eps")
-                                          + _void("y save_mean save_invstd ws") + _int("B H W Cin Cout pool dtype")
-                                          + _void("stream")),
-}
-_TABLE = {**SIGNATURES, **EMBEDDING_SIGNATURES, **DROPOUT_SIGNATURES, **FEATURES_SIGNATURES, **OVERLAY_SIGNATURES,
-          **CONV1_SIGNATURES}
-_INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _TABLE.items()}
+RESTYPES = {"coattn_last_error": C.c_char_p}
+RESTYPES.update(dict.fromkeys(("coattn_adam_workspace_bytes", "coattn_bn_workspace_bytes", "coattn_bn_exact_workspace_bytes",
+                               "coattn_conv1_bn_exact_workspace_bytes", "coattn_conv1_bn_recompute_workspace_bytes",
+                               "coattn_linear_workspace_bytes", "coattn_linear_wgrad_workspace_bytes"), C.c_size_t))
+EXPORTS = tuple(SIGNATURES)   # every symbol include/coattn.h declares
+_INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in SIGNATURES.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
-_DEFAULTS = dict.fromkeys("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1 bad_maps".split())
+_DEFAULTS = dict.fromkeys(("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1 bad_maps "
+                           "conv_bias stats_out x_out dlogits x_masked g_xmasked dX").split())
 _DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
 
 
@@ -248,15 +291,19 @@ def _as_arg(value, ctype):
 
 class Call(tuple):
     """The positional arguments of the entry point `name`, as bind() lays them out.  call() issues it and raises on an error
-    code; a call bound without `stream` (always the last argument) takes it then: call(stream).  The tuple keeps the host
-    arrays and structures it points to alive."""
+    code, call.code() issues it and returns the code (the status calls: -2 is theirs to interpret); a call bound without
+    `stream` (always the last argument) takes it then: call(stream).  The tuple keeps the host arrays and structures it points
+    to alive."""
+
+    def code(self, *stream) -> int:
+        return self.fn(*self, *stream)
 
     def __call__(self, *stream):
-        check(self.fn(*self, *stream), self.name)
+        check(self.code(*stream), self.name)
 
     def replace(self, **kw):
         """The same call with the given arguments replaced (one list copy: cheap enough for every step)."""
-        sig, index, vals = _TABLE[self.name], _INDEX[self.name], list(self)
+        sig, index, vals = SIGNATURES[self.name], _INDEX[self.name], list(self)
         for n, v in kw.items():
             if n not in index:
                 raise TypeError("%s has no argument %r" % (self.name, n))
@@ -279,7 +326,7 @@ def bind(name: str, **kw) -> Call:
     if unknown:
         raise TypeError("%s has no argument %s" % (name, ", ".join(sorted(unknown))))
     vals = []
-    for n, ctype in _TABLE[name]:
+    for n, ctype in SIGNATURES[name]:
         if n in kw:
             vals.append(_as_arg(kw[n], ctype))
         elif n in _DEFAULTS:
@@ -313,101 +360,11 @@ def load() -> C.CDLL:
         raise RuntimeError("HIP extension %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(there is no CPU fallback for the co-attention path)" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name in EXPORTS:
+    for name, sig in SIGNATURES.items():
         if not hasattr(lib, name):
             raise RuntimeError("libcoattn_hip.so lacks symbol %s" % name)
-    lib.coattn_version.restype = C.c_int
-    lib.coattn_last_error.restype = C.c_char_p
-    for name, sig in _TABLE.items():                     # the co-attention, alternating, head and embedding calls: the tables
-        getattr(lib, name).argtypes = [ctype for _, ctype in sig]
-    lib.coattn_fused_supported.argtypes = [C.c_int] * 6
-    lib.coattn_workspace_bytes.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_size_t)] * 3
-    lib.coattn_alt_workspace_bytes.argtypes = [C.c_int] * 7 + [C.POINTER(C.c_size_t)] * 3
-    lib.coattn_gemm_f32.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
-    lib.coattn_gemm_bf16.argtypes = [C.POINTER(GemmDesc), C.c_void_p]
-    lib.coattn_phrase_workspace_bytes.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_size_t)] * 3
-    lib.coattn_phrase_forward.argtypes = [C.c_void_p, C.POINTER(PhraseParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.coattn_phrase_backward.argtypes = [C.c_void_p, C.POINTER(PhraseParams), C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.POINTER(PhraseParamGrads), C.c_int, C.c_void_p,
-                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.coattn_ce_workspace_bytes.argtypes = [C.c_int] * 3 + [C.POINTER(C.c_size_t)]
-    lib.coattn_ce_forward.argtypes = [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]
-    lib.coattn_linear_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.coattn_linear_workspace_bytes.restype = C.c_size_t
-    lib.coattn_linear_forward.argtypes = ([C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int] * 3
-                                          + [C.c_float, C.c_int, C.c_void_p])
-    lib.coattn_linear_wgrad_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.coattn_linear_wgrad_workspace_bytes.restype = C.c_size_t
-    lib.coattn_linear_weight_grad.argtypes = ([C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-                                              + [C.c_int] * 4 + [C.c_void_p])
-    lib.coattn_ce_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    lib.coattn_status.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.POINTER(C.c_float)]
-    lib.coattn_phrase_status.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.POINTER(C.c_float)]
-    lib.coattn_status_accumulate.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
-    lib.coattn_phrase_status_accumulate.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p]
-    lib.coattn_p2p_enable_peer.argtypes = [C.c_int]
-    lib.coattn_p2p_reduce_scatter.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p]
-    lib.coattn_p2p_all_gather.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int64, C.c_void_p]
-    lib.coattn_profile_begin.argtypes = [C.c_void_p]
-    lib.coattn_profile_end.argtypes = [C.POINTER(C.c_float), C.c_char_p, C.c_int, C.c_int]
-    lib.coattn_features_native.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                           C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.coattn_head_status.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]
-    lib.coattn_head_workspace_bytes.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_size_t)] * 2
-    # soft answer targets (v0.12.0): (ans_idx, ans_score, A, kind) where the hard-label calls take `labels`
-    lib.coattn_soft_loss_forward.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]
-    lib.coattn_vqa_score.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]
-    # the optimiser step (v0.13.0): (list, n_tensors, step, lr, beta1, beta2, eps, weight_decay, max_grad_norm, norm_out, ws,
-    # ws_bytes, stream)
-    lib.coattn_adam_workspace_bytes.argtypes = [C.POINTER(AdamTensor), C.c_int]
-    lib.coattn_adam_workspace_bytes.restype = C.c_size_t
-    lib.coattn_adam_step.argtypes = ([C.POINTER(AdamTensor), C.c_int, C.c_int] + [C.c_double] * 6
-                                     + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
-    # the frozen encoder's BatchNorm + ReLU + max-pool (v0.14.0): (x, gamma, beta, conv_bias, running_mean, running_var,
-    # momentum, eps, y, stats_out, ws, B, H, W, C, pool, relu, dtype, stream)
-    lib.coattn_bn_supported.argtypes = [C.c_int] * 6
-    lib.coattn_bn_workspace_bytes.argtypes = [C.c_int] * 4
-    lib.coattn_bn_workspace_bytes.restype = C.c_size_t
-    lib.coattn_bn_relu_pool_forward.argtypes = ([C.c_void_p] * 6 + [C.c_double] * 2 + [C.c_void_p] * 3 + [C.c_int] * 7
-                                                + [C.c_void_p])
-    lib.coattn_relu_pool_forward.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]
-    # the stock BatchNorm kernels' bits (v0.15.0): (x, gamma, beta, running_mean, running_var, momentum, eps, y, save_mean,
-    # save_invstd, ws, B, H, W, C, pool, relu, dtype, stream)
-    lib.coattn_bn_exact_geometry.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)]
-    lib.coattn_bn_exact_workspace_bytes.argtypes = [C.c_int] * 4
-    lib.coattn_bn_exact_workspace_bytes.restype = C.c_size_t
-    lib.coattn_bn_exact_forward.argtypes = ([C.c_void_p] * 5 + [C.c_double] * 2 + [C.c_void_p] * 4 + [C.c_int] * 7
-                                            + [C.c_void_p])
-    # layer 1 of the frozen encoder, convolution + statistics in one pass (v0.16.0): (image, weight, gamma, beta, running_mean,
-    # running_var, momentum, eps, x_out, y, save_mean, save_invstd, ws, B, H, W, Cin, Cout, pool, dtype, stream)
-    lib.coattn_conv1_bn_exact_supported.argtypes = [C.c_int] * 7
-    lib.coattn_conv1_bn_exact_workspace_bytes.argtypes = [C.c_int] * 4
-    lib.coattn_conv1_bn_exact_workspace_bytes.restype = C.c_size_t
-    lib.coattn_conv1_bn_exact_forward.argtypes = ([C.c_void_p] * 6 + [C.c_double] * 2 + [C.c_void_p] * 5 + [C.c_int] * 7
-                                                  + [C.c_void_p])
-    lib.coattn_conv1_probe.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]
-    # the same without x (v0.22.0): the forward is tabled (CONV1_SIGNATURES); (B, H, W)
-    lib.coattn_conv1_bn_recompute_workspace_bytes.argtypes = [C.c_int] * 3
-    lib.coattn_conv1_bn_recompute_workspace_bytes.restype = C.c_size_t
-    # the sentence LSTM (v0.17.0): (X, len, p, out, x_masked, saved, ws, B, T, E, H, dtype, flags, stream) and
-    # (X, len, p, out, saved, g_out, g_xmasked, dX, pg, accumulate, ws, B, T, E, H, dtype, flags, stream)
-    lib.coattn_lstm_supported.argtypes = [C.c_int] * 5
-    lib.coattn_lstm_workspace_bytes.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_size_t)] * 3
-    lib.coattn_lstm_forward.argtypes = ([C.c_void_p] * 2 + [C.POINTER(LstmParams)] + [C.c_void_p] * 4 + [C.c_int] * 6
-                                        + [C.c_void_p])
-    lib.coattn_lstm_backward.argtypes = ([C.c_void_p] * 2 + [C.POINTER(LstmParams)] + [C.c_void_p] * 5
-                                         + [C.POINTER(LstmParamGrads)] + [C.c_int] + [C.c_void_p] + [C.c_int] * 6
-                                         + [C.c_void_p])
-    # the word embedding (v0.18.0): forward and backward are tabled (EMBEDDING_SIGNATURES)
-    lib.coattn_embedding_supported.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int]
-    lib.coattn_embedding_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
-    # feature dropout (v0.19.0): forward and backward are tabled (DROPOUT_SIGNATURES)
-    lib.coattn_dropout_supported.argtypes = [C.c_int64]
-    # cached image features (v0.20.0): the gather is tabled (FEATURES_SIGNATURES); (S, B, N, d, table_dtype, flags)
-    lib.coattn_features_gather_supported.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int]
-    # attention overlays (v0.21.0): the render is tabled (OVERLAY_SIGNATURES); (B, L, H, W, Gh, Gw, T, strip_h, mode)
-    lib.coattn_overlay_supported.argtypes = [C.c_int] * 9
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = [ctype for _, ctype in sig], RESTYPES.get(name, C.c_int)
     _lib = lib
     return lib
 
@@ -450,16 +407,20 @@ def _acc(dev):
 def fold_range() -> None:
     """Fold the status words of every tolerance-mode forward noted since the last fold into the per-device accumulators.
     Asynchronous (one 256-thread launch per call, on the stream the call ran on)."""
-    lib = load()
     while _pending:
         kind, buf, dims, dev, st = _pending.pop(0)
-        acc = _acc(dev)
         with on_device(dev):
-            if kind == "coattn":
-                rc = lib.coattn_status_accumulate(C.c_void_p(buf.data_ptr()), *dims, F32, C.c_void_p(acc.data_ptr()), C.c_void_p(st))
-            else:
-                rc = lib.coattn_phrase_status_accumulate(C.c_void_p(buf.data_ptr()), *dims, C.c_void_p(acc.data_ptr()), C.c_void_p(st))
-        check(rc, "coattn_status_accumulate" if kind == "coattn" else "coattn_phrase_status_accumulate")
+            status_accumulate(kind, buf, dims, _acc(dev), st)()
+
+
+def status_accumulate(kind, saved, dims, acc, stream) -> Call:
+    """The fold of one forward's status words into `acc`: coattn_status_accumulate over dims (B, N, T, d, L) for kind "coattn",
+    coattn_phrase_status_accumulate over (B, T, E) otherwise."""
+    if kind == "coattn":
+        B, N, T, d, L = dims
+        return bind("coattn_status_accumulate", saved=saved, B=B, N=N, T=T, d=d, L=L, dtype=F32, acc=acc, stream=stream)
+    B, T, E = dims
+    return bind("coattn_phrase_status_accumulate", saved=saved, B=B, T=T, E=E, acc=acc, stream=stream)
 
 
 def range_maxima(reset: bool = True):
@@ -498,6 +459,15 @@ def check(rc: int, what: str) -> None:
         raise RuntimeError("%s failed (%d): %s" % (what, rc, load().coattn_last_error().decode()))
 
 
+def check_label_status(call: Call) -> None:
+    """Issue a bound coattn_ce_status / coattn_head_status (they synchronise the stream): IndexError with the library's message
+    for -2, a label or answer index out of range; any other code as check()."""
+    rc = call.code()
+    if rc == -2:
+        raise IndexError(load().coattn_last_error().decode())
+    check(rc, call.name)
+
+
 class _NoGuard:
     def __enter__(self):
         return None
@@ -530,6 +500,21 @@ def _bytes(symbol, n_out, *dims):
         check(getattr(load(), symbol)(*dims, *[C.byref(o) for o in out]), symbol)
         hit = _bytes_cache[key] = tuple(o.value for o in out)
     return hit
+
+
+def size_bytes(symbol, *args) -> int:
+    """The byte count of a *_workspace_bytes entry point that returns size_t; 0 for a shape or list it does not take."""
+    return getattr(load(), symbol)(*args)
+
+
+def phrase_workspace_bytes(B, T, E):
+    """(saved, ws_fwd, ws_bwd) in bytes of the phrase level."""
+    return _bytes("coattn_phrase_workspace_bytes", 3, B, T, E, F32)
+
+
+def ce_workspace_bytes(B, K):
+    """ws in bytes of the cross entropy, the soft-target losses and the score."""
+    return _bytes("coattn_ce_workspace_bytes", 1, B, K, F32)[0]
 
 
 def workspace_bytes(B, N, T, d, L, flags=0):

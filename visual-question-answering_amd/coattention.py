@@ -12,7 +12,6 @@ tensors (the C-ABI's ``coattn_forward_maps`` / ``coattn_backward_maps``), for lo
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Sequence
 
@@ -20,7 +19,6 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import ptr as _ptr
 
 
 def _impl_flag() -> int:
@@ -87,15 +85,17 @@ def native_features(x_img: torch.Tensor, out: torch.Tensor = None) -> torch.Tens
         out = torch.empty((B, N, d), device=x_img.device, dtype=torch.float32)
     elif (tuple(out.shape) != (B, N, d) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x_img.device):
         raise RuntimeError("native_features: `out` must be a contiguous fp32 [B,N,d] tensor on the features' device")
-    lib = _lib.load()
-    sB, sN, sD = _strides(x_img)
-    if min(sB, sN, sD) < 0:
+    if min(_strides(x_img)) < 0:
         raise RuntimeError("native_features: negative strides")
     with _lib.on_device(x_img.device):
-        _lib.check(lib.coattn_features_native(_ptr(x_img), _lib.BF16 if x_img.dtype == torch.bfloat16 else _lib.F32,
-                                              sB, sN, sD, _ptr(out), B, N, d, C.c_void_p(_lib.stream_ptr(x_img.device))),
-                   "coattn_features_native")
+        _features_native_call(x_img, out, _lib.stream_ptr(x_img.device))()
     return out
+
+
+def _features_native_call(x_img, out, stream):
+    (B, N, d), (sB, sN, sD) = x_img.shape, _strides(x_img)
+    return _lib.bind("coattn_features_native", x=x_img, x_dtype=_lib.BF16 if x_img.dtype == torch.bfloat16 else _lib.F32,
+                     sB=sB, sN=sN, sD=sD, out=out, B=B, N=N, d=d, stream=stream)
 
 
 def question_lengths(x_ques_lens, B: int, device) -> torch.Tensor:

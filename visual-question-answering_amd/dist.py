@@ -196,7 +196,6 @@ class GradReducer:
         try block whose outcome is what the rank contributes (a rank that raised before the collective left the
         others waiting in it).  A rank that raises afterwards leaves no peer waiting (the caller's consensus all-reduce
         comes next on every rank)."""
-        import ctypes as C
         mine = None
         self.rank = dist.get_rank(self.group)
         try:
@@ -229,7 +228,7 @@ class GradReducer:
                         from . import _lib
                         _lib.check(self._lib.coattn_p2p_enable_peer(t.device.index), "coattn_p2p_enable_peer")
                     b.flat.new_empty(4).copy_(t[:4])
-            b.peer_ptrs = (C.c_void_p * self.world)(*[t.data_ptr() for t in b.peers])
+            b.peer_ptrs = _lib.ptr_array(b.peers)
 
     def _p2p_sync(self):
         """Every rank's work enqueued so far is done before any rank's later work starts."""
@@ -249,20 +248,22 @@ class GradReducer:
         torch.cuda.synchronize(self._dev)
         dist.barrier(group=self.group)
 
-    def _p2p_finish(self):
+    def _p2p_call(self, symbol, b, stream, **scale):
         from . import _lib
+        return _lib.bind(symbol, peer_bufs=b.peer_ptrs, world=self.world, rank=self.rank, shard_elems=b.flat.numel() // self.world,
+                         stream=stream, **scale)
+
+    def _p2p_finish(self):
         # (the buckets' own device and its current stream, whatever device the caller has selected: as head.py / loss.py)
         stream = torch.cuda.current_stream(self._dev).cuda_stream
         self._p2p_sync()                                               # every rank's buckets are packed
         with torch.cuda.device(self._dev):
             for b in self.buckets:
-                _lib.check(self._lib.coattn_p2p_reduce_scatter(b.peer_ptrs, self.world, self.rank, b.flat.numel() // self.world,
-                                                               1.0 / self.world, stream), "coattn_p2p_reduce_scatter")
+                self._p2p_call("coattn_p2p_reduce_scatter", b, stream, scale=1.0 / self.world)()
         self._p2p_sync()                                               # every shard is reduced
         with torch.cuda.device(self._dev):
             for b in self.buckets:
-                _lib.check(self._lib.coattn_p2p_all_gather(b.peer_ptrs, self.world, self.rank, b.flat.numel() // self.world,
-                                                           stream), "coattn_p2p_all_gather")
+                self._p2p_call("coattn_p2p_all_gather", b, stream)()
         self._p2p_sync()                                               # nobody still reads a bucket that is packed next
 
     def _launch(self, b):

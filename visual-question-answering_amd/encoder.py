@@ -23,7 +23,6 @@ layer takes what:
 ``VQA_ENCODER_FUSED=0`` keeps every stock kernel."""
 from __future__ import annotations
 
-import ctypes as C
 import os
 import warnings
 
@@ -66,11 +65,28 @@ def relu_pool(x: torch.Tensor) -> torch.Tensor:
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(memory_format=torch.channels_last)):
         raise ValueError("relu_pool: needs a CUDA fp32 channels_last [B,C,H,W] tensor, got %s %s strides %s"
                          % (tuple(x.shape), x.dtype, x.stride()))
-    y = torch.empty((B, Ch, H // 2, W // 2), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    y = _empty_y(x, Ch, True)
     with _lib.on_device(x.device):
-        _lib.check(_lib.load().coattn_relu_pool_forward(_lib.ptr(x), _lib.ptr(y), B, H, W, Ch, _lib.F32,
-                                                        C.c_void_p(_lib.stream_ptr(x.device))), "coattn_relu_pool_forward")
+        _relu_pool_call(x, y, _lib.stream_ptr(x.device))()
     return y
+
+
+def _relu_pool_call(x, y, stream):
+    B, Ch, H, W = x.shape
+    return _lib.bind("coattn_relu_pool_forward", x=x, y=y, B=B, H=H, W=W, C=Ch, dtype=_lib.F32, stream=stream)
+
+
+def _empty_y(x, Ch: int, pool: bool):
+    """The channels_last fp32 [B,Ch,H,W] result of a group over x [B,.,H,W], H and W halved by the pool."""
+    B, _, H, W = x.shape
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    return torch.empty((B, Ch, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+
+
+def _workspace(dev, symbol, *dims):
+    """The fp32 workspace `symbol` sizes for dims, from torch's allocator under the current stream, per call: the encoder may
+    run one step ahead on its own stream while an inline pass runs on the main one."""
+    return torch.empty((_lib.size_bytes(symbol, *dims) + 3) // 4, device=dev, dtype=torch.float32)
 
 
 def modules_fusable(conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, x: torch.Tensor) -> bool:
@@ -119,13 +135,19 @@ def output_fusable(z: torch.Tensor, bn: nn.BatchNorm2d, pool: bool) -> bool:
     return bool(_lib.load().coattn_bn_supported(B, H, W, Ch, int(pool), _lib.F32))
 
 
+def _bn_relu_pool_call(x, bn, conv_bias, y, stats_out, ws, pool, stream):
+    B, Ch, H, W = x.shape
+    return _lib.bind("coattn_bn_relu_pool_forward", x=x, gamma=bn.weight, beta=bn.bias, conv_bias=conv_bias,
+                     running_mean=bn.running_mean, running_var=bn.running_var, momentum=float(bn.momentum), eps=float(bn.eps), y=y,
+                     stats_out=stats_out, ws=ws, B=B, H=H, W=W, C=Ch, pool=int(pool), relu=1, dtype=_lib.F32, stream=stream)
+
+
 def bn_relu_pool(x: torch.Tensor, bn: nn.BatchNorm2d, conv_bias=None, pool: bool = False, stats_out=None) -> torch.Tensor:
     """relu(max_pool2d(bn(x), 2, 2)) (pool) or relu(bn(x)) of a channels_last fp32 [B,C,H,W] tensor with `bn` in train
     mode, as a channels_last tensor; `bn`'s running statistics and num_batches_tracked move as nn.BatchNorm2d moves them.
     `conv_bias`: the frozen bias of the convolution that produced x WITHOUT it -- added to the running mean, the only place
     it survives batch normalisation.  `stats_out`: an fp32 [2, C] tensor that receives the batch mean of x and its biased
     variance.  Forward only; runs on torch's current stream."""
-    lib = _lib.load()
     B, Ch, H, W = x.shape
     for t, shape in ((conv_bias, (Ch,)), (stats_out, (2, Ch))):
         if t is not None and not (t.dtype == torch.float32 and t.device == x.device and t.is_contiguous()
@@ -134,17 +156,9 @@ def bn_relu_pool(x: torch.Tensor, bn: nn.BatchNorm2d, conv_bias=None, pool: bool
     if not output_fusable(x, bn, pool):
         raise ValueError("bn_relu_pool: needs a CUDA fp32 channels_last [B,C,H,W] tensor of a shape coattn_bn_supported "
                          "takes, got %s %s strides %s" % (tuple(x.shape), x.dtype, x.stride()))
-    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    y = torch.empty((B, Ch, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
-    # the workspace comes from torch's allocator under the current stream, per call: the encoder may run one step ahead
-    # on its own stream while an inline pass runs on the main one
-    ws = torch.empty((lib.coattn_bn_workspace_bytes(B, H, W, Ch) + 3) // 4, device=x.device, dtype=torch.float32)
+    y, ws = _empty_y(x, Ch, pool), _workspace(x.device, "coattn_bn_workspace_bytes", B, H, W, Ch)
     with torch.no_grad(), _lib.on_device(x.device):
-        rc = lib.coattn_bn_relu_pool_forward(_lib.ptr(x), _lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(conv_bias),
-                                             _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.momentum),
-                                             float(bn.eps), _lib.ptr(y), _lib.ptr(stats_out), _lib.ptr(ws), B, H, W, Ch,
-                                             int(pool), 1, _lib.F32, C.c_void_p(_lib.stream_ptr(x.device)))
-        _lib.check(rc, "coattn_bn_relu_pool_forward")
+        _bn_relu_pool_call(x, bn, conv_bias, y, stats_out, ws, pool, _lib.stream_ptr(x.device))()
         if bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)
     return y
@@ -160,7 +174,7 @@ _exact = {}
 def exact_geometry(B: int, H: int, W: int, Ch: int):
     """The geometry MIOpen's multi-kernel BatchNorm runs a channels_last fp32 [B,Ch,H,W] tensor with, as coattn_bn_exact_geometry
     reproduces it (a dict over GEOMETRY_FIELDS), or None for a shape the rule does not cover."""
-    out = (C.c_int * len(GEOMETRY_FIELDS))()
+    out = (_lib.C.c_int * len(GEOMETRY_FIELDS))()
     n = _lib.load().coattn_bn_exact_geometry(B, H, W, Ch, _lib.F32, out)
     return dict(zip(GEOMETRY_FIELDS, out)) if n == len(GEOMETRY_FIELDS) else None
 
@@ -181,19 +195,23 @@ def exact_report() -> dict:
     return {k: {n: dict(t) if n in ("conv1", "conv1_recompute") else t for n, t in v.items()} for k, v in _exact.items()}
 
 
-def _bn_exact_raw(x, weight, bias, running_mean, running_var, momentum, eps, pool: bool):
-    lib = _lib.load()
+def _exact_buffers(x, Ch: int, pool: bool, symbol, *dims):
+    """What the three exact entry points write: y, the saved statistics [2,Ch] (mean, invstd) and the workspace."""
+    return _empty_y(x, Ch, pool), torch.empty((2, Ch), device=x.device, dtype=torch.float32), _workspace(x.device, symbol, *dims)
+
+
+def _bn_exact_call(x, gamma, beta, running_mean, running_var, momentum, eps, y, save, ws, pool, stream):
     B, Ch, H, W = x.shape
-    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    y = torch.empty((B, Ch, Ho, Wo), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
-    save = torch.empty((2, Ch), device=x.device, dtype=torch.float32)
-    ws = torch.empty((lib.coattn_bn_exact_workspace_bytes(B, H, W, Ch) + 3) // 4, device=x.device, dtype=torch.float32)
+    return _lib.bind("coattn_bn_exact_forward", x=x, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var,
+                     momentum=float(momentum), eps=float(eps), y=y, save_mean=save[0], save_invstd=save[1], ws=ws, B=B, H=H, W=W,
+                     C=Ch, pool=int(pool), relu=1, dtype=_lib.F32, stream=stream)
+
+
+def _bn_exact_raw(x, weight, bias, running_mean, running_var, momentum, eps, pool: bool):
+    B, Ch, H, W = x.shape
+    y, save, ws = _exact_buffers(x, Ch, pool, "coattn_bn_exact_workspace_bytes", B, H, W, Ch)
     with torch.no_grad(), _lib.on_device(x.device):
-        rc = lib.coattn_bn_exact_forward(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
-                                         _lib.ptr(running_var), float(momentum), float(eps), _lib.ptr(y), _lib.ptr(save[0]),
-                                         _lib.ptr(save[1]), _lib.ptr(ws), B, H, W, Ch, int(pool), 1, _lib.F32,
-                                         C.c_void_p(_lib.stream_ptr(x.device)))
-        _lib.check(rc, "coattn_bn_exact_forward")
+        _bn_exact_call(x, weight, bias, running_mean, running_var, momentum, eps, y, save, ws, pool, _lib.stream_ptr(x.device))()
     return y, save[0], save[1]
 
 
@@ -317,20 +335,23 @@ def conv1_recompute_enabled() -> bool:
     return os.environ.get("VQA_ENCODER_CONV1_RECOMPUTE", "1") != "0"
 
 
+def _conv1_call(image, weight, gamma, beta, running_mean, running_var, momentum, eps, y, save, ws, pool, stream, **x_out):
+    """The first group's call: given x_out (a tensor, or None: x is kept in ws) the form that stores the convolution output,
+    coattn_conv1_bn_exact_forward; without it coattn_conv1_bn_recompute_forward."""
+    B, _, H, W = image.shape
+    return _lib.bind("coattn_conv1_bn_exact_forward" if x_out else "coattn_conv1_bn_recompute_forward", image=image, weight=weight,
+                     gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var, momentum=float(momentum),
+                     eps=float(eps), y=y, save_mean=save[0], save_invstd=save[1], ws=ws, B=B, H=H, W=W, Cin=3, Cout=64,
+                     pool=int(pool), dtype=_lib.F32, stream=stream, **x_out)
+
+
 def _conv1_recompute_raw(image, weight, gamma, beta, running_mean, running_var, momentum, eps, pool: bool):
     """(y, save_mean, save_invstd) of coattn_conv1_bn_recompute_forward: the convolution output is never stored."""
-    lib = _lib.load()
     B, _, H, W = image.shape
-    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    dev = image.device
-    y = torch.empty((B, 64, Ho, Wo), device=dev, dtype=torch.float32, memory_format=torch.channels_last)
-    save = torch.empty((2, 64), device=dev, dtype=torch.float32)
-    ws = torch.empty((lib.coattn_conv1_bn_recompute_workspace_bytes(B, H, W) + 3) // 4, device=dev, dtype=torch.float32)
-    with torch.no_grad(), _lib.on_device(dev):
-        _lib.bind("coattn_conv1_bn_recompute_forward", image=image, weight=weight, gamma=gamma, beta=beta,
-                  running_mean=running_mean, running_var=running_var, momentum=float(momentum), eps=float(eps), y=y,
-                  save_mean=save[0], save_invstd=save[1], ws=ws, B=B, H=H, W=W, Cin=3, Cout=64, pool=int(pool), dtype=_lib.F32,
-                  stream=_lib.stream_ptr(dev))()
+    y, save, ws = _exact_buffers(image, 64, pool, "coattn_conv1_bn_recompute_workspace_bytes", B, H, W)
+    with torch.no_grad(), _lib.on_device(image.device):
+        _conv1_call(image, weight, gamma, beta, running_mean, running_var, momentum, eps, y, save, ws, pool,
+                    _lib.stream_ptr(image.device))()
     return y, save[0], save[1]
 
 
@@ -340,21 +361,12 @@ def _conv1_raw(image, weight, gamma, beta, running_mean, running_var, momentum, 
     the stored form with x in its workspace)."""
     if not want_x and (conv1_recompute_enabled() if recompute is None else recompute):
         return (None,) + _conv1_recompute_raw(image, weight, gamma, beta, running_mean, running_var, momentum, eps, pool)
-    lib = _lib.load()
     B, _, H, W = image.shape
-    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    dev = image.device
-    y = torch.empty((B, 64, Ho, Wo), device=dev, dtype=torch.float32, memory_format=torch.channels_last)
-    x = torch.empty((B, 64, H, W), device=dev, dtype=torch.float32, memory_format=torch.channels_last) if want_x else None
-    save = torch.empty((2, 64), device=dev, dtype=torch.float32)
-    # (from torch's allocator under the current stream, per call, as bn_relu_pool's: x lives in it when the caller wants none)
-    ws = torch.empty((lib.coattn_conv1_bn_exact_workspace_bytes(B, H, W, int(not want_x)) + 3) // 4, device=dev, dtype=torch.float32)
-    with torch.no_grad(), _lib.on_device(dev):
-        rc = lib.coattn_conv1_bn_exact_forward(_lib.ptr(image), _lib.ptr(weight), _lib.ptr(gamma), _lib.ptr(beta),
-                                               _lib.ptr(running_mean), _lib.ptr(running_var), float(momentum), float(eps),
-                                               _lib.ptr(x), _lib.ptr(y), _lib.ptr(save[0]), _lib.ptr(save[1]), _lib.ptr(ws), B, H, W,
-                                               3, 64, int(pool), _lib.F32, C.c_void_p(_lib.stream_ptr(dev)))
-        _lib.check(rc, "coattn_conv1_bn_exact_forward")
+    y, save, ws = _exact_buffers(image, 64, pool, "coattn_conv1_bn_exact_workspace_bytes", B, H, W, int(not want_x))
+    x = _empty_y(image, 64, False) if want_x else None
+    with torch.no_grad(), _lib.on_device(image.device):
+        _conv1_call(image, weight, gamma, beta, running_mean, running_var, momentum, eps, y, save, ws, pool,
+                    _lib.stream_ptr(image.device), x_out=x)()
     return x, y, save[0], save[1]
 
 

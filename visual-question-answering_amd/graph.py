@@ -51,7 +51,6 @@ step).  A gradient arriving for ``logits`` is added by the head's backward in ea
 """
 from __future__ import annotations
 
-import ctypes as C
 import sys
 from typing import Sequence
 
@@ -218,11 +217,10 @@ class HotPathGraph:
     # the C-ABI calls on `stream`, reading the inputs `ins` = (V [B,N,d] in a native layout, Q_w, Q_p, Q_s, labels)
     def _enqueue(self, ins, stream, fwd=True, bwd=True, advance=1):
         plan = self._plan(ins)
-        st = C.c_void_p(stream)
         if fwd:
-            self._forward_pair(plan, st, advance)
+            self._forward_pair(plan, stream, advance)
         if bwd:
-            self._backward_pair(plan, st)
+            self._backward_pair(plan, stream)
 
     def usable_in_place(self, ins) -> bool:
         B, N, T, d, _, _ = self.dims
@@ -281,7 +279,7 @@ class HotPathGraph:
             pair[0 if fwd else 1].replay()
             return
         plan = plan or self._plan(ins)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        st = _lib.stream_ptr(self.device)
         with _lib.on_device(self.device):
             if fwd:
                 self._forward_pair(plan, st)

@@ -7,7 +7,6 @@ tile products; with labels the loss and d loss / d logits come out of the same f
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Optional, Sequence
 
@@ -128,12 +127,8 @@ def check_labels() -> None:
     if _last is None:
         return
     saved, B, d, mlp, K, dev = _last
-    lib = _lib.load()
     with _lib.on_device(dev):
-        rc = lib.coattn_head_status(_lib.ptr(saved), B, d, mlp, K, C.c_void_p(_lib.stream_ptr(dev)))
-    if rc == -2:
-        raise IndexError(lib.coattn_last_error().decode())
-    _lib.check(rc, "coattn_head_status")
+        _lib.check_label_status(_lib.bind("coattn_head_status", saved=saved, B=B, d=d, mlp=mlp, K=K, stream=_lib.stream_ptr(dev)))
 
 
 def _as_3bd(x) -> torch.Tensor:

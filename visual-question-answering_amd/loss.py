@@ -5,15 +5,30 @@ logits (model.py:400-434) is the stock module of ``modules.py``.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-from ._lib import ptr as _ptr
 
 
 _last = None          # (ws, B, device) of the last call: check_labels() reads its status word
+
+
+def _ce_call(logits, labels, loss, dlogits, ws, stream):
+    B, K = logits.shape
+    return _lib.bind("coattn_ce_forward", logits=logits, labels=labels, loss=loss, dlogits=dlogits, ws=ws, B=B, K=K,
+                     dtype=_lib.F32, stream=stream)
+
+
+def _soft_loss_call(logits, ans_idx, ans_score, kind, loss, dlogits, ws, stream):
+    B, K = logits.shape
+    return _lib.bind("coattn_soft_loss_forward", logits=logits, ans_idx=ans_idx, ans_score=ans_score, A=ans_idx.shape[1],
+                     kind=kind, loss=loss, dlogits=dlogits, ws=ws, B=B, K=K, dtype=_lib.F32, stream=stream)
+
+
+def _score_call(logits, ans_idx, ans_score, pred, row_score, score_sum, ws, stream):
+    B, K = logits.shape
+    return _lib.bind("coattn_vqa_score", logits=logits, ans_idx=ans_idx, ans_score=ans_score, A=ans_idx.shape[1], pred=pred,
+                     row_score=row_score, score_sum=score_sum, ws=ws, B=B, K=K, dtype=_lib.F32, stream=stream)
 
 
 class _CrossEntropyFn(torch.autograd.Function):
@@ -26,21 +41,16 @@ class _CrossEntropyFn(torch.autograd.Function):
             raise RuntimeError("cross_entropy (HIP) needs tensors on the GPU")
         if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0] or labels.dtype != torch.int64:
             raise RuntimeError("cross_entropy: logits [B,K] fp32 and labels [B] int64 expected")
-        lib = _lib.load()
         B, K = logits.shape
         z = logits.contiguous()
         lab = labels.contiguous()
         dev = z.device
-        n = C.c_size_t()
-        _lib.check(lib.coattn_ce_workspace_bytes(B, K, _lib.F32, C.byref(n)), "coattn_ce_workspace_bytes")
-        ws = torch.empty(n.value // 4, device=dev, dtype=torch.float32)
+        ws = torch.empty(_lib.ce_workspace_bytes(B, K) // 4, device=dev, dtype=torch.float32)
         loss = torch.empty((), device=dev, dtype=torch.float32)
         need = ctx.needs_input_grad[0]
         dz = torch.empty_like(z) if need else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with _lib.on_device(dev):
-            _lib.check(lib.coattn_ce_forward(_ptr(z), _ptr(lab), _ptr(loss), _ptr(dz), _ptr(ws), B, K, _lib.F32,
-                                             stream), "coattn_ce_forward")
+            _ce_call(z, lab, loss, dz, ws, _lib.stream_ptr(dev))()
         global _last
         _last = (ws, B, dev)
         if need:
@@ -62,12 +72,8 @@ def check_labels() -> None:
     if _last is None:
         return
     ws, B, dev = _last
-    lib = _lib.load()
     with _lib.on_device(dev):
-        rc = lib.coattn_ce_status(_ptr(ws), B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc == -2:
-        raise IndexError(lib.coattn_last_error().decode())
-    _lib.check(rc, "coattn_ce_status")
+        _lib.check_label_status(_lib.bind("coattn_ce_status", ws=ws, B=B, stream=_lib.stream_ptr(dev)))
 
 
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
@@ -135,21 +141,15 @@ class _SoftTargetLossFn(torch.autograd.Function):
         if not logits.is_cuda:
             raise RuntimeError("soft_target_loss (HIP) needs tensors on the GPU")
         _check_targets("soft_target_loss", logits, ans_idx, ans_score)
-        lib = _lib.load()
         B, K = logits.shape
-        A = ans_idx.shape[1]
         z, ai, sc = logits.contiguous(), ans_idx.contiguous(), ans_score.contiguous()
         dev = z.device
-        n = C.c_size_t()
-        _lib.check(lib.coattn_ce_workspace_bytes(B, K, _lib.F32, C.byref(n)), "coattn_ce_workspace_bytes")
-        ws = torch.empty(n.value // 4, device=dev, dtype=torch.float32)
+        ws = torch.empty(_lib.ce_workspace_bytes(B, K) // 4, device=dev, dtype=torch.float32)
         loss = torch.empty((), device=dev, dtype=torch.float32)
         need = ctx.needs_input_grad[0]
         dz = torch.empty_like(z) if need else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with _lib.on_device(dev):
-            _lib.check(lib.coattn_soft_loss_forward(_ptr(z), _ptr(ai), _ptr(sc), A, kind, _ptr(loss), _ptr(dz), _ptr(ws),
-                                                    B, K, _lib.F32, stream), "coattn_soft_loss_forward")
+            _soft_loss_call(z, ai, sc, kind, loss, dz, ws, _lib.stream_ptr(dev))()
         global _last
         _last = (ws, B, dev)
         if need:
@@ -194,19 +194,15 @@ def vqa_score_sum(logits, ans_idx, ans_score, row_score: bool = True):
     if logits.dtype != torch.float32:
         raise RuntimeError("vqa_score (HIP) computes in fp32; got %s" % logits.dtype)
     _check_targets("vqa_score", logits, ans_idx, ans_score)
-    lib = _lib.load()
     B, K = logits.shape
     z, ai, sc = logits.detach().contiguous(), ans_idx.contiguous(), ans_score.contiguous()
     dev = z.device
-    n = C.c_size_t()
-    _lib.check(lib.coattn_ce_workspace_bytes(B, K, _lib.F32, C.byref(n)), "coattn_ce_workspace_bytes")
-    ws = torch.empty(n.value // 4, device=dev, dtype=torch.float32)
+    ws = torch.empty(_lib.ce_workspace_bytes(B, K) // 4, device=dev, dtype=torch.float32)
     pred = torch.empty(B, device=dev, dtype=torch.int32)
     rows = torch.empty(B, device=dev, dtype=torch.float32) if row_score else None
     total = torch.empty((), device=dev, dtype=torch.float32)
     with _lib.on_device(dev):
-        _lib.check(lib.coattn_vqa_score(_ptr(z), _ptr(ai), _ptr(sc), ai.shape[1], _ptr(pred), _ptr(rows), _ptr(total), _ptr(ws),
-                                        B, K, _lib.F32, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "coattn_vqa_score")
+        _score_call(z, ai, sc, pred, rows, total, ws, _lib.stream_ptr(dev))()
     global _last
     _last = (ws, B, dev)
     return pred, rows, total

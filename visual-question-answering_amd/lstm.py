@@ -6,12 +6,9 @@ the C-ABI of ``include/coattn.h`` on the caller's current stream.  DESIGN.md sec
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-from ._lib import ptr as _ptr
 
 
 def supported(B, T, E, H) -> bool:
@@ -24,6 +21,18 @@ def device_lengths(lens, device):
     if torch.is_tensor(lens):
         return lens.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
     return torch.as_tensor(list(lens), dtype=torch.int32).to(device, non_blocking=True)
+
+
+def _forward_call(X, lens, p, out, x_masked, saved, ws, stream):
+    (B, T, E), H = X.shape, out.shape[2]
+    return _lib.bind("coattn_lstm_forward", X=X, len=lens, p=p, out=out, x_masked=x_masked, saved=saved, ws=ws, B=B, T=T, E=E,
+                     H=H, dtype=_lib.F32, flags=0, stream=stream)
+
+
+def _backward_call(X, lens, p, saved, g_out, g_xmasked, dX, pg, ws, H, stream):
+    B, T, E = X.shape                                    # (out: reserved by the header, NULL)
+    return _lib.bind("coattn_lstm_backward", X=X, len=lens, p=p, out=None, saved=saved, g_out=g_out, g_xmasked=g_xmasked, dX=dX,
+                     pg=pg, accumulate=0, ws=ws, B=B, T=T, E=E, H=H, dtype=_lib.F32, flags=0, stream=stream)
 
 
 class _SentenceLstmFn(torch.autograd.Function):
@@ -44,7 +53,6 @@ class _SentenceLstmFn(torch.autograd.Function):
         if tuple(w_ih.shape) != (4 * H, E) or tuple(w_hh.shape) != (4 * H, H) or tuple(b_ih.shape) != (4 * H,) \
                 or tuple(b_hh.shape) != (4 * H,):
             raise RuntimeError("LSTM parameters must be [4H,E], [4H,H], [4H], [4H] with E = %d, H = %d" % (E, H))
-        lib = _lib.load()
         X = x.contiguous()
         ps = [t.contiguous() for t in (w_ih, w_hh, b_ih, b_hh)]
         need_grad = any(ctx.needs_input_grad)
@@ -54,10 +62,8 @@ class _SentenceLstmFn(torch.autograd.Function):
         saved = torch.empty(sb, dtype=torch.uint8, device=x.device) if need_grad else None
         ws = torch.empty(fb, dtype=torch.uint8, device=x.device)
         p = _lib.LstmParams(*[t.data_ptr() for t in ps])
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         with _lib.on_device(x.device):
-            _lib.check(lib.coattn_lstm_forward(_ptr(X), _ptr(lens), C.byref(p), _ptr(out), _ptr(x_masked), _ptr(saved),
-                                               _ptr(ws), B, T, E, H, _lib.F32, 0, stream), "coattn_lstm_forward")
+            _forward_call(X, lens, p, out, x_masked, saved, ws, _lib.stream_ptr(x.device))()
         if need_grad:
             ctx.save_for_backward(X, lens, saved, *ps)           # (not out: the backward takes h_{t-1} from saved)
         return out, x_masked
@@ -69,7 +75,6 @@ class _SentenceLstmFn(torch.autograd.Function):
         X, lens, saved, *ps = ctx.saved_tensors
         B, T, E = X.shape
         H = ps[1].shape[1]
-        lib = _lib.load()
         g_out = X.new_zeros((B, T, H)) if g_out is None else g_out.contiguous().float()
         g_xm = None if g_xm is None else g_xm.contiguous().float()
         _, _, bb = _lib.lstm_workspace_bytes(B, T, E, H)
@@ -78,11 +83,8 @@ class _SentenceLstmFn(torch.autograd.Function):
         grads = [torch.empty_like(t) for t in ps]
         p = _lib.LstmParams(*[t.data_ptr() for t in ps])
         pg = _lib.LstmParamGrads(*[t.data_ptr() for t in grads])
-        stream = C.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
         with _lib.on_device(X.device):
-            _lib.check(lib.coattn_lstm_backward(_ptr(X), _ptr(lens), C.byref(p), None, _ptr(saved), _ptr(g_out),
-                                                _ptr(g_xm), _ptr(dX), C.byref(pg), 0, _ptr(ws), B, T, E, H, _lib.F32, 0,
-                                                stream), "coattn_lstm_backward")
+            _backward_call(X, lens, p, saved, g_out, g_xm, dX, pg, ws, H, _lib.stream_ptr(X.device))()
         return (dX, None, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:])])
 
 

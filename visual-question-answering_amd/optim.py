@@ -4,8 +4,6 @@ and gradient clipping by global norm (``torch.nn.utils.clip_grad_norm_``) in the
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -110,7 +108,6 @@ class HipAdam(torch.optim.Optimizer):
         if clip > 0.0 and len(by_step) > 1:
             raise RuntimeError("HipAdam: the parameters of a clipped group must share one step count (the norm is taken over "
                                "one call); put parameters that joined later into a group of their own")
-        lib = _lib.load()
         stream_ptr = torch.cuda.current_stream(dev).cuda_stream
         for step, entries in by_step.items():
             arr = (_lib.AdamTensor * len(entries))()
@@ -119,7 +116,7 @@ class HipAdam(torch.optim.Optimizer):
             ws = norm = None
             nbytes = 0
             if clip > 0.0:
-                nbytes = lib.coattn_adam_workspace_bytes(arr, len(entries))
+                nbytes = _lib.size_bytes("coattn_adam_workspace_bytes", arr, len(entries))
                 if nbytes == 0:
                     _lib.check(-1, "coattn_adam_workspace_bytes")
                 ws = _lib.scratch(nbytes, dev, stream_ptr)
@@ -128,8 +125,11 @@ class HipAdam(torch.optim.Optimizer):
                     norm = self._norm_out[dev.index] = torch.zeros((), device=dev, dtype=torch.float32)
                 self.grad_norm = norm
             with _lib.on_device(dev):
-                _lib.check(lib.coattn_adam_step(arr, len(entries), step, float(group["lr"]), float(beta1), float(beta2),
-                                                float(group["eps"]), wd, clip,
-                                                C.c_void_p(norm.data_ptr() if norm is not None else 0),
-                                                C.c_void_p(ws.data_ptr() if ws is not None else 0), nbytes,
-                                                C.c_void_p(stream_ptr)), "coattn_adam_step")
+                _step_call(arr, step, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), wd, clip, norm, ws,
+                           nbytes, stream_ptr)()
+
+
+def _step_call(arr, step, lr, beta1, beta2, eps, weight_decay, max_grad_norm, norm_out, ws, ws_bytes, stream):
+    return _lib.bind("coattn_adam_step", t=arr, n_tensors=len(arr), step=step, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                     weight_decay=weight_decay, max_grad_norm=max_grad_norm, norm_out=norm_out, ws=ws, ws_bytes=ws_bytes,
+                     stream=stream)

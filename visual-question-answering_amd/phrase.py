@@ -5,19 +5,21 @@ C-ABI of ``include/coattn.h`` on the caller's current stream.  SURVEY.md section
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-from ._lib import ptr as _ptr
 
 
-def _workspace_bytes(B, T, E):
-    s, f, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
-    _lib.check(_lib.load().coattn_phrase_workspace_bytes(B, T, E, _lib.F32, C.byref(s), C.byref(f), C.byref(b)),
-               "coattn_phrase_workspace_bytes")
-    return s.value, f.value, b.value
+def _forward_call(X, p, out, saved, ws, flags, stream):
+    B, T, E = X.shape
+    return _lib.bind("coattn_phrase_forward", X=X, p=p, out=out, saved=saved, ws=ws, B=B, T=T, E=E, dtype=_lib.F32, flags=flags,
+                     stream=stream)
+
+
+def _backward_call(X, p, out, saved, g_out, dX, pg, ws, flags, stream):
+    B, T, E = X.shape
+    return _lib.bind("coattn_phrase_backward", X=X, p=p, out=out, saved=saved, g_out=g_out, dX=dX, pg=pg, accumulate=0, ws=ws,
+                     B=B, T=T, E=E, dtype=_lib.F32, flags=flags, stream=stream)
 
 
 class _PhraseConvPoolFn(torch.autograd.Function):
@@ -33,19 +35,16 @@ class _PhraseConvPoolFn(torch.autograd.Function):
         B, T, E = x.shape
         if tuple(W1.shape) != (E, E, 1) or tuple(W2.shape) != (E, E, 2) or tuple(W3.shape) != (E, E, 3):
             raise RuntimeError("n-gram conv weights must be [E,E,1], [E,E,2], [E,E,3] with E = %d" % E)
-        lib = _lib.load()
         X = x.contiguous()
         ps = [t.contiguous() for t in (W1, b1, W2, b2, W3, b3)]
         need_grad = any(ctx.needs_input_grad)
-        sb, fb, _ = _workspace_bytes(B, T, E)
+        sb, fb, _ = _lib.phrase_workspace_bytes(B, T, E)
         out = torch.empty_like(X)
         saved = torch.empty(sb, dtype=torch.uint8, device=x.device) if need_grad else None
         ws = torch.empty(fb, dtype=torch.uint8, device=x.device)
         p = _lib.PhraseParams(*[t.data_ptr() for t in ps])
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         with _lib.on_device(x.device):
-            _lib.check(lib.coattn_phrase_forward(_ptr(X), C.byref(p), _ptr(out), _ptr(saved), _ptr(ws), B, T, E,
-                                                 _lib.F32, flags, stream), "coattn_phrase_forward")
+            _forward_call(X, p, out, saved, ws, flags, _lib.stream_ptr(x.device))()
         if (flags & _lib.FLAG_FAST16) and saved is not None:   # tolerance mode: this call's status words, for _lib.check_range()
             _lib.note_status("phrase", saved, (B, T, E), x.device)
         if need_grad:
@@ -58,19 +57,15 @@ class _PhraseConvPoolFn(torch.autograd.Function):
     def backward(ctx, g):
         X, out, saved, *ps = ctx.saved_tensors
         B, T, E = X.shape
-        lib = _lib.load()
         g = g.contiguous().float()
-        _, _, bb = _workspace_bytes(B, T, E)
+        _, _, bb = _lib.phrase_workspace_bytes(B, T, E)
         ws = torch.empty(bb, dtype=torch.uint8, device=X.device)
         dX = torch.empty_like(X) if ctx.needs_input_grad[0] else None
         grads = [torch.empty_like(t) for t in ps]
         p = _lib.PhraseParams(*[t.data_ptr() for t in ps])
         pg = _lib.PhraseParamGrads(*[t.data_ptr() for t in grads])
-        stream = C.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
         with _lib.on_device(X.device):
-            _lib.check(lib.coattn_phrase_backward(_ptr(X), C.byref(p), _ptr(out), _ptr(saved), _ptr(g), _ptr(dX),
-                                                  C.byref(pg), 0, _ptr(ws), B, T, E, _lib.F32, ctx.flags, stream),
-                       "coattn_phrase_backward")
+            _backward_call(X, p, out, saved, g, dX, pg, ws, ctx.flags, _lib.stream_ptr(X.device))()
         return (dX, *grads, None)
 
 
