@@ -1,5 +1,5 @@
 /*
- * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward; v0.20.0: the gather of cached image features from a table; v0.21.0: attention overlays, the maps upsampled over the image and blended into it as uint8 pictures; v0.22.0: the first convolution computed twice and never stored).
+ * coattn.h -- C-ABI of the MI355X (gfx950) Hierarchical Co-Attention path (parallel and, from v0.11.0, alternating; v0.12.0: soft answer targets; v0.13.0: the optimiser step; v0.14.0: the frozen encoder's BatchNorm + ReLU + max-pool; v0.15.0: the same with the stock BatchNorm kernels' bits; v0.16.0: the encoder's first convolution and its BatchNorm statistics in one pass, the stock kernels' bits; v0.17.0: the sentence LSTM; v0.18.0: the word embedding and its dense gradient; v0.19.0: feature dropout with a counter RNG, the mask regenerated in the backward; v0.20.0: the gather of cached image features from a table; v0.21.0: attention overlays, the maps upsampled over the image and blended into it as uint8 pictures; v0.22.0: the first convolution computed twice and never stored).  This header is the 78 functions of 0.22.0; what later versions add -- v0.23.0: image preprocessing -- is declared in include/coattn_ext.h.
  *
  * Drop-in boundary.  The reference exposes no FFI: its boundary is the
  * Python nn.Module surface

@@ -22,9 +22,11 @@ from . import features  # noqa: F401
 from .features import FeatureTable, gather_features  # noqa: F401
 from . import overlay  # noqa: F401
 from .overlay import render_attention  # noqa: F401
+from . import preprocess  # noqa: F401
+from .preprocess import ImagePreprocessor, preprocess_host  # noqa: F401
 
 __all__ = ["word_embedding", "embedding","ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
            "SoftTargetLoss", "vqa_score", "HipAdam", "sentence_lstm", "_lib",
            "check_range", "RangeError", "dropout", "DropoutState", "feature_dropout", "rank_seed",
            "features", "FeatureTable", "gather_features",
-           "overlay", "render_attention"]
+           "overlay", "render_attention", "preprocess", "ImagePreprocessor", "preprocess_host"]

@@ -1,4 +1,4 @@
-"""ctypes binding of ``libcoattn_hip.so`` (C-ABI declared in ``include/coattn.h``)."""
+"""ctypes binding of ``libcoattn_hip.so`` (C-ABI declared in ``include/coattn.h`` and, after 0.22.0, ``include/coattn_ext.h``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -251,10 +251,30 @@ RESTYPES.update(dict.fromkeys(("coattn_adam_workspace_bytes", "coattn_bn_workspa
                                "coattn_conv1_bn_exact_workspace_bytes", "coattn_conv1_bn_recompute_workspace_bytes",
                                "coattn_linear_workspace_bytes", "coattn_linear_wgrad_workspace_bytes"), C.c_size_t))
 EXPORTS = tuple(SIGNATURES)   # every symbol include/coattn.h declares
-_INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in SIGNATURES.items()}
+
+
+class PreprocessDesc(C.Structure):
+    # one image of coattn_preprocess_images (v0.23.0): where its pixels start, its size, where its two coefficient tables start
+    _fields_ = [("offset", C.c_int64)] + [(n, C.c_int) for n in ("h", "w", "tab_x", "tab_y", "taps_x", "taps_y")]
+
+
+PREPROCESS_ROWS, PREPROCESS_MAX_TAPS = 16, 1024   # COATTN_PREPROCESS_ROWS, COATTN_PREPROCESS_MAX_TAPS
+# The entry points after 0.22.0, declared in include/coattn_ext.h: a second table of the same form (tests/test_preprocess_cpu.py
+# holds it against that header).  SIGNATURES, RESTYPES and EXPORTS stay the 78 functions of include/coattn.h; load(), bind() and
+# Call.replace() serve both tables.
+EXT_SIGNATURES = {
+    "coattn_preprocess_supported": _int("B S max_h max_w"),
+    "coattn_preprocess_images": (_void("pixels") + _i64("pixel_bytes") + _void("desc coef") + _i64("coef_count") + _void("lut out")
+                                 + _i64("sB sC sH sW") + _void("bad_images") + _int("B S max_h max_w") + _void("stream")),
+}
+EXT_RESTYPES = {}
+EXT_EXPORTS = tuple(EXT_SIGNATURES)
+_ALL_SIGNATURES = {**SIGNATURES, **EXT_SIGNATURES}
+_ALL_RESTYPES = {**RESTYPES, **EXT_RESTYPES}
+_INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _ALL_SIGNATURES.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
 _DEFAULTS = dict.fromkeys(("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1 bad_maps "
-                           "conv_bias stats_out x_out dlogits x_masked g_xmasked dX").split())
+                           "conv_bias stats_out x_out dlogits x_masked g_xmasked dX bad_images").split())
 _DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
 
 
@@ -303,7 +323,7 @@ class Call(tuple):
 
     def replace(self, **kw):
         """The same call with the given arguments replaced (one list copy: cheap enough for every step)."""
-        sig, index, vals = SIGNATURES[self.name], _INDEX[self.name], list(self)
+        sig, index, vals = _ALL_SIGNATURES[self.name], _INDEX[self.name], list(self)
         for n, v in kw.items():
             if n not in index:
                 raise TypeError("%s has no argument %r" % (self.name, n))
@@ -319,14 +339,14 @@ def _call(name, vals):
 
 
 def bind(name: str, **kw) -> Call:
-    """The call of SIGNATURES[name] with its arguments given by name: tensors go in as their device pointers, ctypes
-    structures by reference, None as NULL; an omitted nullable pointer is NULL, an omitted dV stride 0, `stream` may be left
+    """The call of SIGNATURES[name] (or EXT_SIGNATURES[name]) with its arguments given by name: tensors go in as their device
+    pointers, ctypes structures by reference, None as NULL; an omitted nullable pointer is NULL, an omitted dV stride 0, `stream` may be left
     for the call itself.  Raises TypeError on a name the entry point does not have and on a missing required one."""
     unknown = kw.keys() - _INDEX[name].keys()
     if unknown:
         raise TypeError("%s has no argument %s" % (name, ", ".join(sorted(unknown))))
     vals = []
-    for n, ctype in SIGNATURES[name]:
+    for n, ctype in _ALL_SIGNATURES[name]:
         if n in kw:
             vals.append(_as_arg(kw[n], ctype))
         elif n in _DEFAULTS:
@@ -360,11 +380,11 @@ def load() -> C.CDLL:
         raise RuntimeError("HIP extension %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(there is no CPU fallback for the co-attention path)" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, sig in SIGNATURES.items():
+    for name, sig in _ALL_SIGNATURES.items():
         if not hasattr(lib, name):
             raise RuntimeError("libcoattn_hip.so lacks symbol %s" % name)
         fn = getattr(lib, name)
-        fn.argtypes, fn.restype = [ctype for _, ctype in sig], RESTYPES.get(name, C.c_int)
+        fn.argtypes, fn.restype = [ctype for _, ctype in sig], _ALL_RESTYPES.get(name, C.c_int)
     _lib = lib
     return lib
 

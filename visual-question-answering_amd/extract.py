@@ -12,6 +12,11 @@ evaluate with -- and the split's ``SyntheticVQADataset`` is walked in index orde
 (``torch.backends.cudnn.deterministic`` for the pass: the default ones do not repeat their own bits, and a table should be a
 function of the weights and the images alone).  ``--features_dtype bf16`` rounds to nearest even (torch's cast).  The
 co-attention models only: the baseline has no grid.  With ``{rank}`` in ``--out`` every rank of a launcher writes its own table.
+
+``--synthetic false --split train|val|test`` with that split's data file, image directory and ``--vocab_file`` encodes the
+DISTINCT images of the data file, one row each in first-seen order (``data.VQAFileDataset.image_names``; ``--samples`` is
+ignored); the sidecar additionally records ``"source": "files"``, the image count and the SHA-256 of the newline-joined names,
+which ``FeatureTable.check_files`` holds a run's file list against.
 """
 from __future__ import annotations
 
@@ -56,10 +61,18 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.model not in MODELS:
         ap.error("feature tables hold the co-attention models' grid (--model %s); %r has none" % (" | ".join(MODELS), args.model))
-    if args.samples < 1 or not args.out:
+    files = not args.synthetic
+    if not args.out or (args.samples < 1 and not files):
         ap.error("--samples S >= 1 and --out PATH are required")
-    if not args.synthetic:
-        raise SystemExit("only --synthetic true is available: the VQA dataset is not present in this environment")
+    vocab = None
+    if files:
+        if args.image_features:
+            ap.error("--image_features is what this command writes (--out); it reads the images")
+        try:
+            T.check_files(args, args.split, int(os.environ.get("WORLD_SIZE", "1")))
+            vocab = T.file_vocab(args)
+        except (ValueError, OSError) as e:
+            raise SystemExit(str(e))
     rank = int(os.environ.get("RANK", "0"))
     out_path = args.out.replace("{rank}", str(rank))
     if torch.cuda.is_available():
@@ -78,9 +91,20 @@ def main(argv=None):
         model.image_encoder.to(memory_format=torch.channels_last)
     model.eval()
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
-    seed = split_seed(args.split, rank)
-    ds = T.SyntheticVQADataset(args.samples, size, args.max_seq_length, args.vocab_size, args.num_cls + 1, seed)
-    loader = torch.utils.data.DataLoader(ds, args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
+    file_images = names = None
+    if files:
+        # one row per DISTINCT image of the data file, in first-seen order (data.VQAFileDataset.image_names): VQA asks about
+        # three questions per image, and `train.py --image_features` maps every line to its image's row
+        from . import data as D
+        ds = D.DistinctImages(T.file_dataset(args, args.split, vocab))
+        names = ds.ds.image_names
+        seed, args.samples = 0, len(names)
+        file_images = T.FileImages(args, size[0], device)
+        loader = T.file_loader(ds, args, shuffle=False)
+    else:
+        seed = split_seed(args.split, rank)
+        ds = T.SyntheticVQADataset(args.samples, size, args.max_seq_length, args.vocab_size, args.num_cls + 1, seed)
+        loader = torch.utils.data.DataLoader(ds, args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
     bf16 = args.features_dtype == "bf16"
     # A table is a function of the weights and the images alone: the convolutions run on MIOpen's deterministic solvers here.
     # (The default solvers do not repeat their own bits -- measured: the eval-mode features of two passes over one batch differ
@@ -88,25 +112,36 @@ def main(argv=None):
     # are identical, whatever the order of the samples inside the batch.)
     deterministic, torch.backends.cudnn.deterministic = torch.backends.cudnn.deterministic, True
     try:
-        _, N, d = _encode(model, loader, device, cl, args, out_path, bf16)
+        _, N, d = _encode(model, loader, device, cl, args, out_path, bf16, file_images)
     finally:
         torch.backends.cudnn.deterministic = deterministic
+    if files and file_images.hip is not None:
+        from .preprocess import bad_images
+        n_bad = bad_images()
+        if n_bad:
+            raise ValueError("%d images were refused by the preprocessing launch (their rows are those of zeros)" % n_bad)
     meta = FT.make_meta(args.model, size[0], N, d, args.features_dtype, args.split, seed, args.samples)
+    if files:
+        meta = FT.files_meta(meta, names)
     with open(FT.sidecar_path(out_path), "w") as fh:
         json.dump(meta, fh, indent=1, sort_keys=True)
     print(json.dumps({"out": out_path, **meta}))
     return meta
 
 
-def _encode(model, loader, device, cl, args, out_path, bf16):
-    """Walk `loader` in order and write row i of the table at `out_path`; returns (rows written, N, d)."""
+def _encode(model, loader, device, cl, args, out_path, bf16, file_images=None):
+    """Walk `loader` in order and write row i of the table at `out_path`; returns (rows written, N, d).  `file_images`
+    (train.FileImages): the batches carry decoded pixels, resized and normalised here."""
     table = None
     start = 0
     with torch.no_grad():
         for b in loader:
-            image = b["image"].to(device)
-            if cl:
-                image = image.contiguous(memory_format=torch.channels_last)
+            if file_images is not None:
+                image = file_images.device_images(file_images.host(b["image"]), cl)
+            else:
+                image = b["image"].to(device)
+                if cl:
+                    image = image.contiguous(memory_format=torch.channels_last)
             with T.autocast_for(args.opt_lvl, device):
                 feats = native_features(model.image_encoder(image))
             if bf16:

@@ -186,3 +186,19 @@ class FeatureTable:
                             ("S", int(S))):
             if self.meta.get(field) != mine:
                 raise ValueError("feature table: %s is %r in the sidecar, %r in this run" % (field, self.meta.get(field), mine))
+
+    def check_files(self, model_name, image_size, split, image_names) -> None:
+        """The same for a table of file data (``extract.py --synthetic false``: one row per distinct image, in the order of
+        ``VQAFileDataset.image_names``): the model, the image size, the split, and the file list -- its source, its length and
+        the SHA-256 of its newline-joined names -- must be this run's."""
+        from .data import names_digest
+        for field, mine in (("model", model_name), ("image_size", int(image_size)), ("split", split), ("source", "files"),
+                            ("images", len(image_names)), ("S", len(image_names)), ("names_sha256", names_digest(image_names))):
+            if self.meta.get(field) != mine:
+                raise ValueError("feature table: %s is %r in the sidecar, %r in this run" % (field, self.meta.get(field), mine))
+
+
+def files_meta(meta: dict, image_names) -> dict:
+    """`make_meta`'s record plus what a table of file data records besides: where its rows come from."""
+    from .data import names_digest
+    return {**meta, "source": "files", "images": len(image_names), "names_sha256": names_digest(image_names)}

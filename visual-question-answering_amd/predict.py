@@ -33,7 +33,12 @@ README roadmap.  Same command line as ``train.py`` (the reference's flags) plus 
   (``vqa_amd.overlay.render_attention``); only the chosen samples' bytes come to the host.
 
 The maps come from the forward-only co-attention (``coattn_infer``): no state for a backward is written.  One process:
-multi-GPU prediction is not offered.  Data: the synthetic test split (its own seed), every sample (no drop_last).
+multi-GPU prediction is not offered.  Data: the synthetic test split (its own seed), every sample (no drop_last) -- or, with
+``--synthetic false --test_file F --test_img DIR --vocab_file V``, the reference's dataset files (``vqa_amd.data``; images
+resized and normalised by ``vqa_amd.preprocess``, ``--preprocess hip | host``): every record then gains ``image`` (the file
+name), ``question`` (the cleaned words) and ``answers`` (the top-k answers as strings, through the vocabulary's ``idx2label``);
+``--image_features`` takes a table of ``extract.py --synthetic false --split test``, and ``--image_mean`` / ``--image_std``
+also set the normalisation the images are given.
 """
 from __future__ import annotations
 
@@ -101,14 +106,17 @@ def main(argv=None):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         ap.error("prediction runs in one process (WORLD_SIZE=%s): multi-GPU prediction is not offered"
                  % os.environ["WORLD_SIZE"])
-    if not args.synthetic:
-        raise SystemExit("only --synthetic true is available: the VQA dataset is not present in this environment")
+    files = not args.synthetic             # the reference's dataset files: --test_file / --test_img / --vocab_file
+    vocab = None
     try:
+        if files:
+            T.check_files(args, "test")
+            vocab = T.file_vocab(args)
         T.check_loss(args.loss, args.num_answers)
         if args.val_image_features:
             raise ValueError("--val_image_features is train.py's; prediction takes the test split's table as --image_features")
         T.check_image_features(args)
-    except ValueError as e:
+    except (ValueError, OSError) as e:
         ap.error(str(e))
     cached = bool(args.image_features)     # the test split's feature table (extract --split test) in place of the encoder
 
@@ -132,17 +140,28 @@ def main(argv=None):
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
     k = min(args.topk, n_cls)
-    ds = T.SyntheticVQADataset(args.test_size, size, args.max_seq_length, args.vocab_size, n_cls, TEST_SEED,
-                               num_answers=args.num_answers if soft else 0, images=not cached)
+    file_images = None
+    if files:
+        ds = T.file_dataset(args, "test", vocab)
+        file_images = T.FileImages(args, size[0], device, args.image_mean, args.image_std)
+    else:
+        ds = T.SyntheticVQADataset(args.test_size, size, args.max_seq_length, args.vocab_size, n_cls, TEST_SEED,
+                                   num_answers=args.num_answers if soft else 0, images=not cached)
     feats = None
     if cached:
         from .features import FeatureTable, bad_indices
         feats = FeatureTable.load(args.image_features, device)
         try:
-            feats.check(args.model, size[0], "test", TEST_SEED, args.test_size)
+            if files:
+                feats.check_files(args.model, size[0], "test", ds.image_names)
+            else:
+                feats.check(args.model, size[0], "test", TEST_SEED, args.test_size)
         except ValueError as e:
             ap.error(str(e))
-    loader = torch.utils.data.DataLoader(ds, args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
+    if files:
+        loader = T.file_loader(ds, args, shuffle=False)
+    else:
+        loader = torch.utils.data.DataLoader(ds, args.batch_size, shuffle=False, drop_last=False, num_workers=args.num_workers)
     maps = bool(args.attention_maps)
     overlays = bool(args.attention_overlays)
     if overlays:
@@ -173,14 +192,16 @@ def main(argv=None):
             start += n
             # sorted by question length for packing (main.py:196-202); the index rides along as a second label column
             extras = (b["answers"], b["answer_scores"]) if soft else ()
+            if files:
+                b["image"] = file_images.host(b["image"])       # the decoded pixels, packed (hip) or preprocessed (host)
             image, question, il, ques_len, *extras = T.sort_batch(b["image"], b["question"], torch.stack([index, b["label"]], 1),
                                                                   b["ques_len"], *extras)
             targets = [e.to(device) for e in extras]
             idx, label = il[:, 0], il[:, 1]
-            image = image.to(device)
+            image = file_images.device_images(image, cl and not cached) if files else image.to(device)
             if cached:
                 image = feats.gather(image)                     # `image` held the batch's row indices
-            elif cl:
+            elif cl and not files:
                 image = image.contiguous(memory_format=torch.channels_last)
             question, label_d = question.to(device), label.to(device)
             draw = overlays and int(idx.min()) < n_over         # a chosen sample is in this batch
@@ -221,6 +242,10 @@ def main(argv=None):
         torch.cuda.synchronize()
         if cached and bad_indices():
             raise IndexError("image indices lay outside the feature table (their rows were zeros)")
+        if files and file_images.hip is not None:
+            from .preprocess import bad_images
+            if bad_images():
+                raise ValueError("images were refused by the preprocessing launch (their pixels were zeros)")
         if overlays and OV.bad_maps():
             raise FloatingPointError("attention maps could not be normalised for their overlays (NaN, infinite, negative or all "
                                      "zero); those panels were drawn without attention")
@@ -235,6 +260,9 @@ def main(argv=None):
         with open(args.predictions, "w") as fh:
             for i in range(S):
                 rec = {"index": i, "label": int(labels[i]), "top": top[i].tolist(), "prob": [float(x) for x in prob[i]]}
+                if files:                                       # the sample in words: its image, its question, the answers
+                    rec.update(image=ds.samples[i][0], question=ds.words(i),
+                               answers=[vocab["idx2label"][int(t)] for t in top[i]])
                 if soft:
                     rec["score"] = float(scores[i])
                 fh.write(json.dumps(rec) + "\n")

@@ -7,6 +7,11 @@ gradient all-reduce (``vqa_amd.dist``).  apex AMP (main.py:185) is CUDA-only; ``
 encoders while the co-attention path keeps computing in fp32.
 
 Run:  python -m torch.distributed.run --nproc-per-node N -m vqa_amd.train --synthetic ...
+
+``--synthetic false --train_file F --train_img DIR --vocab_file V [--val_file F --val_img DIR] [--preprocess hip|host]`` trains
+on the reference's dataset files (``vqa_amd.data``): the vocabulary sets the vocabulary size and the question length, an epoch
+is one pass over the file, and the images are resized and normalised per batch by ``vqa_amd.preprocess`` -- on a GPU in one HIP
+launch that the prefetcher queues on its copy stream behind the batch's decoded pixels.
 """
 from __future__ import annotations
 
@@ -247,6 +252,93 @@ def check_image_features(args, world: int = 1, validates: bool = False) -> None:
                                  "every rank reads its own table" % (flag, world))
 
 
+PREPROCESS = ("hip", "host")
+FILE_FLAGS = {"train": ("train_file", "train_img"), "val": ("val_file", "val_img"), "test": ("test_file", "test_img")}
+
+
+def check_files(args, split: str = "train", world: int = 1, validates: bool = False) -> None:
+    """--synthetic false: the reference's dataset files (vqa_amd.data).  `split`'s data file, its image directory (not needed
+    on cached features: no image is opened then) and --vocab_file are required; a validating training run needs --val_file
+    (and --val_img) too.  Refused: --loss soft_ce | bce (a line of the text format carries one answer), the BERT models (their
+    tokeniser is not offered), data-parallel runs, --preprocess hip without a GPU."""
+    cached = bool(getattr(args, "image_features", None))
+    needed = [split] + (["val"] if validates and split == "train" else [])
+    for s in needed:
+        file_flag, img_flag = FILE_FLAGS[s]
+        if not getattr(args, file_flag, None):
+            raise ValueError("--synthetic false needs --%s (lines of `img_name \\t question \\t answer`)" % file_flag)
+        if not cached and not getattr(args, img_flag, None):
+            raise ValueError("--synthetic false needs --%s (the image directory of --%s)" % (img_flag, file_flag))
+    if not args.vocab_file:
+        raise ValueError("--synthetic false needs --vocab_file (python -m vqa_amd.data vocab, or the reference's prepare_data.py)")
+    if args.loss != "ce":
+        raise ValueError("--loss %s needs soft answer targets; the data files carry one answer per line: use --loss ce" % args.loss)
+    if args.model in ("bert", "attention_bert"):
+        raise ValueError("--model %s reads BERT token ids; the BERT tokeniser is not offered with file data" % args.model)
+    if world > 1:
+        raise ValueError("file data with WORLD_SIZE = %d: data-parallel runs are offered on synthetic data only" % world)
+    pre = getattr(args, "preprocess", None)
+    if pre not in (None,) + PREPROCESS:
+        raise ValueError("--preprocess must be one of %s, got %r" % (PREPROCESS, pre))
+    if pre == "hip" and not torch.cuda.is_available():
+        raise ValueError("--preprocess hip runs on the GPU (there is no CPU fallback); use --preprocess host")
+
+
+def file_vocab(args) -> dict:
+    """The vocabulary of --vocab_file; args.vocab_size and args.max_seq_length become its values, and its label table must
+    have --num_cls + 1 entries (UNKNOWN and the K answers): the model is built from these."""
+    from . import data as D
+    vocab = D.load_vocab(args.vocab_file)
+    if len(vocab["label2idx"]) != args.num_cls + 1:
+        raise ValueError("%s holds %d labels (UNKNOWN included); --num_cls %d needs %d" % (args.vocab_file, len(vocab["label2idx"]),
+                                                                                          args.num_cls, args.num_cls + 1))
+    args.vocab_size, args.max_seq_length = len(vocab["word2idx"]), int(vocab["max_seq_length"])
+    return vocab
+
+
+def file_dataset(args, split: str, vocab: dict):
+    """`split`'s VQAFileDataset: pixels, or table rows on cached features."""
+    from . import data as D
+    file_flag, img_flag = FILE_FLAGS[split]
+    return D.VQAFileDataset(getattr(args, file_flag), getattr(args, img_flag, None), vocab,
+                            images="row" if getattr(args, "image_features", None) else "pixels")
+
+
+def file_loader(ds, args, shuffle: bool, seed: int = 0, drop_last: bool = False):
+    from . import data as D
+    return torch.utils.data.DataLoader(ds, args.batch_size, shuffle=shuffle, drop_last=drop_last, num_workers=args.num_workers,
+                                       collate_fn=D.collate, generator=torch.Generator().manual_seed(seed) if shuffle else None)
+
+
+class FileImages:
+    """What turns a batch's decoded images into the network's input: --preprocess hip (the default on a GPU) packs them for
+    ``ImagePreprocessor`` -- the launch itself is queued by whoever copies the batch (DevicePrefetcher, or ``device()`` here)
+    --, --preprocess host resizes and normalises on the CPU (``preprocess_host``)."""
+
+    def __init__(self, args, size: int, device, mean=None, std=None):
+        from . import preprocess as PP
+        self.mode = getattr(args, "preprocess", None) or ("hip" if device.type == "cuda" else "host")
+        self.size, self.device = int(size), device
+        self.mean, self.std = tuple(mean or PP.IMAGENET_MEAN), tuple(std or PP.IMAGENET_STD)
+        self.hip = PP.ImagePreprocessor(self.size, self.mean, self.std, device) if self.mode == "hip" else None
+
+    def host(self, images):
+        """A list of uint8 arrays -> a PackedBatch (hip) or the fp32 tensor (host); tensors (table rows) pass through."""
+        if torch.is_tensor(images):
+            return images
+        if self.hip is not None:
+            return self.hip.pack(images)
+        from .preprocess import preprocess_host
+        return preprocess_host(images, self.size, self.mean, self.std)
+
+    def device_images(self, image, channels_last: bool = False):
+        """What ``host`` returned -> the fp32 [B, 3, S, S] tensor on the device, on the current stream."""
+        if torch.is_tensor(image):
+            image = image.to(self.device)
+            return image.contiguous(memory_format=torch.channels_last) if channels_last and image.dim() == 4 else image
+        return self.hip(image, channels_last=channels_last)
+
+
 def build_model(model_name: str, vocab_size: int, num_cls: int, question_mask: bool = False, affinity: str = "reference",
                 co_attention: str = "parallel", **kw) -> nn.Module:
     """K + 1 output classes: index 0 is UNKNOWN (main.py:155).  question_mask: see `set_question_mask`; affinity: see
@@ -403,9 +495,12 @@ class DevicePrefetcher:
 
     _END = object()
 
-    def __init__(self, batches, device, channels_last: bool = False, depth: int = 2):
+    def __init__(self, batches, device, channels_last: bool = False, depth: int = 2, preprocess=None):
         self.device = device
         self.cl = channels_last
+        # file data (--preprocess hip): a batch's `image` is a preprocess.PackedBatch of decoded pixels; its bytes go through
+        # the pinned ring, and `preprocess` (an ImagePreprocessor) queues its one launch on the side stream behind the copy
+        self.preprocess = preprocess
         self.next = None
         if device.type != "cuda":
             self._it = iter(batches)
@@ -438,10 +533,22 @@ class DevicePrefetcher:
                     buf.copy_(t)
                     return buf
 
+                def pin_bytes(name, t):                         # a 1-D buffer whose length differs batch to batch: grow only
+                    buf = slot.get(name)
+                    if buf is None or buf.numel() < t.numel():
+                        buf = torch.empty(max(t.numel(), 2 * buf.numel() if buf is not None else 0), dtype=t.dtype).pin_memory()
+                        slot[name] = buf
+                    buf[:t.numel()].copy_(t)
+                    return buf[:t.numel()]
+
                 with torch.cuda.stream(self.stream):
-                    im = pin("image", image).to(self.device, non_blocking=True)
-                    if self.cl:
-                        im = im.contiguous(memory_format=torch.channels_last)
+                    if torch.is_tensor(image):
+                        im = pin("image", image).to(self.device, non_blocking=True)
+                        if self.cl:
+                            im = im.contiguous(memory_format=torch.channels_last)
+                    else:
+                        packed = image.with_buf(pin_bytes("pixels", image.buf).to(self.device, non_blocking=True))
+                        im = self.preprocess.launch(packed, channels_last=self.cl)
                     qu = pin("question", question).to(self.device, non_blocking=True)
                     la = pin("label", label).to(self.device, non_blocking=True)
                     ex = [pin("extra%d" % j, e).to(self.device, non_blocking=True) for j, e in enumerate(extras)]
@@ -801,8 +908,8 @@ class SyntheticVQADataset(torch.utils.data.Dataset):
 
 def build_parser():
     """The reference's command line (main.py:34-78; same names, types and meanings) plus what it lacks here: synthetic
-    data, precision, data-parallel launch through the environment.  The dataset / vocabulary flags are accepted so that
-    a reference command line parses; only --synthetic data exists in this environment."""
+    data, precision, data-parallel launch through the environment.  The dataset / vocabulary flags are the reference's and
+    are read with --synthetic false (check_files); --synthetic true, the default, needs none of them."""
     ap = argparse.ArgumentParser(description="Visual Question Answering (MI355X co-attention path)")
     # Experiment params (main.py:37-41; not `required` here: synthetic runs need no directory)
     ap.add_argument("--mode", default="train", choices=["train", "test"])
@@ -843,7 +950,15 @@ def build_parser():
     ap.add_argument("--precision", default="exact", choices=["fast", "exact"],
                     help="fp32 products of the HIP path: fp32-accurate (default: the reference's --opt_lvl 0 arithmetic) or the "
                          "opt-in tolerance mode (include/coattn.h COATTN_FLAG_FAST16; range-checked at every --log_interval)")
-    ap.add_argument("--synthetic", type=str2bool, default="true", help="synthetic data (the only source here)")
+    ap.add_argument("--synthetic", type=str2bool, default="true",
+                    help="synthetic data (the default); false: the reference's dataset files -- --train_file / --train_img / "
+                         "--vocab_file [--val_file / --val_img], see vqa_amd.data")
+    ap.add_argument("--test_file", type=str, default=None, help="the test split's data file (predict.py, extract.py --split test)")
+    ap.add_argument("--test_img", type=str, default=None, help="the test split's image directory")
+    ap.add_argument("--preprocess", default=None, choices=list(PREPROCESS),
+                    help="file data: where images are resized and normalised -- 'hip' (the default on a GPU): one HIP launch "
+                         "per batch on the prefetcher's copy stream, the GPU receives the decoded uint8 pixels; 'host' (the "
+                         "default on the CPU): PIL and a lookup table per image, the reference's transform")
     ap.add_argument("--vocab_size", type=int, default=10000)
     ap.add_argument("--max_seq_length", type=int, default=26)
     ap.add_argument("--image_size", type=int, default=0, help="override the model's image size (0 = registry)")
@@ -914,12 +1029,15 @@ def main(argv=None):
     check_optimizer(args.optimizer, args.weight_decay, args.clip_grad_norm)
     if args.mode == "test":
         raise NotImplementedError("TODO: test mode")          # as the reference, main.py:286-287
-    if not args.synthetic:
-        raise SystemExit("only --synthetic true is available: the VQA dataset is not present in this environment")
+    files = not args.synthetic                                  # the reference's dataset files (vqa_amd.data)
     n_val = args.val_batches or args.val_size // args.batch_size
+    vocab = None
     try:
+        if files:
+            check_files(args, "train", int(os.environ.get("WORLD_SIZE", "1")), validates=n_val > 0)
+            vocab = file_vocab(args)                            # (the model below is built from its sizes)
         check_image_features(args, int(os.environ.get("WORLD_SIZE", "1")), validates=n_val > 0)
-    except ValueError as e:
+    except (ValueError, OSError) as e:
         raise SystemExit(str(e))
 
     rank, world, local = vdist.init_from_env()
@@ -954,10 +1072,14 @@ def main(argv=None):
 
     cached = bool(args.image_features)                           # the `image` slot of a batch then holds table rows' indices
 
-    def table(path, split, seed, n_samples):
+    def table(path, split, seed, n_samples, ds=None):
         from .features import FeatureTable
         tab = FeatureTable.load(path.replace("{rank}", str(rank)), device)
-        tab.check(args.model, size[0], split, seed, n_samples)   # (before the first step: a table of another run is refused)
+        # (before the first step: a table of another run, or of another file list, is refused)
+        if ds is not None:
+            tab.check_files(args.model, size[0], split, ds.image_names)
+        else:
+            tab.check(args.model, size[0], split, seed, n_samples)
         return tab
 
     def loader(n_samples, seed):
@@ -968,22 +1090,44 @@ def main(argv=None):
 
     def sorted_host(batch):                                      # main.py:196-202
         extras = (batch["answers"], batch["answer_scores"]) if n_ans else ()
+        if files:
+            batch["image"] = file_images.host(batch["image"])    # the decoded pixels, packed (hip) or preprocessed (host)
         image, question, label, ques_len, *extras = sort_batch(batch["image"], batch["question"], batch["label"],
                                                                batch["ques_len"], *extras)
         return (image, question, ques_len, label, *extras)
 
-    train_loader = loader(args.num_steps * args.batch_size, 1234 + rank)
+    file_images = train_ds = val_ds = None
+    if files:
+        # an epoch is one pass over --train_file (shuffled, the last partial batch dropped: main.py:129-130)
+        file_images = FileImages(args, size[0], device)
+        train_ds = file_dataset(args, "train", vocab)
+        train_loader = file_loader(train_ds, args, shuffle=True, seed=1234 + rank, drop_last=True)
+        if rank == 0:
+            print(json.dumps({"data": "files", "samples": len(train_ds), "images": len(train_ds.image_names),
+                              "steps_per_epoch": len(train_loader), "preprocess": "none (cached features)" if cached else
+                              file_images.mode, "note": "--num_steps is ignored: an epoch is one pass over --train_file"}))
+        if len(train_loader) == 0:
+            raise SystemExit("--train_file holds %d samples: fewer than one batch of %d" % (len(train_ds), args.batch_size))
+    else:
+        train_loader = loader(args.num_steps * args.batch_size, 1234 + rank)
     steps_per_epoch = len(train_loader)
-    feats = table(args.image_features, "train", 1234 + rank, args.num_steps * args.batch_size) if cached else None
+    feats = table(args.image_features, "train", 1234 + rank, args.num_steps * args.batch_size, train_ds) if cached else None
+    if files and n_val > 0:
+        val_ds = file_dataset(args, "val", vocab)
+    val_feats = (table(args.val_image_features, "val", 987654 + rank, n_val * args.batch_size, val_ds)
+                 if cached and n_val > 0 else None)
     val = []
     if n_val > 0:
-        val_feats = table(args.val_image_features, "val", 987654 + rank, n_val * args.batch_size) if cached else None
-        for b in loader(n_val * args.batch_size, 987654 + rank):
+        val_batches = (file_loader(val_ds, args, shuffle=False) if files else loader(n_val * args.batch_size, 987654 + rank))
+        for i, b in enumerate(val_batches):
+            if i >= n_val:                                       # (file data: the first n_val batches of --val_file)
+                break
             image, question, ques_len, label, *extras = sorted_host(b)
-            image = image.to(device)
+            # (file data: the pixels are resized and normalised here, in the layout the encoder runs in)
+            image = file_images.device_images(image, cl and not cached) if files else image.to(device)
             if cached:
                 image = val_feats.gather(image)                  # this batch's rows, gathered once
-            elif cl:
+            elif cl and not files:
                 image = image.contiguous(memory_format=torch.channels_last)
             val.append((image, question.to(device), ques_len, label.to(device), *[e.to(device) for e in extras]))
     val_every = args.val_interval or (args.log_interval if val else 0)
@@ -991,7 +1135,8 @@ def main(argv=None):
     t0 = time.time()
     step = 0
     for epoch in range(args.num_epochs):
-        batches = DevicePrefetcher((sorted_host(b) for b in train_loader), device, cl and not cached)
+        batches = DevicePrefetcher((sorted_host(b) for b in train_loader), device, cl and not cached,
+                                   preprocess=file_images.hip if files else None)
         for image, question, ques_len, label, *extras in batches:
             validate_now = bool(val) and val_every > 0 and (step + 1) % val_every == 0
             if cached:                                           # `image`: the batch's row indices, on the device
@@ -1010,6 +1155,11 @@ def main(argv=None):
                     n_bad = bad_indices()
                     if n_bad:
                         raise IndexError("%d image indices lay outside the feature table (their rows were zeros)" % n_bad)
+                if files and file_images.hip is not None:
+                    from .preprocess import bad_images
+                    n_bad = bad_images()
+                    if n_bad:
+                        raise ValueError("%d images were refused by the preprocessing launch (their pixels were zeros)" % n_bad)
                 if rank == 0:
                     print(json.dumps({"epoch": epoch + 1, "step": step + 1, "steps_per_epoch": steps_per_epoch,
                                       "loss": round(float(loss), 5), "precision": trainer.precision,
