@@ -30,8 +30,9 @@ def layout_geometry(B, N, d, layout):
     strided: location-major rows padded to sN = d + 4, every sample padded by 8 floats (neither dense layout);
     sd2: every second float of a [B,N,2d] buffer (sD = 2: neither axis contiguous).  Not in LAYOUTS (tests/_fused.py): the
     dense layouts with a gap behind every sample -- lm_gap (sB = N d + 64), lm_gap4 (+ 4), lm_gap1 (+ 1: samples off the
-    16-byte boundary), cm_gap (sB = d N + 64), cm_gap1 (+ 1)."""
-    gaps = {"lm_gap": 64, "lm_gap4": 4, "lm_gap1": 1, "cm_gap": 64, "cm_gap1": 1}
+    16-byte boundary), cm_gap (sB = d N + 64), cm_gap4 (+ 4), cm_gap1 (+ 1) -- and pitch, location-major rows d + 8 floats
+    apart with the samples abutting (sB = N sN: tests/test_gpu_backward_routes.py's general-shape rows)."""
+    gaps = {"lm_gap": 64, "lm_gap4": 4, "lm_gap1": 1, "cm_gap": 64, "cm_gap4": 4, "cm_gap1": 1}
     if layout in gaps:
         sB = N * d + gaps[layout]
         return B * sB, ((sB, d, 1) if layout.startswith("lm") else (sB, 1, N))
@@ -44,6 +45,8 @@ def layout_geometry(B, N, d, layout):
         return B * sB, (sB, d + 4, 1)
     if layout == "sd2":
         return B * N * 2 * d, (N * 2 * d, 2 * d, 2)
+    if layout == "pitch":
+        return B * N * (d + 8), (N * (d + 8), d + 8, 1)
     raise ValueError(layout)
 
 
@@ -115,7 +118,8 @@ def profile_marks(lib):
 
 
 def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=None, layout="cm", dv_layout="same",
-        flags=_lib.IMPL_GENERAL, accumulate=0, grads_init=None, v_off=0, q_off=0, attn=False, profile=False, allow_nan=False):
+        flags=_lib.IMPL_GENERAL, accumulate=0, grads_init=None, v_off=0, q_off=0, attn=False, profile=False, allow_nan=False,
+        profile_bwd=False):
     """One forward (+ backward when gv is given) through the C-ABI.  V [B,d,N] values (as oracle.coattn_oracle makes them),
     handed over in the physical `layout` (LAYOUTS); family (FAMILIES): coattn_forward / _backward ("plain"), their _len
     forms ("len", with `lens`), coattn_forward_maps / _backward_maps ("maps", "maps_len": g_av / g_aq may be given) or
@@ -130,7 +134,8 @@ def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=N
     v_off / q_off: floats (0 or 1) by which the V view / every Q_l is moved off its 16-byte aligned start.  attn (families
     "plain" and "len"): coattn_attention_forward(_len) follows on the same `saved` with fresh NaN-filled v, q and workspace
     arenas; v, q are then that call's and "v_fwd", "q_fwd" the forward's.  profile: the forward call(s) run between
-    coattn_profile_begin / _end and "marks" is the list of launch marks.  allow_nan: outputs may hold NaN (poisoned inputs)."""
+    coattn_profile_begin / _end and "marks" is the list of launch marks; profile_bwd: so does the backward call, a profile of
+    its own, and "marks_bwd" is the list of its launch marks.  allow_nan: outputs may hold NaN (poisoned inputs)."""
     lib = _lib.load()
     DEV = _dev()
     assert family in FAMILIES
@@ -245,8 +250,12 @@ def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=N
             assert g_av is None and g_aq is None
             symbol = "coattn_backward" + sfx
         call = _lib.bind(symbol, **bwd)
+        if profile_bwd:
+            torch.cuda.synchronize()
+            _lib.check(lib.coattn_profile_begin(st), "coattn_profile_begin")
         rc = call.fn(*call)
         assert rc == 0, (symbol, lib.coattn_last_error())
+        marks_bwd = profile_marks(lib) if profile_bwd else None
         torch.cuda.synchronize()
         out["dV_phys"] = dV.permute(0, 2, 1) if dV is not None else None
         out["dQ"] = torch.stack(dQ)
@@ -263,6 +272,8 @@ def run(V, Qs, P, family="plain", lens=None, gv=None, gq=None, g_av=None, g_aq=N
     res = {k: (x.detach().cpu().contiguous() if x is not None else None) for k, x in out.items()}
     if profile:
         res["marks"] = marks
+    if profile_bwd and gv is not None:
+        res["marks_bwd"] = marks_bwd
     return res
 
 

@@ -8,8 +8,9 @@ exact mode, 1e-4 in the tolerance mode (COATTN_FLAG_FAST16), and in the reduced-
 exact arithmetic and are compared as absolute errors.
 
 The single-product weight-gradient route (gemm_bf.hip's 256 x 256 tiles, bf16-stored dP) wants contraction lengths B N and
-B T that are multiples of 32 and a dQ projection of 256 rows or more: it is not in this table of small batches;
-test_gpu_edges.py::test_bf16_mode_stores_its_gemm_only_gradients_as_bf16 (d = 2048, B = 160) stays its cover.
+B T that are multiples of 32 and a dQ projection of 256 rows or more: it is not in this table, whose T is 26, but it is
+reached at B = 16, T = 16, N = 32 / 96, d = 512 by tests/test_gpu_fused_backward.py (rows dpb_* and bf_tn_*), beside
+test_gpu_edges.py::test_bf16_mode_stores_its_gemm_only_gradients_as_bf16 (d = 2048, B = 160).
 """
 import ctypes as C
 

@@ -418,6 +418,9 @@ void decide_route(const Ctx& c, const Off& o, Route& r) {
   r.sum_in_gemm = r.tn_v && L == 3 && !c.dV;
   if (r.sum_in_gemm) tnv.a_term = ko_sum3 ? 0 : (long)o.BNd;
   r.bf_tn = r.tn_v && r.tn_q && gemm_bf_tn_supported(tnv) && gemm_bf_tn_supported(tnq);
+  // (gemm_bf.hip's weight-gradient launch carries no dQ tiles: below the 256 rows its own projection kernel wants -- B T = 128 ..
+  //  224 with B N and B T multiples of 32 -- the projection is a launch of its own in front of the dA V kernel, which adds onto it)
+  if (r.bf_tn) r.combine = r.own_dq = r.late_dq = false;
   if (!r.tn_v || !r.tn_q || r.bf_tn) return;
   // two-piece width: 128 x 256 tiles on 512-thread workgroups (gemm_tn_wide.hip) -- the same split-K partition, pieces and
   // order of products, so the same bits as the 128 x 128 kernel
@@ -659,7 +662,6 @@ int run_dw_bf_tn(const Ctx& c, const Route& r, const Off& o) {
   CA_TRY(run_small_reductions(c, o));
   CA_TRY(launch_gemm_bf_tn(both, spp, parts, 2, c.s));
   prof_mark(c.s, "bwd_gemm_dw");
-  if (r.combine) CA_TRY(run_own_dq(c, r, o));
   CA_TRY(launch_reduce_partials2(part, (float*)c.pg->dW_v, parts[0], both[1].C, (float*)c.pg->dW_q, parts[1], (int64_t)d * d,
                                  c.accumulate, c.s));
   prof_mark(c.s, "reduce_partials");
