@@ -6,6 +6,8 @@
  *
  * v0.23.0: image preprocessing -- the reference's per-sample transform Resize((S, S)) -> ToTensor -> Normalize
  * (/root/reference/main.py:126) for a whole batch of decoded uint8 images of different sizes, in one launch.
+ * v0.24.0: the frozen VGG encoder in EVAL mode -- BatchNorm on its running statistics, the convolution bias, the ReLU and the
+ * 2x2 pool in one launch per group, the first group from the image.
  */
 #ifndef COATTN_EXT_H
 #define COATTN_EXT_H
@@ -81,6 +83,66 @@ int coattn_preprocess_supported(int B, int S, int max_h, int max_w);
 int coattn_preprocess_images(const void* pixels, long long pixel_bytes, const void* desc, const void* coef, long long coef_count,
                              const void* lut, void* out, int64_t sB, int64_t sC, int64_t sH, int64_t sW, int32_t* bad_images,
                              int B, int S, int max_h, int max_w, void* stream);
+
+/* ---- the frozen encoder in eval mode: running statistics, one launch per group (v0.24.0; csrc/encoder.hip) ----
+ * Train mode (coattn.h: coattn_bn_exact_forward, 0.15.0, and the conv1 forms, 0.16.0 / 0.22.0) has to sum the batch first.  In
+ * eval mode BatchNorm2d is an elementwise map with per-channel constants, so everything after the convolution rides on ONE read
+ * of its output x, and the first group goes from the image to y without x ever existing.  fp32, physically [B][H][W][C]
+ * (channels_last), forward only, no workspace.
+ *   x            : fp32 [B][H][W][C], the convolution output (without its bias, if conv_bias is given); 16-byte aligned
+ *   conv_bias    : fp32 [C] or NULL; 16-byte aligned
+ *   gamma, beta  : fp32 [C], BatchNorm2d's weight and bias; 16-byte aligned
+ *   running_mean, running_var : fp32 [C]; 16-byte aligned; READ ONLY -- eval mode moves no statistic
+ *   y            : fp32 [B][H/2][W/2][C] (pool) or [B][H][W][C]; 16-byte aligned; every element written, nothing else; not x
+ *   relu         : 0 leaves the ReLU out
+ *
+ * THE ARITHMETIC IS THE CONTRACT: the stock chain's bits, that is MIOpen's spatial inference kernel behind the stock
+ * convolution's separate bias add.  Per channel c, once:
+ *     e      = (float)eps                                   the double rounded to fp32 first
+ *     a      = fabs(running_var[c] + e)                     one fp32 add; the absolute value: a negative variance gives no NaN
+ *     invstd = rsqrt(a)                                     the device library's fp32 rsqrt (HIP's rsqrtf, OpenCL's rsqrt): v_rsq_f32,
+ *                                                           with a small a -- a subnormal one too -- scaled by an even power of
+ *                                                           two first and the result by its root.  Not the bare instruction (a
+ *                                                           subnormal a gives another result) and not 1 / sqrt(a)
+ * Per element, in fp32, each line one rounding:
+ *     v = x + conv_bias[c]                                  only with conv_bias; without it v = x, no operation (-0 stays -0)
+ *     d = v - running_mean[c]
+ *     n = d * invstd
+ *     t = fma(gamma[c], n, beta[c])                         one rounding
+ * pool: m = max(max(t00, t01), max(t10, t11)) over the window rows 2 ho, 2 ho + 1 and columns 2 wo, 2 wo + 1 (floor mode: an odd
+ * last row or column is never read), where max(a, b) = a if a > b or a is NaN, else b: a NaN wins, as in PyTorch.  The affine map
+ * goes first because gamma may be negative.  relu: y = m < 0 ? 0 : m (a NaN stays).  A NaN or an infinity of one sample stays in
+ * the elements and windows it belongs to.
+ * Supported: what the kernels need and no more -- coattn_bn_supported's conditions (coattn.h: C a power of two in 16 .. 512, B H W
+ * below 2^31, B H W C below 2^31, at least two pixels, H and W >= 2 with pool); NOT coattn_bn_exact_geometry's observed shapes, which
+ * exist for the order of a sum and nothing is summed here.  coattn_conv1_bn_eval_*: Cin = 3, Cout = 64 too, and at most
+ * 65535 * COATTN_CONV1_RECOMPUTE_CHUNK samples.
+ *
+ * coattn_conv1_bn_eval_forward: the first group.  image fp32 [B][H][W][3] and weight fp32 [64][3][3][3] = [co][ky][kx][c], both
+ * 4-byte aligned; x = the 3x3 / padding-1 convolution in the stock convolution's arithmetic -- one chain of sixteen
+ * v_mfma_f32_32x32x2_f32 from 0 over the 27 terms (ky, kx, c) padded to 32, in the term order coattn.h gives for
+ * coattn_conv1_bn_exact_forward -- then exactly the lines above.  It is the third kernel of coattn_conv1_bn_recompute_forward with the
+ * bias and the running statistics in place of the saved ones: tiles of 2 rows x 16 columns (pool) or 32 pixels, one workgroup per
+ * tile and chunk of COATTN_CONV1_RECOMPUTE_CHUNK samples.  Its y is coattn_bn_eval_forward's of the x of
+ * coattn_conv1_bn_exact_forward, bit for bit.  The ReLU is always applied.
+ *
+ * Argument errors -- an unsupported shape, a NULL pointer other than conv_bias, a misaligned pointer, y == x or y == image,
+ * eps <= 0 --: -1 with a coattn_last_error message before any HIP call.  *_supported makes no GPU call.  No allocation, no
+ * synchronisation: the calls can be captured into a HIP graph.
+ *
+ * coattn_bn_eval_probe is the developer's slow form for tools/probe_encoder_eval.py (one thread per element, no pool, no ReLU, no
+ * bias), every choice of the candidate space switchable: rsqrt 0 v_rsq_f32, 1 the device library's rsqrt, 2 1 / sqrt, 3 the scaled
+ * v_rsq_f32 spelled out; step 0 fma, 1 multiply then add; eps_mode 0 var + (float)eps, 1 (float)((double)var + eps). */
+int coattn_bn_eval_supported(int B, int H, int W, int C, int pool, int dtype);
+int coattn_bn_eval_forward(const void* x, const void* conv_bias, const void* gamma, const void* beta, const void* running_mean,
+                           const void* running_var, double eps, void* y, int B, int H, int W, int C, int pool, int relu, int dtype,
+                           void* stream);
+int coattn_conv1_bn_eval_supported(int B, int H, int W, int Cin, int Cout, int pool, int dtype);
+int coattn_conv1_bn_eval_forward(const void* image, const void* weight, const void* conv_bias, const void* gamma, const void* beta,
+                                 const void* running_mean, const void* running_var, double eps, void* y, int B, int H, int W,
+                                 int Cin, int Cout, int pool, int dtype, void* stream);
+int coattn_bn_eval_probe(const void* x, const void* gamma, const void* beta, const void* running_mean, const void* running_var,
+                         double eps, void* y, int B, int H, int W, int C, int rsqrt, int step, int eps_mode, void* stream);
 
 #ifdef __cplusplus
 }

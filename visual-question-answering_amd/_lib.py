@@ -266,6 +266,14 @@ EXT_SIGNATURES = {
     "coattn_preprocess_supported": _int("B S max_h max_w"),
     "coattn_preprocess_images": (_void("pixels") + _i64("pixel_bytes") + _void("desc coef") + _i64("coef_count") + _void("lut out")
                                  + _i64("sB sC sH sW") + _void("bad_images") + _int("B S max_h max_w") + _void("stream")),
+    # the frozen encoder in eval mode (v0.24.0)
+    "coattn_bn_eval_supported": _int("B H W C pool dtype"),
+    "coattn_bn_eval_forward": (_void("x conv_bias gamma beta running_mean running_var") + _f64("eps") + _void("y") + _BN_DIMS),
+    "coattn_conv1_bn_eval_supported": _int("B H W Cin Cout pool dtype"),
+    "coattn_conv1_bn_eval_forward": (_void("image weight conv_bias gamma beta running_mean running_var") + _f64("eps") + _void("y")
+                                     + _int("B H W Cin Cout pool dtype") + _void("stream")),
+    "coattn_bn_eval_probe": (_void("x gamma beta running_mean running_var") + _f64("eps") + _void("y")
+                             + _int("B H W C rsqrt step eps_mode") + _void("stream")),
 }
 EXT_RESTYPES = {}
 EXT_EXPORTS = tuple(EXT_SIGNATURES)

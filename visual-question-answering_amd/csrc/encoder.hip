@@ -42,6 +42,7 @@
 // convolution again and normalises, pools and writes y.
 #include <math.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "common.h"
@@ -529,6 +530,26 @@ __device__ __forceinline__ float window_max1(float t00, float t01, float t10, fl
   return max_nan1(max_nan1(t00, t01), max_nan1(t10, t11));
 }
 
+// The eval forms (v0.24.0): MIOpen's spatial inference kernel computes, per channel, invVariance = rsqrt(fabs(variance + (float)
+// epsilon)) and, per element, mad(scale, (x - mean) * invVariance, bias) -- affine1<true> with the running statistics.  A
+// convolution bias the caller left out of x is one fp32 add in front (the stock convolution's separate add).
+// The reciprocal square root is the candidate tools/probe_encoder_eval.py found equal to the stock kernel's on every operand
+// (DESIGN 3.19): 1, the device library's rsqrt.  0 the bare v_rsq_f32 (differs where var + eps is subnormal), 2 1 / sqrt, each
+// correctly rounded (differs in the last bit), 3 v_rsq_f32 of an operand scaled out of the subnormal range (equal on all of them).
+template <int V>
+__device__ __forceinline__ float eval_rsqrt(float a) {
+  if (V == 0) return __builtin_amdgcn_rsqf(a);
+  if (V == 1) return rsqrtf(a);
+  if (V == 2) return __fdiv_rn(1.f, __fsqrt_rn(a));
+  const bool small = a < 0x1p-100f;
+  return __builtin_amdgcn_rsqf(small ? a * 0x1p+100f : a) * (small ? 0x1p+50f : 1.f);
+}
+constexpr int kEvalRsqrt = 1;
+__device__ __forceinline__ float eval_invstd(float var, float eps) { return eval_rsqrt<kEvalRsqrt>(__builtin_fabsf(var + eps)); }
+// EVAL: 0 the batch statistics of the train forms, 1 running statistics, 2 running statistics and a convolution bias
+template <int EVAL>
+__device__ __forceinline__ float add_bias1(float v, float bias) { return EVAL == 2 ? __fadd_rn(v, bias) : v; }
+
 template <bool STOCK>
 __device__ __forceinline__ f32x4 affine(const f32x4 v, const Affine& a) {
   f32x4 t;
@@ -552,24 +573,34 @@ __device__ __forceinline__ f32x4 relu_nan(const f32x4 a) {
 // One thread per 16 bytes of output: o = output pixel * c4 + channel group.  total4 = output pixels * c4; H, W: the INPUT's.
 // AFFINE = false: the 2x2 maximum and the ReLU alone (ws_f, beta not read): max and ReLU are exact, so the result has the bits of
 // max_pool2d followed by relu.  STOCK: ws_f = save_mean, ws_f + 2 C = save_invstd (the caller passes `scale` itself) and
-// `gamma` is read: the stock normalise kernel's map.
-template <bool POOL, bool AFFINE = true, bool STOCK = false>
+// `gamma` is read: the stock normalise kernel's map.  EVAL (with STOCK; coattn_bn_eval_forward): ws_f = running_mean, `scale` =
+// running_var, from which the prologue computes invstd as the stock inference kernel does; EVAL == 2: `conv_bias` is added to x first.
+template <bool POOL, bool AFFINE = true, bool STOCK = false, int EVAL = 0>
 __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __restrict__ x, const float* __restrict__ ws_f,
                                                                 const float* __restrict__ scale, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, f32x4* __restrict__ y,
-                                                                int H, int W, int C, int c4_shift, int64_t total4, int relu) {
+                                                                int H, int W, int C, int c4_shift, int64_t total4, int relu,
+                                                                const float* __restrict__ conv_bias = nullptr, float eps = 0.f) {
   const int tid = threadIdx.x;
   const int c4 = C >> 2;
   const int cg = tid & (c4 - 1);                                    // (block starts and the grid stride are multiples of c4)
   Affine a;
+  f32x4 cb = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     a.mean[e] = AFFINE ? ws_f[4 * cg + e] : 0.f;
     a.lo[e] = AFFINE && !STOCK ? ws_f[C + 4 * cg + e] : 0.f;
     a.scale[e] = AFFINE ? scale[4 * cg + e] : 1.f;
+    if (EVAL) a.scale[e] = eval_invstd(a.scale[e], eps);
     a.gamma[e] = STOCK ? gamma[4 * cg + e] : 1.f;
     a.beta[e] = AFFINE ? beta[4 * cg + e] : 0.f;
+    if (EVAL == 2) cb[e] = conv_bias[4 * cg + e];
   }
+  auto biased = [&](f32x4 v) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = add_bias1<EVAL>(v[e], cb[e]);
+    return v;
+  };
   const int64_t stride = (int64_t)gridDim.x * kThreads;
   int64_t o = (int64_t)blockIdx.x * kThreads + tid;
   if (!POOL) {
@@ -581,7 +612,7 @@ __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __r
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         if (o + u * stride < total4) {
-          const f32x4 t = affine<STOCK>(v[u], a);
+          const f32x4 t = affine<STOCK>(biased(v[u]), a);
           y[o + u * stride] = relu ? relu_nan(t) : t;
         }
     }
@@ -609,8 +640,8 @@ __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __r
 #pragma unroll
     for (int u = 0; u < 2; ++u)
       if (live[u]) {
-        const f32x4 t = AFFINE ? window_max(affine<STOCK>(v[u][0], a), affine<STOCK>(v[u][1], a), affine<STOCK>(v[u][2], a),
-                                            affine<STOCK>(v[u][3], a))
+        const f32x4 t = AFFINE ? window_max(affine<STOCK>(biased(v[u][0]), a), affine<STOCK>(biased(v[u][1]), a),
+                                            affine<STOCK>(biased(v[u][2]), a), affine<STOCK>(biased(v[u][3]), a))
                                : window_max(v[u][0], v[u][1], v[u][2], v[u][3]);
         y[o + u * stride] = relu ? relu_nan(t) : t;
       }
@@ -635,11 +666,13 @@ __global__ __launch_bounds__(kThreads) void bn_relu_pool_kernel(const f32x4* __r
 // 163 VGPRs (both accumulators included), no LDS, no scratch: three waves per SIMD, which the occupancy hint asks for.
 constexpr int kConv1NormChunk = COATTN_CONV1_RECOMPUTE_CHUNK;
 
-template <int D, bool POOL>
+// EVAL (coattn_conv1_bn_eval_forward: the whole group in this one launch): save_mean = running_mean, save_invstd = running_var,
+// turned into invstd here as the stock inference kernel does; EVAL == 2: `conv_bias` is added to every convolution output first.
+template <int D, bool POOL, int EVAL = 0>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void conv1_norm_pool_kernel(
     const float* __restrict__ image, const float* __restrict__ weight, const float* __restrict__ save_mean,
     const float* __restrict__ save_invstd, const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y,
-    int B, int H, int W, int cbs) {
+    int B, int H, int W, int cbs, const float* __restrict__ conv_bias = nullptr, float eps = 0.f) {
   const int lane = threadIdx.x, g = lane >> 5, p = lane & 31;
   const int HW = H * W, Ho = H >> 1, Wo = W >> 1;
   const int n0 = blockIdx.y * kConv1NormChunk, n1 = n0 + kConv1NormChunk < B ? n0 + kConv1NormChunk : B;
@@ -657,7 +690,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void co
   unsigned boff[kConv1Mfmas];
 #pragma unroll
   for (int i = 0; i < kConv1Mfmas; ++i) boff[i] = (unsigned)off[i] * 4u;
-  const float mean[2] = {save_mean[p], save_mean[32 + p]}, invstd[2] = {save_invstd[p], save_invstd[32 + p]};
+  const float mean[2] = {save_mean[p], save_mean[32 + p]};
+  float invstd[2] = {save_invstd[p], save_invstd[32 + p]};
+  if (EVAL) invstd[0] = eval_invstd(invstd[0], eps), invstd[1] = eval_invstd(invstd[1], eps);
+  const float cbias[2] = {EVAL == 2 ? conv_bias[p] : 0.f, EVAL == 2 ? conv_bias[32 + p] : 0.f};
   const float gm[2] = {gamma[p], gamma[32 + p]}, bt[2] = {beta[p], beta[32 + p]};
   const int64_t sample = (int64_t)HW * 3;
   float even[kConv1Mfmas], odd[kConv1Mfmas];
@@ -682,10 +718,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void co
       if (POOL) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-          const float m = window_max1(affine1<true>(acc[hh][4 * b], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]),
-                                      affine1<true>(acc[hh][4 * b + 1], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]),
-                                      affine1<true>(acc[hh][4 * b + 2], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]),
-                                      affine1<true>(acc[hh][4 * b + 3], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]));
+          auto t = [&](int r) {
+            return affine1<true>(add_bias1<EVAL>(acc[hh][4 * b + r], cbias[hh]), mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]);
+          };
+          const float m = window_max1(t(0), t(1), t(2), t(3));
           if (full || wo + 2 * b < Wo) yo[2 * b * 64 + 32 * hh] = relu_nan1(m);
         }
       } else {
@@ -693,7 +729,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void co
         for (int v = 0; v < 16; ++v)
           if (full || pbase + 8 * (v >> 2) + 4 * g + (v & 3) < HW)
             yo[(8 * (v >> 2) + (v & 3)) * 64 + 32 * hh] =
-                relu_nan1(affine1<true>(acc[hh][v], mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]));
+                relu_nan1(affine1<true>(add_bias1<EVAL>(acc[hh][v], cbias[hh]), mean[hh], 0.f, invstd[hh], gm[hh], bt[hh]));
       }
     }
     yo += ystep;
@@ -1068,5 +1104,148 @@ extern "C" int coattn_conv1_probe(const void* image, const void* weight, void* x
                        (const float*)weight, (float*)x, total, H, W, order, step, halves, skip);
   }
   CA_CHECK_LAUNCH("conv1_probe");
+  return 0;
+}
+
+// ---- eval mode: running statistics, the whole map in one launch (v0.24.0; include/coattn_ext.h) --------------------------------
+namespace {
+
+// The slow probe of tools/probe_encoder_eval.py: one thread per element of x, no pool, every choice of the candidate space switchable.
+//   rsqrt   : eval_rsqrt's candidates 0 .. 3
+//   step    : 0 fma(gamma, (x - mean) * invstd, beta)   1 the same with a rounded product and a separate add
+//   eps_mode: 0 var + (float)eps in fp32   1 (float)((double)var + eps)
+__device__ __noinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float prod = a * b;
+  return prod + c;
+}
+__global__ __launch_bounds__(256) void bn_eval_probe_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, const float* __restrict__ running_mean,
+                                                            const float* __restrict__ running_var, double eps, float* __restrict__ y,
+                                                            int64_t total, int C, int rsqrt, int step, int eps_mode) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int c = (int)(i % C);
+  const float a = __builtin_fabsf(eps_mode ? (float)((double)running_var[c] + eps) : running_var[c] + (float)eps);
+  const float inv = rsqrt == 0 ? eval_rsqrt<0>(a) : rsqrt == 1 ? eval_rsqrt<1>(a) : rsqrt == 2 ? eval_rsqrt<2>(a) : eval_rsqrt<3>(a);
+  const float xhat = __fmul_rn(__fsub_rn(x[i], running_mean[c]), inv);
+  y[i] = step == 0 ? __builtin_fmaf(gamma[c], xhat, beta[c]) : mul_then_add(gamma[c], xhat, beta[c]);
+}
+
+inline bool aligned16(std::initializer_list<const void*> ps) {
+  uintptr_t bits = 0;
+  for (const void* p : ps) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & 15) == 0;
+}
+
+template <bool POOL>
+void launch_bn_eval(const void* x, const void* conv_bias, const void* gamma, const void* beta, const void* running_mean,
+                    const void* running_var, float eps, void* y, int H, int W, int C, int64_t total4, int relu, unsigned blocks,
+                    hipStream_t s) {
+  const int shift = log2_exact(C / 4);
+  if (conv_bias)
+    hipLaunchKernelGGL((bn_relu_pool_kernel<POOL, true, true, 2>), dim3(blocks), dim3(kThreads), 0, s, (const f32x4*)x,
+                       (const float*)running_mean, (const float*)running_var, (const float*)gamma, (const float*)beta, (f32x4*)y, H,
+                       W, C, shift, total4, relu, (const float*)conv_bias, eps);
+  else
+    hipLaunchKernelGGL((bn_relu_pool_kernel<POOL, true, true, 1>), dim3(blocks), dim3(kThreads), 0, s, (const f32x4*)x,
+                       (const float*)running_mean, (const float*)running_var, (const float*)gamma, (const float*)beta, (f32x4*)y, H,
+                       W, C, shift, total4, relu, (const float*)nullptr, eps);
+}
+
+template <bool POOL>
+void launch_conv1_eval(const void* image, const void* weight, const void* conv_bias, const void* gamma, const void* beta,
+                       const void* running_mean, const void* running_var, float eps, void* y, int B, int H, int W, dim3 grid, int cbs,
+                       hipStream_t s) {
+  if (conv_bias)
+    hipLaunchKernelGGL((conv1_norm_pool_kernel<kConv1PairDistance, POOL, 2>), grid, dim3(64), 0, s, (const float*)image,
+                       (const float*)weight, (const float*)running_mean, (const float*)running_var, (const float*)gamma,
+                       (const float*)beta, (float*)y, B, H, W, cbs, (const float*)conv_bias, eps);
+  else
+    hipLaunchKernelGGL((conv1_norm_pool_kernel<kConv1PairDistance, POOL, 1>), grid, dim3(64), 0, s, (const float*)image,
+                       (const float*)weight, (const float*)running_mean, (const float*)running_var, (const float*)gamma,
+                       (const float*)beta, (float*)y, B, H, W, cbs, (const float*)nullptr, eps);
+}
+
+}  // namespace
+
+extern "C" int coattn_bn_eval_supported(int B, int H, int W, int C, int pool, int dtype) {
+  return coattn_bn_supported(B, H, W, C, pool, dtype);
+}
+
+extern "C" int coattn_bn_eval_forward(const void* x, const void* conv_bias, const void* gamma, const void* beta,
+                                      const void* running_mean, const void* running_var, double eps, void* y, int B, int H, int W,
+                                      int C, int pool, int relu, int dtype, void* stream) {
+  CA_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && C >= 1 && coattn_bn_eval_supported(B, H, W, C, pool, dtype),
+               "bn_eval_forward: B=%d H=%d W=%d C=%d pool=%d dtype=%d is not supported (coattn_bn_eval_supported)", B, H, W, C, pool,
+               dtype);
+  CA_CHECK_ARG(x && gamma && beta && running_mean && running_var && y,
+               "bn_eval_forward: a null x / gamma / beta / running_mean / running_var / y");
+  CA_CHECK_ARG(aligned16({x, conv_bias, gamma, beta, running_mean, running_var, y}),
+               "bn_eval_forward: every pointer must be 16-byte aligned");
+  CA_CHECK_ARG(x != y, "bn_eval_forward: y must not be x");
+  CA_CHECK_ARG(eps > 0.0, "bn_eval_forward: eps %g (must be > 0)", eps);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t out_pixels = pool ? (int64_t)B * (H / 2) * (W / 2) : (int64_t)B * H * W;
+  const int64_t total4 = out_pixels * (C / 4);
+  const int per_thread = pool ? 2 : 4;
+  int64_t blocks = (total4 + (int64_t)kThreads * per_thread - 1) / ((int64_t)kThreads * per_thread);
+  if (blocks > kMaxNormBlocks) blocks = kMaxNormBlocks;
+  if (pool)
+    launch_bn_eval<true>(x, conv_bias, gamma, beta, running_mean, running_var, (float)eps, y, H, W, C, total4, relu, (unsigned)blocks, s);
+  else
+    launch_bn_eval<false>(x, conv_bias, gamma, beta, running_mean, running_var, (float)eps, y, H, W, C, total4, relu, (unsigned)blocks, s);
+  CA_CHECK_LAUNCH("bn_eval");
+  prof_mark(s, "bn_eval");
+  return 0;
+}
+
+extern "C" int coattn_conv1_bn_eval_supported(int B, int H, int W, int Cin, int Cout, int pool, int dtype) {
+  if (Cin != 3 || Cout != 64 || !coattn_bn_eval_supported(B, H, W, Cout, pool, dtype)) return 0;
+  // the kernel's 32-bit indices: byte offsets into one image sample, and a grid row of sample chunks
+  return (int64_t)H * W * 12 < ((int64_t)1 << 29) && (B + kConv1NormChunk - 1) / kConv1NormChunk <= 65535 ? 1 : 0;
+}
+
+extern "C" int coattn_conv1_bn_eval_forward(const void* image, const void* weight, const void* conv_bias, const void* gamma,
+                                            const void* beta, const void* running_mean, const void* running_var, double eps, void* y,
+                                            int B, int H, int W, int Cin, int Cout, int pool, int dtype, void* stream) {
+  CA_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && coattn_conv1_bn_eval_supported(B, H, W, Cin, Cout, pool, dtype),
+               "conv1_bn_eval_forward: B=%d H=%d W=%d Cin=%d Cout=%d pool=%d dtype=%d is not supported "
+               "(coattn_conv1_bn_eval_supported)", B, H, W, Cin, Cout, pool, dtype);
+  CA_CHECK_ARG(image && weight && gamma && beta && running_mean && running_var && y,
+               "conv1_bn_eval_forward: a null image / weight / gamma / beta / running_mean / running_var / y");
+  CA_CHECK_ARG(aligned16({y, conv_bias, gamma, beta, running_mean, running_var}) &&
+                   ((reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(weight)) & 3) == 0,
+               "conv1_bn_eval_forward: y, conv_bias and the BatchNorm vectors must be 16-byte aligned, image and weight 4-byte aligned");
+  CA_CHECK_ARG(y != image, "conv1_bn_eval_forward: image and y must be two buffers");
+  CA_CHECK_ARG(eps > 0.0, "conv1_bn_eval_forward: eps %g (must be > 0)", eps);
+  hipStream_t s = (hipStream_t)stream;
+  const int chunks = (B + kConv1NormChunk - 1) / kConv1NormChunk;
+  if (pool) {
+    const int cbs = (W / 2 + 7) / 8;
+    launch_conv1_eval<true>(image, weight, conv_bias, gamma, beta, running_mean, running_var, (float)eps, y, B, H, W,
+                            dim3((unsigned)((H / 2) * cbs), chunks), cbs, s);
+  } else {
+    launch_conv1_eval<false>(image, weight, conv_bias, gamma, beta, running_mean, running_var, (float)eps, y, B, H, W,
+                             dim3((unsigned)((H * W + kConv1Pixels - 1) / kConv1Pixels), chunks), 0, s);
+  }
+  CA_CHECK_LAUNCH("conv1_bn_eval");
+  prof_mark(s, "conv1_bn_eval");
+  return 0;
+}
+
+extern "C" int coattn_bn_eval_probe(const void* x, const void* gamma, const void* beta, const void* running_mean,
+                                    const void* running_var, double eps, void* y, int B, int H, int W, int C, int rsqrt, int step,
+                                    int eps_mode, void* stream) {
+  CA_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && C >= 1 && (int64_t)B * H * W * C < ((int64_t)1 << 31), "bn_eval_probe: B=%d H=%d W=%d C=%d",
+               B, H, W, C);
+  CA_CHECK_ARG(x && gamma && beta && running_mean && running_var && y && x != y, "bn_eval_probe: a null pointer, or y is x");
+  CA_CHECK_ARG(rsqrt >= 0 && rsqrt <= 3 && (step == 0 || step == 1) && (eps_mode == 0 || eps_mode == 1),
+               "bn_eval_probe: rsqrt=%d step=%d eps_mode=%d", rsqrt, step, eps_mode);
+  const int64_t total = (int64_t)B * H * W * C;
+  hipLaunchKernelGGL(bn_eval_probe_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                     (const float*)gamma, (const float*)beta, (const float*)running_mean, (const float*)running_var, eps, (float*)y,
+                     total, C, rsqrt, step, eps_mode);
+  CA_CHECK_LAUNCH("bn_eval_probe");
   return 0;
 }

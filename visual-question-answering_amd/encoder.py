@@ -20,7 +20,13 @@ layer takes what:
   output, statistics in double.  More accurate than the stock chain, but not its bits: a training trajectory leaves the stock
   one at rounding level and drifts from there.  Opt-in: ``VQA_ENCODER_FUSED=1``.
 
-``VQA_ENCODER_FUSED=0`` keeps every stock kernel."""
+* ``bn_eval`` / ``conv1_bn_eval`` (include/coattn_ext.h v0.24.0): EVAL-mode ``BatchNorm2d`` on its running statistics, the
+  convolution's bias, the ReLU and an optional ``MaxPool2d(2, 2)`` in ONE launch over the convolution output, in the stock
+  inference kernel's arithmetic; the first group in one launch from the image.  Opt-in (``eval_impl="hip"``,
+  ``--encoder_eval hip``), and again only for a shape that ``bn_eval_or_stock`` / ``conv1_bn_eval_or_stock`` has compared with the
+  stock chain once in this process and found equal in every bit (``eval_report()``).
+
+``VQA_ENCODER_FUSED=0`` keeps every stock kernel of the train-mode routes."""
 from __future__ import annotations
 
 import os
@@ -453,3 +459,220 @@ def conv1_bn_exact_or_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d
     the stock kernels the first time (the comparison itself; not while the stream is capturing) and for good after a
     difference, which is reported once.  The caller has checked conv1_modules_fusable."""
     return bn_exact_or_stock(x, bn, pool, conv=conv)
+
+
+# ---- eval mode: BatchNorm on running statistics, the bias, the ReLU and the pool in one launch; verified per shape, or not used ----
+EVAL_IMPLS = ("stock", "hip")
+# (device index, B, C, H, W, pool, Cin) of a group's convolution output and input channels -> {"verified", "first_difference",
+# "bias": "kernel" / "convolution" / None}, and for the first group also "conv1": {"verified", "first_difference"}
+_eval = {}
+
+
+def eval_report() -> dict:
+    """{(device index, B, C, H, W, pool, Cin): {"verified", "first_difference", "bias"}} of every eval-mode group compared so far
+    under eval_impl "hip".  "bias" says where the convolution's bias is added on the verified route: "kernel" (the convolution is
+    issued without it), "convolution" (the stock convolution keeps it) or None (there is none).  The entry of a first group holds
+    "conv1": {"verified", "first_difference"} too, once conv1_bn_eval_or_stock has compared the one-launch form."""
+    return {k: {n: dict(t) if n == "conv1" else t for n, t in v.items()} for k, v in _eval.items()}
+
+
+def eval_group_fusable(conv: nn.Conv2d, bn: nn.BatchNorm2d, pool, x: torch.Tensor) -> bool:
+    """_group_fusable's conditions with eval mode in place of train mode (running statistics to normalise with; no momentum is
+    needed, nothing moves), and no autocast."""
+    if not x.is_cuda or torch.is_autocast_enabled():
+        return False
+    if bn.training or not bn.affine or bn.running_mean is None or bn.running_var is None:
+        return False
+    params = (conv.weight, conv.bias, bn.weight, bn.bias)
+    if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)):
+        return False
+    if conv.padding_mode != "zeros":
+        return False
+    b = conv.bias
+    if b is not None and (b.requires_grad or b.dtype != torch.float32 or b.device != x.device or not b.is_contiguous()
+                          or b.data_ptr() % 16 != 0):
+        return False
+    return pool is None or pool_is_2x2(pool)
+
+
+def eval_output_fusable(z: torch.Tensor, bn: nn.BatchNorm2d, pool: bool) -> bool:
+    """output_fusable (whose shape rule is coattn_bn_eval_supported's) and 16-byte aligned tensors throughout.  No MIOpen
+    geometry: nothing is summed."""
+    return output_fusable(z, bn, pool) and all(t.data_ptr() % 16 == 0 for t in (z, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+
+def _bn_eval_raw(x, conv_bias, gamma, beta, running_mean, running_var, eps, pool: bool, relu: bool = True):
+    B, Ch, H, W = x.shape
+    y = _empty_y(x, Ch, pool)
+    with torch.no_grad(), _lib.on_device(x.device):
+        _lib.bind("coattn_bn_eval_forward", x=x, conv_bias=conv_bias, gamma=gamma, beta=beta, running_mean=running_mean,
+                  running_var=running_var, eps=float(eps), y=y, B=B, H=H, W=W, C=Ch, pool=int(pool), relu=int(relu), dtype=_lib.F32,
+                  stream=_lib.stream_ptr(x.device))()
+    return y
+
+
+def bn_eval(x: torch.Tensor, bn: nn.BatchNorm2d, conv_bias=None, pool: bool = False) -> torch.Tensor:
+    """relu(max_pool2d(bn(x + conv_bias), 2, 2)) (pool) or relu(bn(x + conv_bias)) of a channels_last fp32 [B,C,H,W] tensor with `bn`
+    in EVAL mode, in one launch and in the stock inference kernel's arithmetic (include/coattn_ext.h v0.24.0), as a channels_last
+    tensor.  `conv_bias`: the fp32 [C] bias of the convolution that produced x WITHOUT it, or None.  `bn`'s buffers are read only.
+    Forward only; runs on torch's current stream."""
+    Ch = x.shape[1] if x.dim() == 4 else -1
+    if conv_bias is not None and not (conv_bias.dtype == torch.float32 and conv_bias.device == x.device and conv_bias.is_contiguous()
+                                      and tuple(conv_bias.shape) == (Ch,) and conv_bias.data_ptr() % 16 == 0):
+        raise ValueError("bn_eval: conv_bias must be a contiguous 16-byte aligned fp32 [C] tensor on x's device")
+    if bn.training or bn.running_mean is None or bn.running_var is None or not bn.affine:
+        raise ValueError("bn_eval: needs an affine BatchNorm2d in eval mode with running statistics")
+    if not eval_output_fusable(x, bn, pool):
+        raise ValueError("bn_eval: needs a CUDA fp32 channels_last [B,C,H,W] tensor of a shape coattn_bn_eval_supported takes and "
+                         "16-byte aligned tensors, got %s %s strides %s" % (tuple(x.shape), x.dtype, x.stride()))
+    return _bn_eval_raw(x, conv_bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, pool)
+
+
+def conv1_eval_inputs_fusable(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool: bool) -> bool:
+    """conv1_inputs_fusable with coattn_conv1_bn_eval_supported's shape rule in place of the exact route's."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    if not (conv.in_channels == 3 and conv.out_channels == 64 and _pair(conv.kernel_size) == (3, 3) and _pair(conv.stride) == (1, 1)
+            and not isinstance(conv.padding, str) and _pair(conv.padding) == (1, 1) and _pair(conv.dilation) == (1, 1)
+            and conv.groups == 1 and conv.padding_mode == "zeros" and x.shape[1] == 3):
+        return False
+    w = conv.weight
+    if not (w.dtype == torch.float32 and w.device == x.device and w.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        if t is None or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or t.data_ptr() % 16 != 0:
+            return False
+    if bn.num_features != 64 or x.data_ptr() % 4 != 0 or w.data_ptr() % 4 != 0:
+        return False
+    B, _, H, W = x.shape
+    return bool(_lib.load().coattn_conv1_bn_eval_supported(B, H, W, 3, 64, int(pool), _lib.F32))
+
+
+def _conv1_eval_raw(image, weight, conv_bias, gamma, beta, running_mean, running_var, eps, pool: bool):
+    B, _, H, W = image.shape
+    y = _empty_y(image, 64, pool)
+    with torch.no_grad(), _lib.on_device(image.device):
+        _lib.bind("coattn_conv1_bn_eval_forward", image=image, weight=weight, conv_bias=conv_bias, gamma=gamma, beta=beta,
+                  running_mean=running_mean, running_var=running_var, eps=float(eps), y=y, B=B, H=H, W=W, Cin=3, Cout=64,
+                  pool=int(pool), dtype=_lib.F32, stream=_lib.stream_ptr(image.device))()
+    return y
+
+
+def conv1_bn_eval(image: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool: bool) -> torch.Tensor:
+    """relu([max_pool2d](bn(conv(image)))) of the encoder's first group with `bn` in EVAL mode, from the channels_last [B,3,H,W]
+    image to the result in ONE launch: the convolution in the stock kernel's arithmetic, its bias, then bn_eval's map.  The
+    convolution output is never stored and there is no workspace.  Forward only; runs on torch's current stream."""
+    if bn.training or not bn.affine or not conv1_eval_inputs_fusable(image, conv, bn, pool):
+        raise ValueError("conv1_bn_eval: needs a CUDA fp32 channels_last [B,3,H,W] image, a 3 -> 64 channel 3x3 / stride 1 / padding 1 "
+                         "convolution with channels_last weights, an affine BatchNorm2d in eval mode and a shape "
+                         "coattn_conv1_bn_eval_supported covers, got %s %s strides %s" % (tuple(image.shape), image.dtype, image.stride()))
+    b = conv.bias
+    if b is not None and not (b.dtype == torch.float32 and b.device == image.device and b.is_contiguous() and b.data_ptr() % 16 == 0):
+        raise ValueError("conv1_bn_eval: the convolution's bias must be a contiguous 16-byte aligned fp32 tensor on the image's device")
+    return _conv1_eval_raw(image, conv.weight, b, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, pool)
+
+
+def _conv(x, conv: nn.Conv2d, bias):
+    return torch.nn.functional.conv2d(x, conv.weight, bias, conv.stride, conv.padding, conv.dilation, conv.groups)
+
+
+def _eval_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+    """What an eval-mode group runs under eval_impl "stock": the convolution with its bias, then the stock chain."""
+    return _stock_chain(conv(x), bn, pool)
+
+
+def _eval_key(x, conv, z_shape, pool):
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    return (dev, z_shape[0], z_shape[1], z_shape[2], z_shape[3], pool is not None, conv.in_channels)
+
+
+def _conv_out_shape(x, conv: nn.Conv2d):
+    """The [B,C,H,W] of conv(x), without running it."""
+    if isinstance(conv.padding, str):
+        return None
+    hw = []
+    for n, k, s, p, d in zip(x.shape[2:], _pair(conv.kernel_size), _pair(conv.stride), _pair(conv.padding), _pair(conv.dilation)):
+        hw.append((n + 2 * p - d * (k - 1) - 1) // s + 1)
+    return (x.shape[0], conv.out_channels, hw[0], hw[1])
+
+
+def _verify_eval(x, conv, bn, pool, key) -> torch.Tensor:
+    """The first call of a shape: the stock group's result, and beside it bn_eval, compared bit for bit; the bias goes into the
+    kernel only where, under deterministic solvers, the convolution without it plus an exact add gave the stock convolution's
+    bits.  One host synchronisation."""
+    with torch.no_grad():
+        z = conv(x)
+        if not eval_output_fusable(z, bn, pool is not None):
+            return _stock_chain(z, bn, pool)                        # (another layout: nothing compared, nothing remembered)
+        b, flags, z0 = conv.bias, [], None
+        if b is not None and torch.backends.cudnn.deterministic:
+            z0 = _conv(x, conv, None)
+            if eval_output_fusable(z0, bn, pool is not None):
+                flags.append(_differs(z0 + b.view(1, -1, 1, 1), z))
+            else:
+                z0 = None
+        y = _stock_chain(z, bn, pool)                               # (eval-mode bn(z) writes a new tensor: z stays)
+        mine_z = _bn_eval_raw(z, None, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, pool is not None)
+        flags.append(_differs(mine_z, y))
+        if z0 is not None:
+            mine_b = _bn_eval_raw(z0, b, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, pool is not None)
+            flags.append(_differs(mine_b, y))
+        flags = torch.stack(flags).tolist()
+    in_kernel = z0 is not None and not flags[0] and not flags[2]
+    first = "y" if flags[1 if z0 is not None else 0] else None
+    _eval[key] = {"verified": first is None, "first_difference": first,
+                  "bias": None if b is None else "kernel" if in_kernel else "convolution"}
+    if first is not None:
+        warnings.warn("encoder: bn_eval does not reproduce the stock eval-mode BatchNorm for B=%d C=%d H=%d W=%d pool=%d (%s differs); "
+                      "this shape stays on the stock kernels" % (key[1:5] + (int(key[5]), first)))
+    return y
+
+
+def bn_eval_or_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+    """relu([max_pool2d](bn(conv(x)))) of an eval-mode group, `pool` a 2x2 MaxPool2d or None, with the stock kernels' bits: the stock
+    convolution, then bn_eval, for a (device, B, C, H, W, pool, Cin) whose first call in this process -- which runs the stock chain
+    and returns its result -- found the two equal in every bit; the stock chain for good after a difference, which is reported once.
+    Nothing is compared or remembered while the stream is capturing.  The convolution is issued without its bias, which the
+    kernel adds, only where that first call ran under torch.backends.cudnn.deterministic and also found
+    conv2d(x, w, None) + b equal to conv2d(x, w, b) in every bit (eval_report()'s "bias").  The caller has checked
+    eval_group_fusable."""
+    shape = _conv_out_shape(x, conv)
+    if shape is None:
+        return _eval_stock(x, conv, bn, pool)
+    key = _eval_key(x, conv, shape, pool)
+    state = _eval.get(key)
+    if state is None:
+        if torch.cuda.is_current_stream_capturing():
+            return _eval_stock(x, conv, bn, pool)
+        return _verify_eval(x, conv, bn, pool, key)
+    if not state["verified"]:
+        return _eval_stock(x, conv, bn, pool)
+    in_kernel = state["bias"] == "kernel"
+    z = _conv(x, conv, None if in_kernel else conv.bias)
+    if not eval_output_fusable(z, bn, pool is not None):            # (never seen: the first call had the same layout)
+        if in_kernel:
+            z = z + conv.bias.view(1, -1, 1, 1)
+        return _stock_chain(z, bn, pool)
+    return bn_eval(z, bn, conv_bias=conv.bias if in_kernel else None, pool=pool is not None)
+
+
+def conv1_bn_eval_or_stock(x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, pool) -> torch.Tensor:
+    """bn_eval_or_stock for the encoder's first group with the convolution inside the contract: conv1_bn_eval, one launch from the
+    image, for a shape whose first call found it equal in every bit to the stock convolution and chain; otherwise
+    bn_eval_or_stock, which has a verdict of its own.  The caller has checked eval_group_fusable and conv1_eval_inputs_fusable."""
+    B, _, H, W = x.shape
+    key = _eval_key(x, conv, (B, 64, H, W), pool)
+    state = (_eval.get(key) or {}).get("conv1")
+    if state is not None and state["verified"]:
+        return conv1_bn_eval(x, conv, bn, pool is not None)
+    y = bn_eval_or_stock(x, conv, bn, pool)
+    if state is not None or torch.cuda.is_current_stream_capturing() or key not in _eval:
+        return y
+    with torch.no_grad():
+        mine = _conv1_eval_raw(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, pool is not None)
+        differs = bool(_differs(mine, y))
+    _eval[key]["conv1"] = {"verified": not differs, "first_difference": "y" if differs else None}
+    if differs:
+        warnings.warn("encoder: the one-launch eval-mode first group does not reproduce the stock kernels for B=%d H=%d W=%d pool=%d "
+                      "(y differs); this shape keeps the stock convolution" % (B, H, W, int(pool is not None)))
+    return y

@@ -68,7 +68,7 @@ def _load_vgg_weights(features: nn.Module, classifier: nn.Module | None, weights
     return True
 
 
-def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
+def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor, eval_impl: str = "stock") -> torch.Tensor:
     """Runs a Conv2d / BatchNorm2d / ReLU / MaxPool2d ``Sequential`` (the VGG ``features``) with the
     same stock kernels but two value-preserving graph rewrites that save whole elementwise passes
     over the largest activations:
@@ -104,9 +104,20 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
 
     ``VQA_ENCODER_FUSED=0`` keeps the stock kernels.
 
-    Anything that does not match these patterns (eval-mode BatchNorm, trainable bias, NCHW, autocast, other modules)
-    is executed as is.  ``VQA_ENCODER_REWRITE=0`` disables all of it."""
+    EVAL-mode BatchNorm (``Trainer.validate``, ``predict.py``, ``extract.py``) is executed as is by default
+    (``eval_impl="stock"``: the convolution with its bias, the stock BatchNorm, then the ReLU / pool pass above).  With
+    ``eval_impl="hip"`` a whole ``Conv2d -> BatchNorm2d -> ReLU [-> MaxPool2d(2, 2)]`` group whose BatchNorm normalises with its
+    running statistics runs everything after the convolution -- the bias add, the BatchNorm, the ReLU, the pool -- in ONE launch
+    in the stock inference kernel's arithmetic (``encoder.bn_eval_or_stock``), and the first group runs in one launch from the
+    image (``encoder.conv1_bn_eval_or_stock``).  Per shape verified against the stock chain on its first call like the routes
+    above, or not used (``encoder.eval_report()``).  Under ``encoder.eval_group_fusable``'s conditions only -- a CUDA tensor, a
+    frozen group or no_grad, no autocast -- and never for a train-mode BatchNorm, whose branches below do not look at ``eval_impl``.
+
+    Anything that does not match these patterns (trainable bias, NCHW, autocast, other modules) is executed as is.
+    ``VQA_ENCODER_REWRITE=0`` disables all of it."""
     mods = list(seq)
+    if eval_impl not in encoder.EVAL_IMPLS:
+        raise ValueError("eval_impl must be one of %s, got %r" % (encoder.EVAL_IMPLS, eval_impl))
     if os.environ.get("VQA_ENCODER_REWRITE", "1") == "0":
         return seq(x)
     i, n = 0, len(mods)
@@ -115,6 +126,13 @@ def run_conv_bn_stack(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
         nxt = mods[i + 1] if i + 1 < n else None
         pool = mods[i + 3] if i + 3 < n and isinstance(mods[i + 3], nn.MaxPool2d) else None
         group = isinstance(m, nn.Conv2d) and isinstance(nxt, nn.BatchNorm2d) and i + 2 < n and isinstance(mods[i + 2], nn.ReLU)
+        if eval_impl == "hip" and group and not nxt.training and encoder.eval_group_fusable(m, nxt, pool, x):
+            if i == 0 and encoder.conv1_eval_inputs_fusable(x, m, nxt, pool is not None):
+                x = encoder.conv1_bn_eval_or_stock(x, m, nxt, pool)
+            else:
+                x = encoder.bn_eval_or_stock(x, m, nxt, pool)
+            i += 3 if pool is None else 4
+            continue
         fuse = group and encoder.modules_fusable(m, nxt, pool, x)
         exact = group and encoder.exact_modules_fusable(m, nxt, pool, x)
         if (isinstance(m, nn.Conv2d) and (fuse or exact or (m.bias is not None and not m.bias.requires_grad))
@@ -156,12 +174,13 @@ class ImageCoAttentionEncoder(nn.Module):
         self.vgg11_encoder = vgg11_bn_features()
         _load_vgg_weights(self.vgg11_encoder, None, weights_path)
         self.flatten = nn.Flatten(start_dim=2, end_dim=3)
+        self.eval_impl = "stock"       # eval-mode groups: "stock" or "hip" (run_conv_bn_stack; a plain attribute, not state)
         if not is_trainable:                      # frozen; BatchNorm stays in train mode (model.py:239-241)
             for prm in self.vgg11_encoder.parameters():
                 prm.requires_grad = False
 
     def forward(self, x_img):
-        grid = self.flatten(run_conv_bn_stack(self.vgg11_encoder, x_img))      # [B, 512, N]
+        grid = self.flatten(run_conv_bn_stack(self.vgg11_encoder, x_img, self.eval_impl))      # [B, 512, N]
         return grid.permute(0, 2, 1)                         # [B, N, 512] view, strides (512N, 1, N)
 
 

@@ -126,10 +126,15 @@ def main(argv=None):
         torch.set_num_threads(max(1, min(4, T.usable_cpus())))
     else:
         device = torch.device("cpu")
+    try:
+        T.check_encoder_eval(args.model, args.encoder_eval, args.channels_last, device.type, args.opt_lvl)
+    except ValueError as e:
+        ap.error(str(e))
     torch.manual_seed(0)
     model, cfg = T.model_from_args(args)
     model.load_state_dict(torch.load(T.checkpoint_path(args), map_location="cpu"))
     model.to(device)
+    T.set_encoder_eval(model, args.encoder_eval)
     cl = args.channels_last and device.type == "cuda" and args.model.startswith("attention")
     if cl:
         model.image_encoder.to(memory_format=torch.channels_last)

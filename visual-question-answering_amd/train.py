@@ -188,6 +188,46 @@ def set_sentence_lstm(model: nn.Module, sentence_lstm: str) -> None:
     enc.sentence_impl = sentence_lstm
 
 
+ENCODER_EVALS = ("stock", "hip")
+ENCODER_EVAL_MODELS = ("attention", "attention_bert")
+
+
+def check_encoder_eval(model_name: str, encoder_eval: str, channels_last: bool = True, device_type: str = "cuda",
+                       opt_lvl: int = 0) -> None:
+    """--encoder_eval hip: the frozen VGG's eval-mode groups (validation, prediction, feature extraction) on the one-launch HIP
+    passes of encoder.bn_eval / conv1_bn_eval; "stock", the default, leaves every route as it is.  "hip" is refused for a model
+    without a VGG grid, with --channels_last false (the kernels read [B][H][W][C]), on a CPU device and with --opt_lvl >= 1
+    (under autocast the stock BatchNorm sees another dtype)."""
+    if encoder_eval not in ENCODER_EVALS:
+        raise ValueError("--encoder_eval must be one of %s, got %r" % (ENCODER_EVALS, encoder_eval))
+    if encoder_eval == "stock":
+        return
+    if model_name not in ENCODER_EVAL_MODELS:
+        raise ValueError("--encoder_eval hip applies to the models with a VGG grid (--model %s), not to %s"
+                         % (" | ".join(ENCODER_EVAL_MODELS), model_name))
+    if not channels_last:
+        raise ValueError("--encoder_eval hip is not available with --channels_last false: the kernels read channels_last tensors")
+    if device_type != "cuda":
+        raise ValueError("--encoder_eval hip needs a GPU: the kernels have no CPU form (device %s)" % device_type)
+    if opt_lvl > 0:
+        raise ValueError("--encoder_eval hip is not available with --opt_lvl >= 1 (the reduced-precision mode)")
+
+
+def set_encoder_eval(model: nn.Module, encoder_eval: str) -> None:
+    """--encoder_eval on a built model: a module attribute (ImageCoAttentionEncoder.eval_impl), not part of the state_dict.  A
+    model whose image encoder has no such switch has nothing to set: asking for "hip" there is an error."""
+    if encoder_eval not in ENCODER_EVALS:
+        raise ValueError("--encoder_eval must be one of %s, got %r" % (ENCODER_EVALS, encoder_eval))
+    enc = getattr(model, "image_encoder", None)
+    if enc is None or not hasattr(enc, "eval_impl"):
+        if encoder_eval != "stock":
+            raise ValueError("--encoder_eval hip applies to the models with a VGG grid (--model %s), not to %s%s"
+                             % (" | ".join(ENCODER_EVAL_MODELS), type(model).__name__,
+                                "" if enc is None else " with " + type(enc).__name__))
+        return
+    enc.eval_impl = encoder_eval
+
+
 WORD_EMBEDDINGS = ("stock", "hip")
 
 
@@ -624,8 +664,15 @@ class Trainer:
                  bucket_mb: float = 16.0, encoder_runahead: bool = True, graph: bool = False, static_hot_path: bool = True,
                  precision: str = "exact", loss: str = "ce", optimizer: str = "torch", weight_decay: float = 0.0,
                  clip_grad_norm=None, sentence_lstm=None, word_embedding=None, feature_dropout: float = 0.0,
-                 dropout_seed: int = 0):
+                 dropout_seed: int = 0, encoder_eval=None):
         check_loss(loss)
+        if encoder_eval is not None:                             # "stock" | "hip" (set_encoder_eval); None: leave the model's
+            dev = device or next(model.parameters()).device
+            if encoder_eval == "hip" and torch.device(dev).type != "cuda":
+                raise ValueError("Trainer(encoder_eval='hip') needs a model on the GPU (the kernels have no CPU form)")
+            if encoder_eval == "hip" and opt_lvl > 0:
+                raise ValueError("Trainer(encoder_eval='hip') is not available with opt_lvl >= 1 (the reduced-precision mode)")
+            set_encoder_eval(model, encoder_eval)
         if word_embedding is not None:                           # "stock" | "hip" (set_word_embedding); None: leave the model's
             set_word_embedding(model, word_embedding)
         if sentence_lstm is not None:                            # "stock" | "hip" (set_sentence_lstm); None: leave the model's
@@ -987,6 +1034,10 @@ def build_parser():
                          "pad_packed_sequence as the reference (model.py:286-296); 'hip' = the length-aware HIP forward / "
                          "backward on the same parameters (exact fp32, no packing, no host read of the lengths).  "
                          "Co-attention models only; a checkpoint does not depend on it")
+    ap.add_argument("--encoder_eval", default="stock", choices=list(ENCODER_EVALS),
+                    help="the frozen VGG's eval-mode groups (validation, predict.py, extract.py): stock (the default: every route as "
+                         "it is) or hip (BatchNorm on running statistics + bias + ReLU + pool in one HIP launch per group, the first "
+                         "group from the image; verified per shape against the stock kernels, same bits)")
     ap.add_argument("--word_embedding", default="stock", choices=list(WORD_EMBEDDINGS),
                     help="the question encoder's word level: 'stock' = nn.Embedding and PyTorch's embedding backward; 'hip' = "
                          "the HIP gather and its dense gradient in one launch each on the same parameter (fixed summation "
@@ -1050,6 +1101,10 @@ def main(argv=None):
         # the step is GPU work; the host side only launches kernels and stages batches.  ATen's default of
         # one thread per logical CPU oversubscribes a containerised rank (measured: 39.7 vs 26.3 ms/step)
         torch.set_num_threads(max(1, min(4, usable_cpus())))
+    try:
+        check_encoder_eval(args.model, args.encoder_eval, args.channels_last, device.type, args.opt_lvl)
+    except ValueError as e:
+        raise SystemExit(str(e))
     torch.manual_seed(0)                                        # identical weights on every rank
     model, cfg = model_from_args(args)
     # log directory expt_dir/expt_name/run_name (main.py:110-114): checkpoints model_{step}.pth live there (main.py:260-263)
@@ -1065,7 +1120,7 @@ def main(argv=None):
     trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss,
                       optimizer=args.optimizer, weight_decay=args.weight_decay, clip_grad_norm=args.clip_grad_norm,
                       sentence_lstm=args.sentence_lstm, word_embedding=args.word_embedding, feature_dropout=args.dropout,
-                      dropout_seed=args.dropout_seed)
+                      dropout_seed=args.dropout_seed, encoder_eval=args.encoder_eval)
     n_ans = args.num_answers if args.loss != "ce" else 0
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
