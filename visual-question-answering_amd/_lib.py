@@ -1,4 +1,5 @@
-"""ctypes binding of ``libcoattn_hip.so`` (C-ABI declared in ``include/coattn.h`` and, after 0.22.0, ``include/coattn_ext.h``)."""
+"""ctypes binding of ``libcoattn_hip.so`` (C-ABI declared in ``include/coattn.h``, after 0.22.0 in ``include/coattn_ext.h``, the
+recurrent entry points after 0.24.0 in ``include/coattn_rnn.h``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -88,6 +89,15 @@ class LstmParams(C.Structure):
 
 
 class LstmParamGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+class GruParams(C.Structure):
+    # the question GRU of the baseline model (v0.25.0): nn.GRU's weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+class GruParamGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
 
 
@@ -277,12 +287,24 @@ EXT_SIGNATURES = {
 }
 EXT_RESTYPES = {}
 EXT_EXPORTS = tuple(EXT_SIGNATURES)
-_ALL_SIGNATURES = {**SIGNATURES, **EXT_SIGNATURES}
-_ALL_RESTYPES = {**RESTYPES, **EXT_RESTYPES}
+# The recurrent entry points after 0.24.0, declared in include/coattn_rnn.h: a third table of the same form (tests/test_gru_cpu.py
+# holds it against that header).  The two tables above keep their contents and order.
+RNN_SIGNATURES = {
+    # the question GRU of the baseline model (v0.25.0)
+    "coattn_gru_supported": _int("B T E H dtype"),
+    "coattn_gru_workspace_bytes": _int("B T E H dtype") + _THREE_SIZES,
+    "coattn_gru_forward": _void("X len") + _to(GruParams) + _void("seq_out h_last saved ws") + _LSTM_DIMS,
+    "coattn_gru_backward": (_void("X len") + _to(GruParams) + _void("saved g_seq g_last dX") + _to(GruParamGrads, "pg")
+                            + _int("accumulate") + _void("ws") + _LSTM_DIMS),
+}
+RNN_RESTYPES = {}
+RNN_EXPORTS = tuple(RNN_SIGNATURES)
+_ALL_SIGNATURES = {**SIGNATURES, **EXT_SIGNATURES, **RNN_SIGNATURES}
+_ALL_RESTYPES = {**RESTYPES, **EXT_RESTYPES, **RNN_RESTYPES}
 _INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _ALL_SIGNATURES.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
 _DEFAULTS = dict.fromkeys(("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1 bad_maps "
-                           "conv_bias stats_out x_out dlogits x_masked g_xmasked dX bad_images").split())
+                           "conv_bias stats_out x_out dlogits x_masked g_xmasked dX bad_images h_last g_seq g_last").split())
 _DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
 
 
@@ -347,7 +369,7 @@ def _call(name, vals):
 
 
 def bind(name: str, **kw) -> Call:
-    """The call of SIGNATURES[name] (or EXT_SIGNATURES[name]) with its arguments given by name: tensors go in as their device
+    """The call of SIGNATURES[name] (or EXT_SIGNATURES[name], RNN_SIGNATURES[name]) with its arguments given by name: tensors go in as their device
     pointers, ctypes structures by reference, None as NULL; an omitted nullable pointer is NULL, an omitted dV stride 0, `stream` may be left
     for the call itself.  Raises TypeError on a name the entry point does not have and on a missing required one."""
     unknown = kw.keys() - _INDEX[name].keys()
@@ -558,6 +580,11 @@ def alt_workspace_bytes(B, N, T, d, L):
 def lstm_workspace_bytes(B, T, E, H):
     """(saved, ws_fwd, ws_bwd) in bytes of the sentence LSTM."""
     return _bytes("coattn_lstm_workspace_bytes", 3, B, T, E, H, F32)
+
+
+def gru_workspace_bytes(B, T, E, H):
+    """(saved, ws_fwd, ws_bwd) in bytes of the question GRU."""
+    return _bytes("coattn_gru_workspace_bytes", 3, B, T, E, H, F32)
 
 
 def embedding_workspace_bytes(n, V, E):

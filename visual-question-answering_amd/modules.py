@@ -590,7 +590,7 @@ class HierarchicalCoAttentionNet(nn.Module):
         return hp(x_img_features, x_ques_features, labels if targets is None else targets, q_len=x_ques_lens)
 
 
-# ---- baseline model (BASELINE config 1: CPU plumbing, no custom kernels) ------------------
+# ---- baseline model (BASELINE config 1: stock PyTorch plumbing; the question GRU on csrc/gru.hip on request) ------------------
 class ImageBaselineEncoder(nn.Module):
     """VGG11-bn up to fc7 (4096), L2-normalised, -> 1024 tanh."""
 
@@ -612,8 +612,34 @@ class ImageBaselineEncoder(nn.Module):
         return self.embedding_layer(F.normalize(self.vgg11_encoder(x_img), dim=1, p=2))
 
 
+GRU_IMPLS = ("stock", "hip")
+
+
+def _hip_gru(enc, emb) -> bool:
+    """Does this forward of the baseline's question encoder take the HIP GRU on `emb`, the GRU's input?  ``enc.gru_impl``:
+    "stock" (the default: pack_padded_sequence -> nn.GRU) or "hip" (gru.question_gru on the nn.GRU's own parameters: a CUDA
+    input of a supported shape that is fp32, or any floating type under CUDA autocast, where question_gru is an fp32 island
+    that casts it, and an nn.GRU of one layer, one direction, with bias and without dropout; CPU tensors, other shapes,
+    other dtypes outside autocast and other GRUs take the stock lines)."""
+    impl = enc.gru_impl
+    if impl not in GRU_IMPLS:
+        raise ValueError("gru_impl must be one of %s, got %r" % (GRU_IMPLS, impl))
+    if impl != "hip" or not emb.is_cuda:
+        return False
+    if emb.dtype != torch.float32 and not (emb.is_floating_point() and torch.is_autocast_enabled("cuda")):
+        return False
+    rnn = enc.gru
+    if not isinstance(rnn, nn.GRU) or rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.dropout != 0:
+        return False
+    from . import gru
+    B, T, E = emb.shape
+    return E == rnn.input_size and gru.supported(B, T, E, rnn.hidden_size)
+
+
 class QuestionBaselineEncoder(nn.Module):
-    """Embedding + tanh -> GRU (last non-pad state via packing) -> 1024 tanh."""
+    """Embedding + tanh -> GRU (last non-pad state via packing) -> 1024 tanh.
+    ``gru_impl``: "stock" (default) or "hip" (`_hip_gru`: the GRU on csrc/gru.hip with the nn.GRU's own parameters, the
+    lengths read on the device in any order, nothing packed).  Not part of the state_dict."""
 
     def __init__(self, vocab_size, word_emb_dim, hidden_dim):
         super().__init__()
@@ -621,10 +647,17 @@ class QuestionBaselineEncoder(nn.Module):
         self.word_embedding = nn.Sequential(nn.Embedding(vocab_size, word_emb_dim), nn.Tanh())
         self.gru = nn.GRU(word_emb_dim, hidden_dim)
         self.embedding_layer = nn.Sequential(nn.Linear(hidden_dim, 1024), nn.Tanh())
+        self.gru_impl = "stock"
 
     def forward(self, x, seq_lengths):
+        emb = self.word_embedding(x)
+        if _hip_gru(self, emb):                                       # opt-in: csrc/gru.hip, lengths stay on the device
+            from .gru import question_gru
+            rnn = self.gru
+            _, h_last = question_gru(emb, seq_lengths, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
+            return self.embedding_layer(h_last)
         lens = seq_lengths.cpu() if torch.is_tensor(seq_lengths) else seq_lengths
-        packed = pack_padded_sequence(self.word_embedding(x), lens, batch_first=True)
+        packed = pack_padded_sequence(emb, lens, batch_first=True)
         _, hidden = self.gru(packed)
         return self.embedding_layer(torch.squeeze(hidden, dim=0))
 

@@ -188,6 +188,25 @@ def set_sentence_lstm(model: nn.Module, sentence_lstm: str) -> None:
     enc.sentence_impl = sentence_lstm
 
 
+QUESTION_GRUS = ("stock", "hip")
+
+
+def set_question_gru(model: nn.Module, question_gru: str) -> None:
+    """--question_gru: "stock" (the default: pack_padded_sequence -> nn.GRU, sorted lengths, a host read of them) or "hip" (the
+    baseline question encoder's GRU on gru.question_gru: same parameters, lengths read on the device in any order).  A module
+    attribute (QuestionBaselineEncoder.gru_impl), not part of the state_dict: a checkpoint does not depend on it.  The models
+    whose question encoder has no GRU have nothing to switch: asking for "hip" there is an error."""
+    if question_gru not in QUESTION_GRUS:
+        raise ValueError("--question_gru must be one of %s, got %r" % (QUESTION_GRUS, question_gru))
+    enc = getattr(model, "question_encoder", None)
+    if enc is None or not hasattr(enc, "gru_impl"):
+        if question_gru != "stock":
+            raise ValueError("--question_gru hip applies to the baseline model (--model baseline), not to %s"
+                             % type(model).__name__)
+        return
+    enc.gru_impl = question_gru
+
+
 ENCODER_EVALS = ("stock", "hip")
 ENCODER_EVAL_MODELS = ("attention", "attention_bert")
 
@@ -407,6 +426,7 @@ def model_from_args(args):
     set_question_mask(model, getattr(args, "question_mask", False))
     set_affinity(model, affinity)
     set_sentence_lstm(model, getattr(args, "sentence_lstm", "stock"))
+    set_question_gru(model, getattr(args, "question_gru", "stock"))
     set_word_embedding(model, getattr(args, "word_embedding", "stock"))
     return model, cfg
 
@@ -664,8 +684,10 @@ class Trainer:
                  bucket_mb: float = 16.0, encoder_runahead: bool = True, graph: bool = False, static_hot_path: bool = True,
                  precision: str = "exact", loss: str = "ce", optimizer: str = "torch", weight_decay: float = 0.0,
                  clip_grad_norm=None, sentence_lstm=None, word_embedding=None, feature_dropout: float = 0.0,
-                 dropout_seed: int = 0, encoder_eval=None):
+                 dropout_seed: int = 0, encoder_eval=None, question_gru=None):
         check_loss(loss)
+        if question_gru is not None:                             # "stock" | "hip" (set_question_gru); None: leave the model's
+            set_question_gru(model, question_gru)
         if encoder_eval is not None:                             # "stock" | "hip" (set_encoder_eval); None: leave the model's
             dev = device or next(model.parameters()).device
             if encoder_eval == "hip" and torch.device(dev).type != "cuda":
@@ -1034,6 +1056,11 @@ def build_parser():
                          "pad_packed_sequence as the reference (model.py:286-296); 'hip' = the length-aware HIP forward / "
                          "backward on the same parameters (exact fp32, no packing, no host read of the lengths).  "
                          "Co-attention models only; a checkpoint does not depend on it")
+    ap.add_argument("--question_gru", default="stock", choices=list(QUESTION_GRUS),
+                    help="the baseline question encoder's GRU: 'stock' = pack_padded_sequence -> nn.GRU as the reference "
+                         "(model.py:86-100; sorted lengths, read on the host); 'hip' = the length-aware HIP forward / backward on "
+                         "the same parameters (exact fp32, no packing, no host read of the lengths, any order).  --model baseline "
+                         "only; a checkpoint does not depend on it")
     ap.add_argument("--encoder_eval", default="stock", choices=list(ENCODER_EVALS),
                     help="the frozen VGG's eval-mode groups (validation, predict.py, extract.py): stock (the default: every route as "
                          "it is) or hip (BatchNorm on running statistics + bias + ReLU + pool in one HIP launch per group, the first "
@@ -1120,7 +1147,7 @@ def main(argv=None):
     trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss,
                       optimizer=args.optimizer, weight_decay=args.weight_decay, clip_grad_norm=args.clip_grad_norm,
                       sentence_lstm=args.sentence_lstm, word_embedding=args.word_embedding, feature_dropout=args.dropout,
-                      dropout_seed=args.dropout_seed, encoder_eval=args.encoder_eval)
+                      dropout_seed=args.dropout_seed, encoder_eval=args.encoder_eval, question_gru=args.question_gru)
     n_ans = args.num_answers if args.loss != "ce" else 0
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
