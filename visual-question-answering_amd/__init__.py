@@ -16,6 +16,8 @@ from .optim import HipAdam  # noqa: F401
 from .lstm import sentence_lstm  # noqa: F401
 from . import gru  # noqa: F401
 from .gru import question_gru  # noqa: F401
+from . import fusion  # noqa: F401
+from .fusion import fusion_head  # noqa: F401
 from . import embedding  # noqa: F401
 from .embedding import word_embedding  # noqa: F401
 from . import dropout  # noqa: F401
@@ -28,7 +30,7 @@ from . import preprocess  # noqa: F401
 from .preprocess import ImagePreprocessor, preprocess_host  # noqa: F401
 
 __all__ = ["word_embedding", "embedding","ParallelCoAttention", "AlternatingCoAttention", "coattention", "native_features", "answer_head", "cross_entropy", "CrossEntropyLoss", "soft_target_loss",
-           "SoftTargetLoss", "vqa_score", "HipAdam", "sentence_lstm", "gru", "question_gru", "_lib",
+           "SoftTargetLoss", "vqa_score", "HipAdam", "sentence_lstm", "gru", "question_gru", "fusion", "fusion_head", "_lib",
            "check_range", "RangeError", "dropout", "DropoutState", "feature_dropout", "rank_seed",
            "features", "FeatureTable", "gather_features",
            "overlay", "render_attention", "preprocess", "ImagePreprocessor", "preprocess_host"]

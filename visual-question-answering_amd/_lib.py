@@ -1,5 +1,5 @@
 """ctypes binding of ``libcoattn_hip.so`` (C-ABI declared in ``include/coattn.h``, after 0.22.0 in ``include/coattn_ext.h``, the
-recurrent entry points after 0.24.0 in ``include/coattn_rnn.h``)."""
+recurrent entry points after 0.24.0 in ``include/coattn_rnn.h``, the fusion head of 0.26.0 in ``include/coattn_fusion.h``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -99,6 +99,18 @@ class GruParams(C.Structure):
 
 class GruParamGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+FUSION_PARAM_NAMES = ("W_i", "b_i", "W_q", "b_q", "W_m", "b_m", "W_f", "b_f")
+
+
+class FusionParams(C.Structure):
+    # the fusion head of the baseline model (v0.26.0): image_embedding, embedding_layer, mlp and fc_final as nn.Linear stores them
+    _fields_ = [(n, C.c_void_p) for n in FUSION_PARAM_NAMES]
+
+
+class FusionParamGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in FUSION_PARAM_NAMES]
 
 
 class OverlayParams(C.Structure):
@@ -299,12 +311,25 @@ RNN_SIGNATURES = {
 }
 RNN_RESTYPES = {}
 RNN_EXPORTS = tuple(RNN_SIGNATURES)
-_ALL_SIGNATURES = {**SIGNATURES, **EXT_SIGNATURES, **RNN_SIGNATURES}
-_ALL_RESTYPES = {**RESTYPES, **EXT_RESTYPES, **RNN_RESTYPES}
+# The fusion head of the baseline model (v0.26.0), declared in include/coattn_fusion.h: a fourth table of the same form
+# (tests/test_fusion_cpu.py holds it against that header).  The three tables above keep their contents and order.
+_FUSION_IN = _void("f") + _i64("ld_f") + _void("h") + _i64("ld_h") + _to(FusionParams)
+_FUSION_DIMS = _int("B Di H J Mh K dtype flags") + _void("stream")
+FUSION_SIGNATURES = {
+    "coattn_fusion_supported": _int("B Di H J Mh K dtype"),
+    "coattn_fusion_workspace_bytes": _int("B Di H J Mh K dtype") + _sizes("saved ws_bwd"),
+    "coattn_fusion_forward": _FUSION_IN + _void("logits saved") + _f32("p_drop") + _void("drop_state") + _FUSION_DIMS,
+    "coattn_fusion_backward": (_FUSION_IN + _void("saved g_logits dh") + _to(FusionParamGrads, "pg") + _int("accumulate")
+                               + _f32("p_drop") + _void("drop_state ws") + _FUSION_DIMS),
+}
+FUSION_RESTYPES = {}
+FUSION_EXPORTS = tuple(FUSION_SIGNATURES)
+_ALL_SIGNATURES = {**SIGNATURES, **EXT_SIGNATURES, **RNN_SIGNATURES, **FUSION_SIGNATURES}
+_ALL_RESTYPES = {**RESTYPES, **EXT_RESTYPES, **RNN_RESTYPES, **FUSION_RESTYPES}
 _INDEX = {name: {n: i for i, (n, _) in enumerate(sig)} for name, sig in _ALL_SIGNATURES.items()}
 # what bind() fills in for an argument it is not given: NULL for the pointers the header lets be NULL, 0 for dV's strides
 _DEFAULTS = dict.fromkeys(("q_len av_out aq_out saved g_av g_aq dV labels loss g_loss g_logits dv dq bad_ids bad_idx x1 y1 bad_maps "
-                           "conv_bias stats_out x_out dlogits x_masked g_xmasked dX bad_images h_last g_seq g_last").split())
+                           "conv_bias stats_out x_out dlogits x_masked g_xmasked dX bad_images h_last g_seq g_last dh drop_state").split())
 _DEFAULTS.update(dv_sB=0, dv_sN=0, dv_sD=0)
 
 
@@ -369,7 +394,7 @@ def _call(name, vals):
 
 
 def bind(name: str, **kw) -> Call:
-    """The call of SIGNATURES[name] (or EXT_SIGNATURES[name], RNN_SIGNATURES[name]) with its arguments given by name: tensors go in as their device
+    """The call of SIGNATURES[name] (or EXT_SIGNATURES[name], RNN_SIGNATURES[name], FUSION_SIGNATURES[name]) with its arguments given by name: tensors go in as their device
     pointers, ctypes structures by reference, None as NULL; an omitted nullable pointer is NULL, an omitted dV stride 0, `stream` may be left
     for the call itself.  Raises TypeError on a name the entry point does not have and on a missing required one."""
     unknown = kw.keys() - _INDEX[name].keys()
@@ -585,6 +610,11 @@ def lstm_workspace_bytes(B, T, E, H):
 def gru_workspace_bytes(B, T, E, H):
     """(saved, ws_fwd, ws_bwd) in bytes of the question GRU."""
     return _bytes("coattn_gru_workspace_bytes", 3, B, T, E, H, F32)
+
+
+def fusion_workspace_bytes(B, Di, H, J, Mh, K):
+    """(saved, ws_bwd) in bytes of the baseline model's fusion head."""
+    return _bytes("coattn_fusion_workspace_bytes", 2, B, Di, H, J, Mh, K, F32)
 
 
 def embedding_workspace_bytes(n, V, E):

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "fused.h"
 #include "../../include/coattn_rnn.h"
+#include "../../include/coattn_fusion.h"
 
 #include <string.h>
 
@@ -17,7 +18,7 @@ void coattn_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int coattn_version(void) { return 2500; }   // 0.25.0: the question GRU of the baseline model, length-aware forward and backward (coattn_gru_supported, coattn_gru_workspace_bytes, coattn_gru_forward, coattn_gru_backward: gru.hip; declared in include/coattn_rnn.h); 0.24.0: the frozen encoder in eval mode, BatchNorm on running statistics + convolution bias + ReLU + pool in one launch, the first group from the image (coattn_bn_eval_supported, coattn_bn_eval_forward, coattn_conv1_bn_eval_supported, coattn_conv1_bn_eval_forward, the developer probe coattn_bn_eval_probe: encoder.hip); 0.23.0: image preprocessing, Pillow's 8-bit bilinear resize and the ToTensor + Normalize lookup for a batch of decoded images in one launch (coattn_preprocess_supported, coattn_preprocess_images: preprocess.hip; declared in include/coattn_ext.h, as every entry point after 0.22.0); 0.22.0: layer 1 of the frozen encoder with the convolution computed twice and never stored (coattn_conv1_bn_recompute_workspace_bytes, coattn_conv1_bn_recompute_forward: encoder.hip); 0.21.0: attention overlays (coattn_overlay_render: overlay.hip); 0.20.0: cached image features, the rows of a batch gathered from an fp32 or bf16 feature table in one launch (coattn_features_gather_supported, coattn_features_gather: features.hip); 0.19.0: feature dropout, a Philox4x32-10 mask regenerated in the backward from a device-side step counter (coattn_dropout_supported, coattn_dropout_forward, coattn_dropout_backward: dropout.hip); 0.18.0: the word embedding, gather and ordered dense gradient (coattn_embedding_supported, coattn_embedding_workspace_bytes, coattn_embedding_forward, coattn_embedding_backward: embedding.hip); 0.17.0: the sentence LSTM, length-aware forward and backward (coattn_lstm_supported, coattn_lstm_workspace_bytes, coattn_lstm_forward, coattn_lstm_backward: lstm.hip); 0.16.0: layer 1 of the frozen encoder, convolution and BatchNorm statistics in one pass with the stock kernels' bits (coattn_conv1_bn_exact_supported, coattn_conv1_bn_exact_workspace_bytes, coattn_conv1_bn_exact_forward, coattn_conv1_probe: encoder.hip); 0.15.0: the stock BatchNorm kernels' bits in two passes (coattn_bn_exact_geometry, coattn_bn_exact_workspace_bytes, coattn_bn_exact_forward: encoder.hip); 0.14.0: the frozen encoder's train-mode BatchNorm + ReLU + 2x2 max-pool (coattn_bn_supported, coattn_bn_workspace_bytes, coattn_bn_relu_pool_forward: encoder.hip); 0.13.0: the optimiser step (coattn_adam_workspace_bytes, coattn_adam_step: adam.hip); 0.12.0: soft answer targets (coattn_soft_loss_forward, coattn_vqa_score, coattn_head_forward_soft); 0.11.0: alternating co-attention (coattn_alt_workspace_bytes / _forward / _backward); 0.10.0: COATTN_FLAG_BILINEAR (the affinity tanh(Q W_b^T + b_b) V^T; W_b / b_b, dW_b / db_b appended to the parameter structs); 0.9.0: coattn_forward_maps(_len) / coattn_backward_maps(_len) (differentiable attention maps); 0.8.0: the length-masked forms coattn_forward_len / _infer_len / _attention_forward_len / _backward_len; 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
+extern "C" int coattn_version(void) { return 2600; }   // 0.26.0: the fusion head of the baseline model, row norm + two embeddings + product + Linear -> Philox dropout -> tanh + classifier, forward and backward (coattn_fusion_supported, coattn_fusion_workspace_bytes, coattn_fusion_forward, coattn_fusion_backward: fusion.hip; declared in include/coattn_fusion.h); 0.25.0: the question GRU of the baseline model, length-aware forward and backward (coattn_gru_supported, coattn_gru_workspace_bytes, coattn_gru_forward, coattn_gru_backward: gru.hip; declared in include/coattn_rnn.h); 0.24.0: the frozen encoder in eval mode, BatchNorm on running statistics + convolution bias + ReLU + pool in one launch, the first group from the image (coattn_bn_eval_supported, coattn_bn_eval_forward, coattn_conv1_bn_eval_supported, coattn_conv1_bn_eval_forward, the developer probe coattn_bn_eval_probe: encoder.hip); 0.23.0: image preprocessing, Pillow's 8-bit bilinear resize and the ToTensor + Normalize lookup for a batch of decoded images in one launch (coattn_preprocess_supported, coattn_preprocess_images: preprocess.hip; declared in include/coattn_ext.h, as every entry point after 0.22.0); 0.22.0: layer 1 of the frozen encoder with the convolution computed twice and never stored (coattn_conv1_bn_recompute_workspace_bytes, coattn_conv1_bn_recompute_forward: encoder.hip); 0.21.0: attention overlays (coattn_overlay_render: overlay.hip); 0.20.0: cached image features, the rows of a batch gathered from an fp32 or bf16 feature table in one launch (coattn_features_gather_supported, coattn_features_gather: features.hip); 0.19.0: feature dropout, a Philox4x32-10 mask regenerated in the backward from a device-side step counter (coattn_dropout_supported, coattn_dropout_forward, coattn_dropout_backward: dropout.hip); 0.18.0: the word embedding, gather and ordered dense gradient (coattn_embedding_supported, coattn_embedding_workspace_bytes, coattn_embedding_forward, coattn_embedding_backward: embedding.hip); 0.17.0: the sentence LSTM, length-aware forward and backward (coattn_lstm_supported, coattn_lstm_workspace_bytes, coattn_lstm_forward, coattn_lstm_backward: lstm.hip); 0.16.0: layer 1 of the frozen encoder, convolution and BatchNorm statistics in one pass with the stock kernels' bits (coattn_conv1_bn_exact_supported, coattn_conv1_bn_exact_workspace_bytes, coattn_conv1_bn_exact_forward, coattn_conv1_probe: encoder.hip); 0.15.0: the stock BatchNorm kernels' bits in two passes (coattn_bn_exact_geometry, coattn_bn_exact_workspace_bytes, coattn_bn_exact_forward: encoder.hip); 0.14.0: the frozen encoder's train-mode BatchNorm + ReLU + 2x2 max-pool (coattn_bn_supported, coattn_bn_workspace_bytes, coattn_bn_relu_pool_forward: encoder.hip); 0.13.0: the optimiser step (coattn_adam_workspace_bytes, coattn_adam_step: adam.hip); 0.12.0: soft answer targets (coattn_soft_loss_forward, coattn_vqa_score, coattn_head_forward_soft); 0.11.0: alternating co-attention (coattn_alt_workspace_bytes / _forward / _backward); 0.10.0: COATTN_FLAG_BILINEAR (the affinity tanh(Q W_b^T + b_b) V^T; W_b / b_b, dW_b / db_b appended to the parameter structs); 0.9.0: coattn_forward_maps(_len) / coattn_backward_maps(_len) (differentiable attention maps); 0.8.0: the length-masked forms coattn_forward_len / _infer_len / _attention_forward_len / _backward_len; 0.7.0: coattn_infer (forward only, attention maps to caller buffers); 0.6.1: coattn_status_accumulate / coattn_phrase_status_accumulate (sticky range report in a caller-owned accumulator); 0.6.0: flags = 0 is the exact mode, COATTN_FLAG_FAST16 the tolerance mode, coattn_status / coattn_phrase_status; 0.5.2: forward-side contractions on two FP16 pieces (COATTN_FLAG_F16PAIR); 0.5.1: coattn_features_native; 0.5.0: widths of the fp32 mode (COATTN_FLAG_EXACT3 / _SPLIT2), coattn_profile_*
 
 // ---------------------------------------------------------------------------------------
 // per-kernel timing (bench.py's backward roofline legs): HIP events recorded between the launches of the calls made

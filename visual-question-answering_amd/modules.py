@@ -590,7 +590,9 @@ class HierarchicalCoAttentionNet(nn.Module):
         return hp(x_img_features, x_ques_features, labels if targets is None else targets, q_len=x_ques_lens)
 
 
-# ---- baseline model (BASELINE config 1: stock PyTorch plumbing; the question GRU on csrc/gru.hip on request) ------------------
+# ---- baseline model (BASELINE config 1: stock PyTorch plumbing by default; on request the question GRU on csrc/gru.hip and
+# everything behind the two encoders -- row norm, the two embeddings, the product, Linear -> Dropout -> Tanh with the dropout
+# drawn inside the head, the classifier -- on csrc/fusion.hip) -------------------------------------------------------------
 class ImageBaselineEncoder(nn.Module):
     """VGG11-bn up to fc7 (4096), L2-normalised, -> 1024 tanh."""
 
@@ -649,6 +651,18 @@ class QuestionBaselineEncoder(nn.Module):
         self.embedding_layer = nn.Sequential(nn.Linear(hidden_dim, 1024), nn.Tanh())
         self.gru_impl = "stock"
 
+    def encode_hidden(self, x, seq_lengths):
+        """The GRU's hidden state after each question's last token, [B, hidden_dim], without the embedding layer behind it:
+        what the HIP fusion head of VQABaselineNet takes.  From question_gru or the packed stock GRU, as ``gru_impl`` says
+        (the stock ``forward`` below does not go through here)."""
+        emb = self.word_embedding(x)
+        if _hip_gru(self, emb):
+            from .gru import question_gru
+            rnn = self.gru
+            return question_gru(emb, seq_lengths, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)[1]
+        lens = seq_lengths.cpu() if torch.is_tensor(seq_lengths) else seq_lengths
+        return torch.squeeze(self.gru(pack_padded_sequence(emb, lens, batch_first=True))[1], dim=0)
+
     def forward(self, x, seq_lengths):
         emb = self.word_embedding(x)
         if _hip_gru(self, emb):                                       # opt-in: csrc/gru.hip, lengths stay on the device
@@ -662,8 +676,47 @@ class QuestionBaselineEncoder(nn.Module):
         return self.embedding_layer(torch.squeeze(hidden, dim=0))
 
 
+FUSION_IMPLS = ("stock", "hip")
+
+
+def _linear_tanh(seq) -> bool:
+    return (isinstance(seq, nn.Sequential) and len(seq) == 2 and isinstance(seq[0], nn.Linear) and seq[0].bias is not None
+            and isinstance(seq[1], nn.Tanh))
+
+
+def _hip_fusion(net, f, h) -> bool:
+    """Does this forward of the baseline model take the HIP fusion head on `f`, the image encoder's fc7 features, and `h`, the
+    GRU's last hidden state?  ``net.fusion_impl``: "stock" (the default: the nn modules) or "hip" (fusion.fusion_head on the
+    modules' own parameters: CUDA tensors that are fp32, or any floating type under CUDA autocast, where fusion_head is an
+    fp32 island that casts them; a supported shape; a frozen image encoder -- `f` carries no gradient, the head has none for
+    it; and the expected structure, ``mlp = [Linear, Dropout, Tanh]``, both ``embedding_layer = [Linear, Tanh]``, fc_final
+    a Linear, all with bias.  Everything else takes the stock lines)."""
+    impl = net.fusion_impl
+    if impl not in FUSION_IMPLS:
+        raise ValueError("fusion_impl must be one of %s, got %r" % (FUSION_IMPLS, impl))
+    if impl != "hip" or not (f.is_cuda and h.is_cuda) or f.requires_grad:
+        return False
+    for t in (f, h):
+        if t.dtype != torch.float32 and not (t.is_floating_point() and torch.is_autocast_enabled("cuda")):
+            return False
+    ie, qe, mlp, fc = net.image_encoder.embedding_layer, net.question_encoder.embedding_layer, net.mlp, net.fc_final
+    if not (_linear_tanh(ie) and _linear_tanh(qe) and isinstance(fc, nn.Linear) and fc.bias is not None
+            and isinstance(mlp, nn.Sequential) and len(mlp) == 3 and isinstance(mlp[0], nn.Linear) and mlp[0].bias is not None
+            and isinstance(mlp[1], nn.Dropout) and isinstance(mlp[2], nn.Tanh)):
+        return False
+    if f.dim() != 2 or h.dim() != 2 or f.shape[0] != h.shape[0] or f.shape[1] != ie[0].in_features \
+            or h.shape[1] != qe[0].in_features or ie[0].out_features != qe[0].out_features \
+            or mlp[0].in_features != ie[0].out_features or fc.in_features != mlp[0].out_features:
+        return False
+    from . import fusion
+    return fusion.supported(f.shape[0], f.shape[1], h.shape[1], ie[0].out_features, mlp[0].out_features, fc.out_features)
+
+
 class VQABaselineNet(nn.Module):
-    """Element-wise product of image and question embeddings -> MLP -> logits."""
+    """Element-wise product of image and question embeddings -> MLP -> logits.
+    ``fusion_impl``: "stock" (default) or "hip" (`_hip_fusion`: everything behind the VGG and the GRU on csrc/fusion.hip with
+    these modules' own parameters; the dropout of ``mlp[1]`` drawn inside the head from ``fusion_dropout_state``, a
+    DropoutState, never from torch's generators).  Neither is part of the state_dict."""
 
     def __init__(self, ques_enc_params, img_enc_params, K):
         super().__init__()
@@ -671,10 +724,38 @@ class VQABaselineNet(nn.Module):
         self.question_encoder = QuestionBaselineEncoder(**ques_enc_params)
         self.mlp = nn.Sequential(nn.Linear(1024, 1000), nn.Dropout(0.5), nn.Tanh())
         self.fc_final = nn.Linear(1000, K)
+        self.fusion_impl = "stock"
+        self.fusion_dropout_state = None
 
     def forward(self, x_img, x_ques, x_ques_len):
+        if self.fusion_impl != "stock":                               # opt-in: csrc/fusion.hip behind the two encoders
+            hip = self._forward_hip(x_img, x_ques, x_ques_len)
+            if hip is not None:
+                return hip
         joint = self.image_encoder(x_img) * self.question_encoder(x_ques, x_ques_len)
         return self.fc_final(self.mlp(joint))
+
+    def _forward_hip(self, x_img, x_ques, x_ques_len):
+        """The logits through fusion.fusion_head, or None where `_hip_fusion` says the stock lines apply (decided on the image
+        features, before the question encoder runs: nothing is computed twice)."""
+        if self.fusion_impl not in FUSION_IMPLS:
+            raise ValueError("fusion_impl must be one of %s, got %r" % (FUSION_IMPLS, self.fusion_impl))
+        enc = self.image_encoder
+        if not x_img.is_cuda or any(p.requires_grad for p in enc.vgg11_encoder.parameters()):
+            return None
+        f = enc.vgg11_encoder(x_img)
+        h = self.question_encoder.encode_hidden(x_ques, x_ques_len)
+        if not _hip_fusion(self, f, h):                               # (the stock tail on what is already there)
+            joint = enc.embedding_layer(F.normalize(f, dim=1, p=2)) * self.question_encoder.embedding_layer(h)
+            return self.fc_final(self.mlp(joint))
+        from .fusion import fusion_head
+        p = self.mlp[1].p if self.training else 0.0
+        if p > 0 and self.fusion_dropout_state is None:
+            raise RuntimeError("VQABaselineNet: fusion_impl = 'hip' with dropout needs fusion_dropout_state (a DropoutState on "
+                               "the model's device): train.set_fusion_head(model, 'hip', seed) sets both")
+        li, lq, lm, lf = enc.embedding_layer[0], self.question_encoder.embedding_layer[0], self.mlp[0], self.fc_final
+        return fusion_head(f, h, li.weight, li.bias, lq.weight, lq.bias, lm.weight, lm.bias, lf.weight, lf.bias,
+                           p=p, state=self.fusion_dropout_state, training=self.training)
 
 
 def set_feature_dropout(model: nn.Module, p: float, seed: int = 0) -> None:

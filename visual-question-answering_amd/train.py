@@ -28,7 +28,7 @@ import torch.utils.data
 
 from . import dist as vdist
 from .loss import CrossEntropyLoss, SoftTargetLoss
-from .dropout import rank_seed
+from .dropout import DropoutState, rank_seed
 from .modules import HierarchicalCoAttentionNet, VQABaselineNet, set_feature_dropout  # noqa: F401  (set_feature_dropout: re-exported)
 
 PATH_VGG_WEIGHTS = None      # the reference hard-codes a local .pth (utils.py:15); none ships here
@@ -268,6 +268,48 @@ def set_word_embedding(model: nn.Module, word_embedding: str) -> None:
     enc.word_impl = word_embedding
 
 
+FUSION_HEADS = ("stock", "hip")
+
+
+def check_fusion_head(model_name: str, fusion_head: str, vgg_train: bool = False, opt_lvl: int = 0) -> None:
+    """--fusion_head: "stock" (the default: the nn modules behind the two encoders) or "hip" (fusion.fusion_head).  "hip" exists
+    for --model baseline with a frozen image encoder in exact fp32: another model, --vgg_train true (the head has no gradient
+    for the image features) and --opt_lvl >= 1 are errors, by name, before any step."""
+    if fusion_head not in FUSION_HEADS:
+        raise ValueError("--fusion_head must be one of %s, got %r" % (FUSION_HEADS, fusion_head))
+    if fusion_head == "stock":
+        return
+    if str(model_name) != "baseline":
+        raise ValueError("--fusion_head hip applies to the baseline model (--model baseline), not to %s" % model_name)
+    if vgg_train:
+        raise ValueError("--fusion_head hip is not available with --vgg_train true: the HIP fusion head has no gradient for the "
+                         "image features (a trainable image encoder is out of scope)")
+    if opt_lvl > 0:
+        raise ValueError("--fusion_head hip is not available with --opt_lvl >= 1 (the reduced-precision mode): the head is "
+                         "built in exact fp32 only")
+
+
+def set_fusion_head(model: nn.Module, fusion_head: str, seed: int = 0) -> None:
+    """--fusion_head on a model: ``VQABaselineNet.fusion_impl`` and, for "hip" on a model whose parameters are on the GPU,
+    ``fusion_dropout_state`` = a fresh DropoutState(seed) there -- call it after moving the model.  On the CPU the attribute
+    is set and the forward takes the stock lines (as --question_gru hip does).  Module attributes, not part of the state_dict.
+    A model without a fusion head has nothing to switch: asking for "hip" there is an error, and so is a baseline model whose
+    image encoder is trainable."""
+    if fusion_head not in FUSION_HEADS:
+        raise ValueError("--fusion_head must be one of %s, got %r" % (FUSION_HEADS, fusion_head))
+    if not hasattr(model, "fusion_impl"):
+        if fusion_head != "stock":
+            raise ValueError("--fusion_head hip applies to the baseline model (--model baseline), not to %s"
+                             % type(model).__name__)
+        return
+    if fusion_head == "hip" and any(p.requires_grad for p in model.image_encoder.vgg11_encoder.parameters()):
+        raise ValueError("--fusion_head hip is not available with a trainable image encoder (--vgg_train true): the HIP fusion "
+                         "head has no gradient for the image features")
+    model.fusion_impl = fusion_head
+    dev = next(model.parameters()).device
+    model.fusion_dropout_state = DropoutState(seed, dev) if fusion_head == "hip" and dev.type == "cuda" else None
+
+
 def check_dropout(model_name: str, dropout: float, opt_lvl: int = 0) -> None:
     """--dropout P: feature dropout on the six attended features in front of the answer head (dropout.py), 0 = off (the
     default).  P must lie in [0, 1); P > 0 exists for the co-attention models only and not in the reduced-precision mode
@@ -418,6 +460,7 @@ def model_from_args(args):
     affinity = getattr(args, "affinity", "reference")
     check_affinity(args.model, affinity, getattr(args, "opt_lvl", 0))
     check_dropout(args.model, getattr(args, "dropout", 0.0), getattr(args, "opt_lvl", 0))
+    check_fusion_head(args.model, getattr(args, "fusion_head", "stock"), getattr(args, "vgg_train", False), getattr(args, "opt_lvl", 0))
     co_attention = getattr(args, "co_attention", "parallel")
     check_co_attention(args.model, co_attention, affinity, getattr(args, "opt_lvl", 0), getattr(args, "precision", "exact"))
     cfg = setup_model_configs(args, args.vocab_size)             # (as main.py:388)
@@ -427,6 +470,8 @@ def model_from_args(args):
     set_affinity(model, affinity)
     set_sentence_lstm(model, getattr(args, "sentence_lstm", "stock"))
     set_question_gru(model, getattr(args, "question_gru", "stock"))
+    if getattr(args, "fusion_head", "stock") != "stock":        # (the dropout state: Trainer, once the model is on its device)
+        model.fusion_impl = args.fusion_head
     set_word_embedding(model, getattr(args, "word_embedding", "stock"))
     return model, cfg
 
@@ -684,8 +729,12 @@ class Trainer:
                  bucket_mb: float = 16.0, encoder_runahead: bool = True, graph: bool = False, static_hot_path: bool = True,
                  precision: str = "exact", loss: str = "ce", optimizer: str = "torch", weight_decay: float = 0.0,
                  clip_grad_norm=None, sentence_lstm=None, word_embedding=None, feature_dropout: float = 0.0,
-                 dropout_seed: int = 0, encoder_eval=None, question_gru=None):
+                 dropout_seed: int = 0, encoder_eval=None, question_gru=None, fusion_head=None):
         check_loss(loss)
+        if fusion_head is not None:                              # "stock" | "hip" (set_fusion_head); None: leave the model's
+            if fusion_head == "hip" and opt_lvl > 0:
+                raise ValueError("Trainer(fusion_head='hip') is not available with opt_lvl >= 1 (the reduced-precision mode)")
+            set_fusion_head(model, fusion_head, rank_seed(dropout_seed, vdist.rank()))
         if question_gru is not None:                             # "stock" | "hip" (set_question_gru); None: leave the model's
             set_question_gru(model, question_gru)
         if encoder_eval is not None:                             # "stock" | "hip" (set_encoder_eval); None: leave the model's
@@ -1061,6 +1110,12 @@ def build_parser():
                          "(model.py:86-100; sorted lengths, read on the host); 'hip' = the length-aware HIP forward / backward on "
                          "the same parameters (exact fp32, no packing, no host read of the lengths, any order).  --model baseline "
                          "only; a checkpoint does not depend on it")
+    ap.add_argument("--fusion_head", default="stock", choices=list(FUSION_HEADS),
+                    help="the baseline model behind its two encoders (row norm, the two embeddings, the product, Linear -> "
+                         "Dropout -> Tanh, the classifier): 'stock' = the nn modules as the reference (model.py:10-38); 'hip' = "
+                         "four HIP launches forward and three backward on the same parameters (exact fp32; the dropout drawn "
+                         "inside the head from --dropout_seed + rank, nothing from torch's generators).  --model baseline only, "
+                         "not with --vgg_train true or --opt_lvl >= 1; a checkpoint does not depend on it")
     ap.add_argument("--encoder_eval", default="stock", choices=list(ENCODER_EVALS),
                     help="the frozen VGG's eval-mode groups (validation, predict.py, extract.py): stock (the default: every route as "
                          "it is) or hip (BatchNorm on running statistics + bias + ReLU + pool in one HIP launch per group, the first "
@@ -1147,7 +1202,8 @@ def main(argv=None):
     trainer = Trainer(model, args.learning_rate, device, args.opt_lvl, precision=args.precision, loss=args.loss,
                       optimizer=args.optimizer, weight_decay=args.weight_decay, clip_grad_norm=args.clip_grad_norm,
                       sentence_lstm=args.sentence_lstm, word_embedding=args.word_embedding, feature_dropout=args.dropout,
-                      dropout_seed=args.dropout_seed, encoder_eval=args.encoder_eval, question_gru=args.question_gru)
+                      dropout_seed=args.dropout_seed, encoder_eval=args.encoder_eval, question_gru=args.question_gru,
+                      fusion_head=args.fusion_head)
     n_ans = args.num_answers if args.loss != "ce" else 0
     size = (args.image_size, args.image_size) if args.image_size else cfg["image_size"]
     n_cls = args.num_cls + 1
