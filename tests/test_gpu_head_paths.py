@@ -6,7 +6,7 @@ Which branch a case reaches rests on these rules (head.hip; shapes are (B, d, ml
                   `saved` and `ws` (backward) are 16-byte aligned; else a lane per element.  The logits layer's backward
                   (vec_h; BwdAll::vec0 in the one-launch form) also needs an added g_logits to have K % 4 == 0 and be aligned
   straddle        d % 32 != 0: the chunk / dW tile that holds the concatenation [q_l + v_l | h] boundary sums three loads per
-                  element (stage_comp's third branch, dw_tile MODE 2)
+                  element (the third branch of stage2 on a CompR, dw_tile MODE 2)
   chunks          a contraction of length L (d, 2 d, mlp or K) is ceil(L / 32) chunks dealt round-robin to eight waves; dx_tile takes
                   two per trip and leaves its loop from two places; dw_tile does the same over ceil(B / 32) row blocks
   one-launch form forward grid = min(256, most tiles of a layer), backward grid 256; barrier groups by blockIdx.x & 7

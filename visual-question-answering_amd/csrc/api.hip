@@ -76,7 +76,7 @@ extern "C" int coattn_profile_end(float* us, char* names, int names_bytes, int m
 extern "C" const char* coattn_last_error(void) { return g_err; }
 
 // ---------------------------------------------------------------------------------------
-// buffer plans (in floats, every region aligned to 64 floats = 256 B: fused.h fal64)
+// buffer plans (in floats, every region aligned to 64 floats = 256 B: common.h al64)
 // ---------------------------------------------------------------------------------------
 static const int kMaxSplits = 32;
 
@@ -86,18 +86,18 @@ struct BwdPlan {
 static BwdPlan plan_bwd(int B, int N, int T, int d, int L) {
   BwdPlan p;
   size_t o = 0;
-  p.Hv = o;  o += fal64((size_t)B * N * d);
-  p.dPv = o; o += fal64((size_t)B * N * d);
-  p.dZq = o; o += fal64((size_t)B * T * d);
-  p.dPq = o; o += fal64((size_t)L * B * T * d);
-  p.dC = o;  o += fal64((size_t)L * B * T * N);
-  p.dav = o; o += fal64((size_t)L * B * N);
-  p.dsv = o; o += fal64((size_t)L * B * N);
-  p.daq = o; o += fal64((size_t)L * B * T);
-  p.dsq = o; o += fal64((size_t)L * B * T);
+  p.Hv = o;  o += al64((size_t)B * N * d);
+  p.dPv = o; o += al64((size_t)B * N * d);
+  p.dZq = o; o += al64((size_t)B * T * d);
+  p.dPq = o; o += al64((size_t)L * B * T * d);
+  p.dC = o;  o += al64((size_t)L * B * T * N);
+  p.dav = o; o += al64((size_t)L * B * N);
+  p.dsv = o; o += al64((size_t)L * B * N);
+  p.daq = o; o += al64((size_t)L * B * T);
+  p.dsq = o; o += al64((size_t)L * B * T);
   size_t part = (size_t)kMaxSplits * d * d;
   size_t cs = (size_t)260 * d;
-  p.part = o; o += fal64(part > cs ? part : cs);
+  p.part = o; o += al64(part > cs ? part : cs);
   p.total = o;
   return p;
 }
@@ -107,17 +107,17 @@ static BwdPlan plan_bwd(int B, int N, int T, int d, int L) {
 static bool bilinear(int flags) { return (flags & COATTN_FLAG_BILINEAR) != 0; }
 static size_t wchunks(int d) { return (size_t)((d + 31) / 32) * ((d + 15) / 16); }
 static size_t bil_floats(int B, int T, int d, int L, bool bil) {
-  return bil ? fal64((size_t)L * B * T * d) + fal64(wchunks(d)) : 0;
+  return bil ? al64((size_t)L * B * T * d) + al64(wchunks(d)) : 0;
 }
 static size_t saved_floats(int B, int N, int T, int d, int L, bool bil) {
   return saved_off(B, N, T, d, L).total + bil_floats(B, T, d, L, bil);
 }
 static size_t bil_bwd_floats(int B, int T, int d, int L) {
-  const size_t k = fal64((size_t)L * B * T * d);
-  return 3 * k + fal64((size_t)2 * d * d) + fal64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1) + fal64((size_t)L * B * d);
+  const size_t k = al64((size_t)L * B * T * d);
+  return 3 * k + al64((size_t)2 * d * d) + al64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1) + al64((size_t)L * B * d);
 }
 static size_t fwd_ws_floats(int B, int N, int T, int d, int L, bool bil = false) {
-  return saved_floats(B, N, T, d, L, bil) + fal64((size_t)B * N * d);
+  return saved_floats(B, N, T, d, L, bil) + al64((size_t)B * N * d);
 }
 static size_t bwd_ws_floats(int B, int N, int T, int d, int L, bool bil = false) {
   size_t bw = plan_bwd(B, N, T, d, L).total;
@@ -602,7 +602,7 @@ int bilinear_projection(const Ctx& c, char* wimg_b) {
   WGemm wk = wq;
   wk.Wf = wimg_b; wk.C = c.K; wk.bias_n = c.bb; wk.out_scale = 1.f; wk.rowbits = nullptr;
   float* status = sv + sp.status;
-  float* wb_words = c.K + fal64((size_t)c.L * c.B * c.T * c.d);
+  float* wb_words = c.K + al64((size_t)c.L * c.B * c.T * c.d);
   wk.status = f16 ? status : nullptr;
   const WSplit job{c.Wb, wimg_b, c.d, c.d, 0, c.d, wimg_pieces(wk), f16 ? wb_words : nullptr};
   CA_TRY(launch_wsplit(&job, 1, c.s));
@@ -908,10 +908,10 @@ static int backward_impl(Ctx c, int dtype, int flags) {
     c.Wb = (const float*)p->W_b; c.bb = (const float*)p->b_b;
     c.K = const_cast<float*>(c.saved) + saved_off(B, N, T, d, L).total;
     c.dK = c.ws + bwd_ws_floats(B, N, T, d, L, false);
-    const size_t k = fal64((size_t)L * B * T * d);
+    const size_t k = al64((size_t)L * B * T * d);
     bb.Wb = c.Wb; bb.K = c.K; bb.dK = c.dK; bb.dpk = c.dK + k; bb.wstack = c.dK + 3 * k;
-    bb.wimg = c.dK + 3 * k + fal64((size_t)2 * d * d);
-    bb.zeros = (float*)bb.wimg + fal64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1);
+    bb.wimg = c.dK + 3 * k + al64((size_t)2 * d * d);
+    bb.zeros = (float*)bb.wimg + al64(wsplit_bytes(d, 2 * d) / sizeof(float) + 1);
     bb.dWb = (float*)pg->dW_b; bb.dbb = (float*)pg->db_b;
     c.bil = &bb;
   }

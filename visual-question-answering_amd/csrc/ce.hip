@@ -223,8 +223,6 @@ __global__ __launch_bounds__(256) void vqa_score_kernel(const float* __restrict_
   }
 }
 
-inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
-
 }  // namespace
 
 // rows + mean for the answer head (head.hip): row_loss [B] scratch, dlogits [B][ldd] (ldd = 0: K) or NULL.

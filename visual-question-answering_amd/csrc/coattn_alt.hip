@@ -329,26 +329,26 @@ struct AltSaved {                      // offsets in floats (forward -> backward
 AltSaved alt_saved(int B, int N, int T, int d, int L) {
   AltSaved s;
   size_t o = 0;
-  s.x13 = o; o += fal64((size_t)L * B * T * 2 * d);   // [X1 | X3] = Q_l [W_x1; W_x3]^T + [b_x1; b_x3]
-  s.x2 = o;  o += fal64((size_t)B * N * d);           // X2 = V W_x2^T + b_x2
-  s.g2 = o;  o += fal64((size_t)L * B * d);           // s^ W_g2^T + b_g2
-  s.g3 = o;  o += fal64((size_t)L * B * d);           // v^ W_g3^T + b_g3
-  s.sh = o;  o += fal64((size_t)L * B * d);           // s^
-  s.vh = o;  o += fal64((size_t)L * B * d);           // v^
-  s.as = o;  o += fal64((size_t)L * B * T);
-  s.av = o;  o += fal64((size_t)L * B * N);
-  s.aq = o;  o += fal64((size_t)L * B * T);
+  s.x13 = o; o += al64((size_t)L * B * T * 2 * d);   // [X1 | X3] = Q_l [W_x1; W_x3]^T + [b_x1; b_x3]
+  s.x2 = o;  o += al64((size_t)B * N * d);           // X2 = V W_x2^T + b_x2
+  s.g2 = o;  o += al64((size_t)L * B * d);           // s^ W_g2^T + b_g2
+  s.g3 = o;  o += al64((size_t)L * B * d);           // v^ W_g3^T + b_g3
+  s.sh = o;  o += al64((size_t)L * B * d);           // s^
+  s.vh = o;  o += al64((size_t)L * B * d);           // v^
+  s.as = o;  o += al64((size_t)L * B * T);
+  s.av = o;  o += al64((size_t)L * B * N);
+  s.aq = o;  o += al64((size_t)L * B * T);
   s.total = o;
   return s;
 }
 // floats of the weight image a linear job writes for W [N][K] (AltLinear::img), the size of every img* slot of both plans
-size_t alt_img_floats(int N, int K) { return fal64(wsplit_bytes(N, K) / sizeof(float) + 1); }
+size_t alt_img_floats(int N, int K) { return al64(wsplit_bytes(N, K) / sizeof(float) + 1); }
 struct AltFwdWs { size_t wcat, bcat, img13, img2, imgg2, imgg3, total; };    // floats, after the saved-sized block
 AltFwdWs alt_fwd_ws(int d) {
   AltFwdWs w;
   size_t o = 0;
-  w.wcat = o; o += fal64((size_t)2 * d * d);
-  w.bcat = o; o += fal64((size_t)2 * d);
+  w.wcat = o; o += al64((size_t)2 * d * d);
+  w.bcat = o; o += al64((size_t)2 * d);
   w.img13 = o; o += alt_img_floats(2 * d, d);
   w.img2 = o; o += alt_img_floats(d, d);
   w.imgg2 = o; o += alt_img_floats(d, d);
@@ -361,18 +361,18 @@ constexpr int kAltMaxParts = 32;
 AltBwdWs alt_bwd_ws(int B, int N, int T, int d, int L) {
   AltBwdWs w;
   size_t o = 0;
-  w.dh13 = o; o += fal64((size_t)L * B * T * 2 * d);
-  w.dx2 = o;  o += fal64((size_t)B * N * d);
-  w.dg1 = o;  o += fal64((size_t)L * B * d);
-  w.dg2 = o;  o += fal64((size_t)L * B * d);
-  w.dg3 = o;  o += fal64((size_t)L * B * d);
-  w.dvt = o;  o += fal64((size_t)L * B * d);
-  w.dsh = o;  o += fal64((size_t)L * B * d);
-  w.wp1 = o;  o += fal64((size_t)L * B * (d + 1));
-  w.wp2 = o;  o += fal64((size_t)B * (d + 1));
-  w.wp3 = o;  o += fal64((size_t)L * B * (d + 1));
-  w.part = o; o += fal64((size_t)kAltMaxParts * 2 * d * d);   // split-K parts of the weight gradients
-  w.wcat = o; o += fal64((size_t)2 * d * d);
+  w.dh13 = o; o += al64((size_t)L * B * T * 2 * d);
+  w.dx2 = o;  o += al64((size_t)B * N * d);
+  w.dg1 = o;  o += al64((size_t)L * B * d);
+  w.dg2 = o;  o += al64((size_t)L * B * d);
+  w.dg3 = o;  o += al64((size_t)L * B * d);
+  w.dvt = o;  o += al64((size_t)L * B * d);
+  w.dsh = o;  o += al64((size_t)L * B * d);
+  w.wp1 = o;  o += al64((size_t)L * B * (d + 1));
+  w.wp2 = o;  o += al64((size_t)B * (d + 1));
+  w.wp3 = o;  o += al64((size_t)L * B * (d + 1));
+  w.part = o; o += al64((size_t)kAltMaxParts * 2 * d * d);   // split-K parts of the weight gradients
+  w.wcat = o; o += al64((size_t)2 * d * d);
   w.img13 = o; o += alt_img_floats(d, 2 * d);
   w.img2 = o; o += alt_img_floats(d, d);
   w.imgg2 = o; o += alt_img_floats(d, d);

@@ -76,6 +76,11 @@ static inline int dev_env_int(const char* name, int dflt) {
 #endif
 }
 
+// ---- buffer plans and alignment ----------------------------------------------------------------------------------------
+// buffer plans are in floats, every region aligned to 64 floats = 256 B
+inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
+inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
 // ---- per-kernel timing marks (coattn_profile_begin / _end, api.hip) ----------------------------------------------
 // Between coattn_profile_begin and coattn_profile_end on the calling thread, prof_mark(s, name) records a HIP event on `s`:
 // the time since the previous mark is attributed to `name` (the launches issued in between).  Off (one thread-local

@@ -10,27 +10,12 @@
 // before it takes a ticket from state word 4, and the workgroup that draws the last ticket -- after every other one has read
 // the step -- stores step + 1 and leaves the ticket at 0 (the pattern of ce.hip's mean).  No launch in front, no host state:
 // the call can be captured, and every replay draws a fresh mask.
-#include "common.h"
+#include "philox.h"   // the counter RNG and the mask's arithmetic: shared with fusion.hip
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr long long kMaxN = 2147483644ll;                    // 2^31 - 4: element indices fit 32 bits with the block's last word
-constexpr unsigned kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-
-struct u32x4 { unsigned x, y, z, w; };
-
-__device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(kM0, c.x), lo0 = kM0 * c.x;
-    const unsigned hi1 = __umulhi(kM1, c.z), lo1 = kM1 * c.z;
-    c = u32x4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += kW0;
-    k1 += kW1;
-  }
-  return c;
-}
 
 struct DropArgs {
   const float* x0; float* y0;
@@ -45,14 +30,11 @@ struct DropArgs {
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void dropout_kernel(DropArgs a) {
   const unsigned long long j = (unsigned long long)blockIdx.x * kThreads + threadIdx.x;
-  const unsigned k0 = a.state[0], k1 = a.state[1];
-  unsigned long long step = (unsigned long long)a.state[2] | ((unsigned long long)a.state[3] << 32);
-  step += (unsigned long long)(a.advance != 0);
+  const Drop d = drop_load(a.state, a.thr, a.scale, a.advance);
   const unsigned i0 = (unsigned)(j << 2);                    // (j < 2^29 for every thread with an element)
   if (j < (((unsigned long long)a.n + 3) >> 2)) {
-    const u32x4 r = philox4x32_10(u32x4{(unsigned)j, (unsigned)(j >> 32), (unsigned)step, (unsigned)(step >> 32)}, k0, k1);
-    const float m0 = r.x >= a.thr ? a.scale : 0.0f, m1 = r.y >= a.thr ? a.scale : 0.0f;
-    const float m2 = r.z >= a.thr ? a.scale : 0.0f, m3 = r.w >= a.thr ? a.scale : 0.0f;
+    const u32x4 r = drop_block(d, j);
+    const float m0 = drop_word(d, r.x), m1 = drop_word(d, r.y), m2 = drop_word(d, r.z), m3 = drop_word(d, r.w);
     const unsigned left = a.n - i0;                          // >= 1
     if (VEC && left >= 4) {
       const f32x4 m = {m0, m1, m2, m3};
@@ -79,8 +61,8 @@ __global__ __launch_bounds__(kThreads) void dropout_kernel(DropArgs a) {
   if (threadIdx.x == 0) {
     const unsigned ticket = atomicAdd(a.state + 4, 1u);
     if (ticket == gridDim.x - 1) {                           // every other workgroup has read the step as well
-      a.state[2] = (unsigned)step;
-      a.state[3] = (unsigned)(step >> 32);
+      a.state[2] = d.s0;
+      a.state[3] = d.s1;
       a.state[4] = 0u;
     }
   }
@@ -98,8 +80,9 @@ int launch(const char* what, const void* x0, void* y0, const void* x1, void* y1,
   DropArgs a = {};
   a.x0 = (const float*)x0; a.y0 = (float*)y0; a.x1 = (const float*)x1; a.y1 = (float*)y1;
   a.n = (unsigned)n;
-  a.thr = (unsigned)(unsigned long long)((double)p * 4294967296.0);    // floor: the product is exact and below 2^32
-  a.scale = (float)(1.0 / (1.0 - (double)p));
+  const DropHost dh = drop_host(p);
+  a.thr = dh.thr;
+  a.scale = dh.scale;
   a.state = (unsigned*)state;
   a.advance = advance ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;

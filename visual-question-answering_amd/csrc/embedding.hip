@@ -196,8 +196,6 @@ bool shape_ok(long long n, long long V, int E) {
   return n >= 1 && n <= kMaxN && V >= 1 && V <= kMaxV && E >= 4 && E <= kMaxE && E % 4 == 0;
 }
 
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 int check_call(const char* what, long long n, long long V, int E, long long padding_idx, int dtype, int flags) {
   CA_CHECK_ARG(dtype == COATTN_F32, "%s: unsupported dtype %d (only COATTN_F32)", what, dtype);
   CA_CHECK_ARG(n > 0 && V > 0 && E > 0, "%s: non-positive size n=%lld V=%lld E=%d", what, n, V, E);

@@ -65,8 +65,6 @@ bool shape_ok(long long S, long long B, int N, int d, int table_dtype) {
   return B * row_passes(row_vectors(N, d, table_dtype)) <= kMaxGrid;
 }
 
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int coattn_features_gather_supported(long long S, long long B, int N, int d, int table_dtype, int flags) {

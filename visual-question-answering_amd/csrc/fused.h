@@ -672,29 +672,26 @@ int launch_bwd_dq32(const DqArgs& a, int lm, hipStream_t s);
 int fused32_forward(const FwdArgs& a, hipStream_t s);
 int launch_attend_v_lm(const float* V, long v_sB, const float* av, float* v_out, int B, int N, int d, int L, hipStream_t s);
 
-// buffer plans are in floats, every region aligned to 64 floats = 256 B
-inline size_t fal64(size_t n) { return (n + 63) & ~(size_t)63; }
-
 struct SavedOff {
   size_t Pv, Pq, C, av, aq, Hq, wqT, status, rowcnt, rowbits, total;
 };
 inline SavedOff saved_off(int B, int N, int T, int d, int L) {   // the one layout of `saved`
   SavedOff p;
   size_t o = 0;
-  p.Pv = o; o += fal64((size_t)B * N * d);
-  p.Pq = o; o += fal64((size_t)L * B * T * d);
-  p.C = o;  o += fal64((size_t)L * B * T * N);
-  p.av = o; o += fal64((size_t)L * B * N);
-  p.aq = o; o += fal64((size_t)L * B * T);
-  p.Hq = o; o += fal64((size_t)L * B * T * d);
+  p.Pv = o; o += al64((size_t)B * N * d);
+  p.Pq = o; o += al64((size_t)L * B * T * d);
+  p.C = o;  o += al64((size_t)L * B * T * N);
+  p.av = o; o += al64((size_t)L * B * N);
+  p.aq = o; o += al64((size_t)L * B * T);
+  p.Hq = o; o += al64((size_t)L * B * T * d);
   // W_q split for the backward's dQ projection (gemm_w.hip, wsplit_bytes(d, d)): written by the forward's weight-split
   // launch, so that the backward has no split launch of its own
-  p.wqT = o; o += fal64((size_t)((d + 31) / 32) * ((d + 15) / 16) * 768);
-  p.status = o; o += fal64(status_floats(d, d, 2));   // range report of the tolerance mode (W_v, W_q images)
+  p.wqT = o; o += al64((size_t)((d + 31) / 32) * ((d + 15) / 16) * 768);
+  p.status = o; o += al64(status_floats(d, d, 2));   // range report of the tolerance mode (W_v, W_q images)
   // bitmap of the question rows that are not all zeros (RowFlagJob; one word per 32 rows and level) and, in front of it, eight
   // words of counters: the exact forward writes it, the backward's weight gradients contract over the live rows only
   p.rowcnt = o; o += 64;
-  p.rowbits = o; o += fal64(rowbits_words(B * T, L));
+  p.rowbits = o; o += al64(rowbits_words(B * T, L));
   p.total = o;
   return p;
 }
@@ -713,22 +710,22 @@ constexpr int kMaxParts = 40;   // split-K parts of the weight-gradient GEMMs (3
 inline FusedBwdOff fused_bwd_off(int B, int N, int T, int d, int L) {
   FusedBwdOff p;
   size_t o = 0;
-  p.dsv = o; o += fal64((size_t)L * B * N);
-  p.dsq = o; o += fal64((size_t)L * B * 32);
-  p.dPq = o; o += fal64((size_t)L * B * T * d);
-  p.dPv = o; o += fal64((size_t)L * B * N * d);
-  p.dA = o;  o += fal64((size_t)L * B * T * N);
-  p.dwv_part = o; o += fal64((size_t)L * B * d);
-  p.dbv_part = o; o += fal64((size_t)L * B * d);
-  p.dbq_part = o; o += fal64((size_t)L * B * d);
-  p.dwq_part = o; o += fal64((size_t)L * B * d);
-  p.dcs_part = o; o += fal64((size_t)L * B * 2);
+  p.dsv = o; o += al64((size_t)L * B * N);
+  p.dsq = o; o += al64((size_t)L * B * 32);
+  p.dPq = o; o += al64((size_t)L * B * T * d);
+  p.dPv = o; o += al64((size_t)L * B * N * d);
+  p.dA = o;  o += al64((size_t)L * B * T * N);
+  p.dwv_part = o; o += al64((size_t)L * B * d);
+  p.dbv_part = o; o += al64((size_t)L * B * d);
+  p.dbq_part = o; o += al64((size_t)L * B * d);
+  p.dwq_part = o; o += al64((size_t)L * B * d);
+  p.dcs_part = o; o += al64((size_t)L * B * 2);
   p.dynplan = o; o += 64;                          // TnDynPlan of a device-planned weight-gradient launch
-  p.rowbits = o; o += fal64(rowbits_words(B * T, L));   // the bitmap that plan counted (the forward's, or all rows live)
+  p.rowbits = o; o += al64(rowbits_words(B * T, L));   // the bitmap that plan counted (the forward's, or all rows live)
   // shared scratch: split-K partials of the weight-gradient GEMMs (<= kMaxParts x d x d) and, before them, the da_v
   // partials of bwd_dav_kernel ([B][d/64][3][N]), which outgrow the former at large B
   const size_t part_gemm = (size_t)kMaxParts * d * d, part_dav = (size_t)B * (d / 64) * 3 * N;
-  p.part = o; o += fal64(part_gemm > part_dav ? part_gemm : part_dav);
+  p.part = o; o += al64(part_gemm > part_dav ? part_gemm : part_dav);
   p.total = o;
   return p;
 }

@@ -8,154 +8,47 @@
 //   logits = m W_f^T + b_f                                    [B, K]
 //
 // The products are the attention head's kind (head.hip: B = 160 rows, contraction 1000 - 4096), so the tiles are its form and
-// the pieces below the tile bodies are shared with it (head_tile.h): 32 x 32 output tiles on v_mfma_f32_32x32x2_f32, one
+// the forward and dX tile loops are shared with it (head_tile.h): 32 x 32 output tiles on v_mfma_f32_32x32x2_f32, one
 // 512-thread workgroup each, the contraction split over the eight waves and summed through LDS in wave order; weight-gradient
-// tiles one wave each, in the launch of their layer's dX tiles; unconditional raw buffer loads.  The tile bodies here are this
-// file's own because its operand forms are: the product e_i e_q as the A operand of m and the X operand of dW_m (j is never
-// stored), the row scale inv_b on the dY operand of dW_i (db_i sums the unscaled values), and the epilogues -- row scale,
-// Philox dropout + tanh, the two tanh' products of one dX tile.  The dropout mask is v0.19.0's (dropout.hip) over element
-// i = b Mh + n, drawn in the epilogue of m and regenerated in the epilogue of dpre: nothing of it is stored.
-// Forward: 4 launches {e_q, row norms} {e_i} {m} {logits, step + 1}; backward: 3 launches {dW_f, db_f, dpre}
-// {dW_m, db_m, dp_i, dp_q} {dW_i, db_i, dW_q, db_q, dh}.  Deterministic: no atomics.
+// tiles one wave each, in the launch of their layer's dX tiles; unconditional raw buffer loads.  This file's own are its
+// operand forms: the product e_i e_q as the A operand of m (MatOp: a policy of the shared loops) and the X operand of dW_m (j
+// is never stored), the row scale inv_b on the dY operand of dW_i (db_i sums the unscaled values) -- the weight-gradient tile
+// is all operand form and stays here whole --, and the epilogues: row scale, Philox dropout + tanh, the two tanh' products of
+// one dX tile.  The dropout mask is v0.19.0's (philox.h, with dropout.hip) over element i = b Mh + n, drawn in the epilogue of
+// m and regenerated in the epilogue of dpre: nothing of it is stored.  Forward: 4 launches {e_q, row norms} {e_i} {m}
+// {logits, step + 1}; backward: 3 launches {dW_f, db_f, dpre} {dW_m, db_m, dp_i, dp_q} {dW_i, db_i, dW_q, db_q, dh}.
+// Deterministic: no atomics.
 #include "head_tile.h"
+#include "philox.h"
 #include <type_traits>
 #include "../../include/coattn_fusion.h"
 
 namespace {
-
-// ---- v0.19.0's mask: element i belongs to Philox block i >> 2, word i & 3; the block is a function of (block, step, seed) ----
-constexpr unsigned kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-struct Drop { unsigned k0, k1, s0, s1, thr; float scale; };
-__device__ __forceinline__ float drop_factor(const Drop& d, unsigned i) {
-  unsigned c0 = i >> 2, c1 = 0u, c2 = d.s0, c3 = d.s1, k0 = d.k0, k1 = d.k1;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(kM0, c0), lo0 = kM0 * c0;
-    const unsigned hi1 = __umulhi(kM1, c2), lo1 = kM1 * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += kW0;
-    k1 += kW1;
-  }
-  const unsigned w = i & 3u, r = w == 0u ? c0 : (w == 1u ? c1 : (w == 2u ? c2 : c3));
-  return r >= d.thr ? d.scale : 0.0f;
-}
-// the mask's parameters from the state words (seed lo, hi, step lo, hi); `next`: the mask this launch draws is step + 1
-__device__ __forceinline__ Drop drop_load(const unsigned* state, unsigned thr, float scale, int next) {
-  unsigned long long step = (unsigned long long)state[2] | ((unsigned long long)state[3] << 32);
-  step += (unsigned long long)(next != 0);
-  return Drop{state[0], state[1], (unsigned)step, (unsigned)(step >> 32), thr, scale};
-}
-
-// cross-wave sum of the eight partial 32 x 32 accumulators in wave order; epi(m, n, sum) for every element inside the matrix
-template <class Epi>
-__device__ __forceinline__ void reduce_epi(const f32x16& acc, float* red, int m0, int n0, int M, int N, int w, Epi epi) {
-  const int lane = threadIdx.x & 63;
-  __syncthreads();                                   // every wave is done with its staging images
-#pragma unroll
-  for (int g = 0; g < 16; ++g) red[(w * 16 + g) * 64 + lane] = acc[g];
-  __syncthreads();
-#pragma unroll
-  for (int gg = 0; gg < 2; ++gg) {
-    const int g = w + 8 * gg;
-    float s = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < kWaves; ++ww) s += red[(ww * 16 + g) * 64 + lane];
-    const int m = m0 + crow32(g, lane >> 5), n = n0 + (lane & 31);
-    if (m < M && n < N) epi(m, n, s);
-  }
-}
 
 // the tight extent of a [rows][ld] operand whose rows hold `cols` floats: rows >= `rows` start past it and read 0
 __device__ __forceinline__ rsrc_t mat_rsrc(const float* p, int rows, int ld, int cols) {
   return mk_rsrc(p, ((long)(rows - 1) * ld + cols) * 4);
 }
 
-// ---- forward tile: epi(m, n, sum_k A(m, k) W[n][k]);  A(m, k) = a0[m][k] (PROD: * a1[m][k]), all rows 16-byte aligned ----
-template <bool PROD, class Epi>
-__device__ __forceinline__ void fwd_tile(const float* a0, const float* a1, int lda, const float* __restrict__ W, int M, int N, int K,
-                                         int m0, int n0, float* smem, Epi epi) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, lh = lane >> 5;
-  float* imgA = smem + w * (2 * 32 * LDR);
-  float* imgB = imgA + 32 * LDR;
-  f32x16 acc = {};
-  const int nchunks = (K + KC - 1) / KC;
-  const rsrc_t ar = mat_rsrc(a0, M, lda, K), ar1 = mat_rsrc(PROD ? a1 : a0, M, lda, K), wr = mat_rsrc(W, N, K, K);
-  Stage sa, sa1, sb;
-  auto stage = [&](int c) {
-    stage_lin<true>(sa, ar, lda, K, lane, m0, c * KC);
-    if constexpr (PROD) stage_lin<true>(sa1, ar1, lda, K, lane, m0, c * KC);
-    stage_lin<true>(sb, wr, K, K, lane, n0, c * KC);
-  };
-  int c = w;                                         // chunks interleaved over the waves: neighbouring lines together
-  if (c < nchunks) stage(c);
-  for (; c < nchunks; c += kWaves) {
-    if constexpr (PROD) {                            // both register sets are kept until here: the product waits for no load early
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sa.v[i] = sa.v[i] * sa1.v[i];
-    }
-    stage_store<true>(sa, imgA, lane);
-    stage_store<true>(sb, imgB, lane);
-    if (c + kWaves < nchunks) stage(c + kWaves);     // next chunk's lines in flight behind this chunk's MFMAs
-    __builtin_amdgcn_wave_barrier();
-    mfma_chunk<false>(acc, imgA, imgB, li, lh);
-    __builtin_amdgcn_wave_barrier();
+// the staged operand of head_tile.h's loops: X(m, k) = x0[m][k] (PROD: * x1[m][k]) over [M][K], rows ld floats apart;
+// VEC: the rows are 16-byte aligned (g_logits with K % 4 != 0 is not)
+template <bool VEC, bool PROD>
+struct MatOp {
+  rsrc_t r0, r1; int ld, K; Stage s0, s1;
+  __device__ __forceinline__ MatOp(const float* x0, const float* x1, int M, int ld_, int K_)
+      : r0(mat_rsrc(x0, M, ld_, K_)), r1(mat_rsrc(PROD ? x1 : x0, M, ld_, K_)), ld(ld_), K(K_) {}
+  __device__ __forceinline__ void load(int lane, int m0, int k0) {
+    stage_lin<VEC>(s0, r0, ld, K, lane, m0, k0);
+    if constexpr (PROD) stage_lin<VEC>(s1, r1, ld, K, lane, m0, k0);
   }
-  reduce_epi(acc, smem, m0, n0, M, N, w, epi);
-}
-
-// ---- dX tile: epi(m, k', sum_n Y[m][n] W[n][k']);  VEC: the rows of Y are 16-byte aligned (g_logits with K % 4 != 0 is not) ----
-template <bool VEC, class Epi>
-__device__ __forceinline__ void dx_tile(const float* Y, int ldy, const float* __restrict__ W, int ldw, int M, int Nc /* contraction */,
-                                        int Kout, int m0, int k0, float* smem, Epi epi) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, lh = lane >> 5;
-  float* imgA = smem + w * (2 * 32 * LDR);
-  f32x16 acc = {};
-  const rsrc_t yr = mat_rsrc(Y, M, ldy, Nc), wr = mat_rsrc(W, Nc, ldw, Kout);
-  const int nchunks = (Nc + KC - 1) / KC;
-  // a lane per output column: 128-byte row segments of W; the lane half takes 4 consecutive contraction rows
-  const int bvoff = k0 + li < Kout ? (4 * lh * ldw + k0 + li) * 4 : kOut;
-  Stage sa;
-  float fb0[16], fb1[16];
-  auto loadB = [&](float (&fb)[16], int nc) {               // contraction rows nc + 8 u + 4 lh + e; rows >= Nc read 0
+  __device__ __forceinline__ void store(float* img, int lane) {
+    if constexpr (PROD) {                            // both register sets are kept until here: no load is waited for early
 #pragma unroll
-    for (int j = 0; j < 16; ++j) fb[j] = bl1(wr, bvoff, (nc + 8 * (j >> 2) + (j & 3)) * ldw * 4);
-  };
-  auto compute = [&](const float (&fb)[16]) {
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int u = 0; u < KC / 8; ++u) {
-      const f32x4 fa = *reinterpret_cast<const f32x4*>(imgA + li * LDR + 8 * u + 4 * lh);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = mfma2(fa[e], fb[4 * u + e], acc);
+      for (int i = 0; i < 4; ++i) s0.v[i] = s0.v[i] * s1.v[i];
     }
-    __builtin_amdgcn_wave_barrier();
-  };
-  int c = w;
-  if (c < nchunks) {
-    stage_lin<VEC>(sa, yr, ldy, Nc, lane, m0, c * KC);
-    loadB(fb0, c * KC);
+    stage_store<VEC>(s0, img, lane);
   }
-  while (c < nchunks) {                                      // two chunks per trip: the register sets alternate
-    stage_store<VEC>(sa, imgA, lane);
-    int cn = c + kWaves;
-    if (cn < nchunks) {
-      stage_lin<VEC>(sa, yr, ldy, Nc, lane, m0, cn * KC);
-      loadB(fb1, cn * KC);
-    }
-    compute(fb0);
-    c = cn;
-    if (c >= nchunks) break;
-    stage_store<VEC>(sa, imgA, lane);
-    cn = c + kWaves;
-    if (cn < nchunks) {
-      stage_lin<VEC>(sa, yr, ldy, Nc, lane, m0, cn * KC);
-      loadB(fb0, cn * KC);
-    }
-    compute(fb1);
-    c = cn;
-  }
-  reduce_epi(acc, smem, m0, k0, M, Kout, w, epi);
-}
+};
 
 // ---- dW tile (one WAVE): dW[n][k'] (+)= sum_m Y[m][n] (SCALE: * inv[m]) X(m, k');  db[n] (+)= sum_m Y[m][n], unscaled, from
 // the tiles with k0 = 0.  X(m, k) = x0[m][k] (PROD: * x1[m][k]).  Rows in increasing m, two per MFMA.
@@ -260,28 +153,29 @@ __global__ __launch_bounds__(kThreads) void fusion_fwd_kernel(const FusFwd a) {
   }
   const int ntn = (a.N + 31) / 32;
   const int m0 = 32 * ((int)blockIdx.x / ntn), n0 = 32 * ((int)blockIdx.x % ntn);
+  auto tile = [&](auto epi) {                                // (STAGE 2: the product e_i e_q is the A operand of m)
+    fwd_tile<true, false>(MatOp<true, STAGE == 2>(a.a0, a.a1, a.M, a.lda, a.K), mat_rsrc(a.W, a.N, a.K, a.K), a.K, a.M, a.N,
+                          a.K, m0, n0, smem, epi);
+  };
   if constexpr (STAGE == 0) {
-    fwd_tile<false>(a.a0, nullptr, a.lda, a.W, a.M, a.N, a.K, m0, n0, smem,
-                    [&](int m, int n, float s) { a.C[(long)m * a.N + n] = tanhf(s + a.bias[n]); });
+    tile([&](int m, int n, float s) { a.C[(long)m * a.N + n] = tanhf(s + a.bias[n]); });
   } else if constexpr (STAGE == 1) {
-    fwd_tile<false>(a.a0, nullptr, a.lda, a.W, a.M, a.N, a.K, m0, n0, smem,
-                    [&](int m, int n, float s) { a.C[(long)m * a.N + n] = tanhf(a.inv[m] * s + a.bias[n]); });
+    tile([&](int m, int n, float s) { a.C[(long)m * a.N + n] = tanhf(a.inv[m] * s + a.bias[n]); });
   } else if constexpr (STAGE == 2) {
     Drop d = {};
     if (a.drop) d = drop_load(a.state, a.thr, a.scale, 1);
-    fwd_tile<true>(a.a0, a.a1, a.lda, a.W, a.M, a.N, a.K, m0, n0, smem, [&](int m, int n, float s) {
+    tile([&](int m, int n, float s) {
       float pre = s + a.bias[n];
       if (a.drop) pre *= drop_factor(d, (unsigned)m * (unsigned)a.N + (unsigned)n);
       a.C[(long)m * a.N + n] = tanhf(pre);
     });
   } else {
     if (a.advance && blockIdx.x == 0 && threadIdx.x == 0) {  // the mask of stage 2 is drawn: its launch is complete
-      const unsigned long long step = ((unsigned long long)a.state[2] | ((unsigned long long)a.state[3] << 32)) + 1ull;
+      const unsigned long long step = drop_step(a.state, 1);
       a.state[2] = (unsigned)step;
       a.state[3] = (unsigned)(step >> 32);
     }
-    fwd_tile<false>(a.a0, nullptr, a.lda, a.W, a.M, a.N, a.K, m0, n0, smem,
-                    [&](int m, int n, float s) { a.C[(long)m * a.N + n] = s + a.bias[n]; });
+    tile([&](int m, int n, float s) { a.C[(long)m * a.N + n] = s + a.bias[n]; });
   }
 }
 
@@ -303,25 +197,28 @@ __global__ __launch_bounds__(kThreads) void fusion_bwd_kernel(const FusBwd a) {
   if (bid < a.nx) {
     const int ntk = (a.Kout + 31) / 32;
     const int m0 = 32 * (bid / ntk), k0 = 32 * (bid % ntk);
+    auto tile = [&](auto epi) {
+      dx_tile<false>(MatOp<VEC, false>(a.Y, nullptr, a.M, a.ldy, a.Nc), mat_rsrc(a.W, a.Nc, a.ldw, a.Kout), a.ldw, a.M, a.Nc,
+                     a.Kout, m0, k0, smem, epi);
+    };
     if constexpr (STAGE == 0) {
       Drop d = {};
       if (a.drop) d = drop_load(a.state, a.thr, a.scale, 0);
-      dx_tile<VEC>(a.Y, a.ldy, a.W, a.ldw, a.M, a.Nc, a.Kout, m0, k0, smem, [&](int m, int n, float s) {
+      tile([&](int m, int n, float s) {
         const float mv = a.act0[(long)m * a.Kout + n];
         float v = s * (1.f - mv * mv);
         if (a.drop) v *= drop_factor(d, (unsigned)m * (unsigned)a.Kout + (unsigned)n);
         a.out0[(long)m * a.Kout + n] = v;
       });
     } else if constexpr (STAGE == 1) {
-      dx_tile<VEC>(a.Y, a.ldy, a.W, a.ldw, a.M, a.Nc, a.Kout, m0, k0, smem, [&](int m, int n, float s) {
+      tile([&](int m, int n, float s) {
         const long i = (long)m * a.Kout + n;
         const float ei = a.act0[i], eq = a.act1[i];
         a.out0[i] = s * eq * (1.f - ei * ei);
         a.out1[i] = s * ei * (1.f - eq * eq);
       });
     } else {
-      dx_tile<VEC>(a.Y, a.ldy, a.W, a.ldw, a.M, a.Nc, a.Kout, m0, k0, smem,
-                   [&](int m, int n, float s) { a.out0[(long)m * a.Kout + n] = s; });
+      tile([&](int m, int n, float s) { a.out0[(long)m * a.Kout + n] = s; });
     }
     return;
   }
@@ -344,7 +241,6 @@ __global__ __launch_bounds__(kThreads) void fusion_bwd_kernel(const FusBwd a) {
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
 struct Saved { size_t inv, ei, eq, m, total; };
 inline Saved saved_plan(int B, int J, int Mh) {
   Saved s;
@@ -367,7 +263,6 @@ inline BwdWs bwd_plan(int B, int J, int Mh) {
   return s;
 }
 
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 bool width_ok(int n) { return n >= 4 && n <= 8192 && (n % 4) == 0; }
 // every operand is addressed through a buffer descriptor with 32-bit byte offsets below 1 GB (2^28 floats)
 bool shape_ok(long B, long Di, long H, long J, long Mh, long K) {
@@ -403,11 +298,6 @@ int check_operands(const char* what, const void* f, int64_t ld_f, const void* h,
                al16(p->W_f) && al16(p->b_f) && (((uintptr_t)state) & 3) == 0,
                "%s: f, h and every parameter must be 16-byte aligned (the state: 4)", what);
   return 0;
-}
-
-struct DropHost { unsigned thr; float scale; };
-DropHost drop_host(float p) {
-  return DropHost{(unsigned)(unsigned long long)((double)p * 4294967296.0), (float)(1.0 / (1.0 - (double)p))};
 }
 
 template <int STAGE>

@@ -148,9 +148,9 @@ struct Saved { size_t gates, hn, hprev, total; };
 Saved saved_plan(int B, int T, int H) {
   Saved p;
   size_t o = 0;
-  p.gates = o; o += fal64((size_t)B * T * 3 * H);
-  p.hn = o;    o += fal64((size_t)B * T * H);
-  p.hprev = o; o += fal64((size_t)B * T * H);
+  p.gates = o; o += al64((size_t)B * T * 3 * H);
+  p.hn = o;    o += al64((size_t)B * T * H);
+  p.hprev = o; o += al64((size_t)B * T * H);
   p.total = o;
   return p;
 }
@@ -159,7 +159,7 @@ struct FwdWs { size_t gx, wimg, bytes; };            // gx in floats; wimg, byte
 FwdWs fwd_plan(int B, int T, int E, int H) {
   FwdWs p;
   p.gx = 0;
-  p.wimg = fal64((size_t)B * T * 3 * H) * sizeof(float);
+  p.wimg = al64((size_t)B * T * 3 * H) * sizeof(float);
   p.bytes = p.wimg + wsplit_bytes(3 * H, E);
   return p;
 }
@@ -168,15 +168,15 @@ struct BwdWs { size_t dgx, dgh, dhc, part, wimg, total; };    // floats
 BwdWs bwd_plan(int B, int T, int E, int H) {
   BwdWs p;
   size_t o = 0;
-  p.dgx = o; o += fal64((size_t)B * T * 3 * H);
-  p.dgh = o; o += fal64((size_t)B * T * 3 * H);
-  p.dhc = o; o += fal64((size_t)B * H);
+  p.dgx = o; o += al64((size_t)B * T * 3 * H);
+  p.dgh = o; o += al64((size_t)B * T * 3 * H);
+  p.dhc = o; o += al64((size_t)B * H);
   const size_t pi = (size_t)wgrad_parts(B * T, 3 * H, E) * 3 * H * E, ph = (size_t)wgrad_parts(B * T, 3 * H, H) * 3 * H * H;
   const size_t pb = (size_t)256 * 3 * H;            // grad_colsum: at most 256 chunks of rows
   size_t part = pi > ph ? pi : ph;
   part = part > pb ? part : pb;
-  p.part = o; o += fal64(part);
-  p.wimg = o; o += fal64(wsplit_bytes(E, 3 * H) / sizeof(float) + 1);
+  p.part = o; o += al64(part);
+  p.wimg = o; o += al64(wsplit_bytes(E, 3 * H) / sizeof(float) + 1);
   p.total = o;
   return p;
 }

@@ -28,7 +28,7 @@
 // are fetched as whole 128-byte lines (8 rows per wave instruction), staged in a per-wave LDS image with padded rows and
 // read back as fragments (ds_read_b128, conflict-free); operands contiguous along the tile index (the weight in dX, both
 // operands of dW) go straight to registers (a lane per column: 128-byte row segments).  Deterministic: no atomics.
-#include "head_tile.h"   // the buffer loads, the staging of a block and the MFMAs on it: shared with fusion.hip
+#include "head_tile.h"   // the buffer loads, the staging, the MFMAs on a block, the forward / dX tile loops: with fusion.hip
 #include <type_traits>
 
 namespace {
@@ -66,8 +66,8 @@ struct Stage2 {
   Stage a, b; bool two; float sc;   // value = a * sc + (two ? b : 0)
 };
 // COH (the one-launch forms): the hidden part `h` was stored by another workgroup of this launch -- agent-coherent loads
-template <bool VEC, bool COH = false>
-__device__ __forceinline__ void stage_comp(Stage2& s, const CompR& c, int lane, int m0, int k0) {
+template <bool VEC, bool COH>
+__device__ __forceinline__ void stage2(Stage2& s, const CompR& c, int lane, int m0, int k0) {
   constexpr int HA = COH ? kSC1 : 0;
   s.sc = 1.f;
   s.two = false;
@@ -88,21 +88,26 @@ __device__ __forceinline__ void stage_comp(Stage2& s, const CompR& c, int lane, 
     }
   }
 }
-template <bool VEC, bool COH = false>
-__device__ __forceinline__ void stage_dy(Stage2& s, const DYR& y, int lane, int m0, int n0) {
+template <bool VEC, bool COH>
+__device__ __forceinline__ void stage2(Stage2& s, const DYR& y, int lane, int m0, int n0) {
   s.sc = y.sc;
   s.two = y.has_add;
   stage_lin<VEC, COH ? kSC1 : 0>(s.a, y.p, y.ld, y.N, lane, m0, n0);
   if (y.has_add) stage_lin<VEC>(s.b, y.add, y.ld_add, y.N, lane, m0, n0);
 }
-// (stage_store of a plain Stage: head_tile.h)
-template <bool VEC>
-__device__ __forceinline__ void stage_store(const Stage2& s, float* img, int lane) {
-  Stage t;
+// either of the two (R: CompR, DYR) as the staged operand of head_tile.h's loops
+template <bool VEC, bool COH, class R>
+struct Op2 {
+  R r; Stage2 s;
+  __device__ __forceinline__ explicit Op2(const R& r_) : r(r_) {}
+  __device__ __forceinline__ void load(int lane, int m0, int k0) { stage2<VEC, COH>(s, r, lane, m0, k0); }
+  __device__ __forceinline__ void store(float* img, int lane) const {
+    Stage t;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) t.v[i] = s.two ? s.a.v[i] * s.sc + s.b.v[i] : s.a.v[i] * s.sc;
-  stage_store<VEC>(t, img, lane);
-}
+    for (int i = 0; i < 4; ++i) t.v[i] = s.two ? s.a.v[i] * s.sc + s.b.v[i] : s.a.v[i] * s.sc;
+    stage_store<VEC>(t, img, lane);
+  }
+};
 struct TileOut {
   float* C; int ldc;              // plain output rows
   const float* bias;              // [n] or NULL
@@ -111,131 +116,41 @@ struct TileOut {
   int hsplit; const float* hid; int ldhid; float* Ch; int ldch;
   float* C2;                      // second copy of the plain columns (dq beside dv), may be NULL
 };
-
-// cross-wave sum of the eight partial 32 x 32 accumulators in a fixed order + epilogue
+// the epilogue of a forward or dX tile, on the cross-wave sum of element (m, n)
 // COH (the one-launch forms): the outputs another workgroup of the launch reads next go out as agent-scope stores
-template <bool COH = false>
-__device__ __forceinline__ void reduce_store(const f32x16& acc, float* red, const TileOut& o, int m0, int n0, int M, int N, int w) {
-  const int lane = threadIdx.x & 63;
-  __syncthreads();                                   // every wave is done with its staging images
-#pragma unroll
-  for (int g = 0; g < 16; ++g) red[(w * 16 + g) * 64 + lane] = acc[g];
-  __syncthreads();
-#pragma unroll
-  for (int gg = 0; gg < 2; ++gg) {
-    const int g = w + 8 * gg;
-    float s = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < kWaves; ++ww) s += red[(ww * 16 + g) * 64 + lane];
-    const int m = m0 + crow32(g, lane >> 5), n = n0 + (lane & 31);
-    if (m < M && n < N) {
-      if (o.bias) s += o.bias[n];
-      if (o.act) s = tanhf(s);
-      auto put = [](float* p, float v) {
-        if constexpr (COH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *p = v;
-      };
-      if (n >= o.hsplit) {
-        const float hv = o.hid[(long)m * o.ldhid + (n - o.hsplit)];
-        put(&o.Ch[(long)m * o.ldch + (n - o.hsplit)], s * (1.f - hv * hv));
-      } else {
-        if (o.C) put(&o.C[(long)m * o.ldc + n], s);
-        if (o.C2) o.C2[(long)m * o.ldc + n] = s;
-      }
-    }
-  }
-}
-
-// ---- forward tile: C[m][n] = act(sum_k X(m, k) W[n][k] + bias[n]) --------------------------------------------------
-template <bool VEC, bool BF, bool COH = false>
-__device__ __forceinline__ void fwd_tile(const Comp& A, const float* __restrict__ W, int ldw, const TileOut& o, int M, int N, int K,
-                                         int m0, int n0, float* smem) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, lh = lane >> 5;
-  float* imgA = smem + w * (2 * 32 * LDR);
-  float* imgB = imgA + 32 * LDR;
-  f32x16 acc = {};
-  const int nchunks = (K + KC - 1) / KC;
-  const CompR ar = comp_rsrc(A, M, K);
-  const rsrc_t wr = mk_rsrc(W, (long)N * ldw * 4);
-  Stage2 sa;
-  Stage sb;
-  int c = w;                                         // chunks interleaved over the waves: neighbouring lines together
-  if (c < nchunks) {
-    stage_comp<VEC, COH>(sa, ar, lane, m0, c * KC);
-    stage_lin<VEC>(sb, wr, ldw, K, lane, n0, c * KC);
-  }
-  for (; c < nchunks; c += kWaves) {
-    stage_store<VEC>(sa, imgA, lane);
-    stage_store<VEC>(sb, imgB, lane);
-    if (c + kWaves < nchunks) {                      // next chunk's lines in flight behind this chunk's MFMAs
-      stage_comp<VEC, COH>(sa, ar, lane, m0, (c + kWaves) * KC);
-      stage_lin<VEC>(sb, wr, ldw, K, lane, n0, (c + kWaves) * KC);
-    }
-    __builtin_amdgcn_wave_barrier();
-    mfma_chunk<BF>(acc, imgA, imgB, li, lh);
-    __builtin_amdgcn_wave_barrier();
-  }
-  reduce_store<COH>(acc, smem, o, m0, n0, M, N, w);
-}
-
-// ---- dX tile: dX[m][k'] = sum_n dY(m, n) W[n][k'] -------------------------------------------------------------------
-template <bool VEC, bool BF, bool COH = false>
-__device__ __forceinline__ void dx_tile(const DY& Y, const float* __restrict__ W, int ldw, const TileOut& o, int M, int Nc /* contraction */,
-                                        int Kout, int m0, int k0, float* smem) {
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, lh = lane >> 5;
-  float* imgA = smem + w * (2 * 32 * LDR);
-  f32x16 acc = {};
-  const DYR yr = dy_rsrc(Y, M, Nc);
-  const rsrc_t wr = mk_rsrc(W, (long)Nc * ldw * 4);
-  const int nchunks = (Nc + KC - 1) / KC;
-  // a lane per output column: 128-byte row segments of W; the lane half takes 4 (BF: 8) consecutive contraction rows
-  const int bvoff = k0 + li < Kout ? ((BF ? 8 : 4) * lh * ldw + k0 + li) * 4 : kOut;
-  Stage2 sa;
-  float fb0[16], fb1[16];
-  auto loadB = [&](float (&fb)[16], int nc) {               // contraction rows nc + 8 u + 4 lh + e (BF: nc + 16 ks + 8 lh + i); rows >= Nc read 0
-#pragma unroll
-    for (int j = 0; j < 16; ++j) fb[j] = bl1(wr, bvoff, (nc + (BF ? 16 * (j >> 3) + (j & 7) : 8 * (j >> 2) + (j & 3))) * ldw * 4);
-  };
-  auto compute = [&](const float (&fb)[16]) {
-    __builtin_amdgcn_wave_barrier();
-    if constexpr (BF) {
-#pragma unroll
-      for (int ks = 0; ks < KC / 16; ++ks) acc = mfma16(frag16(imgA, li, lh, ks), pack8(&fb[8 * ks]), acc);
+template <bool COH>
+struct TileEpi {
+  const TileOut o;                // (a copy, as the operand objects are: head_tile.h says why)
+  __device__ __forceinline__ void operator()(int m, int n, float s) const {
+    if (o.bias) s += o.bias[n];
+    if (o.act) s = tanhf(s);
+    auto put = [](float* p, float v) {
+      if constexpr (COH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else *p = v;
+    };
+    if (n >= o.hsplit) {
+      const float hv = o.hid[(long)m * o.ldhid + (n - o.hsplit)];
+      put(&o.Ch[(long)m * o.ldch + (n - o.hsplit)], s * (1.f - hv * hv));
     } else {
-#pragma unroll
-      for (int u = 0; u < KC / 8; ++u) {
-        const f32x4 fa = *reinterpret_cast<const f32x4*>(imgA + li * LDR + 8 * u + 4 * lh);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = mfma2(fa[e], fb[4 * u + e], acc);
-      }
+      if (o.C) put(&o.C[(long)m * o.ldc + n], s);
+      if (o.C2) o.C2[(long)m * o.ldc + n] = s;
     }
-    __builtin_amdgcn_wave_barrier();
-  };
-  int c = w;
-  if (c < nchunks) {
-    stage_dy<VEC, COH>(sa, yr, lane, m0, c * KC);
-    loadB(fb0, c * KC);
   }
-  while (c < nchunks) {                                      // two chunks per trip: the register sets alternate
-    stage_store<VEC>(sa, imgA, lane);
-    int cn = c + kWaves;
-    if (cn < nchunks) {
-      stage_dy<VEC, COH>(sa, yr, lane, m0, cn * KC);
-      loadB(fb1, cn * KC);
-    }
-    compute(fb0);
-    c = cn;
-    if (c >= nchunks) break;
-    stage_store<VEC>(sa, imgA, lane);
-    cn = c + kWaves;
-    if (cn < nchunks) {
-      stage_dy<VEC, COH>(sa, yr, lane, m0, cn * KC);
-      loadB(fb0, cn * KC);
-    }
-    compute(fb1);
-    c = cn;
-  }
-  reduce_store<COH>(acc, smem, o, m0, k0, M, Kout, w);
+};
+
+// ---- forward tile: C[m][n] = act(sum_k X(m, k) W[n][k] + bias[n]);  dX tile: dX[m][k'] = sum_n dY(m, n) W[n][k'] ----
+// (the loops: head_tile.h; every descriptor covers rows x ld floats)
+template <bool VEC, bool BF, bool COH = false>
+__device__ __forceinline__ void head_fwd_tile(const Comp& A, const float* __restrict__ W, int ldw, const TileOut& o, int M, int N,
+                                              int K, int m0, int n0, float* smem) {
+  fwd_tile<VEC, BF>(Op2<VEC, COH, CompR>(comp_rsrc(A, M, K)), mk_rsrc(W, (long)N * ldw * 4), ldw, M, N, K, m0, n0, smem,
+                    TileEpi<COH>{o});
+}
+template <bool VEC, bool BF, bool COH = false>
+__device__ __forceinline__ void head_dx_tile(const DY& Y, const float* __restrict__ W, int ldw, const TileOut& o, int M,
+                                             int Nc /* contraction */, int Kout, int m0, int k0, float* smem) {
+  dx_tile<BF>(Op2<VEC, COH, DYR>(dy_rsrc(Y, M, Nc)), mk_rsrc(W, (long)Nc * ldw * 4), ldw, M, Nc, Kout, m0, k0, smem,
+              TileEpi<COH>{o});
 }
 
 // ---- dW tile (one WAVE): dW[n][k'] (+)= sum_m dY(m, n) X(m, k');  db[n] (+)= sum_m dY(m, n) for the tiles with k0 = 0 ----
@@ -328,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void head_fwd_kernel(const FwdLayer L) {
   TileOut o = {};
   o.C = L.C; o.ldc = L.ldc; o.bias = L.bias; o.act = L.act; o.hsplit = 0x7fffffff;
   if (L.zero2 && blockIdx.x == 0 && threadIdx.x == 0) { L.zero2[0] = 0; L.zero2[1] = 0; }
-  fwd_tile<VEC, BF>(L.A, L.W, L.K, o, L.M, L.N, L.K, 32 * mt, 32 * nt, smem);
+  head_fwd_tile<VEC, BF>(L.A, L.W, L.K, o, L.M, L.N, L.K, 32 * mt, 32 * nt, smem);
 }
 
 struct BwdLayer {
@@ -347,7 +262,7 @@ __global__ __launch_bounds__(kThreads) void head_bwd_kernel(const BwdLayer L) {
   if ((int)blockIdx.x < L.nx) {
     const int ntk = (L.Kin + 31) / 32;
     const int mt = blockIdx.x / ntk, kt = blockIdx.x % ntk;
-    dx_tile<VEC, BF>(L.Y, L.W, L.Kin, L.o, L.M, L.N, L.Kin, 32 * mt, 32 * kt, smem);
+    head_dx_tile<VEC, BF>(L.Y, L.W, L.Kin, L.o, L.M, L.N, L.Kin, 32 * mt, 32 * kt, smem);
     return;
   }
   const int ntk = (L.Kin + 31) / 32, ntn = (L.N + 31) / 32;
@@ -422,7 +337,7 @@ __global__ __launch_bounds__(kThreads) void head_fwd_persistent_kernel(const Fwd
     TileOut o = {};
     o.C = L.C; o.ldc = L.ldc; o.bias = L.bias; o.act = L.act; o.hsplit = 0x7fffffff;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-      fwd_tile<VEC, false, true>(L.A, L.W, L.K, o, L.M, L.N, L.K, 32 * (t / ntn), 32 * (t % ntn), smem);
+      head_fwd_tile<VEC, false, true>(L.A, L.W, L.K, o, L.M, L.N, L.K, 32 * (t / ntn), 32 * (t % ntn), smem);
       __syncthreads();                                        // the reduction slots become staging images again
     }
     if (l < 3) grid_barrier(a.bar, (unsigned)(l + 1));
@@ -440,8 +355,9 @@ __global__ __launch_bounds__(kThreads) void head_bwd_persistent_kernel(const Bwd
     for (int wk = blockIdx.x; wk < L.nx + ngroups; wk += gridDim.x) {
       if (wk < L.nx) {
         // (the last layer's dY rows are K floats: whole-line staging only when the host found them aligned)
-        if (VEC && (l > 0 || a.vec0)) dx_tile<true, false, true>(L.Y, L.W, L.Kin, L.o, L.M, L.N, L.Kin, 32 * (wk / ntk), 32 * (wk % ntk), smem);
-        else dx_tile<false, false, true>(L.Y, L.W, L.Kin, L.o, L.M, L.N, L.Kin, 32 * (wk / ntk), 32 * (wk % ntk), smem);
+        const int m0 = 32 * (wk / ntk), k0 = 32 * (wk % ntk);
+        if (VEC && (l > 0 || a.vec0)) head_dx_tile<true, false, true>(L.Y, L.W, L.Kin, L.o, L.M, L.N, L.Kin, m0, k0, smem);
+        else head_dx_tile<false, false, true>(L.Y, L.W, L.Kin, L.o, L.M, L.N, L.Kin, m0, k0, smem);
         __syncthreads();
       } else {
         const int tile = (wk - L.nx) * kWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -453,7 +369,6 @@ __global__ __launch_bounds__(kThreads) void head_bwd_persistent_kernel(const Bwd
   poison_on_timeout(a.bar, a.poison);
 }
 
-inline size_t al64(size_t n) { return (n + 63) & ~(size_t)63; }
 inline int kpad(int K) { return (K + 3) & ~3; }   // row stride of the saved d loss / d logits: whole-line staging in the backward
 struct HeadSaved { size_t hw, hp, hs, dl, rl, st, total; };
 inline HeadSaved head_saved(int B, int d, int mlp, int K) {
@@ -478,8 +393,6 @@ inline HeadBwd head_bwd(int B, int d, int mlp) {
   s.total = o;
   return s;
 }
-
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 int check_dims(int B, int d, int mlp, int K, int dtype) {
   CA_CHECK_ARG(dtype == COATTN_F32, "head: unsupported dtype %d (only COATTN_F32)", dtype);

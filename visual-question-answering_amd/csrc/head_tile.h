@@ -1,9 +1,14 @@
 // What the two heads share (head.hip: MLPClassifier of the attention model; fusion.hip: the fusion head of the baseline model):
 // the pieces of a 32 x 32 output tile whose contraction is split over the eight waves of a 512-thread workgroup -- raw buffer
 // loads through descriptors, the staging of a [32 rows][KC] block that is contiguous along the contraction index into a
-// per-wave LDS image, and the MFMAs on a staged chunk.  The operand forms (sums, concatenations, products, row scales), the
-// tile bodies around these pieces and every epilogue stay with the file that owns them.  Everything sits in an anonymous
-// namespace: each file that includes this header gets its own copies, as it would of its own helpers.
+// per-wave LDS image, the MFMAs on a staged chunk -- and the loops around these pieces: the pipelined forward and dX tiles
+// (next chunk's loads in flight behind this chunk's MFMAs) and the cross-wave sum in wave order.  What stays with the file
+// that owns it: the operand forms (sums, concatenations, products, row scales) as policy objects of the loops, with their
+// descriptors; every epilogue as a functor epi(m, n, sum); and the weight-gradient tiles whole -- their loads and products ARE
+// their operand forms (three column modes and a deferred scale in head.hip, a row scale or a second factor in fusion.hip),
+// and what the two have in common is an eight-line loop over M and the twelve-line store of dW and db: a template over both
+// would be more text than it removes.  Everything sits in an anonymous namespace: each file that includes this header gets
+// its own copies, as it would of its own helpers.
 #pragma once
 #include "common.h"
 #include "fused.h"
@@ -109,6 +114,123 @@ __device__ __forceinline__ void mfma_chunk(f32x16& acc, const float* imgA, const
       for (int e = 0; e < 4; ++e) acc = mfma2(fa[e], fb[e], acc);
     }
   }
+}
+
+// cross-wave sum of the eight partial 32 x 32 accumulators in wave order; epi(m, n, sum) for every element inside the matrix
+template <class Epi>
+__device__ __forceinline__ void reduce_epi(const f32x16& acc, float* red, int m0, int n0, int M, int N, int w, Epi epi) {
+  const int lane = threadIdx.x & 63;
+  __syncthreads();                                   // every wave is done with its staging images
+#pragma unroll
+  for (int g = 0; g < 16; ++g) red[(w * 16 + g) * 64 + lane] = acc[g];
+  __syncthreads();
+#pragma unroll
+  for (int gg = 0; gg < 2; ++gg) {
+    const int g = w + 8 * gg;
+    float s = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < kWaves; ++ww) s += red[(ww * 16 + g) * 64 + lane];
+    const int m = m0 + crow32(g, lane >> 5), n = n0 + (lane & 31);
+    if (m < M && n < N) epi(m, n, s);
+  }
+}
+
+// ---- the tile loops ------------------------------------------------------------------------------------------------------
+// The operand that is staged (A of the forward, dY of dX) is a policy object of the including file: load(lane, row0, k0) issues
+// the loads of the block at (row0, k0) into registers the object keeps, store(img, lane) writes them -- combined, where the
+// operand is a sum or a product: only then do the loads have to be back -- into the wave's LDS image.  The object owns its
+// descriptors, as the caller owns W's: the extents differ between the two heads.  It is taken BY VALUE and built in the call
+// (a prvalue: nothing is copied), and the epilogue functor holds a copy of its record: in this form every kernel of the two
+// heads compiles to the register counts it had with loops of its own (profiles/head_tile_regs.txt), head.hip's per-element
+// backward kernels included, which a first shared dX loop took from 148 to 116 VGPRs -- one of the two prefetch sets.
+
+// forward tile: epi(m, n, sum_k A(m, k) W[n][k])
+template <bool VEC, bool BF, class Op, class Epi>
+__device__ __forceinline__ void fwd_tile(Op A, rsrc_t wr, int ldw, int M, int N, int K, int m0, int n0, float* smem, Epi epi) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, lh = lane >> 5;
+  float* imgA = smem + w * (2 * 32 * LDR);
+  float* imgB = imgA + 32 * LDR;
+  f32x16 acc = {};
+  const int nchunks = (K + KC - 1) / KC;
+  Stage sb;
+  int c = w;                                         // chunks interleaved over the waves: neighbouring lines together
+  if (c < nchunks) {
+    A.load(lane, m0, c * KC);
+    stage_lin<VEC>(sb, wr, ldw, K, lane, n0, c * KC);
+  }
+  for (; c < nchunks; c += kWaves) {
+    A.store(imgA, lane);
+    stage_store<VEC>(sb, imgB, lane);
+    if (c + kWaves < nchunks) {                      // next chunk's lines in flight behind this chunk's MFMAs
+      A.load(lane, m0, (c + kWaves) * KC);
+      stage_lin<VEC>(sb, wr, ldw, K, lane, n0, (c + kWaves) * KC);
+    }
+    __builtin_amdgcn_wave_barrier();
+    mfma_chunk<BF>(acc, imgA, imgB, li, lh);
+    __builtin_amdgcn_wave_barrier();
+  }
+  reduce_epi(acc, smem, m0, n0, M, N, w, epi);
+}
+
+// dX tile: epi(m, k', sum_n Y(m, n) W[n][k']), W [Nc][ldw] straight to registers
+template <bool BF, class Op, class Epi>
+__device__ __forceinline__ void dx_tile(Op Y, rsrc_t wr, int ldw, int M, int Nc /* contraction */, int Kout, int m0, int k0,
+                                        float* smem, Epi epi) {
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 31, lh = lane >> 5;
+  float* imgA = smem + w * (2 * 32 * LDR);
+  f32x16 acc = {};
+  const int nchunks = (Nc + KC - 1) / KC;
+  // a lane per output column: 128-byte row segments of W; the lane half takes 4 (BF: 8) consecutive contraction rows
+  const int bvoff = k0 + li < Kout ? ((BF ? 8 : 4) * lh * ldw + k0 + li) * 4 : kOut;
+  float fb0[16], fb1[16];
+  // contraction rows nc + 8 u + 4 lh + e (BF: nc + 16 ks + 8 lh + i); rows >= Nc read 0
+  auto loadB = [&](float (&fb)[16], int nc) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int row = nc + (BF ? 16 * (j >> 3) + (j & 7) : 8 * (j >> 2) + (j & 3));
+      fb[j] = bl1(wr, bvoff, row * ldw * 4);
+    }
+  };
+  auto compute = [&](const float (&fb)[16]) {
+    __builtin_amdgcn_wave_barrier();
+    if constexpr (BF) {
+#pragma unroll
+      for (int ks = 0; ks < KC / 16; ++ks) acc = mfma16(frag16(imgA, li, lh, ks), pack8(&fb[8 * ks]), acc);
+    } else {
+#pragma unroll
+      for (int u = 0; u < KC / 8; ++u) {
+        const f32x4 fa = *reinterpret_cast<const f32x4*>(imgA + li * LDR + 8 * u + 4 * lh);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = mfma2(fa[e], fb[4 * u + e], acc);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  };
+  int c = w;
+  if (c < nchunks) {
+    Y.load(lane, m0, c * KC);
+    loadB(fb0, c * KC);
+  }
+  while (c < nchunks) {                                      // two chunks per trip: the register sets alternate
+    Y.store(imgA, lane);
+    int cn = c + kWaves;
+    if (cn < nchunks) {
+      Y.load(lane, m0, cn * KC);
+      loadB(fb1, cn * KC);
+    }
+    compute(fb0);
+    c = cn;
+    if (c >= nchunks) break;
+    Y.store(imgA, lane);
+    cn = c + kWaves;
+    if (cn < nchunks) {
+      Y.load(lane, m0, cn * KC);
+      loadB(fb0, cn * KC);
+    }
+    compute(fb1);
+    c = cn;
+  }
+  reduce_epi(acc, smem, m0, k0, M, Kout, w, epi);
 }
 
 }  // namespace

@@ -167,9 +167,9 @@ struct Saved { size_t gates, c, hprev, total; };
 Saved saved_plan(int B, int T, int H) {
   Saved p;
   size_t o = 0;
-  p.gates = o; o += fal64((size_t)B * T * 4 * H);
-  p.c = o;     o += fal64((size_t)B * T * H);
-  p.hprev = o; o += fal64((size_t)B * T * H);
+  p.gates = o; o += al64((size_t)B * T * 4 * H);
+  p.c = o;     o += al64((size_t)B * T * H);
+  p.hprev = o; o += al64((size_t)B * T * H);
   p.total = o;
   return p;
 }
@@ -178,8 +178,8 @@ struct FwdWs { size_t gx, c, wimg, bytes; };         // gx, c in floats; wimg, b
 FwdWs fwd_plan(int B, int T, int E, int H) {
   FwdWs p;
   p.gx = 0;
-  p.c = fal64((size_t)B * T * 4 * H);
-  p.wimg = (p.c + fal64((size_t)B * T * H)) * sizeof(float);
+  p.c = al64((size_t)B * T * 4 * H);
+  p.wimg = (p.c + al64((size_t)B * T * H)) * sizeof(float);
   p.bytes = p.wimg + wsplit_bytes(4 * H, E);
   return p;
 }
@@ -188,14 +188,14 @@ struct BwdWs { size_t dgates, dc, part, wimg, total; };    // floats
 BwdWs bwd_plan(int B, int T, int E, int H) {
   BwdWs p;
   size_t o = 0;
-  p.dgates = o; o += fal64((size_t)B * T * 4 * H);
-  p.dc = o;     o += fal64((size_t)B * H);
+  p.dgates = o; o += al64((size_t)B * T * 4 * H);
+  p.dc = o;     o += al64((size_t)B * H);
   const size_t pi = (size_t)wgrad_parts(B * T, 4 * H, E) * 4 * H * E, ph = (size_t)wgrad_parts(B * T, 4 * H, H) * 4 * H * H;
   const size_t pb = (size_t)256 * 4 * H;            // grad_colsum: at most 256 chunks of rows
   size_t part = pi > ph ? pi : ph;
   part = part > pb ? part : pb;
-  p.part = o; o += fal64(part);
-  p.wimg = o; o += fal64(wsplit_bytes(E, 4 * H) / sizeof(float) + 1);
+  p.part = o; o += al64(part);
+  p.wimg = o; o += al64(wsplit_bytes(E, 4 * H) / sizeof(float) + 1);
   p.total = o;
   return p;
 }

@@ -136,6 +136,4 @@ int dx_product(const float* dG, const float* Wih, float* dX, void* wimg, int B, 
   return launch_gemm_f32(d, s);
 }
 
-bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace
