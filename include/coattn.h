@@ -501,9 +501,16 @@ int coattn_head_backward(const void* const* v, const void* const* q, const coatt
  * indices in a row add; a row of empty slots is legal: t[b][:] = 0), which is never formed in memory.  An index >= K or
  * < -1 makes the loss NaN and raises the status word of the hard-label loss: coattn_ce_status / coattn_head_status
  * return -2 and name the row; the call stays asynchronous.
+ * A LIVE slot's non-finite score propagates as it would through the dense target: a NaN score makes t[b][k] NaN -- the row's
+ * loss (and with it the mean) NaN under both kinds, the row's whole gradient NaN under SOFT_CE (through S_b), the entry k alone
+ * under BCE, the row's score NaN where k is the predicted class -- and a score of +inf is a target of +inf, which BCE and the
+ * score clamp to 1.  min(t, 1) below means "1 where t > 1, else t", never a min that drops a NaN.  Other rows keep their bits.
  * Loss kinds, with S_b = sum_k t[b][k] and the mean taken over the B rows (loss = (1/B) sum_b row):
  *   COATTN_LOSS_SOFT_CE: row = S_b logsumexp(z_b) - sum_k t z           d loss / d z = (S_b softmax(z) - t) / B
- *                        (for a row whose only slot is (label, 1.0) this IS coattn_ce_forward's cross entropy, bit for bit)
+ *                        (for a row whose only slot is (label, 1.0) this IS coattn_ce_forward's cross entropy, bit for bit;
+ *                        the sum runs over the classes with t != 0, so a class WITHOUT a target may be masked with a logit
+ *                        of -inf, as under coattn_ce_forward: finite loss, gradient +0 there; a +inf logit gives
+ *                        logsumexp = +inf as torch.logsumexp does: gradient NaN at that class alone)
  *   COATTN_LOSS_BCE    : row = sum_k (softplus(z) - min(t, 1) z)        d loss / d z = (sigmoid(z) - min(t, 1)) / B
  *                        (binary cross entropy with logits summed over the classes; the target is clamped to 1, and
  *                        softplus is max(z, 0) + log1p(exp(-|z|)): finite for every finite logit)
@@ -516,6 +523,8 @@ int coattn_soft_loss_forward(const void* logits, const void* ans_idx, const void
                              void* loss, void* dlogits, void* ws, int B, int K, int dtype, void* stream);
 /* Evaluation: pred[b] = argmax_k z[b][k] (the lowest index among equal maxima), row_score[b] = min(1, t[b][pred[b]]) -- the
  * VQA accuracy of the predicted answer -- and score_sum[0] = their sum in a fixed order, in one launch.
+ * argmax treats a NaN logit as numpy.argmax and torch.argmax do: it counts as the maximum, and the lowest index of a NaN wins,
+ * also over a larger finite logit or +inf in the same row; a row of -inf alone predicts index 0.  pred[b] < K always.
  * pred: int32 [B]; row_score: fp32 [B], may be NULL; score_sum: fp32 [1]; ws as above (K <= 2^24). */
 int coattn_vqa_score(const void* logits, const void* ans_idx, const void* ans_score, int A,
                      void* pred, void* row_score, void* score_sum,

@@ -5,7 +5,7 @@ test_soft_loss_cpu.py and test_gpu_soft_loss.py.  The dense target is built from
 
 and the two losses are their definitions in torch float64 with autograd, mean over the batch:
 
-    soft cross entropy   row = S_b * logsumexp(z_b) - sum_k t z,     S_b = sum_k t[b, k]
+    soft cross entropy   row = S_b * logsumexp(z_b) - sum_k t z,     S_b = sum_k t[b, k]      (the sum over the k with t != 0)
     binary cross entropy row = sum_k (softplus(z) - min(t, 1) z),    softplus(z) = max(z, 0) + log1p(exp(-|z|))
 """
 import numpy as np
@@ -34,7 +34,8 @@ def dense(ans_idx, ans_score, K):
 
 def row_losses(z, t, kind):
     if kind in ("soft_ce", SOFT_CE):
-        return t.sum(1) * torch.logsumexp(z, 1) - (t * z).sum(1)
+        tz = torch.where(t != 0, t * z, torch.zeros_like(z))        # a class without a target may be masked with -inf: no term
+        return t.sum(1) * torch.logsumexp(z, 1) - tz.sum(1)
     softplus = z.clamp(min=0) + torch.log1p(torch.exp(-z.abs()))
     return (softplus - t.clamp(max=1.0) * z).sum(1)
 

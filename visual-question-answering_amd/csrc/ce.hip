@@ -105,6 +105,8 @@ __device__ __forceinline__ float target_of(const int* idx, const float* sc, int 
   for (int a = 0; a < A; ++a) t += idx[a] == k ? sc[a] : 0.f;
   return t;
 }
+// min(t, 1) that lets a NaN through (fminf would return its other argument: a NaN score in a live slot would become a target of 1)
+__device__ __forceinline__ float clamp_one(float t) { return t > 1.f ? 1.f : t; }
 // max(z, 0) + log1p(exp(-|z|)): finite for every finite z
 __device__ __forceinline__ float softplus_safe(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
 __device__ __forceinline__ float sigmoid_safe(float z) {
@@ -114,6 +116,7 @@ __device__ __forceinline__ float sigmoid_safe(float z) {
 
 // KIND = COATTN_LOSS_SOFT_CE: row = S lse(z) - sum_k t z,                      d / dz = (S softmax(z) - t) / B
 // KIND = COATTN_LOSS_BCE    : row = sum_k softplus(z) - min(t, 1) z,           d / dz = (sigmoid(z) - min(t, 1)) / B
+//                             (min(t, 1) = clamp_one: a NaN target stays NaN, as SOFT_CE's does through S and t z)
 // Everything else -- one workgroup per row, the padded gradient row, the status word for an index outside [-1, K), the mean by
 // the last-ticket workgroup in sum_all's order -- is ce_rows_kernel's.  For a row whose only slot is (label, 1) the soft cross
 // entropy's expressions reduce to ce_rows_kernel's operation for operation (S = 1, t z = z[label], t / B = inv_b): same bits.
@@ -139,14 +142,16 @@ __global__ __launch_bounds__(256) void soft_rows_kernel(const float* __restrict_
     float tz = 0.f;
     for (int k = threadIdx.x; k < K; k += 256) {
       s += expf(z[k] - m);
-      tz += target_of(sl.idx, sl.sc, A, k) * z[k];
+      const float t = target_of(sl.idx, sl.sc, A, k);
+      tz += t != 0.f ? t * z[k] : 0.f;                // (a class without a target may be masked with -inf: 0 * -inf is no term)
     }
     s = block_sum(s, sh);
+    if (m == INFINITY) s = INFINITY;                  // a +inf logit: logsumexp = +inf, softmax NaN there and 0 elsewhere (torch.logsumexp)
     tz = block_sum(tz, sh);
     row = (S * (logf(s) + m) - tz) * inv_b;
   } else {
     float acc = 0.f;
-    for (int k = threadIdx.x; k < K; k += 256) acc += softplus_safe(z[k]) - fminf(target_of(sl.idx, sl.sc, A, k), 1.f) * z[k];
+    for (int k = threadIdx.x; k < K; k += 256) acc += softplus_safe(z[k]) - clamp_one(target_of(sl.idx, sl.sc, A, k)) * z[k];
     row = block_sum(acc, sh) * inv_b;
   }
   if (threadIdx.x == 0) {
@@ -162,7 +167,7 @@ __global__ __launch_bounds__(256) void soft_rows_kernel(const float* __restrict_
         dlogits[(long)i * ldd + k] = k < K ? expf(z[k] - m) * inv - target_of(sl.idx, sl.scb, A, k) : 0.f;
     } else {
       for (int k = threadIdx.x; k < ldd; k += 256)
-        dlogits[(long)i * ldd + k] = k < K ? (sigmoid_safe(z[k]) - fminf(target_of(sl.idx, sl.sc, A, k), 1.f)) * inv_b : 0.f;
+        dlogits[(long)i * ldd + k] = k < K ? (sigmoid_safe(z[k]) - clamp_one(target_of(sl.idx, sl.sc, A, k))) * inv_b : 0.f;
     }
   }
   __syncthreads();
@@ -179,8 +184,9 @@ __global__ __launch_bounds__(256) void soft_rows_kernel(const float* __restrict_
   }
 }
 
-// Evaluation: pred[i] = argmax_k z[i][k] (the lowest index among equal maxima), row score = min(1, t[i][pred[i]]) -- the VQA
-// accuracy of the predicted answer -- and the fixed-order sum of the row scores by the last-ticket workgroup, as above.
+// Evaluation: pred[i] = argmax_k z[i][k] (the lowest index among equal maxima; a NaN logit counts as the maximum, the lowest
+// such index winning, as in numpy and torch), row score = min(1, t[i][pred[i]]) (a NaN score in a live slot stays NaN) -- the
+// VQA accuracy of the predicted answer -- and the fixed-order sum of the row scores by the last-ticket workgroup, as above.
 // (the index reduction rides on wave_max: -(float)k is exact for k < 2^24)
 __global__ __launch_bounds__(256) void vqa_score_kernel(const float* __restrict__ logits, const int* __restrict__ ans_idx,
                                                         const float* __restrict__ ans_score, int A, int* __restrict__ pred,
@@ -196,12 +202,18 @@ __global__ __launch_bounds__(256) void vqa_score_kernel(const float* __restrict_
   load_slots(sl, ans_idx, ans_score, A, i, K, 1.f, S, ok);
   float best = -INFINITY;
   int at = threadIdx.x < (unsigned)K ? (int)threadIdx.x : K;     // (K: no candidate; thread 0 always has one, so pred < K)
-  for (int k = threadIdx.x; k < K; k += 256)
-    if (z[k] > best) { best = z[k]; at = k; }
+  int nan_at = K;                                                // the thread's lowest index of a NaN logit (K: none)
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const float v = z[k];
+    if (v > best) { best = v; at = k; }
+    if (v != v && nan_at == K) nan_at = k;
+  }
   const float m = block_max(best, sh);
-  const int p = (int)-block_max(best == m ? -(float)at : -(float)K, sh);
+  int p = (int)-block_max(best == m ? -(float)at : -(float)K, sh);
+  const int pn = (int)-block_max(-(float)nan_at, sh);            // numpy's and torch's argmax: the first NaN wins
+  if (pn < K) p = pn;
   if (threadIdx.x == 0) {
-    const float sc = ok ? fminf(target_of(sl.idx, sl.sc, A, p), 1.f) : NAN;
+    const float sc = ok ? clamp_one(target_of(sl.idx, sl.sc, A, p)) : NAN;
     pred[i] = p;
     if (row_score) row_score[i] = sc;
     __hip_atomic_store(&row_ws[i], sc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

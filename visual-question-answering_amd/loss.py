@@ -125,7 +125,8 @@ def soft_target_loss_stock(logits, ans_idx, ans_score, kind: str = "soft_ce") ->
     _kind(kind)
     t = dense_targets(ans_idx, ans_score, logits.shape[1], logits.dtype)
     if kind == "soft_ce":
-        rows = t.sum(1) * torch.logsumexp(logits, 1) - (t * logits).sum(1)
+        tz = torch.where(t != 0, t * logits, torch.zeros_like(logits))      # (a class masked with -inf and no target: no term)
+        rows = t.sum(1) * torch.logsumexp(logits, 1) - tz.sum(1)
     else:
         softplus = logits.clamp(min=0) + torch.log1p(torch.exp(-logits.abs()))      # (F.softplus switches to x beyond 20)
         rows = (softplus - t.clamp(max=1.0) * logits).sum(1)
